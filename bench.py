@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the NASRec hot path on MI355X (contract: see the task statement / DESIGN.md §Measurement).
 
-    python bench.py [--config {2,3,4,5}] [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--config {2,3,4,5}] [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = the reference's training step (train_utils.py:262-286, 386): forward -> BCEWithLogits -> backward ->
@@ -10,7 +10,7 @@ resident in HBM.  Workloads = BASELINE.json `configs`:
   2 (default, the config the headline metric is quoted on)  Criteo best-1shot sub-network, batch 256 per GPU, full tables;
   3  Criteo NASRec-Full (xlarge) supernet, LayerNorm, `default` path sampling / binomial-0.5, batch 4096, full tables;
   4  Avazu NASRec-Full supernet, batch 4096 per GPU;      5  KDD NASRec-Small (autoctr) supernet, 0.5M-capped tables, batch 8192 per GPU.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  `--dump-outputs DIR`: rank 0 also writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import ctypes as C
@@ -19,6 +19,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -95,6 +96,30 @@ class BatchPool:
     def __getitem__(self, i):
         d = self.dense[i % len(self.dense)]
         return d[0], self.ids[i % self.n], d[1]
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # --dump-outputs: array data of all files; with the .npy headers the directory stays under 64 MB
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write {name: tensor} as out_dir/<name>.npy in the tensors' own precision (float32, or float64 on the dry run's stand-in).  The
+    arrays share the byte budget smallest first: one that fits its share is written whole, in its shape; a larger one as a flat sample
+    at sorted element indices drawn from a generator seeded by its name, the same elements in every run and every build."""
+    os.makedirs(out_dir, exist_ok=True)
+    todo = sorted(arrays.items(), key=lambda kv: (kv[1].numel() * kv[1].element_size(), kv[0]))
+    left = budget
+    for i, (name, t) in enumerate(todo):
+        t = t.detach()
+        share = left // (len(todo) - i) // t.element_size()
+        if t.numel() > share:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, t.numel(), (share,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError("--dump-outputs: %s is %s, not float32 / float64" % (name, a.dtype))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def gemm_algorithmic_bytes(d):
@@ -406,11 +431,19 @@ def main():
                     help="row: every rank owns a row range of every table (nasrec_amd/sharded_tables.py: ids / rows / row gradients by all-to-all, "
                          "owner-side dedup + clip + Adagrad) instead of replicated tables with an all-gather of row gradients")
     ap.add_argument("--id-pool", type=int, default=None, help="number of pre-generated id batches (default: enough to overflow the Infinity Cache)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, logits, parameters after the update; large arrays as a "
+                         "fixed seeded sample, under 64 MB in all) as DIR/<name>.npy.  The set-up phase then runs a fixed number of steps instead "
+                         "of a span of time, so that the same arguments dump the same step of the same trajectory in every run")
     args = ap.parse_args()
     w = WORKLOADS[args.config]
     fixed = w["mode"] == "fixed"
     steps = args.steps if args.steps is not None else (300 if fixed else 60)
     warmup = args.warmup if args.warmup is not None else (30 if fixed else 10)
+    if steps < 1 or warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.table_sharding != "none":
+        raise SystemExit("--dump-outputs reads the engine's own tables: not with --table-sharding %s" % args.table_sharding)
     B = w["B"]
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         rc, line = spawn_ranks(args.gpus, sys.argv[1:])
@@ -586,7 +619,10 @@ def main():
     # Setup, not warm-up: the first step compiles the plan and captures the step graph; then the graph is replayed until the GPU has been
     # busy for ~0.1 s (clocks, TLBs and instruction caches of a box that sat idle through a minute of host-side setup), so that a short
     # timed region (the driver's --steps 20 --warmup 5 is 7 ms of GPU time) sees the steady state the default 300-step run sees.
-    settle_ms = 0.0 if dry else float(os.environ.get("NASREC_BENCH_SETTLE_MS", "100"))
+    # --dump-outputs: a fixed number of settle steps instead (about what 100 ms holds: cfg 2 ran ~450 steps, the supernets 23-29), so that the
+    # dumped step is the same step of the same trajectory whatever the speed of the build
+    settle_ms = 0.0 if dry or args.dump_outputs else float(os.environ.get("NASREC_BENCH_SETTLE_MS", "100"))
+    min_settle = 4 if dry or not args.dump_outputs else 450 if fixed else 25
     one_step(0)
     fence()
     import gc
@@ -595,7 +631,7 @@ def main():
     #                serving loop would do the same.  Before the settle phase: a collection between warm-up and timing idles the GPU for tens of ms)
     t_s = time.perf_counter()
     n_settle = 1
-    while (time.perf_counter() - t_s) * 1e3 < settle_ms or n_settle < 4:
+    while (time.perf_counter() - t_s) * 1e3 < settle_ms or n_settle < min_settle:
         one_step(n_settle)
         n_settle += 1
         if n_settle % 16 == 0 and device.type == "cuda":
@@ -611,6 +647,15 @@ def main():
         one_step(n_settle + warmup + i)
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the last timed step computed, as its caller holds it: the loss, the logits of its batch and the parameters after its
+        # update — the dense ones, and of the tables (GBs) the rows its batch's ids index, the only rows the step changed
+        ids = batches[n_settle + warmup + steps - 1][1]
+        prm = eng.params
+        out = {"loss": dp.last_loss(), "logits": dp.last_plan().logits,
+               "embedding_rows": torch.stack([prm["_embedding.%d.weight" % f][ids[:, f]] for f in range(Fs)], 1)}
+        out.update(("param." + k, v) for k, v in prm.items() if not k.startswith("_embedding."))
+        dump_outputs(args.dump_outputs, out)
     # per-step durations (median_ms_per_step, the step-level roofline) from a second, untimed pass with an event behind every step
     nper = 0 if dry else min(steps, 300)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(nper + 1)] if nper else []

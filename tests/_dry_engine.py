@@ -20,14 +20,17 @@ def make(choice_all, choice, Fd, Fs, tables):
     class DryEngine(OracleEngine):
         Fd_ = Fd
 
-        def dp_plan(self, *a, **kw):
-            plan = OracleEngine.dp_plan(self, *a, **kw)
+        def dp_plan(self, choice, *a, **kw):
+            plan = OracleEngine.dp_plan(self, choice, *a, **kw)
             stage = plan.stage
 
             def stage64(int_x, cat_x, y, lr):
                 self.lr = float(lr)
                 stage(int_x.double(), cat_x, y.double(), lr)
+                with torch.no_grad():  # the step's forward logits (parameters before its update), as the engine's plan holds them
+                    plan.logits = O.supernet_forward(self.params, cfg, int_x.double(), cat_x, choice, num_embeddings=tables).view(-1)
             plan.stage = stage64
+            plan.cp = plan  # (DataParallelStep.last_plan: the engine's plan behind the step)
             return plan
 
     cfg = O.NetCfg(choice_all["num_blocks"], O.ops_config_lib[choice_all["config"]], False, "relu", fixed=True)
@@ -37,6 +40,7 @@ def make(choice_all, choice, Fd, Fs, tables):
         O.supernet_forward(P, cfg, int_x.double(), cat_x, choice, num_embeddings=tables)
     P.frozen = True
     eng = DryEngine(cfg, P, Fs)
+    eng.params = P  # the engine's name -> tensor map (bench.py --dump-outputs)
     eng.Fd = Fd
     eng.lr = 1e-3
     return eng

@@ -61,3 +61,37 @@ def test_bench_gpus_2_spawns_its_own_ranks():
                        env=_env(), capture_output=True, text=True, timeout=800, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     _check(p.stdout, 2, 1)
+
+
+@pytest.mark.timeout(900)
+def test_dump_outputs_holds_the_last_timed_step_the_same_in_every_run(tmp_path):
+    """`bench.py --dump-outputs DIR` (one rank, the exchange path): float .npy files under 64 MB in all — the loss, the logits of the
+    batch, the embedding rows of its ids and every dense parameter after the LAST timed step (its loss is the result line's
+    final_loss: the dry run has no untimed pass behind the timed one) — bit-identical in two runs with the same arguments; one more
+    timed step (--steps) dumps another state."""
+    import numpy as np
+
+    def run(d, steps):
+        env = _env()
+        env["MASTER_PORT"] = str(_free_port())
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dp-path", "--steps", str(steps), "--warmup", "1",
+                            "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=800, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        r = json.loads(lines[0])
+        assert r["steps"] == steps and r["warmup"] == 1
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64e6
+        return r, {f[:-4]: np.load(os.path.join(d, f), allow_pickle=False) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
+
+    ra, a = run(tmp_path / "a", 2)
+    _, b = run(tmp_path / "b", 2)
+    _, c = run(tmp_path / "c", 3)
+    assert {"loss", "logits", "embedding_rows"} <= set(a) and any(k.startswith("param.") for k in a)
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(os.listdir(tmp_path / "b")) == sorted(os.listdir(tmp_path / "c"))
+    B = ra["config"]["per_gpu_batch"]
+    assert a["logits"].shape == (B,) and a["embedding_rows"].shape == (B, 26, 16)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert float(a["loss"][0]) == ra["final_loss"]
+    assert all(np.array_equal(a[k], b[k]) for k in a), [k for k in a if not np.array_equal(a[k], b[k])]
+    assert not np.array_equal(a["loss"], c["loss"]) and any(not np.array_equal(a[k], c[k]) for k in a if k.startswith("param."))

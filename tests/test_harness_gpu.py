@@ -143,7 +143,7 @@ def test_finetune_last_layer_only_through_the_harness_leaves_everything_else_unt
     assert TU._fused_step_applies(model, full, lambda m: TU.get_l2_loss(m, 0.0, None, gpu=0), False) is True
 
 
-def test_search_candidates_are_scored_by_last_layer_finetuning(monkeypatch):
+def test_search_candidates_are_scored_by_last_layer_finetuning(monkeypatch, tmp_path):
     """eval_subnet_from_supernet.py's loop on the engine: random candidates of a (capped-table) KDD autoctr supernet, each scored by
     `finetune_and_eval_one_model` from a shared checkpoint — full-path warm-up, pinned path, last layer only.  Workers run inline
     here (a process that holds the GPU must not be duplicated; the CLI's parent process never touches the GPU and spawns one
@@ -156,7 +156,7 @@ def test_search_candidates_are_scored_by_last_layer_finetuning(monkeypatch):
     from nasrec_amd.utils.config import DATASETS
     tables = [min(n, 1000) for n in DATASETS["kdd"]["tables"]]
     args = E.build_parser().parse_args([
-        "--dataset", "kdd", "--root_dir", "synthetic:steps=8,test_steps=2,seed=5,cap=1000", "--logging_dir", "/tmp/nasrec_search_test",
+        "--dataset", "kdd", "--root_dir", "synthetic:steps=8,test_steps=2,seed=5,cap=1000", "--logging_dir", str(tmp_path / "search"),
         "--config", "autoctr", "--num_blocks", "3", "--use_layernorm", "1", "--max_train_steps", "4", "--max_eval_steps", "2",
         "--train_batch_size", "64", "--test_batch_size", "64", "--method", "random", "--random_budget", "3", "--learning_rate", "0.05",
         "--display_interval", "2", "--test_only_at_last_step", "1"])  # as scripts/run_ea/*.sh: one test per candidate
