@@ -84,7 +84,8 @@ enum {
   NASREC_OP_OPT_REDUCE2 = 34,
   NASREC_OP_FINAL_FUSED = 35,
   NASREC_OP_PERSIST = 36,
-  NASREC_OP_WORKLIST_DEV = 38 /* (37 is taken by a layout-check slot of nasrec_desc_sizes) */
+  NASREC_OP_WORKLIST_DEV = 38, /* (37 is taken by a layout-check slot of nasrec_desc_sizes) */
+  NASREC_OP_WEIGHT_DECAY = 39
 };
 
 /* ------------------------------------------------------------------------------------------------
@@ -442,6 +443,52 @@ typedef struct nasrec_opt_apply_desc {
 } nasrec_opt_apply_desc_t;
 
 /* ------------------------------------------------------------------------------------------------
+ * L2 weight decay of the fused step (get_l2_loss, train_utils.py:91-115: wd * sum ||W||^2 over every parameter with >= 2 dims whose
+ * name is not under no_reg_param_name, tables included; backpropagated with the BCE loss, train_utils.py:262-266).  Every regularised
+ * parameter's gradient gets + 2 wd W — every table row too, touched by the batch or not — so the row-sparse table update becomes a
+ * dense one.  Two launches around NASREC_OP_OPT_APPLY (or CLIP_COEF + ADAGRAD_*), 256-thread workgroups, tables walked in TILES of 64
+ * rows (the tiles of the regularised tables numbered consecutively: table f owns tiles [tile_off[f], tile_off[f+1]); its bits in
+ * `bitmap` are the words [2 tile_off[f], 2 tile_off[f+1]), bit (row & 31) of word 2 tile_off[f] + row / 32):
+ *   phase 0 (behind the reduce launch, before the clip): dense arena: g += 2 wd p over add_chunks (parameters the backward reached),
+ *     g = 2 wd p over set_chunks (regularised parameters it did not reach: their grad is the L2 term alone); touched rows (leader != 0,
+ *     id in range, table in reg_mask): the leader's summed row gsum += 2 wd W, and the row's bit is set; every row of a regularised
+ *     table: W^2.  What the norm's sum of squares gains over the reduce launch's partials (sum (g')^2 - g^2 of the dense ranges and
+ *     the touched rows, sum (2 wd W)^2 of all rows) -> clip_partial[0], to be listed among the clip's partial_a; sum of W^2 of every
+ *     regularised parameter (the L2 term / wd, pre-step weights) -> l2_sumsq[0] (fp64).  Per-workgroup fp64 partials in block_part
+ *     [2 nblocks], summed in fixed order by the workgroup that finishes last (counter: zero before, left zero behind).
+ *   phase 1 (behind the Adagrad of the touched rows): every row of a regularised table whose bit is NOT set: g = 2 wd W * coef,
+ *     state += g^2, W -= lr g / (sqrt(state) + eps); the bitmap is left all zero for the next step, and g over set_chunks back at 0.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct nasrec_weight_decay_desc {
+  int32_t kind; /* NASREC_OP_WEIGHT_DECAY */
+  int32_t phase;   /* 0 / 1 (above) */
+  int32_t nblocks; /* workgroups of the launch */
+  int32_t B, Fs;   /* [B, Fs] id / leader arrays (B = 0: no touched rows) */
+  float wd, eps;
+  uint32_t reg_mask; /* bit f: table f is regularised */
+  const int64_t* idx;    /* [B,Fs] */
+  const int32_t* leader; /* [B,Fs] */
+  float* gsum;           /* [B,Fs,16], contiguous: a leader's row holds its summed gradient */
+  float* table[NASREC_MAX_TABLES];
+  float* state[NASREC_MAX_TABLES];
+  int64_t rows[NASREC_MAX_TABLES];
+  int64_t tile_off[NASREC_MAX_TABLES + 1];
+  uint32_t* bitmap;      /* [2 tile_off[Fs]] */
+  float* p;              /* flat dense parameter / gradient arenas */
+  float* g;
+  const int64_t* add_chunks; /* [offset, length] pairs into p / g */
+  int64_t n_add;
+  const int64_t* set_chunks;
+  int64_t n_set;
+  double* block_part;    /* [2 nblocks] */
+  uint32_t* counter;
+  float* clip_partial;   /* [1] */
+  double* l2_sumsq;      /* [1] */
+  const float* lr;       /* device scalars (phase 1) */
+  const float* coef;
+} nasrec_weight_decay_desc_t;
+
+/* ------------------------------------------------------------------------------------------------
  * The row-sparse embedding backward in two halves (round 5).  NASREC_OP_EMB_DEDUP above does everything behind the backward pass;
  * but which sample leads a row, and which samples repeat it, depends on the IDS only — known before the forward pass starts (one
  * GPU: when the batch is staged; N GPUs: when the ids all-gather lands, nasrec_amd/parallel.py).  So:
@@ -727,6 +774,7 @@ int nasrec_opt_apply(void* stream, const nasrec_opt_apply_desc_t* d);
 int nasrec_dedup_ids(void* stream, const nasrec_dedup_ids_desc_t* d);
 int nasrec_opt_reduce2(void* stream, const nasrec_opt_reduce2_desc_t* d);
 int nasrec_final_fused(void* stream, const nasrec_final_desc_t* d);
+int nasrec_weight_decay(void* stream, const nasrec_weight_decay_desc_t* d);
 int nasrec_worklist(void* stream, const nasrec_worklist_desc_t* d);
 
 /* Uncached device memory (hipExtMallocWithFlags(hipDeviceMallocUncached)): the plan arena of a persistent step (NASREC_OP_PERSIST) —

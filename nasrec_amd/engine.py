@@ -362,21 +362,27 @@ class SupernetEngine:
     @_on_device
     def compile(self, choice, B: int, train: bool, clip: Optional[float] = 5.0, eps: float = 1e-2, graph: bool = False,
                 grad_scale: Optional[float] = None, defer_dw: bool = True, row_grad_out: Optional[torch.Tensor] = None,
-                local_optimizer: bool = True) -> CompiledPlan:
+                local_optimizer: bool = True, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None) -> CompiledPlan:
         """row_grad_out: storage [B * Fs * 16] the backward writes the per-sample embedding-row gradients into (a data-parallel step
         hands in the head of its all-gather send buffer: no copy between the backward and the exchange); local_optimizer = False: the
-        plan gets no clip + Adagrad program of its own (a data-parallel step runs its optimizer over the GLOBAL batch)"""
+        plan gets no clip + Adagrad program of its own (a data-parallel step runs its optimizer over the GLOBAL batch).
+        weight_decay != 0: the training step adds get_l2_loss(model, weight_decay, no_reg_param_name)'s gradient (_weight_decay_descs)"""
         rgo = row_grad_out.data_ptr() if row_grad_out is not None else None
-        fast = (id(choice), B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer)
+        weight_decay = float(weight_decay or 0.0)
+        wd_key = (weight_decay, no_reg_param_name) if weight_decay else None
+        if weight_decay and not (train and local_optimizer):
+            raise L.EngineError("weight decay is part of the fused training step's optimizer: it needs train=True, local_optimizer=True")
+        fast = (id(choice), B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, wd_key)
         hit = self._last_plan
         if self.cfg.fixed and hit is not None and hit[0] == fast and hit[1] is choice:  # fixed sub-network, same choice object: skip the JSON key
             return hit[2]
-        key = json.dumps([choice, B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer], sort_keys=True, default=_jsonable)
+        key = json.dumps([choice, B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, wd_key], sort_keys=True, default=_jsonable)
         if key in self._plans:
             self._last_plan = (fast, choice, self._plans[key])
             return self._plans[key]
         arena = None
-        persist = bool(self.persist and self.level_schedule and self.cfg.fixed and B <= 256 and train and local_optimizer)
+        # (weight decay: the default launches — the persistent step is an opt-in that has not been built for it)
+        persist = bool(self.persist and self.level_schedule and self.cfg.fixed and B <= 256 and train and local_optimizer and not weight_decay)
         if self.cfg.fixed and B <= 256 and train and self.level_schedule and (_UC_ARENA or persist):
             arena = Arena(self.device, uncached=True)  # (see _UC_ARENA; the persistent step needs it whatever the knob says)
         if not self.cfg.fixed:
@@ -405,6 +411,7 @@ class SupernetEngine:
         with torch.cuda.stream(self.stream):
             cp = CompiledPlan()
             cp.arena, cp.evicted = arena, False
+            cp.wd, cp.no_reg = weight_decay, no_reg_param_name
             ctx = P.Ctx(B, self.device, self.params, self.grads, shape_only=False, train=train)
             ctx.sk_workspace = self._sk_workspace
             # parked weight-gradient batches are for one-launch-per-operator plans; the level scheduler places the products itself
@@ -704,7 +711,80 @@ class SupernetEngine:
                 for dsc in P.const_i64_descs(cp.chunk_tab.data_ptr(), flat):
                     L.check(lib.nasrec_launch(self.stream.cuda_stream, C.addressof(dsc)))
                 self.stream.synchronize()  # (the descriptors carry the values: they must outlive their launches)
+        if cp.wd:
+            self._weight_decay_tables(cp, ctx, arena, pre)
         cp.bce, cp._pre = bd, pre
+
+    WD_BLOCKS = 2048  # workgroups of the two weight-decay launches (8 per CU: the table pass is a stream over W and its state)
+
+    def _weight_decay_tables(self, cp, ctx, arena, pre):
+        """Chunk tables of a plan with weight decay (csrc/weight_decay.hip): the regularised dense ranges the backward reaches (g += 2 wd W)
+        and the ones it does not (g = 2 wd W: get_l2_loss walks named_parameters(), on the path or off it), and the union of the reached
+        and the regularised ranges, over which Adagrad runs (torch skips grad = None: 1-D parameters off the path).  The clip's sum of
+        squares keeps the reached ranges only — a fixed sub-network gets that table whatever its share of the arena."""
+        names = [n for n in list(ctx.grad_params) + ["_final.weight", "_final.bias"] if not n.startswith("_embedding.")]
+        reached = list(dict.fromkeys(names))
+        reg, cp.wd_tables = P.regularised(self.shapes, cp.no_reg)
+        on = set(reached)
+
+        def chunks(ns):
+            return P.path_chunks([(self.offsets[n], self.params[n].numel()) for n in ns], chunk=1024)
+        parts = [chunks([n for n in reg if n in on]), chunks([n for n in reg if n not in on]), chunks(list(dict.fromkeys(reached + reg)))]
+        if cp.chunk_tab is None:
+            parts.append(chunks(reached))
+        flat = [v for part in parts for v in part]
+        tab = (arena.alloc(max(1, len(flat)), torch.int64).tensor() if (arena is not None and not self.cfg.fixed)
+               else torch.empty(max(1, len(flat)), dtype=torch.int64, device=self.device))
+        if not self.cfg.fixed:
+            pre += P.const_i64_descs(tab.data_ptr(), flat)  # (the slot's arena is reused by other paths: written every step)
+        else:
+            lib = L.load()
+            for dsc in P.const_i64_descs(tab.data_ptr(), flat):
+                L.check(lib.nasrec_launch(self.stream.cuda_stream, C.addressof(dsc)))
+            self.stream.synchronize()
+        ptrs, off = [], 0
+        for part in parts:
+            ptrs.append((tab.data_ptr() + 8 * off, len(part) // 2))
+            off += len(part)
+        cp.wd_add, cp.wd_set, cp.wd_union = ptrs[:3]
+        if cp.chunk_tab is None:
+            cp.chunk_tab, cp.nchunks = tab[off - len(parts[3]):off], ptrs[3][1]
+        cp.wd_tab = tab
+        if getattr(self, "_wd_bitmap", None) is None:  # engine-wide: every plan leaves it all zero behind its step
+            words = sum(2 * ((n + 63) // 64) for n in self.num_embeddings)
+            with torch.cuda.stream(self.stream):
+                self._wd_bitmap = torch.zeros(max(1, words), dtype=torch.int32, device=self.device)
+                self._wd_part = torch.zeros(2 * self.WD_BLOCKS, dtype=torch.float64, device=self.device)
+                self._wd_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
+                self.wd_l2_sumsq = torch.zeros(1, dtype=torch.float64, device=self.device)
+            self.stream.synchronize()
+
+    def _weight_decay_descs(self, cp, Bg, cat_x, gsum, eps, clip_partial):
+        """the two NASREC_OP_WEIGHT_DECAY launches of a plan: (phase 0, in front of the clip; phase 1, behind the touched rows' Adagrad)"""
+        w = L.WeightDecayDesc()
+        w.kind, w.phase, w.nblocks = L.OP_WEIGHT_DECAY, 0, self.WD_BLOCKS
+        w.wd, w.eps = cp.wd, eps
+        w.B, w.Fs = (Bg, self.Fs) if gsum is not None else (0, self.Fs)
+        if gsum is not None:
+            w.idx, w.leader, w.gsum = cat_x.data_ptr(), cp.leader.data_ptr(), gsum
+        mask, t = 0, 0
+        for f in range(self.Fs):
+            w.table[f], w.state[f], w.rows[f] = self.tables[f].data_ptr(), self.table_state[f].data_ptr(), self.num_embeddings[f]
+            w.tile_off[f] = t
+            if f in cp.wd_tables:
+                mask |= 1 << f
+                t += (self.num_embeddings[f] + 63) // 64
+        w.tile_off[self.Fs] = t
+        w.reg_mask = mask
+        w.bitmap = self._wd_bitmap.data_ptr()
+        w.p, w.g = self.flat_p.data_ptr(), self.flat_g.data_ptr()
+        (w.add_chunks, w.n_add), (w.set_chunks, w.n_set) = cp.wd_add, cp.wd_set
+        w.block_part, w.counter = self._wd_part.data_ptr(), self._wd_counter.data_ptr()
+        w.clip_partial, w.l2_sumsq = clip_partial, self.wd_l2_sumsq.data_ptr()
+        w.lr, w.coef = self.lr_dev.data_ptr(), self.clip_out.data_ptr()
+        w1 = L.WeightDecayDesc.from_buffer_copy(w)
+        w1.phase = 1
+        return w, w1
 
     def _optimizer_descs(self, cp, Bg, cat_x, sparse_grad, clip, eps, rank_layout=None):
         """clip_grad_norm_ + Adagrad (train_utils.py:285-286): row-sparse on the tables, flat on the dense arena.
@@ -725,7 +805,7 @@ class SupernetEngine:
             cp.leader = new(Bg * self.Fs, torch.int32)
             cp.gsum = new(Bg * self.Fs * E)
             cp.emb_partial = new(self.Fs * nb)
-            cp.dense_partial = new(256)
+            cp.dense_partial = new(256 + (1 if getattr(cp, "wd", 0.0) else 0))  # (weight decay: + phase 0's share of the norm)
         if sparse_grad is not None:
             dd = L.EmbDedupDesc()
             dd.kind = L.OP_EMB_DEDUP
@@ -746,6 +826,12 @@ class SupernetEngine:
         cc.n_a, cc.n_b = nblk, (self.Fs * nb if sparse_grad is not None else 0)
         cc.max_norm = float(clip) if clip is not None else 0.0
         cc.partial_a, cc.partial_b, cc.out = cp.dense_partial.data_ptr(), cp.emb_partial.data_ptr(), self.clip_out.data_ptr()
+        wd = getattr(cp, "wd", 0.0)
+        if wd:
+            if rank_layout:
+                raise L.EngineError("weight decay: the fused step covers one process (data-parallel runs take the torch route)")
+            cc.n_a = nblk + 1  # partial_a[nblk]: what the L2 gradient adds to the norm's sum of squares (weight-decay phase 0)
+            wd_part = cp.dense_partial.data_ptr() + 4 * nblk
         descs.append(cc)
         ad = L.AdagradDenseDesc()
         ad.kind = L.OP_ADAGRAD_DENSE
@@ -754,6 +840,8 @@ class SupernetEngine:
         ad.lr, ad.coef = self.lr_dev.data_ptr(), self.clip_out.data_ptr()
         if tab is not None:
             ad.chunks, ad.nchunks = tab.data_ptr(), ntab
+        if wd:  # Adagrad over the reached AND the regularised ranges
+            (ad.chunks, ad.nchunks), ntab = cp.wd_union, cp.wd_union[1]
         descs.append(ad)
         if sparse_grad is not None:
             ar = L.AdagradRowsDesc()
@@ -805,6 +893,9 @@ class SupernetEngine:
                 app.clip.partial_b, app.clip.n_b = cp.emb_partial2.data_ptr(), self.Fs + row_blocks
                 app.rows.gsum = sparse_grad.data_ptr()  # summed in place: a leader's row holds its sum
                 app.rows.rank_B, app.rows.rank_stride = r2.rank_B, r2.rank_stride
+                if wd:
+                    w0, w1 = self._weight_decay_descs(cp, Bg, cat_x, sparse_grad.data_ptr(), eps, wd_part)
+                    return [r2, w0, app, w1]
                 return [r2, app]
             if rank_layout:  # (the one-launch kernels read the rows where the all-gather left them; their sums go to the contiguous gsum)
                 dd.rank_B, dd.rank_stride = rank_layout
@@ -813,8 +904,18 @@ class SupernetEngine:
                 red = L.OptReduceDesc()
                 red.kind = L.OP_OPT_REDUCE
                 red.dedup, red.sumsq = dd, sq
+                if wd:
+                    w0, w1 = self._weight_decay_descs(cp, Bg, cat_x, cp.gsum.data_ptr(), eps, wd_part)
+                    return [red, w0, app, w1]
                 return [red, app]
+            if wd:
+                w0, w1 = self._weight_decay_descs(cp, Bg, cat_x, cp.gsum.data_ptr(), eps, wd_part)
+                return [dd, sq, w0, app, w1]
             return [dd, sq, app]  # global batch of a data-parallel step: chunked dedup + merge (two launches), then the same apply
+        if wd:
+            w0, w1 = self._weight_decay_descs(cp, Bg, cat_x, cp.gsum.data_ptr() if sparse_grad is not None else None, eps, wd_part)
+            descs.insert(descs.index(cc), w0)
+            descs.append(w1)
         return descs
 
     @_on_device
@@ -957,10 +1058,12 @@ class SupernetEngine:
 
     @_on_device
     def train_step(self, int_x, cat_x, y, lr: float, choice=None, clip: Optional[float] = 5.0, eps: float = 1e-2, graph: Optional[bool] = False,
-                   staged: bool = False):
+                   staged: bool = False, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None):
         """zero_grad -> forward -> BCE -> backward -> clip_grad_norm_ -> Adagrad (train_utils.py:262-286).
         Returns the (device) loss tensor of this step.  `staged`: inputs are already in the plan's static buffers.  graph: True = replay
-        the captured step, False = launch its program, None = whichever is faster for this plan (prefers_graph)."""
+        the captured step, False = launch its program, None = whichever is faster for this plan (prefers_graph).
+        weight_decay != 0: the step minimises BCE + get_l2_loss(model, weight_decay, no_reg_param_name) (train_utils.py:91-115,262-266):
+        every regularised parameter and EVERY table row is decayed; wd_l2_sumsq then holds sum ||W||^2 of the pre-step weights."""
         choice = choice if choice is not None else self.warm_choice
         if graph is None:
             graph = self.cfg.fixed and self.prefers_graph(int(int_x.shape[0]) if int_x is not None else int(self._last_plan[2].cat_x.shape[0]))
@@ -972,7 +1075,7 @@ class SupernetEngine:
         else:  # pre-staged inputs: the batch size is the one of the plan they were staged into
             assert staged and self._last_plan is not None, "train_step without inputs needs a previously compiled plan holding them"
             B = int(self._last_plan[2].cat_x.shape[0])
-        cp = self.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph)
+        cp = self.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, weight_decay=weight_decay, no_reg_param_name=no_reg_param_name)
         sp = self._sp()
         if not staged:
             whole = not graph and getattr(cp, "fb", None) is not None and not self.host_embedding

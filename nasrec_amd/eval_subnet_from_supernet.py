@@ -16,7 +16,7 @@ from .searcher.searcher_utils import _num_embedding_dict, _num_sparse_inputs_dic
 from .utils.data_pipes import make_loaders
 from .utils.io_utils import create_dir, dump_pickle_data, load_model_checkpoint, load_pickle_data
 from .utils.lr_schedule import ConstantWithWarmup, CosineAnnealingWarmupRestarts
-from .utils.train_utils import get_l2_loss, train_and_test_one_epoch, warmup_supernet_model
+from .utils.train_utils import L2Loss, train_and_test_one_epoch, warmup_supernet_model
 
 
 def finetune_and_eval_one_model(model, args, checkpoint):
@@ -35,8 +35,7 @@ def finetune_and_eval_one_model(model, args, checkpoint):
     else:
         print("Finetuning the whole supernet.")
 
-    def l2_loss_fn(m):
-        return get_l2_loss(m, args.wd, getattr(args, "no_reg_param_name", None), gpu=args.gpu)
+    l2_loss_fn = L2Loss(args.wd, getattr(args, "no_reg_param_name", None), gpu=args.gpu)
 
     if args.optimizer == "adagrad":
         optimizer = torch.optim.Adagrad(model.parameters(), lr=args.learning_rate, eps=1e-2)

@@ -314,6 +314,20 @@ def path_chunks(ranges, chunk=None):
     return flat
 
 
+def regularised(shapes: Dict[str, tuple], no_reg_param_name=None):
+    """-> (dense parameter names, table indices) that get_l2_loss regularises (train_utils.py:91-115): every parameter with >= 2
+    dimensions whose name does not start with no_reg_param_name — the whole model, on a sampled path or off it"""
+    dense, tables = [], []
+    for n, shp in shapes.items():
+        if len(shp) < 2 or (no_reg_param_name is not None and n.startswith(no_reg_param_name)):
+            continue
+        if n.startswith("_embedding."):
+            tables.append(int(n.split(".")[1]))
+        else:
+            dense.append(n)
+    return dense, sorted(tables)
+
+
 def const_i64_descs(dst_ptr, values):
     """NASREC_OP_CONST_I64 launches that write `values` to the int64 array at dst_ptr"""
     out = []

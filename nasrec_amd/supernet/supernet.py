@@ -598,9 +598,12 @@ class SuperNet(nn.Module):
     def fixed_forward(self, int_feats: torch.Tensor, cat_feats: torch.Tensor, choices: Any):
         return self.forward(int_feats, cat_feats, choices)
 
-    def engine_train_step(self, int_feats, cat_feats, y, lr: float, clip: Optional[float] = 5.0, eps: float = 1e-2, graph=None):
+    def engine_train_step(self, int_feats, cat_feats, y, lr: float, clip: Optional[float] = 5.0, eps: float = 1e-2, graph=None,
+                          weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None):
         """Fused step on the engine (forward, BCE, backward, clip_grad_norm_, Adagrad with row-sparse table update):
-        the counterpart of train_utils.py:262-286 for optimizer == Adagrad, weight_decay == 0."""
+        the counterpart of train_utils.py:262-286 for optimizer == Adagrad (torch's own weight_decay == 0).  weight_decay != 0: the loss
+        is BCE + get_l2_loss(self, weight_decay, no_reg_param_name) — every regularised parameter and every table row is decayed
+        (engine_last_l2 = that term on the pre-step weights); one process with whole tables only."""
         if self._place_embedding_on_cpu:
             from .._lib import EngineError
             raise EngineError("engine_train_step needs the tables on the device; with place_embedding_on_cpu use forward / backward "
@@ -614,7 +617,17 @@ class SuperNet(nn.Module):
         d = self.__dict__  # (plain bookkeeping: nn.Module.__setattr__ costs 2 us per assignment)
         d["_engine_steps"] = d.get("_engine_steps", 0) + 1
         d["_last_step_batch"] = int(int_feats.shape[0])
+        weight_decay = float(weight_decay or 0.0)
         d["_last_step_key"] = (choice, clip, eps, graph)
+        d["_last_step_wd"] = (weight_decay, no_reg_param_name)
+        if weight_decay:
+            import torch.distributed as dist
+            if self._table_sharding == "row" or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+                from .._lib import EngineError
+                raise EngineError("weight decay in the fused step covers one process with whole tables: row-sharded tables and "
+                                  "data-parallel runs train with weight decay 0 (or through the torch route)")
+            return self._engine.train_step(int_feats, cat_feats, y, lr, choice, clip, eps, graph=graph, weight_decay=weight_decay,
+                                           no_reg_param_name=no_reg_param_name)
         if self._table_sharding == "row":
             from ..sharded_tables import ShardedTableStep
             st = self.__dict__.get("_sharded_step")
@@ -644,8 +657,18 @@ class SuperNet(nn.Module):
         dp = self.__dict__.get("_dp_step")
         if dp is not None and dp[1].exchange:
             return dp[1].last_plan().logits.view(B, 1)
-        cp = self._engine.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph)
+        wd, no_reg = self.__dict__.get("_last_step_wd", (0.0, None))
+        cp = self._engine.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, weight_decay=wd, no_reg_param_name=no_reg)
         return cp.logits.view(B, 1)
+
+    def engine_last_l2(self):
+        """(device) get_l2_loss(self, weight_decay, no_reg_param_name) of the pre-step weights of the most recent engine_train_step —
+        the `L2:` the reference prints (train_utils.py:262-266); exactly 0 when that step had weight_decay == 0"""
+        wd, _ = self.__dict__.get("_last_step_wd", (0.0, None))
+        eng = self._engine
+        if not wd or getattr(eng, "wd_l2_sumsq", None) is None:
+            return torch.zeros((), device=self._final.weight.device)
+        return (eng.wd_l2_sumsq[0] * wd).to(torch.float32)
 
     def engine_bind_optimizer(self, optimizer):
         """Share the Adagrad accumulators between a torch.optim.Adagrad and the engine: existing `sum` state (a resumed

@@ -18,7 +18,7 @@ from nasrec_amd.main_train import _num_embedding_dict, _num_sparse_inputs_dict, 
 from nasrec_amd.supernet.supernet import SuperNet, ops_config_lib  # noqa: E402
 from nasrec_amd.utils.data_pipes import make_loaders  # noqa: E402
 from nasrec_amd.utils.io_utils import create_dir, dump_pickle_data, load_model_checkpoint, load_optimizer_state, save_model_checkpoint  # noqa: E402
-from nasrec_amd.utils.train_utils import (get_l2_loss, get_model_flops_and_params, init_weights, train_and_test_one_epoch,  # noqa: E402
+from nasrec_amd.utils.train_utils import (L2Loss, get_model_flops_and_params, init_weights, train_and_test_one_epoch,  # noqa: E402
                                           warmup_supernet_model)
 
 
@@ -33,8 +33,7 @@ def train_and_eval_one_model(model, args):
         raise NotImplementedError("Loss function {} is not implemented!".format(args.loss_function))
     loss_fn = torch.nn.BCEWithLogitsLoss()
 
-    def l2_loss_fn(m):
-        return get_l2_loss(m, args.wd, args.no_reg_param_name, gpu=args.gpu)
+    l2_loss_fn = L2Loss(args.wd, args.no_reg_param_name, gpu=args.gpu)
 
     optimizer = build_optimizer(args.optimizer, model, args.learning_rate)
     steps_per_epoch = args.train_limit // args.train_batch_size

@@ -4,7 +4,8 @@
 `train_and_test_one_epoch` keeps the reference's step order (H2D, zero_grad, forward, BCE + L2, backward,
 clip_grad_norm_, optimizer.step, LR step after the optimizer, train_utils.py:255-287,386).  When the run is one the fused
 engine step covers — the model exposes `engine_train_step`, the optimizer is torch.optim.Adagrad without weight/lr decay,
-the L2 term is identically zero (`--wd 0`, the published recipes) and AMP is off — the whole step is ONE engine call
+the L2 term is identically zero (`--wd 0`, the published recipes) or an `L2Loss` spec (any `--wd`, one process with whole
+tables) and AMP is off — the whole step is ONE engine call
 (captured in a hipGraph for fixed sub-networks); anything else takes the reference's operator-by-operator route through
 `model(int_x, cat_x)` + autograd + the torch optimizer, which the module also supports.
 
@@ -51,6 +52,21 @@ def get_l2_loss(model: nn.Module, reg: float, no_reg_param_name: Union[str, None
         term = torch.square(torch.norm(p, p=2)) * reg
         total = term if total is None else total + term
     return total
+
+
+class L2Loss:
+    """get_l2_loss(model, wd, no_reg_param_name, gpu) as a callable the fused engine step can read: calling it returns exactly what
+    get_l2_loss returns, and `wd` / `no_reg_param_name` tell the engine which term to fold into its step (an opaque callable with a
+    non-zero value sends the step to the torch route)."""
+
+    def __init__(self, wd: float, no_reg_param_name: Union[str, None] = None, gpu: Optional[int] = None):
+        self.wd, self.no_reg_param_name, self.gpu = float(wd), no_reg_param_name, gpu
+
+    def __call__(self, model: nn.Module):
+        return get_l2_loss(model, self.wd, self.no_reg_param_name, gpu=self.gpu)
+
+    def __repr__(self):
+        return "L2Loss(wd=%r, no_reg_param_name=%r, gpu=%r)" % (self.wd, self.no_reg_param_name, self.gpu)
 
 
 def accuracy(gt, pred):
@@ -108,6 +124,11 @@ def _fused_step_applies(model, optimizer, l2_loss_fn, use_amp):
         return False
     if {id(p) for p in params} != {id(p) for p in optimizer.param_groups[0]["params"]}:
         return False
+    if isinstance(l2_loss_fn, L2Loss) and l2_loss_fn.wd != 0:
+        # the engine folds the L2 term into its step — for one process holding whole tables (row-sharded tables and data-parallel runs
+        # keep the torch route with weight decay, as before)
+        from .dist import world_info
+        return world_info()[1] <= 1 and getattr(model, "_table_sharding", None) != "row"
     with torch.no_grad():
         return float(l2_loss_fn(model)) == 0.0
 
@@ -161,6 +182,8 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
     from .dist import StepAgreement, allreduce_grads, any_rank, world_info
     world = world_info()[1]
     zero_l2 = None
+    wd = l2_loss_fn.wd if (fused and isinstance(l2_loss_fn, L2Loss)) else 0.0
+    no_reg = l2_loss_fn.no_reg_param_name if wd else None
     for batch_num, (int_x, cat_x, y) in enumerate(_agreed_batches(train_loader, train_batch_size, world, gpu)):
         t_data1 = time.time()
         on_dev = int_x.is_cuda and cat_x.is_cuda and y.is_cuda and (not isinstance(gpu, int) or int_x.device.index == gpu)
@@ -174,13 +197,17 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                 model.engine_bind_optimizer(optimizer)
                 bound = True
             group = optimizer.param_groups[0]
-            loss = model.engine_train_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value, eps=float(group["eps"]))
-            # the step's logits and the (zero) L2 term are only looked at on display steps: fetched there, not 3 900 times per epoch
+            if wd:
+                loss = model.engine_train_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value, eps=float(group["eps"]),
+                                               weight_decay=wd, no_reg_param_name=no_reg)
+            else:
+                loss = model.engine_train_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value, eps=float(group["eps"]))
+            # the step's logits and the L2 term are only looked at on display steps: fetched there, not 3 900 times per epoch
             # (`torch.zeros` is a fill launch on the GPU, `engine_last_logits` a plan lookup)
             res = None
             if zero_l2 is None:
                 zero_l2 = torch.zeros((), device=y.device)
-            l2_loss = zero_l2
+            l2_loss = None if wd else zero_l2
         else:
             optimizer.zero_grad()
             with torch.autocast("cuda", enabled=use_amp):
@@ -214,6 +241,8 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
         if batch_num % display_interval == 0 or last:
             if res is None:
                 res = model.engine_last_logits()
+            if l2_loss is None:
+                l2_loss = model.engine_last_l2()
             y_pred, y_true = res.detach(), y.detach()
             if any_rank(bool(torch.isnan(loss)), gpu):  # happens on KDD: report a diverged model (every rank leaves together)
                 print("Loss NaN. Exiting...")
