@@ -85,8 +85,12 @@ enum {
   NASREC_OP_FINAL_FUSED = 35,
   NASREC_OP_PERSIST = 36,
   NASREC_OP_WORKLIST_DEV = 38, /* (37 is taken by a layout-check slot of nasrec_desc_sizes) */
-  NASREC_OP_WEIGHT_DECAY = 39
+  NASREC_OP_WEIGHT_DECAY = 39,
+  NASREC_OP_OPT_MOMENTS = 40
 };
+
+/* algorithm of NASREC_OP_OPT_MOMENTS */
+enum { NASREC_OPTIM_ADAM = 1, NASREC_OPTIM_SGD = 2 };
 
 /* ------------------------------------------------------------------------------------------------
  * GEMM family.  C(i,j) = epilogue( sum_k A(i,k) * B(j,k) ).   Replaces every nn.Linear / LazyLinear
@@ -489,6 +493,62 @@ typedef struct nasrec_weight_decay_desc {
 } nasrec_weight_decay_desc_t;
 
 /* ------------------------------------------------------------------------------------------------
+ * Adam and momentum SGD of the fused step (torch.optim.Adam(lr, betas, eps): not amsgrad; torch.optim.SGD(lr, momentum, nesterov):
+ * dampening 0; neither with torch's own weight_decay).  g = the clipped gradient (g * coef; with get_l2_loss it includes 2 wd W):
+ *   Adam:  t = step + 1;  m = m + (1 - b1) (g - m);  v = b2 v + (1 - b2) g^2;
+ *          p = p - (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)        (bias corrections in fp64, from the device counter)
+ *   SGD:   buf = momentum buf + g;  d = nesterov ? g + momentum buf : buf;  p = p - lr d
+ * Unlike Adagrad a zero gradient still moves a parameter whose moments are non-zero, so every table row is updated every step.
+ * Two launches, 256-thread workgroups:
+ *   phase 0 (where NASREC_OP_OPT_APPLY runs for Adagrad): every workgroup computes the clip coefficient from `clip` (workgroup 0
+ *     writes clip.out); workgroups [0, dense_blocks) walk `chunks` — [offset, length, parameter] triples, one parameter per chunk —
+ *     over the dense arenas p / g / m / v; the rest take 64 (sample, field) pairs each: a leader row with its id in range gets the
+ *     optimizer with its summed gradient gsum, and its bit is set in `bitmap`.
+ *   phase 1 (behind phase 0): every row of every table whose bit is NOT set: the optimizer with g = 0, or g = 2 wd W * coef for a table
+ *     in reg_mask; the bitmap is left all zero.  g over zero_chunks ([offset, length] pairs) is set back to 0 (weight decay's unreached
+ *     regularised ranges).  The workgroup that finishes last adds 1 to the counters step[inc[i]] (counter: zero before, left zero).
+ * Tables are walked in tiles of 64 rows, tile_off over ALL tables: table f's bits are the words [2 tile_off[f], 2 tile_off[f+1]).
+ * Table f's step counter is step[table_step0 + f].  SGD: m = the momentum buffer, v / tv unused.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct nasrec_opt_moments_desc {
+  int32_t kind;  /* NASREC_OP_OPT_MOMENTS */
+  int32_t phase; /* 0 / 1 (above) */
+  int32_t algo;  /* NASREC_OPTIM_ADAM / NASREC_OPTIM_SGD */
+  int32_t nesterov;
+  int32_t dense_blocks; /* phase 0: workgroups on the dense chunks */
+  int32_t nblocks;      /* phase 1: workgroups */
+  int32_t B, Fs;        /* [B, Fs] id / leader arrays (B = 0: no touched rows) */
+  int32_t table_step0;
+  uint32_t reg_mask;    /* bit f: table f is regularised (phase 1's g = 2 wd W) */
+  float eps, momentum, wd, _pad;
+  double beta1, beta2;
+  nasrec_clip_coef_desc_t clip;
+  const int64_t* chunks; /* [nchunks, 3] */
+  int64_t nchunks;
+  float* p;
+  float* g;
+  float* m;
+  float* v;
+  const int64_t* idx;    /* [B,Fs] */
+  const int32_t* leader; /* [B,Fs] */
+  const float* gsum;     /* [B,Fs,16]: a leader's row holds its summed gradient */
+  float* table[NASREC_MAX_TABLES];
+  float* tm[NASREC_MAX_TABLES];
+  float* tv[NASREC_MAX_TABLES];
+  int64_t rows[NASREC_MAX_TABLES];
+  int64_t tile_off[NASREC_MAX_TABLES + 1];
+  uint32_t* bitmap;      /* [2 tile_off[Fs]] */
+  float* step;           /* per-parameter step counters */
+  const int64_t* inc;    /* phase 1: indices into step */
+  int64_t n_inc;
+  const int64_t* zero_chunks;
+  int64_t n_zero;
+  uint32_t* counter;
+  const float* lr;       /* device scalars */
+  const float* coef;     /* phase 1: clip.out of phase 0 */
+} nasrec_opt_moments_desc_t;
+
+/* ------------------------------------------------------------------------------------------------
  * The row-sparse embedding backward in two halves (round 5).  NASREC_OP_EMB_DEDUP above does everything behind the backward pass;
  * but which sample leads a row, and which samples repeat it, depends on the IDS only — known before the forward pass starts (one
  * GPU: when the batch is staged; N GPUs: when the ids all-gather lands, nasrec_amd/parallel.py).  So:
@@ -775,6 +835,7 @@ int nasrec_dedup_ids(void* stream, const nasrec_dedup_ids_desc_t* d);
 int nasrec_opt_reduce2(void* stream, const nasrec_opt_reduce2_desc_t* d);
 int nasrec_final_fused(void* stream, const nasrec_final_desc_t* d);
 int nasrec_weight_decay(void* stream, const nasrec_weight_decay_desc_t* d);
+int nasrec_opt_moments(void* stream, const nasrec_opt_moments_desc_t* d);
 int nasrec_worklist(void* stream, const nasrec_worklist_desc_t* d);
 
 /* Uncached device memory (hipExtMallocWithFlags(hipDeviceMallocUncached)): the plan arena of a persistent step (NASREC_OP_PERSIST) —

@@ -36,6 +36,8 @@ ACT_BY_NAME = {"identity": ACT_NONE, "relu": ACT_RELU, "silu": ACT_SILU}
  OP_OPT_REDUCE2, OP_FINAL_FUSED, OP_PERSIST) = range(1, 37)
 OP_WORKLIST_DEV = 38  # (37: a layout-check slot of nasrec_desc_sizes)
 OP_WEIGHT_DECAY = 39
+OP_OPT_MOMENTS = 40
+OPTIM_ADAM, OPTIM_SGD = 1, 2  # NASREC_OPTIM_* (algorithm of NASREC_OP_OPT_MOMENTS)
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -236,6 +238,16 @@ class WeightDecayDesc(C.Structure):
                 ("lr", vp), ("coef", vp)]
 
 
+class OptMomentsDesc(C.Structure):
+    _fields_ = [("kind", i32), ("phase", i32), ("algo", i32), ("nesterov", i32), ("dense_blocks", i32), ("nblocks", i32), ("B", i32),
+                ("Fs", i32), ("table_step0", i32), ("reg_mask", C.c_uint32), ("eps", f32), ("momentum", f32), ("wd", f32), ("_pad", f32),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("clip", ClipCoefDesc), ("chunks", vp), ("nchunks", i64), ("p", vp),
+                ("g", vp), ("m", vp), ("v", vp), ("idx", vp), ("leader", vp), ("gsum", vp), ("table", vp * MAX_TABLES),
+                ("tm", vp * MAX_TABLES), ("tv", vp * MAX_TABLES), ("rows", i64 * MAX_TABLES), ("tile_off", i64 * (MAX_TABLES + 1)),
+                ("bitmap", vp), ("step", vp), ("inc", vp), ("n_inc", i64), ("zero_chunks", vp), ("n_zero", i64), ("counter", vp),
+                ("lr", vp), ("coef", vp)]
+
+
 DESC_BY_KIND = {
     OP_GEMM: GemmDesc, OP_EMBED_GATHER: EmbedDesc, OP_DOT_TRI_FWD: DotTriDesc, OP_DOT_TRI_BWD: DotTriDesc, OP_FM_FWD: FmDesc,
     OP_FM_BWD: FmDesc, OP_MHA_FWD: MhaDesc, OP_MHA_BWD: MhaDesc, OP_REDUCE_ROWS: ReduceRowsDesc, OP_COPY_SEGS: CopySegsDesc,
@@ -245,7 +257,7 @@ DESC_BY_KIND = {
     OP_SCALE: ScaleDesc, OP_ACT_BWD: ActBwdDesc, OP_STAGE_INPUTS: StageDesc, OP_OPT_REDUCE: OptReduceDesc, OP_OPT_APPLY: OptApplyDesc,
     OP_WORKLIST: WorklistDesc, OP_CONST_I64: ConstI64Desc, OP_SPLITK_EPILOGUES: SplitkEpiloguesDesc, OP_DEDUP_IDS: DedupIdsDesc,
     OP_OPT_REDUCE2: OptReduce2Desc, OP_FINAL_FUSED: FinalDesc, OP_PERSIST: PersistDesc, OP_WORKLIST_DEV: WorklistDevDesc,
-    OP_WEIGHT_DECAY: WeightDecayDesc,
+    OP_WEIGHT_DECAY: WeightDecayDesc, OP_OPT_MOMENTS: OptMomentsDesc,
 }
 
 # every symbol include/nasrec_hip.h declares
@@ -256,7 +268,7 @@ SYMBOLS = [
     "nasrec_opt_apply", "nasrec_worklist", "nasrec_dedup_ids", "nasrec_opt_reduce2", "nasrec_final_fused", "nasrec_event_create",
     "nasrec_event_record", "nasrec_event_elapsed_ms", "nasrec_event_destroy", "nasrec_last_error", "nasrec_abi_version",
     "nasrec_desc_sizes", "nasrec_tsv_parse", "nasrec_alloc_uncached", "nasrec_free_uncached", "nasrec_persist_prepare", "nasrec_worklist_prepare",
-    "nasrec_weight_decay",
+    "nasrec_weight_decay", "nasrec_opt_moments",
 ]
 
 _lib = None
@@ -297,12 +309,13 @@ def load():
     lib.nasrec_tsv_parse.restype = i64
     for name in ("nasrec_gemm", "nasrec_embedding_gather", "nasrec_embedding_dedup", "nasrec_dot_tri", "nasrec_fm",
                  "nasrec_mha_ffn", "nasrec_layernorm", "nasrec_final_logit", "nasrec_bce_logits", "nasrec_adagrad_dense",
-                 "nasrec_adagrad_rows", "nasrec_opt_reduce", "nasrec_opt_apply", "nasrec_worklist", "nasrec_dedup_ids", "nasrec_opt_reduce2", "nasrec_final_fused", "nasrec_weight_decay"):
+                 "nasrec_adagrad_rows", "nasrec_opt_reduce", "nasrec_opt_apply", "nasrec_worklist", "nasrec_dedup_ids", "nasrec_opt_reduce2", "nasrec_final_fused", "nasrec_weight_decay",
+                 "nasrec_opt_moments"):
         getattr(lib, name).argtypes = [vp, vp]
     if lib.nasrec_abi_version() != 17:
         raise EngineError("ABI version mismatch: library %d, binding 17" % lib.nasrec_abi_version())
-    sizes = (i32 * 40)()
-    n = lib.nasrec_desc_sizes(sizes, 40)
+    sizes = (i32 * 41)()
+    n = lib.nasrec_desc_sizes(sizes, 41)
     for kind, cls in DESC_BY_KIND.items():
         if kind >= n or sizes[kind] != C.sizeof(cls):
             raise EngineError("struct layout mismatch for op kind %d: library %d bytes, binding %d bytes"

@@ -67,6 +67,7 @@ static int dispatch(hipStream_t st, const void* desc) {
     case NASREC_OP_DEDUP_IDS: return launch_dedup_ids(st, (const nasrec_dedup_ids_desc_t*)desc);
     case NASREC_OP_OPT_REDUCE2: return launch_opt_reduce2(st, (const nasrec_opt_reduce2_desc_t*)desc);
     case NASREC_OP_WEIGHT_DECAY: return launch_weight_decay(st, (const nasrec_weight_decay_desc_t*)desc);
+    case NASREC_OP_OPT_MOMENTS: return launch_opt_moments(st, (const nasrec_opt_moments_desc_t*)desc);
     default: return nasrec_set_error(-1, "unknown op kind %d", kind);
   }
 }
@@ -160,6 +161,7 @@ TYPED(nasrec_dedup_ids, nasrec_dedup_ids_desc_t, kind == NASREC_OP_DEDUP_IDS)
 TYPED(nasrec_opt_reduce2, nasrec_opt_reduce2_desc_t, kind == NASREC_OP_OPT_REDUCE2)
 TYPED(nasrec_final_fused, nasrec_final_desc_t, kind == NASREC_OP_FINAL_FUSED)
 TYPED(nasrec_weight_decay, nasrec_weight_decay_desc_t, kind == NASREC_OP_WEIGHT_DECAY)
+TYPED(nasrec_opt_moments, nasrec_opt_moments_desc_t, kind == NASREC_OP_OPT_MOMENTS)
 
 // Device memory that the XCDs' L2 caches do not hold (MTYPE uncached): plain stores go through to memory, and a plain load behind an
 // agent-scope acquire (buffer_inv sc1: the CU's L1) reads what another workgroup of the SAME launch stored — what the persistent step
@@ -251,6 +253,7 @@ int nasrec_desc_sizes(int32_t* out, int n) {
       (int32_t)sizeof(nasrec_persist_item_t),       // 37 (not an op: the item record of NASREC_OP_PERSIST, for the binding's layout check)
       (int32_t)sizeof(nasrec_worklist_dev_desc_t),  // 38
       (int32_t)sizeof(nasrec_weight_decay_desc_t),  // 39
+      (int32_t)sizeof(nasrec_opt_moments_desc_t),   // 40
   };
   const int total = (int)(sizeof(sizes) / sizeof(sizes[0]));
   int w = 0;

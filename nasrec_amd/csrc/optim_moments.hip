@@ -1,0 +1,211 @@
+// Adam and momentum SGD of the fused training step (NASREC_OP_OPT_MOMENTS, include/nasrec_hip.h): torch.optim.Adam / torch.optim.SGD
+// (main_train.py:150-160) on the dense arena and on EVERY table row.  Phase 0 takes the place of Adagrad's apply launch (clip
+// coefficient, dense chunks, the batch's touched rows, which it marks in a bitmap); phase 1 streams the untouched rows of every table
+// (a zero gradient still moves a row whose moments are non-zero: W and its one or two moment arrays, read and written once) and,
+// in the workgroup that finishes last, counts the step of every parameter it updated.
+#include "optimizer_bodies.h"
+
+namespace {
+
+// Adam's per-parameter scalars of this step, from the step counter as torch computes them in Python doubles (torch/optim/adam.py,
+// _multi_tensor_adam): step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t), t = step + 1
+__device__ __forceinline__ void adam_scalars(const nasrec_opt_moments_desc_t& d, float step, float lr, float& step_size, float& bc2_sqrt) {
+  const double t = (double)step + 1.0;
+  step_size = (float)((double)lr / (1.0 - pow(d.beta1, t)));
+  bc2_sqrt = (float)sqrt(1.0 - pow(d.beta2, t));
+}
+
+// one element; g = the clipped gradient.  The statements follow torch's foreach calls one by one (lerp_; mul_ + addcmul_; sqrt, div_,
+// add_; addcdiv_): -ffp-contract=on fuses within a statement only.
+template <int ALGO>
+__device__ __forceinline__ void moments_elem(const nasrec_opt_moments_desc_t& d, float g, float& p, float& m, float& v, float lr,
+                                             float step_size, float bc2_sqrt) {
+  if (ALGO == NASREC_OPTIM_ADAM) {
+    const float w1 = (float)(1.0 - d.beta1), b2 = (float)d.beta2, w2 = (float)(1.0 - d.beta2);
+    m = w1 < 0.5f ? m + w1 * (g - m) : g - (g - m) * (1.f - w1);  // (torch's lerp)
+    v = v * b2;
+    v = v + w2 * (g * g);
+    float den = sqrtf(v) / bc2_sqrt;
+    den = den + d.eps;
+    p = p + (-step_size) * (m / den);
+  } else {
+    m = m * d.momentum;
+    m = m + g;
+    float dir = m;
+    if (d.nesterov) dir = g + d.momentum * m;
+    p = p + (-lr) * dir;
+  }
+}
+
+template <int ALGO>
+__device__ __forceinline__ void moments_vec(const nasrec_opt_moments_desc_t& d, const f32x4& g, f32x4& p, f32x4& m, f32x4& v, float lr,
+                                            float ss, float bs) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float pe = p[e], me = m[e], ve = ALGO == NASREC_OPTIM_ADAM ? v[e] : 0.f;
+    moments_elem<ALGO>(d, g[e], pe, me, ve, lr, ss, bs);
+    p[e] = pe;
+    m[e] = me;
+    if (ALGO == NASREC_OPTIM_ADAM) v[e] = ve;
+  }
+}
+
+// per-table scalars into LDS (threads [first, first + Fs)); the caller synchronises
+template <int ALGO>
+__device__ __forceinline__ void table_scalars(const nasrec_opt_moments_desc_t& d, int first, float lr, float* ss, float* bs) {
+  const int f = (int)threadIdx.x - first;
+  if (ALGO == NASREC_OPTIM_ADAM && f >= 0 && f < d.Fs) adam_scalars(d, d.step[d.table_step0 + f], lr, ss[f], bs[f]);
+}
+
+template <int ALGO>
+__global__ __launch_bounds__(256) void opt_moments_phase0_kernel(const nasrec_opt_moments_desc_t d) {
+  __shared__ float sh_coef;
+  __shared__ float t_ss[NASREC_MAX_TABLES], t_bs[NASREC_MAX_TABLES];
+  const int tid = threadIdx.x, blk = blockIdx.x;
+  const float lr = *d.lr;
+  if (tid < 64) {
+    float total;
+    const float c = clip_coef_wave(d.clip, tid, &total);
+    if (tid == 0) {
+      sh_coef = c;
+      if (blk == 0) {
+        d.clip.out[0] = c;
+        d.clip.out[1] = total;
+      }
+    }
+  }
+  if (blk >= d.dense_blocks) table_scalars<ALGO>(d, 64, lr, t_ss, t_bs);
+  __syncthreads();
+  const float coef = sh_coef;
+  if (blk < d.dense_blocks) {
+    // dense arena: one parameter per chunk (its step counter), float4 pieces, then the chunk's tail
+    for (long c = blk; c < d.nchunks; c += d.dense_blocks) {
+      const long off = d.chunks[3 * c], n = d.chunks[3 * c + 1], k = d.chunks[3 * c + 2], n4 = n >> 2;
+      float ss = 0.f, bs = 1.f;
+      if (ALGO == NASREC_OPTIM_ADAM) adam_scalars(d, d.step[k], lr, ss, bs);
+      float* pp = d.p + off;
+      float* mp = d.m + off;
+      float* vp = ALGO == NASREC_OPTIM_ADAM ? d.v + off : nullptr;
+      const float* gp = d.g + off;
+      for (long i = tid; i < n4; i += 256) {
+        f32x4 g4 = *reinterpret_cast<const f32x4*>(gp + 4 * i);
+        f32x4 p4 = *reinterpret_cast<const f32x4*>(pp + 4 * i), m4 = *reinterpret_cast<const f32x4*>(mp + 4 * i), v4 = {};
+        if (ALGO == NASREC_OPTIM_ADAM) v4 = *reinterpret_cast<const f32x4*>(vp + 4 * i);
+        g4 *= coef;
+        moments_vec<ALGO>(d, g4, p4, m4, v4, lr, ss, bs);
+        *reinterpret_cast<f32x4*>(pp + 4 * i) = p4;
+        *reinterpret_cast<f32x4*>(mp + 4 * i) = m4;
+        if (ALGO == NASREC_OPTIM_ADAM) *reinterpret_cast<f32x4*>(vp + 4 * i) = v4;
+      }
+      for (long j = 4 * n4 + tid; j < n; j += 256) {
+        float pe = pp[j], me = mp[j], ve = ALGO == NASREC_OPTIM_ADAM ? vp[j] : 0.f;
+        moments_elem<ALGO>(d, gp[j] * coef, pe, me, ve, lr, ss, bs);
+        pp[j] = pe;
+        mp[j] = me;
+        if (ALGO == NASREC_OPTIM_ADAM) vp[j] = ve;
+      }
+    }
+    return;
+  }
+  // touched rows: 4 lanes x float4 per (sample, field) pair; the leader of a row id carries the row's summed gradient
+  const long t = (long)(blk - d.dense_blocks) * 256 + tid;
+  const long pair = t >> 2;
+  const int q = (int)(t & 3);
+  if (pair >= (long)d.B * d.Fs) return;
+  const int f = (int)(pair % d.Fs);
+  if (!d.leader[pair]) return;
+  const long row = d.idx[pair];
+  if (row < 0 || row >= d.rows[f]) return;  // (flagged by the gather; never written outside a table)
+  const long o = row * 16 + q * 4;
+  f32x4 g4 = *reinterpret_cast<const f32x4*>(d.gsum + pair * 16 + q * 4);
+  f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o), m4 = *reinterpret_cast<const f32x4*>(d.tm[f] + o), v4 = {};
+  if (ALGO == NASREC_OPTIM_ADAM) v4 = *reinterpret_cast<const f32x4*>(d.tv[f] + o);
+  g4 *= coef;
+  moments_vec<ALGO>(d, g4, p4, m4, v4, lr, ALGO == NASREC_OPTIM_ADAM ? t_ss[f] : 0.f, ALGO == NASREC_OPTIM_ADAM ? t_bs[f] : 1.f);
+  *reinterpret_cast<f32x4*>(d.table[f] + o) = p4;
+  *reinterpret_cast<f32x4*>(d.tm[f] + o) = m4;
+  if (ALGO == NASREC_OPTIM_ADAM) *reinterpret_cast<f32x4*>(d.tv[f] + o) = v4;
+  if (q == 0) atomicOr(d.bitmap + 2 * d.tile_off[f] + (row >> 5), 1u << (row & 31));  // (a set of bits: no value depends on the order)
+}
+
+// phase 1's row update: the optimizer with g = 0, or g = 2 wd W * coef on a regularised table (untouched_rows_pass, optimizer_bodies.h)
+template <int ALGO>
+struct MomentRows {
+  const nasrec_opt_moments_desc_t& d;
+  const float lr, coef, two_r;
+  const float* ss;
+  const float* bs;
+  f32x4 w[TABLE_PASS_UNROLL], m[TABLE_PASS_UNROLL], v[TABLE_PASS_UNROLL];
+  __device__ __forceinline__ void load(int u, int f, long off) {
+    w[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(d.table[f] + off));
+    m[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(d.tm[f] + off));
+    if (ALGO == NASREC_OPTIM_ADAM) v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(d.tv[f] + off));
+  }
+  __device__ __forceinline__ void update(int u, int f, long off) {
+    f32x4 g = {0.f, 0.f, 0.f, 0.f};
+    if ((d.reg_mask >> f) & 1u) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) g[e] = (two_r * w[u][e]) * coef;
+    }
+    moments_vec<ALGO>(d, g, w[u], m[u], v[u], lr, ALGO == NASREC_OPTIM_ADAM ? ss[f] : 0.f, ALGO == NASREC_OPTIM_ADAM ? bs[f] : 1.f);
+    __builtin_nontemporal_store(w[u], reinterpret_cast<f32x4*>(d.table[f] + off));
+    __builtin_nontemporal_store(m[u], reinterpret_cast<f32x4*>(d.tm[f] + off));
+    if (ALGO == NASREC_OPTIM_ADAM) __builtin_nontemporal_store(v[u], reinterpret_cast<f32x4*>(d.tv[f] + off));
+  }
+};
+
+template <int ALGO>
+__global__ __launch_bounds__(256) void opt_moments_phase1_kernel(const nasrec_opt_moments_desc_t d) {
+  __shared__ float t_ss[NASREC_MAX_TABLES], t_bs[NASREC_MAX_TABLES];
+  __shared__ int last;
+  const int tid = threadIdx.x, blk = blockIdx.x, nblk = d.nblocks;
+  const float lr = *d.lr, coef = *d.coef, two_r = 2.f * d.wd;
+  table_scalars<ALGO>(d, 0, lr, t_ss, t_bs);
+  // weight decay's unreached regularised ranges: their gradient (g = 2 wd W, read by phase 0) goes back to zero
+  for (long c = blk; c < d.n_zero; c += nblk) {
+    const long off = d.zero_chunks[2 * c], n = d.zero_chunks[2 * c + 1];
+    for (long i = tid; i < n; i += 256) d.g[off + i] = 0.f;
+  }
+  __syncthreads();
+  MomentRows<ALGO> r{d, lr, coef, two_r, t_ss, t_bs};
+  untouched_rows_pass(d.tile_off, d.rows, d.Fs, d.bitmap, blk, nblk, r);
+  // the step counters move once every workgroup has read them (phase 0 read them in the launch before)
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence();
+    last = atomicAdd(d.counter, 1u) == (unsigned)(nblk - 1);
+  }
+  __syncthreads();
+  if (!last) return;
+  __threadfence();
+  for (long i = tid; i < d.n_inc; i += 256) d.step[d.inc[i]] += 1.f;
+  if (tid == 0) *d.counter = 0u;
+}
+
+template <int ALGO>
+int launch_phases(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
+  if (d->phase == 0) {
+    const long threads = (long)d->B * d->Fs * 4;
+    const int nrows = (int)((threads + 255) / 256);
+    if (d->dense_blocks < 0 || d->dense_blocks + nrows < 1) return nasrec_set_error(-2, "opt_moments: empty launch");
+    if (nrows > 0 && (!d->idx || !d->leader || !d->gsum || !d->bitmap)) return nasrec_set_error(-1, "opt_moments: row inputs missing");
+    hipLaunchKernelGGL(opt_moments_phase0_kernel<ALGO>, dim3((unsigned)(d->dense_blocks + nrows)), dim3(256), 0, st, *d);
+  } else if (d->phase == 1) {
+    if (d->nblocks <= 0) return nasrec_set_error(-1, "opt_moments: nblocks must be positive");
+    if (!d->bitmap || !d->counter || !d->coef) return nasrec_set_error(-1, "opt_moments: phase 1 inputs missing");
+    hipLaunchKernelGGL(opt_moments_phase1_kernel<ALGO>, dim3((unsigned)d->nblocks), dim3(256), 0, st, *d);
+  } else {
+    return nasrec_set_error(-1, "opt_moments: phase %d", d->phase);
+  }
+  return nasrec_check_launch("opt_moments");
+}
+
+}  // namespace
+
+int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
+  if (d->Fs < 0 || d->Fs > NASREC_MAX_TABLES) return nasrec_set_error(-1, "opt_moments: Fs = %d", d->Fs);
+  if (!d->lr || !d->step) return nasrec_set_error(-1, "opt_moments: lr / step missing");
+  if (d->algo == NASREC_OPTIM_ADAM) return launch_phases<NASREC_OPTIM_ADAM>(st, d);
+  if (d->algo == NASREC_OPTIM_SGD) return launch_phases<NASREC_OPTIM_SGD>(st, d);
+  return nasrec_set_error(-1, "opt_moments: algo %d", d->algo);
+}

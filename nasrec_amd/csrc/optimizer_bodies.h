@@ -180,3 +180,61 @@ static inline int adagrad_dense_blocks(long n) {
   long blocks = (n + 255) / 256;
   return (int)(blocks > 2048 ? 2048 : blocks);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// The untouched-row pass over the embedding tables (weight decay's phase 1 under Adagrad, csrc/weight_decay.hip; Adam / SGD's
+// phase 1, csrc/optim_moments.hip).  Tables are walked in tiles of 64 rows (256 threads x one float4: thread `tid` takes row
+// tid / 4, quarter tid % 4), the tiles of the tables that take part numbered consecutively: table f owns tiles
+// [tile_off[f], tile_off[f+1]) and the bits [2 tile_off[f], 2 tile_off[f+1]) words of `bitmap` (bit row & 31 of word
+// 2 tile_off[f] + row / 32).  Each workgroup takes TABLE_PASS_UNROLL tiles per trip; a row whose bit is NOT set is handed to
+// `rows.load(u, f, offset)` (all loads of the trip in flight together), then to `rows.update(u, f, offset)`; the bitmap is left all zero.
+// ---------------------------------------------------------------------------------------------------
+constexpr int TABLE_PASS_TILE = 64;
+constexpr int TABLE_PASS_UNROLL = 4;
+
+// table of tile t (tile_off ascending; a table outside the pass owns no tile)
+__device__ __forceinline__ int table_of_tile(const int64_t* tile_off, int Fs, long t) {
+  int f = 0;
+  while (f + 1 < Fs && tile_off[f + 1] <= t) ++f;
+  return f;
+}
+
+template <class Rows>
+__device__ __forceinline__ void untouched_rows_pass(const int64_t* tile_off, const int64_t* rows, int Fs, uint32_t* bitmap, int blk, int nblk,
+                                                    Rows& r) {
+  const int tid = threadIdx.x, sub = tid >> 2, q = tid & 3;
+  const long ntiles = tile_off[Fs];
+  for (long t0 = blk; t0 < ntiles; t0 += (long)nblk * TABLE_PASS_UNROLL) {
+    long off[TABLE_PASS_UNROLL];
+    int tf[TABLE_PASS_UNROLL];
+    uint32_t* word[TABLE_PASS_UNROLL];
+    uint32_t bits[TABLE_PASS_UNROLL];
+    bool ok[TABLE_PASS_UNROLL];
+#pragma unroll
+    for (int u = 0; u < TABLE_PASS_UNROLL; ++u) {
+      const long t = t0 + (long)u * nblk;
+      ok[u] = false;
+      word[u] = nullptr;
+      bits[u] = 0u;
+      if (t < ntiles) {
+        const int f = table_of_tile(tile_off, Fs, t);
+        const long row = (t - tile_off[f]) * TABLE_PASS_TILE + sub;
+        word[u] = bitmap + 2 * t + (sub >> 5);  // (2 words per tile: 2 tile_off[f] + row / 32)
+        bits[u] = *word[u];
+        if (row < rows[f] && !((bits[u] >> (row & 31)) & 1u)) {
+          ok[u] = true;
+          tf[u] = f;
+          off[u] = row * 16 + q * 4;
+          r.load(u, f, off[u]);
+        }
+      }
+    }
+    __syncthreads();  // every thread has read its word: the first thread of each word's 32 rows clears it
+#pragma unroll
+    for (int u = 0; u < TABLE_PASS_UNROLL; ++u)
+      if ((tid & 127) == 0 && bits[u] != 0u) *word[u] = 0u;
+#pragma unroll
+    for (int u = 0; u < TABLE_PASS_UNROLL; ++u)
+      if (ok[u]) r.update(u, tf[u], off[u]);
+  }
+}

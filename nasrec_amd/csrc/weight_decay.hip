@@ -2,19 +2,15 @@
 // (train_utils.py:91-115) on the dense arena and on EVERY table row.  Phase 0 adds it where the backward left gradients and collects
 // what the clip norm gains; phase 1, behind the Adagrad of the touched rows, streams the untouched rows of the tables (W and its state,
 // read and written once: the bandwidth-bound part of a step with weight decay).
-#include "common.h"
+#include "optimizer_bodies.h"
 
 namespace {
 
-constexpr int kTile = 64;  // rows per tile: 256 threads x one float4 = 64 rows of 16 floats
-constexpr int kUnroll = 4; // tiles per workgroup and trip (four independent 16-byte loads in flight per thread)
+constexpr int kTile = TABLE_PASS_TILE;     // rows per tile: 256 threads x one float4 = 64 rows of 16 floats
+constexpr int kUnroll = TABLE_PASS_UNROLL; // tiles per workgroup and trip (four independent 16-byte loads in flight per thread)
 
 // table of tile t (tile_off ascending; tables outside reg_mask own no tile)
-__device__ __forceinline__ int tile_table(const nasrec_weight_decay_desc_t& d, long t) {
-  int f = 0;
-  while (f + 1 < d.Fs && d.tile_off[f + 1] <= t) ++f;
-  return f;
-}
+__device__ __forceinline__ int tile_table(const nasrec_weight_decay_desc_t& d, long t) { return table_of_tile(d.tile_off, d.Fs, t); }
 
 // fixed-order tree over the workgroup: every thread's pair (a, b) -> thread 0
 __device__ __forceinline__ void block_sum2(double& a, double& b, double* red) {
@@ -136,6 +132,28 @@ __global__ __launch_bounds__(256) void weight_decay_phase0_kernel(const nasrec_w
   }
 }
 
+// phase 1's row update: Adagrad with g = 2 wd W * coef (untouched_rows_pass, optimizer_bodies.h)
+struct AdagradDecayRows {
+  const nasrec_weight_decay_desc_t& d;
+  const float lr, coef, two_r, eps;
+  f32x4 w[TABLE_PASS_UNROLL], st[TABLE_PASS_UNROLL];
+  __device__ __forceinline__ void load(int u, int f, long off) {
+    w[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(d.table[f] + off));
+    st[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(d.state[f] + off));
+  }
+  __device__ __forceinline__ void update(int u, int f, long off) {
+    f32x4 p = w[u], s = st[u];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float g = (two_r * p[e]) * coef;
+      s[e] = fmaf(g, g, s[e]);
+      p[e] = p[e] - lr * (g / (sqrtf(s[e]) + eps));
+    }
+    __builtin_nontemporal_store(s, reinterpret_cast<f32x4*>(d.state[f] + off));
+    __builtin_nontemporal_store(p, reinterpret_cast<f32x4*>(d.table[f] + off));
+  }
+};
+
 __global__ __launch_bounds__(256) void weight_decay_phase1_kernel(const nasrec_weight_decay_desc_t d) {
   const int tid = threadIdx.x, blk = blockIdx.x, nblk = d.nblocks;
   // the set chunks' gradient (phase 0's g = 2 wd W, read by the apply launch) goes back to zero: the backward never writes those ranges,
@@ -144,54 +162,8 @@ __global__ __launch_bounds__(256) void weight_decay_phase1_kernel(const nasrec_w
     const long off = d.set_chunks[2 * c], n = d.set_chunks[2 * c + 1];
     for (long i = tid; i < n; i += 256) d.g[off + i] = 0.f;
   }
-  const float lr = *d.lr, coef = *d.coef, two_r = 2.f * d.wd, eps = d.eps;
-  const long ntiles = d.tile_off[d.Fs];
-  const int sub = tid >> 2, q = tid & 3;
-  for (long t0 = blk; t0 < ntiles; t0 += (long)nblk * kUnroll) {
-    f32x4 w[kUnroll], st[kUnroll];
-    float* wp[kUnroll];
-    float* sp[kUnroll];
-    uint32_t* word[kUnroll];
-    uint32_t bits[kUnroll];
-    bool ok[kUnroll];
-#pragma unroll
-    for (int u = 0; u < kUnroll; ++u) {
-      const long t = t0 + (long)u * nblk;
-      ok[u] = false;
-      word[u] = nullptr;
-      bits[u] = 0u;
-      if (t < ntiles) {
-        const int f = tile_table(d, t);
-        const long row = (t - d.tile_off[f]) * kTile + sub;
-        word[u] = d.bitmap + 2 * t + (sub >> 5);  // (2 words per tile: 2 tile_off[f] + row / 32)
-        bits[u] = *word[u];
-        if (row < d.rows[f] && !((bits[u] >> (row & 31)) & 1u)) {
-          ok[u] = true;
-          wp[u] = d.table[f] + row * 16 + q * 4;
-          sp[u] = d.state[f] + row * 16 + q * 4;
-          w[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(wp[u]));
-          st[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(sp[u]));
-        }
-      }
-    }
-    __syncthreads();  // every thread has read its word: the first thread of each word's 32 rows clears it
-#pragma unroll
-    for (int u = 0; u < kUnroll; ++u)
-      if ((tid & 127) == 0 && bits[u] != 0u) *word[u] = 0u;
-#pragma unroll
-    for (int u = 0; u < kUnroll; ++u) {
-      if (!ok[u]) continue;
-      f32x4 p = w[u], s = st[u];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float g = (two_r * p[e]) * coef;
-        s[e] = fmaf(g, g, s[e]);
-        p[e] = p[e] - lr * (g / (sqrtf(s[e]) + eps));
-      }
-      __builtin_nontemporal_store(s, reinterpret_cast<f32x4*>(sp[u]));
-      __builtin_nontemporal_store(p, reinterpret_cast<f32x4*>(wp[u]));
-    }
-  }
+  AdagradDecayRows r{d, *d.lr, *d.coef, 2.f * d.wd, d.eps};
+  untouched_rows_pass(d.tile_off, d.rows, d.Fs, d.bitmap, blk, nblk, r);
 }
 
 }  // namespace

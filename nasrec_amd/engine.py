@@ -362,27 +362,34 @@ class SupernetEngine:
     @_on_device
     def compile(self, choice, B: int, train: bool, clip: Optional[float] = 5.0, eps: float = 1e-2, graph: bool = False,
                 grad_scale: Optional[float] = None, defer_dw: bool = True, row_grad_out: Optional[torch.Tensor] = None,
-                local_optimizer: bool = True, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None) -> CompiledPlan:
+                local_optimizer: bool = True, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None,
+                optim=None) -> CompiledPlan:
         """row_grad_out: storage [B * Fs * 16] the backward writes the per-sample embedding-row gradients into (a data-parallel step
         hands in the head of its all-gather send buffer: no copy between the backward and the exchange); local_optimizer = False: the
         plan gets no clip + Adagrad program of its own (a data-parallel step runs its optimizer over the GLOBAL batch).
-        weight_decay != 0: the training step adds get_l2_loss(model, weight_decay, no_reg_param_name)'s gradient (_weight_decay_descs)"""
+        weight_decay != 0: the training step adds get_l2_loss(model, weight_decay, no_reg_param_name)'s gradient (_weight_decay_descs).
+        optim: None = Adagrad (eps); an OptimSpec (nasrec_amd/optim_spec.py) of kind adam / sgd = that optimizer (_moments_descs)"""
         rgo = row_grad_out.data_ptr() if row_grad_out is not None else None
         weight_decay = float(weight_decay or 0.0)
         wd_key = (weight_decay, no_reg_param_name) if weight_decay else None
         if weight_decay and not (train and local_optimizer):
             raise L.EngineError("weight decay is part of the fused training step's optimizer: it needs train=True, local_optimizer=True")
-        fast = (id(choice), B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, wd_key)
+        mom = tuple(optim) if optim is not None else None
+        if mom is not None and not (train and local_optimizer):
+            raise L.EngineError("Adam / SGD are the fused training step's optimizer: they need train=True, local_optimizer=True")
+        fast = (id(choice), B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, wd_key, mom)
         hit = self._last_plan
         if self.cfg.fixed and hit is not None and hit[0] == fast and hit[1] is choice:  # fixed sub-network, same choice object: skip the JSON key
             return hit[2]
-        key = json.dumps([choice, B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, wd_key], sort_keys=True, default=_jsonable)
+        key = json.dumps([choice, B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, wd_key, mom], sort_keys=True,
+                         default=_jsonable)
         if key in self._plans:
             self._last_plan = (fast, choice, self._plans[key])
             return self._plans[key]
         arena = None
         # (weight decay: the default launches — the persistent step is an opt-in that has not been built for it)
-        persist = bool(self.persist and self.level_schedule and self.cfg.fixed and B <= 256 and train and local_optimizer and not weight_decay)
+        persist = bool(self.persist and self.level_schedule and self.cfg.fixed and B <= 256 and train and local_optimizer and not weight_decay
+                       and mom is None)
         if self.cfg.fixed and B <= 256 and train and self.level_schedule and (_UC_ARENA or persist):
             arena = Arena(self.device, uncached=True)  # (see _UC_ARENA; the persistent step needs it whatever the knob says)
         if not self.cfg.fixed:
@@ -412,6 +419,7 @@ class SupernetEngine:
             cp = CompiledPlan()
             cp.arena, cp.evicted = arena, False
             cp.wd, cp.no_reg = weight_decay, no_reg_param_name
+            cp.mom = optim
             ctx = P.Ctx(B, self.device, self.params, self.grads, shape_only=False, train=train)
             ctx.sk_workspace = self._sk_workspace
             # parked weight-gradient batches are for one-launch-per-operator plans; the level scheduler places the products itself
@@ -476,7 +484,8 @@ class SupernetEngine:
             cp.fwd_levels = cp.bwd_levels = None
             cp.dead_forward = []
             if train:  # (the backward program decides which forward results are read: built further down, before the packing)
-                self._ensure_table_state()
+                if optim is None:  # (Adagrad's table state: Adam / SGD keep theirs in `moments` instead)
+                    self._ensure_table_state()
                 self._build_training_tail(cp, ctx, w, bptr, fsegs, B, K, grad_scale)
             fwd_list = list(ctx.fwd)
             if self.dead_code_elimination and cfg.fixed:
@@ -713,6 +722,8 @@ class SupernetEngine:
                 self.stream.synchronize()  # (the descriptors carry the values: they must outlive their launches)
         if cp.wd:
             self._weight_decay_tables(cp, ctx, arena, pre)
+        if cp.mom is not None:
+            self._moments_tables(cp, ctx, arena, pre)
         cp.bce, cp._pre = bd, pre
 
     WD_BLOCKS = 2048  # workgroups of the two weight-decay launches (8 per CU: the table pass is a stream over W and its state)
@@ -750,14 +761,138 @@ class SupernetEngine:
         if cp.chunk_tab is None:
             cp.chunk_tab, cp.nchunks = tab[off - len(parts[3]):off], ptrs[3][1]
         cp.wd_tab = tab
-        if getattr(self, "_wd_bitmap", None) is None:  # engine-wide: every plan leaves it all zero behind its step
-            words = sum(2 * ((n + 63) // 64) for n in self.num_embeddings)
+        self._row_bitmap()
+        if getattr(self, "_wd_part", None) is None:
             with torch.cuda.stream(self.stream):
-                self._wd_bitmap = torch.zeros(max(1, words), dtype=torch.int32, device=self.device)
                 self._wd_part = torch.zeros(2 * self.WD_BLOCKS, dtype=torch.float64, device=self.device)
                 self._wd_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
                 self.wd_l2_sumsq = torch.zeros(1, dtype=torch.float64, device=self.device)
             self.stream.synchronize()
+
+    def _row_bitmap(self, sink: bool = False):
+        """engine-wide bitmap of touched table rows, 64-row tiles (csrc/weight_decay.hip, csrc/optim_moments.hip): every plan leaves it
+        all zero behind its step.  sink: one of the same size that is written and never read"""
+        name = "_wd_sink" if sink else "_wd_bitmap"
+        t = getattr(self, name, None)
+        if t is None:
+            words = sum(2 * ((n + 63) // 64) for n in self.num_embeddings)
+            with torch.cuda.stream(self.stream):
+                t = torch.zeros(max(1, words), dtype=torch.int32, device=self.device)
+            self.stream.synchronize()
+            setattr(self, name, t)
+        return t
+
+    def ensure_moments_state(self, kind: str):
+        """Adam's exp_avg / exp_avg_sq or SGD's momentum_buffer for the dense arena (flat, the layout of flat_p) and for every table,
+        allocated on first use, zero; and the per-parameter step counters (dense parameters in dense_names order, then the tables).
+        -> {state key: (flat arena, [table arrays])}"""
+        keys = ("exp_avg", "exp_avg_sq") if kind == "adam" else ("momentum_buffer",)
+        st = self.__dict__.setdefault("moments", {})
+        with torch.cuda.stream(self.stream):
+            for k in keys:
+                if k not in st:
+                    st[k] = (torch.zeros(self.flat_numel, dtype=torch.float32, device=self.device), [torch.zeros_like(t) for t in self.tables])
+            if getattr(self, "opt_steps", None) is None:
+                self.opt_steps = torch.zeros(len(self.dense_names) + self.Fs, dtype=torch.float32, device=self.device)
+                self._mom_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
+                self.param_index = {n: i for i, n in enumerate(self.dense_names)}
+                for f in range(self.Fs):
+                    self.param_index["_embedding.%d.weight" % f] = len(self.dense_names) + f
+        self.stream.synchronize()
+        return {k: st[k] for k in keys}
+
+    def moments_view(self, key: str, name: str):
+        """engine storage of moment `key` of parameter `name` (shape of the parameter)"""
+        flat, tabs = self.moments[key]
+        if name.startswith("_embedding."):
+            return tabs[int(name.split(".")[1])]
+        o, n = self.offsets[name], self.params[name].numel()
+        return flat[o:o + n].view(self.params[name].shape)
+
+    MOM_CHUNK = 1024  # elements per dense chunk of the Adam / SGD launch (one parameter per chunk)
+
+    def _moments_tables(self, cp, ctx, arena, pre):
+        """Chunk table of a plan with Adam / SGD (csrc/optim_moments.hip): [offset, length, parameter] triples over the parameters the
+        step updates — the reached ones (torch skips grad = None) plus, with weight decay, the regularised ones — then the step-counter
+        indices of those parameters and of the tables that move: all of them when the path's backward reaches the embedding stem, else
+        (grad None in torch) only the regularised ones with weight decay, none without.  Always a table: unlike Adagrad, g = 0 is not a
+        no-op."""
+        if self.host_embedding:
+            raise L.EngineError("Adam / SGD in the fused step need the embedding tables on the device")
+        self.ensure_moments_state(cp.mom.kind)
+        names = [n for n in list(ctx.grad_params) + ["_final.weight", "_final.bias"] if not n.startswith("_embedding.")]
+        if cp.wd:
+            names += P.regularised(self.shapes, cp.no_reg)[0]
+        names = list(dict.fromkeys(names))
+        trip = []
+        for n in names:
+            off, cnt, k = self.offsets[n], self.params[n].numel(), self.param_index[n]
+            for o in range(0, cnt, self.MOM_CHUNK):
+                trip += [off + o, min(self.MOM_CHUNK, cnt - o), k]
+        if cp.sparse0.grad_written:
+            cp.mom_tables = list(range(self.Fs))
+        else:
+            cp.mom_tables = sorted(cp.wd_tables) if cp.wd else []
+        inc = [self.param_index[n] for n in names] + [len(self.dense_names) + f for f in cp.mom_tables]
+        flat = trip + inc
+        tab = (arena.alloc(len(flat), torch.int64).tensor() if (arena is not None and not self.cfg.fixed)
+               else torch.empty(len(flat), dtype=torch.int64, device=self.device))
+        if not self.cfg.fixed:
+            pre += P.const_i64_descs(tab.data_ptr(), flat)  # (the slot's arena is reused by other paths: written every step)
+        else:
+            lib = L.load()
+            for dsc in P.const_i64_descs(tab.data_ptr(), flat):
+                L.check(lib.nasrec_launch(self.stream.cuda_stream, C.addressof(dsc)))
+            self.stream.synchronize()
+        cp.mom_tab = tab
+        cp.mom_chunks = (tab.data_ptr(), len(trip) // 3)
+        cp.mom_inc = (tab.data_ptr() + 8 * len(trip), len(inc))
+        cp.mom_names = names
+
+    def _moments_descs(self, cp, Bg, cat_x, gsum, clip_desc):
+        """the two NASREC_OP_OPT_MOMENTS launches of a plan with Adam / SGD: (phase 0 in place of the Adagrad apply launch, phase 1)"""
+        o = cp.mom
+        st = self.moments
+        m = L.OptMomentsDesc()
+        m.kind, m.phase = L.OP_OPT_MOMENTS, 0
+        m.algo = L.OPTIM_ADAM if o.kind == "adam" else L.OPTIM_SGD
+        m.nesterov = int(bool(o.nesterov))
+        m.dense_blocks = min(2048, cp.mom_chunks[1])
+        m.nblocks = self.WD_BLOCKS if cp.mom_tables else 1  # (no table moves: phase 1 only counts the step and restores g)
+        m.B, m.Fs = (Bg, self.Fs) if gsum is not None else (0, self.Fs)
+        m.table_step0 = len(self.dense_names)
+        m.eps, m.momentum, m.wd = o.eps, o.momentum, cp.wd
+        m.beta1, m.beta2 = o.beta1, o.beta2
+        m.clip = clip_desc
+        m.chunks, m.nchunks = cp.mom_chunks
+        m.p, m.g = self.flat_p.data_ptr(), self.flat_g.data_ptr()
+        first, second = (st["exp_avg"], st["exp_avg_sq"]) if o.kind == "adam" else (st["momentum_buffer"], None)
+        m.m = first[0].data_ptr()
+        m.v = second[0].data_ptr() if second is not None else None
+        if gsum is not None:
+            m.idx, m.leader, m.gsum = cat_x.data_ptr(), cp.leader.data_ptr(), gsum
+        mask, t = 0, 0
+        for f in range(self.Fs):
+            m.table[f], m.tm[f], m.rows[f] = self.tables[f].data_ptr(), first[1][f].data_ptr(), self.num_embeddings[f]
+            if second is not None:
+                m.tv[f] = second[1][f].data_ptr()
+            m.tile_off[f] = t
+            if f in cp.mom_tables:  # (a table that does not move owns no tile: phase 1 leaves it alone)
+                t += (self.num_embeddings[f] + 63) // 64
+            if cp.wd and f in cp.wd_tables:
+                mask |= 1 << f
+        m.tile_off[self.Fs] = t
+        m.reg_mask = mask
+        m.bitmap = self._row_bitmap().data_ptr()
+        m.step = self.opt_steps.data_ptr()
+        m.inc, m.n_inc = cp.mom_inc
+        if cp.wd:
+            m.zero_chunks, m.n_zero = cp.wd_set
+        m.counter = self._mom_counter.data_ptr()
+        m.lr, m.coef = self.lr_dev.data_ptr(), self.clip_out.data_ptr()
+        m1 = L.OptMomentsDesc.from_buffer_copy(m)
+        m1.phase = 1
+        return [m, m1]
 
     def _weight_decay_descs(self, cp, Bg, cat_x, gsum, eps, clip_partial):
         """the two NASREC_OP_WEIGHT_DECAY launches of a plan: (phase 0, in front of the clip; phase 1, behind the touched rows' Adagrad)"""
@@ -769,14 +904,20 @@ class SupernetEngine:
             w.idx, w.leader, w.gsum = cat_x.data_ptr(), cp.leader.data_ptr(), gsum
         mask, t = 0, 0
         for f in range(self.Fs):
-            w.table[f], w.state[f], w.rows[f] = self.tables[f].data_ptr(), self.table_state[f].data_ptr(), self.num_embeddings[f]
+            w.table[f], w.rows[f] = self.tables[f].data_ptr(), self.num_embeddings[f]
+            if self.table_state is not None:  # (read by phase 1 only, which Adam / SGD plans do not launch)
+                w.state[f] = self.table_state[f].data_ptr()
             w.tile_off[f] = t
             if f in cp.wd_tables:
                 mask |= 1 << f
                 t += (self.num_embeddings[f] + 63) // 64
         w.tile_off[self.Fs] = t
         w.reg_mask = mask
-        w.bitmap = self._wd_bitmap.data_ptr()
+        w.bitmap = self._row_bitmap().data_ptr()
+        if getattr(cp, "mom", None) is not None and mask != (1 << self.Fs) - 1:
+            # Adam / SGD mark the touched rows of EVERY table, in a layout over all tables: phase 0's marks (over the regularised
+            # tables) would land on other rows' bits there, so they go to a bitmap nobody reads
+            w.bitmap = self._row_bitmap(sink=True).data_ptr()
         w.p, w.g = self.flat_p.data_ptr(), self.flat_g.data_ptr()
         (w.add_chunks, w.n_add), (w.set_chunks, w.n_set) = cp.wd_add, cp.wd_set
         w.block_part, w.counter = self._wd_part.data_ptr(), self._wd_counter.data_ptr()
@@ -827,6 +968,9 @@ class SupernetEngine:
         cc.max_norm = float(clip) if clip is not None else 0.0
         cc.partial_a, cc.partial_b, cc.out = cp.dense_partial.data_ptr(), cp.emb_partial.data_ptr(), self.clip_out.data_ptr()
         wd = getattr(cp, "wd", 0.0)
+        mom = getattr(cp, "mom", None)
+        if mom is not None and rank_layout:
+            raise L.EngineError("Adam / SGD in the fused step cover one process (data-parallel runs take the torch route)")
         if wd:
             if rank_layout:
                 raise L.EngineError("weight decay: the fused step covers one process (data-parallel runs take the torch route)")
@@ -850,7 +994,7 @@ class SupernetEngine:
             ar.idx, ar.leader, ar.gsum = cat_x.data_ptr(), cp.leader.data_ptr(), cp.gsum.data_ptr()
             for f in range(self.Fs):
                 ar.table[f] = self.tables[f].data_ptr()
-                ar.state[f] = self.table_state[f].data_ptr()
+                ar.state[f] = self.table_state[f].data_ptr() if self.table_state is not None else None  # (None: an Adam / SGD plan)
                 ar.rows[f] = self.num_embeddings[f]
             ar.lr, ar.coef = self.lr_dev.data_ptr(), self.clip_out.data_ptr()
             descs.append(ar)
@@ -893,12 +1037,27 @@ class SupernetEngine:
                 app.clip.partial_b, app.clip.n_b = cp.emb_partial2.data_ptr(), self.Fs + row_blocks
                 app.rows.gsum = sparse_grad.data_ptr()  # summed in place: a leader's row holds its sum
                 app.rows.rank_B, app.rows.rank_stride = r2.rank_B, r2.rank_stride
+                if mom is not None:
+                    tail = self._moments_descs(cp, Bg, cat_x, sparse_grad.data_ptr(), app.clip)
+                    if wd:
+                        return [r2, self._weight_decay_descs(cp, Bg, cat_x, sparse_grad.data_ptr(), eps, wd_part)[0]] + tail
+                    return [r2] + tail
                 if wd:
                     w0, w1 = self._weight_decay_descs(cp, Bg, cat_x, sparse_grad.data_ptr(), eps, wd_part)
                     return [r2, w0, app, w1]
                 return [r2, app]
             if rank_layout:  # (the one-launch kernels read the rows where the all-gather left them; their sums go to the contiguous gsum)
                 dd.rank_B, dd.rank_stride = rank_layout
+            if mom is not None:  # (the reduce launches as for Adagrad; Adam / SGD in place of the apply launch)
+                red = [dd, sq]
+                if Bg <= 256:
+                    red = L.OptReduceDesc()
+                    red.kind = L.OP_OPT_REDUCE
+                    red.dedup, red.sumsq = dd, sq
+                    red = [red]
+                if wd:
+                    red.append(self._weight_decay_descs(cp, Bg, cat_x, cp.gsum.data_ptr(), eps, wd_part)[0])
+                return red + self._moments_descs(cp, Bg, cat_x, cp.gsum.data_ptr(), app.clip)
             if Bg <= 256:
                 # the five launches collapse into the two that the grid-wide dependencies require
                 red = L.OptReduceDesc()
@@ -912,6 +1071,11 @@ class SupernetEngine:
                 w0, w1 = self._weight_decay_descs(cp, Bg, cat_x, cp.gsum.data_ptr(), eps, wd_part)
                 return [dd, sq, w0, app, w1]
             return [dd, sq, app]  # global batch of a data-parallel step: chunked dedup + merge (two launches), then the same apply
+        if mom is not None:  # (no gradient reaches the embedding stem: no touched rows)
+            descs = [sq]
+            if wd:
+                descs.append(self._weight_decay_descs(cp, Bg, cat_x, None, eps, wd_part)[0])
+            return descs + self._moments_descs(cp, Bg, cat_x, None, cc)
         if wd:
             w0, w1 = self._weight_decay_descs(cp, Bg, cat_x, cp.gsum.data_ptr() if sparse_grad is not None else None, eps, wd_part)
             descs.insert(descs.index(cc), w0)
@@ -1058,12 +1222,14 @@ class SupernetEngine:
 
     @_on_device
     def train_step(self, int_x, cat_x, y, lr: float, choice=None, clip: Optional[float] = 5.0, eps: float = 1e-2, graph: Optional[bool] = False,
-                   staged: bool = False, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None):
+                   staged: bool = False, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None):
         """zero_grad -> forward -> BCE -> backward -> clip_grad_norm_ -> Adagrad (train_utils.py:262-286).
         Returns the (device) loss tensor of this step.  `staged`: inputs are already in the plan's static buffers.  graph: True = replay
         the captured step, False = launch its program, None = whichever is faster for this plan (prefers_graph).
         weight_decay != 0: the step minimises BCE + get_l2_loss(model, weight_decay, no_reg_param_name) (train_utils.py:91-115,262-266):
-        every regularised parameter and EVERY table row is decayed; wd_l2_sumsq then holds sum ||W||^2 of the pre-step weights."""
+        every regularised parameter and EVERY table row is decayed; wd_l2_sumsq then holds sum ||W||^2 of the pre-step weights.
+        optim: an OptimSpec of kind adam / sgd replaces Adagrad (eps is then unused): torch.optim.Adam / SGD over the parameters the step
+        reaches and EVERY table row, state in `moments` and `opt_steps` (ensure_moments_state)."""
         choice = choice if choice is not None else self.warm_choice
         if graph is None:
             graph = self.cfg.fixed and self.prefers_graph(int(int_x.shape[0]) if int_x is not None else int(self._last_plan[2].cat_x.shape[0]))
@@ -1075,7 +1241,8 @@ class SupernetEngine:
         else:  # pre-staged inputs: the batch size is the one of the plan they were staged into
             assert staged and self._last_plan is not None, "train_step without inputs needs a previously compiled plan holding them"
             B = int(self._last_plan[2].cat_x.shape[0])
-        cp = self.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, weight_decay=weight_decay, no_reg_param_name=no_reg_param_name)
+        cp = self.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, weight_decay=weight_decay, no_reg_param_name=no_reg_param_name,
+                          optim=optim)
         sp = self._sp()
         if not staged:
             whole = not graph and getattr(cp, "fb", None) is not None and not self.host_embedding

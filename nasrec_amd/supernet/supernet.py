@@ -599,11 +599,13 @@ class SuperNet(nn.Module):
         return self.forward(int_feats, cat_feats, choices)
 
     def engine_train_step(self, int_feats, cat_feats, y, lr: float, clip: Optional[float] = 5.0, eps: float = 1e-2, graph=None,
-                          weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None):
+                          weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None):
         """Fused step on the engine (forward, BCE, backward, clip_grad_norm_, Adagrad with row-sparse table update):
         the counterpart of train_utils.py:262-286 for optimizer == Adagrad (torch's own weight_decay == 0).  weight_decay != 0: the loss
         is BCE + get_l2_loss(self, weight_decay, no_reg_param_name) — every regularised parameter and every table row is decayed
-        (engine_last_l2 = that term on the pre-step weights); one process with whole tables only."""
+        (engine_last_l2 = that term on the pre-step weights); one process with whole tables only.  optim: an OptimSpec
+        (nasrec_amd/optim_spec.py) of torch.optim.Adam / SGD replaces Adagrad (eps unused) — every table row moves every step; one process
+        with whole tables only; engine_bind_optimizer / engine_sync_optimizer_steps share its state with the torch optimizer."""
         if self._place_embedding_on_cpu:
             from .._lib import EngineError
             raise EngineError("engine_train_step needs the tables on the device; with place_embedding_on_cpu use forward / backward "
@@ -620,14 +622,15 @@ class SuperNet(nn.Module):
         weight_decay = float(weight_decay or 0.0)
         d["_last_step_key"] = (choice, clip, eps, graph)
         d["_last_step_wd"] = (weight_decay, no_reg_param_name)
-        if weight_decay:
+        d["_last_step_optim"] = optim
+        if weight_decay or optim is not None:
             import torch.distributed as dist
             if self._table_sharding == "row" or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
                 from .._lib import EngineError
-                raise EngineError("weight decay in the fused step covers one process with whole tables: row-sharded tables and "
-                                  "data-parallel runs train with weight decay 0 (or through the torch route)")
+                raise EngineError("weight decay, Adam and SGD in the fused step cover one process with whole tables: row-sharded tables "
+                                  "and data-parallel runs train them through the torch route")
             return self._engine.train_step(int_feats, cat_feats, y, lr, choice, clip, eps, graph=graph, weight_decay=weight_decay,
-                                           no_reg_param_name=no_reg_param_name)
+                                           no_reg_param_name=no_reg_param_name, optim=optim)
         if self._table_sharding == "row":
             from ..sharded_tables import ShardedTableStep
             st = self.__dict__.get("_sharded_step")
@@ -658,7 +661,8 @@ class SuperNet(nn.Module):
         if dp is not None and dp[1].exchange:
             return dp[1].last_plan().logits.view(B, 1)
         wd, no_reg = self.__dict__.get("_last_step_wd", (0.0, None))
-        cp = self._engine.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, weight_decay=wd, no_reg_param_name=no_reg)
+        cp = self._engine.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, weight_decay=wd, no_reg_param_name=no_reg,
+                                  optim=self.__dict__.get("_last_step_optim"))
         return cp.logits.view(B, 1)
 
     def engine_last_l2(self):
@@ -673,9 +677,15 @@ class SuperNet(nn.Module):
     def engine_bind_optimizer(self, optimizer):
         """Share the Adagrad accumulators between a torch.optim.Adagrad and the engine: existing `sum` state (a resumed
         checkpoint) is copied into the engine's arenas, then `optimizer.state[p]["sum"]` aliases them, so
-        `optimizer.state_dict()` stays a faithful checkpoint while the fused step does the updates."""
+        `optimizer.state_dict()` stays a faithful checkpoint while the fused step does the updates.
+        torch.optim.Adam / SGD (OptimSpec.from_optimizer): _bind_moments."""
         eng = self._engine
         assert eng is not None, "run one forward first (lazy shapes)"
+        from ..optim_spec import OptimSpec
+        spec = OptimSpec.from_optimizer(optimizer) if type(optimizer) is not torch.optim.Adagrad else None
+        self.__dict__["_bound_moments"] = spec
+        if spec is not None:
+            return self._bind_moments(optimizer, spec)
         eng._ensure_table_state()
         for name, p in self.named_parameters():
             if name.startswith("_embedding.") and self._table_sharding == "row":
@@ -693,8 +703,59 @@ class SuperNet(nn.Module):
             st.setdefault("step", torch.tensor(0.0))
         self._bound_optimizer_steps = getattr(self, "_engine_steps", 0)
 
+    def _bind_moments(self, optimizer, spec):
+        """Adam / SGD: the engine's step counters and moment arrays take the optimizer's state — a parameter without state (never
+        stepped) starts from zero — and `optimizer.state[p]` of every parameter that has state aliases the engine's arrays.
+        Parameters the fused steps reach later get their entries in engine_sync_optimizer_steps, as torch creates them on a
+        parameter's first step."""
+        eng = self._engine
+        if self._table_sharding == "row":
+            from .._lib import EngineError
+            raise EngineError("Adam / SGD in the fused step need whole tables on the device")
+        eng.ensure_moments_state(spec.kind)
+        counts = torch.zeros(eng.opt_steps.numel(), dtype=torch.float32)
+        with torch.cuda.stream(eng.stream):
+            for name, p in self.named_parameters():
+                if name not in eng.param_index:
+                    continue
+                st = optimizer.state.get(p)
+                for key in spec.state_keys:
+                    tgt = eng.moments_view(key, name)
+                    src = st.get(key) if st else None
+                    if src is None:
+                        tgt.zero_()
+                    elif src.data_ptr() != tgt.data_ptr():
+                        tgt.copy_(src.to(tgt.device).view_as(tgt))
+                if st:
+                    if spec.kind == "adam":
+                        counts[eng.param_index[name]] = float(st.get("step", 0.0))
+                    elif st.get("momentum_buffer") is not None:
+                        counts[eng.param_index[name]] = 1.0  # (SGD keeps no count: "has a buffer" is what the engine needs)
+            eng.opt_steps.copy_(counts.to(eng.device))
+        eng.stream.synchronize()
+        self._alias_moments(optimizer, spec, counts)
+
+    def _alias_moments(self, optimizer, spec, counts):
+        eng = self._engine
+        for name, p in self.named_parameters():
+            k = eng.param_index.get(name)
+            if k is None or counts[k] <= 0:
+                continue
+            st = optimizer.state[p]
+            for key in spec.state_keys:
+                st[key] = eng.moments_view(key, name)
+            if spec.kind == "adam":
+                st["step"] = torch.tensor(float(counts[k]), dtype=torch.float32)
+
     def engine_sync_optimizer_steps(self, optimizer):
-        """add the fused steps taken since engine_bind_optimizer to the optimizer's per-parameter step counters"""
+        """add the fused steps taken since engine_bind_optimizer to the optimizer's per-parameter step counters
+        (Adam / SGD: the counters of the engine, and state entries for the parameters stepped for the first time)"""
+        spec = self.__dict__.get("_bound_moments")
+        if spec is not None:
+            eng = self._engine
+            eng.stream.synchronize()
+            self._alias_moments(optimizer, spec, eng.opt_steps.detach().cpu())
+            return
         done = getattr(self, "_engine_steps", 0) - getattr(self, "_bound_optimizer_steps", 0)
         if done:
             for p in self.parameters():

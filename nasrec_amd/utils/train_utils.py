@@ -3,7 +3,8 @@
 
 `train_and_test_one_epoch` keeps the reference's step order (H2D, zero_grad, forward, BCE + L2, backward,
 clip_grad_norm_, optimizer.step, LR step after the optimizer, train_utils.py:255-287,386).  When the run is one the fused
-engine step covers — the model exposes `engine_train_step`, the optimizer is torch.optim.Adagrad without weight/lr decay,
+engine step covers — the model exposes `engine_train_step`, the optimizer is torch.optim.Adagrad without weight/lr decay
+(or torch.optim.Adam / SGD with momentum as main_train.py builds them, one process with whole tables: optim_spec.py),
 the L2 term is identically zero (`--wd 0`, the published recipes) or an `L2Loss` spec (any `--wd`, one process with whole
 tables) and AMP is off — the whole step is ONE engine call
 (captured in a hipGraph for fixed sub-networks); anything else takes the reference's operator-by-operator route through
@@ -107,11 +108,20 @@ test_one_epoch.__test__ = False  # not a pytest test
 
 
 def _fused_step_applies(model, optimizer, l2_loss_fn, use_amp):
-    if use_amp or not hasattr(model, "engine_train_step") or type(optimizer) is not torch.optim.Adagrad:
+    if use_amp or not hasattr(model, "engine_train_step"):
         return False
+    moments = None
+    if type(optimizer) is not torch.optim.Adagrad:
+        # torch.optim.Adam / SGD with momentum (main_train.py:150-160) under the conditions of OptimSpec.from_optimizer, for one
+        # process holding whole tables (row-sharded tables and data-parallel runs keep the torch route)
+        from ..optim_spec import OptimSpec
+        from .dist import world_info
+        moments = OptimSpec.from_optimizer(optimizer)
+        if moments is None or world_info()[1] > 1 or getattr(model, "_table_sharding", None) == "row":
+            return False
     if getattr(model, "_place_embedding_on_cpu", False):
         return False  # the tables stay on the host: torch's optimizer updates them there
-    for g in optimizer.param_groups:
+    for g in optimizer.param_groups if moments is None else ():  # (Adagrad's own options)
         if g.get("weight_decay", 0) != 0 or g.get("lr_decay", 0) != 0 or g.get("initial_accumulator_value", 0) != 0 or g.get("maximize", False):
             return False
     if len(optimizer.param_groups) != 1:
@@ -184,6 +194,10 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
     zero_l2 = None
     wd = l2_loss_fn.wd if (fused and isinstance(l2_loss_fn, L2Loss)) else 0.0
     no_reg = l2_loss_fn.no_reg_param_name if wd else None
+    optim = None
+    if fused and type(optimizer) is not torch.optim.Adagrad:  # Adam / SGD: the group's hyperparameters (the learning rate per step)
+        from ..optim_spec import OptimSpec
+        optim = OptimSpec.from_optimizer(optimizer)
     for batch_num, (int_x, cat_x, y) in enumerate(_agreed_batches(train_loader, train_batch_size, world, gpu)):
         t_data1 = time.time()
         on_dev = int_x.is_cuda and cat_x.is_cuda and y.is_cuda and (not isinstance(gpu, int) or int_x.device.index == gpu)
@@ -197,7 +211,10 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                 model.engine_bind_optimizer(optimizer)
                 bound = True
             group = optimizer.param_groups[0]
-            if wd:
+            if optim is not None:
+                loss = model.engine_train_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value, weight_decay=wd,
+                                               no_reg_param_name=no_reg, optim=optim)
+            elif wd:
                 loss = model.engine_train_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value, eps=float(group["eps"]),
                                                weight_decay=wd, no_reg_param_name=no_reg)
             else:

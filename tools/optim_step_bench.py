@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""Cost of the optimizer choice (`--optimizer adagrad | adam | sgd`, main_train.py:150-160) on the bench cfg-2 network: the Criteo
+best-1shot sub-network, full tables (33.76 M rows), batch 256, clip 5.0; Adagrad(eps 1e-2), Adam(eps 1e-8), SGD(momentum 0.9,
+Nesterov).  Prints one JSON line per measured (route, optimizer, wd):
+
+    python tools/optim_step_bench.py --route fused --optimizer adam --wd 0     # the fused engine step
+    python tools/optim_step_bench.py --route torch --optimizer adam --wd 0     # forward / autograd / clip_grad_norm_ / torch.optim
+    python tools/optim_step_bench.py --all                                     # every pair, each in a child process of its own
+
+The table pass's bandwidth comes from a kernel trace of the fused route (`rocprofv3 --kernel-trace --stats -- python
+tools/optim_step_bench.py --route fused --optimizer adam --steps 20`): opt_moments_phase1_kernel reads and writes W and its moments
+once (Adam 6 x 2.16 GB, SGD 4 x 2.16 GB) — `--bytes` prints those byte counts for the arithmetic."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+LR = {"adagrad": 1e-3, "adam": 1e-3, "sgd": 1e-3}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--route", choices=["fused", "torch"], default="fused")
+    ap.add_argument("--optimizer", choices=["adagrad", "adam", "sgd"], default="adam")
+    ap.add_argument("--wd", type=float, default=0.0)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--B", type=int, default=256)
+    ap.add_argument("--bytes", action="store_true")
+    ap.add_argument("--all", action="store_true", help="every route x optimizer x wd in {0, 1e-8}, one child process each")
+    ap.add_argument("--timeout", type=int, default=600, help="--all: seconds per child")
+    a = ap.parse_args()
+    from nasrec_amd.utils.config import NUM_EMBEDDINGS_CRITEO
+    tables = list(NUM_EMBEDDINGS_CRITEO)
+    rows = sum(tables)
+    if a.bytes:
+        tb = rows * 64
+        print(json.dumps({"table_rows": rows, "table_bytes": tb, "adam_phase1_bytes": 6 * tb, "sgd_phase1_bytes": 4 * tb,
+                          "adagrad_wd_phase1_bytes": 4 * tb, "wd_phase0_table_bytes": tb}))
+        return
+    if a.all:
+        for route in ("fused", "torch"):
+            for opt in ("adagrad", "adam", "sgd"):
+                for wd in (0.0, 1e-8):
+                    steps = a.steps if route == "fused" else min(a.steps, 20)
+                    cmd = [sys.executable, os.path.abspath(__file__), "--route", route, "--optimizer", opt, "--wd", str(wd), "--steps", str(steps),
+                           "--warmup", str(a.warmup), "--B", str(a.B)]
+                    r = subprocess.run(cmd, timeout=a.timeout, capture_output=True, text=True)
+                    if r.returncode != 0:  # (stop at the first failure: nothing more is started on the GPU)
+                        sys.stderr.write(r.stdout + r.stderr)
+                        raise SystemExit("%s exited with %d" % (" ".join(cmd[2:]), r.returncode))
+                    print(r.stdout.strip().splitlines()[-1], flush=True)
+        return
+
+    import torch
+
+    from bench import synthetic_batches
+    from nasrec_amd import main_train as MT
+    from nasrec_amd.optim_spec import OptimSpec
+    from nasrec_amd.supernet.supernet import SuperNet, ops_config_lib
+    from nasrec_amd.utils.train_utils import get_l2_loss
+    dev = torch.device("cuda", 0)
+    choice_all = json.load(open(os.path.join(ROOT, "nasrec_amd", "configs", "criteo", "ea_criteo_kaggle_xlarge_best_1shot.json")))
+    torch.manual_seed(0)
+    m = SuperNet(num_blocks=choice_all["num_blocks"], ops_config=ops_config_lib[choice_all["config"]], use_layernorm=False, num_embeddings=tables,
+                 sparse_input_size=26, path_sampling_strategy="fixed-path", fixed=True, fixed_choice=choice_all).to(dev)
+    batches = synthetic_batches(8, a.B, 13, tables, dev, seed=1)
+    with torch.no_grad():
+        m(batches[0][0], batches[0][1])
+    lr = LR[a.optimizer]
+    opt = MT.build_optimizer(a.optimizer, m, lr)
+    spec = OptimSpec.from_optimizer(opt) if a.optimizer != "adagrad" else None
+    loss_fn = torch.nn.BCEWithLogitsLoss()
+    if a.route == "fused":
+        m.engine_bind_optimizer(opt)
+
+    def step(i):
+        int_x, cat_x, y = batches[i % len(batches)]
+        if a.route == "fused":
+            if spec is not None:
+                m.engine_train_step(int_x, cat_x, y.view(-1), lr=lr, clip=5.0, weight_decay=a.wd, optim=spec)
+            else:
+                m.engine_train_step(int_x, cat_x, y.view(-1), lr=lr, clip=5.0, eps=1e-2, weight_decay=a.wd)
+            return
+        opt.zero_grad()
+        loss = loss_fn(m(int_x, cat_x), y.view(-1, 1)) + get_l2_loss(m, a.wd, None, gpu=0)
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(m.parameters(), 5.0)
+        opt.step()
+
+    for i in range(a.warmup):
+        step(i)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    for i in range(a.steps):
+        step(i)
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / a.steps
+    print(json.dumps({"route": a.route, "optimizer": a.optimizer, "wd": a.wd, "B": a.B, "steps": a.steps, "ms_per_step": round(ms, 4),
+                      "samples_per_s": round(a.B / ms * 1e3), "wall_ms_per_step": round((time.perf_counter() - t0) / a.steps * 1e3, 4),
+                      "table_rows": rows}))
+
+
+if __name__ == "__main__":
+    main()
