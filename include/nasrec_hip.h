@@ -86,11 +86,12 @@ enum {
   NASREC_OP_PERSIST = 36,
   NASREC_OP_WORKLIST_DEV = 38, /* (37 is taken by a layout-check slot of nasrec_desc_sizes) */
   NASREC_OP_WEIGHT_DECAY = 39,
-  NASREC_OP_OPT_MOMENTS = 40
+  NASREC_OP_OPT_MOMENTS = 40,
+  NASREC_OP_LAST_LAYER_STEP = 41
 };
 
-/* algorithm of NASREC_OP_OPT_MOMENTS */
-enum { NASREC_OPTIM_ADAM = 1, NASREC_OPTIM_SGD = 2 };
+/* algorithm of NASREC_OP_OPT_MOMENTS (ADAGRAD: NASREC_OP_LAST_LAYER_STEP only) */
+enum { NASREC_OPTIM_ADAGRAD = 0, NASREC_OPTIM_ADAM = 1, NASREC_OPTIM_SGD = 2 };
 
 /* ------------------------------------------------------------------------------------------------
  * GEMM family.  C(i,j) = epilogue( sum_k A(i,k) * B(j,k) ).   Replaces every nn.Linear / LazyLinear
@@ -549,6 +550,45 @@ typedef struct nasrec_opt_moments_desc {
 } nasrec_opt_moments_desc_t;
 
 /* ------------------------------------------------------------------------------------------------
+ * The optimizer tail of a last-layer fine-tune step (SuperNet.set_mode_to_finelune_last_only: only _final.{weight [1, K], bias [1]}
+ * train), in ONE workgroup of 256 threads, behind the final-logit backward:
+ *   (a) g = [dw[0..K), dbias[0]]; nsplit > 1: g[j] = sum over r = 0, 1, .., nsplit-1 of partial[r (K+1) + j] (that order; the sums are
+ *       also written to dw / dbias, where NASREC_OP_REDUCE_ROWS would have put them)
+ *   (b) decay_w: g[j] += 2 wd W[j] for j < K (get_l2_loss regularises parameters of >= 2 dims: the bias never)
+ *   (c) ||g||^2: thread t sums j = t, t + 256, .. in fp64, then a fixed LDS tree; total = (float)sqrt; coef = min(1, max_norm /
+ *       (total + 1e-6)), max_norm <= 0: coef = 1 (NASREC_OP_CLIP_COEF's expressions)
+ *   (d) g' = g coef and the optimizer, per element the device functions of NASREC_OP_OPT_APPLY / NASREC_OP_OPT_MOMENTS
+ *       (optimizer_bodies.h): ADAGRAD s = sum; ADAM s = exp_avg, v = exp_avg_sq with step[0] (weight) / step[1] (bias) as torch's
+ *       per-parameter `step` before this one; SGD s = momentum_buffer.  step[0..1] += 1 at the end (ADAM and SGD).
+ * Optional outputs: g_out[K+1] = g', norm_out[2] = {coef, total}.  K + 1 <= NASREC_LAST_LAYER_MAX.  Same inputs -> same bits.
+ * ---------------------------------------------------------------------------------------------- */
+#define NASREC_LAST_LAYER_MAX 8192
+typedef struct nasrec_last_layer_step_desc {
+  int32_t kind;    /* NASREC_OP_LAST_LAYER_STEP */
+  int32_t algo;    /* NASREC_OPTIM_ADAGRAD / _ADAM / _SGD */
+  int32_t K;       /* input width of the final layer */
+  int32_t nsplit;  /* <= 1: g from dw / dbias; > 1: from partial */
+  int32_t decay_w; /* add 2 wd W to the weight's gradient */
+  int32_t nesterov;
+  float max_norm;  /* <= 0: no clip */
+  float wd, eps, momentum;
+  double beta1, beta2;
+  const float* partial; /* [nsplit, K + 1] (column K = bias) */
+  float* dw;            /* [K] */
+  float* dbias;         /* [1] */
+  float* w;             /* [K] */
+  float* bias;          /* [1] */
+  float* s_w;           /* first state array of the weight / of the bias */
+  float* s_b;
+  float* v_w;           /* ADAM: exp_avg_sq */
+  float* v_b;
+  float* step;          /* ADAM / SGD: [2] counters (weight, bias) */
+  const float* lr;      /* device scalar */
+  float* g_out;         /* optional [K + 1] */
+  float* norm_out;      /* optional [2] */
+} nasrec_last_layer_step_desc_t;
+
+/* ------------------------------------------------------------------------------------------------
  * The row-sparse embedding backward in two halves (round 5).  NASREC_OP_EMB_DEDUP above does everything behind the backward pass;
  * but which sample leads a row, and which samples repeat it, depends on the IDS only — known before the forward pass starts (one
  * GPU: when the batch is staged; N GPUs: when the ids all-gather lands, nasrec_amd/parallel.py).  So:
@@ -836,6 +876,7 @@ int nasrec_opt_reduce2(void* stream, const nasrec_opt_reduce2_desc_t* d);
 int nasrec_final_fused(void* stream, const nasrec_final_desc_t* d);
 int nasrec_weight_decay(void* stream, const nasrec_weight_decay_desc_t* d);
 int nasrec_opt_moments(void* stream, const nasrec_opt_moments_desc_t* d);
+int nasrec_last_layer_step(void* stream, const nasrec_last_layer_step_desc_t* d);
 int nasrec_worklist(void* stream, const nasrec_worklist_desc_t* d);
 
 /* Uncached device memory (hipExtMallocWithFlags(hipDeviceMallocUncached)): the plan arena of a persistent step (NASREC_OP_PERSIST) —

@@ -37,7 +37,9 @@ ACT_BY_NAME = {"identity": ACT_NONE, "relu": ACT_RELU, "silu": ACT_SILU}
 OP_WORKLIST_DEV = 38  # (37: a layout-check slot of nasrec_desc_sizes)
 OP_WEIGHT_DECAY = 39
 OP_OPT_MOMENTS = 40
-OPTIM_ADAM, OPTIM_SGD = 1, 2  # NASREC_OPTIM_* (algorithm of NASREC_OP_OPT_MOMENTS)
+OP_LAST_LAYER_STEP = 41
+OPTIM_ADAGRAD, OPTIM_ADAM, OPTIM_SGD = 0, 1, 2  # NASREC_OPTIM_* (algorithm of NASREC_OP_OPT_MOMENTS / _LAST_LAYER_STEP)
+LAST_LAYER_MAX = 8192  # NASREC_LAST_LAYER_MAX: K + 1 of NASREC_OP_LAST_LAYER_STEP
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -248,6 +250,13 @@ class OptMomentsDesc(C.Structure):
                 ("lr", vp), ("coef", vp)]
 
 
+class LastLayerStepDesc(C.Structure):
+    _fields_ = [("kind", i32), ("algo", i32), ("K", i32), ("nsplit", i32), ("decay_w", i32), ("nesterov", i32), ("max_norm", f32),
+                ("wd", f32), ("eps", f32), ("momentum", f32), ("beta1", C.c_double), ("beta2", C.c_double), ("partial", vp), ("dw", vp),
+                ("dbias", vp), ("w", vp), ("bias", vp), ("s_w", vp), ("s_b", vp), ("v_w", vp), ("v_b", vp), ("step", vp), ("lr", vp),
+                ("g_out", vp), ("norm_out", vp)]
+
+
 DESC_BY_KIND = {
     OP_GEMM: GemmDesc, OP_EMBED_GATHER: EmbedDesc, OP_DOT_TRI_FWD: DotTriDesc, OP_DOT_TRI_BWD: DotTriDesc, OP_FM_FWD: FmDesc,
     OP_FM_BWD: FmDesc, OP_MHA_FWD: MhaDesc, OP_MHA_BWD: MhaDesc, OP_REDUCE_ROWS: ReduceRowsDesc, OP_COPY_SEGS: CopySegsDesc,
@@ -257,7 +266,7 @@ DESC_BY_KIND = {
     OP_SCALE: ScaleDesc, OP_ACT_BWD: ActBwdDesc, OP_STAGE_INPUTS: StageDesc, OP_OPT_REDUCE: OptReduceDesc, OP_OPT_APPLY: OptApplyDesc,
     OP_WORKLIST: WorklistDesc, OP_CONST_I64: ConstI64Desc, OP_SPLITK_EPILOGUES: SplitkEpiloguesDesc, OP_DEDUP_IDS: DedupIdsDesc,
     OP_OPT_REDUCE2: OptReduce2Desc, OP_FINAL_FUSED: FinalDesc, OP_PERSIST: PersistDesc, OP_WORKLIST_DEV: WorklistDevDesc,
-    OP_WEIGHT_DECAY: WeightDecayDesc, OP_OPT_MOMENTS: OptMomentsDesc,
+    OP_WEIGHT_DECAY: WeightDecayDesc, OP_OPT_MOMENTS: OptMomentsDesc, OP_LAST_LAYER_STEP: LastLayerStepDesc,
 }
 
 # every symbol include/nasrec_hip.h declares
@@ -268,7 +277,7 @@ SYMBOLS = [
     "nasrec_opt_apply", "nasrec_worklist", "nasrec_dedup_ids", "nasrec_opt_reduce2", "nasrec_final_fused", "nasrec_event_create",
     "nasrec_event_record", "nasrec_event_elapsed_ms", "nasrec_event_destroy", "nasrec_last_error", "nasrec_abi_version",
     "nasrec_desc_sizes", "nasrec_tsv_parse", "nasrec_alloc_uncached", "nasrec_free_uncached", "nasrec_persist_prepare", "nasrec_worklist_prepare",
-    "nasrec_weight_decay", "nasrec_opt_moments",
+    "nasrec_weight_decay", "nasrec_opt_moments", "nasrec_last_layer_step",
 ]
 
 _lib = None
@@ -310,12 +319,12 @@ def load():
     for name in ("nasrec_gemm", "nasrec_embedding_gather", "nasrec_embedding_dedup", "nasrec_dot_tri", "nasrec_fm",
                  "nasrec_mha_ffn", "nasrec_layernorm", "nasrec_final_logit", "nasrec_bce_logits", "nasrec_adagrad_dense",
                  "nasrec_adagrad_rows", "nasrec_opt_reduce", "nasrec_opt_apply", "nasrec_worklist", "nasrec_dedup_ids", "nasrec_opt_reduce2", "nasrec_final_fused", "nasrec_weight_decay",
-                 "nasrec_opt_moments"):
+                 "nasrec_opt_moments", "nasrec_last_layer_step"):
         getattr(lib, name).argtypes = [vp, vp]
     if lib.nasrec_abi_version() != 17:
         raise EngineError("ABI version mismatch: library %d, binding 17" % lib.nasrec_abi_version())
-    sizes = (i32 * 41)()
-    n = lib.nasrec_desc_sizes(sizes, 41)
+    sizes = (i32 * 42)()
+    n = lib.nasrec_desc_sizes(sizes, 42)
     for kind, cls in DESC_BY_KIND.items():
         if kind >= n or sizes[kind] != C.sizeof(cls):
             raise EngineError("struct layout mismatch for op kind %d: library %d bytes, binding %d bytes"

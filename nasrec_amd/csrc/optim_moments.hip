@@ -7,36 +7,6 @@
 
 namespace {
 
-// Adam's per-parameter scalars of this step, from the step counter as torch computes them in Python doubles (torch/optim/adam.py,
-// _multi_tensor_adam): step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t), t = step + 1
-__device__ __forceinline__ void adam_scalars(const nasrec_opt_moments_desc_t& d, float step, float lr, float& step_size, float& bc2_sqrt) {
-  const double t = (double)step + 1.0;
-  step_size = (float)((double)lr / (1.0 - pow(d.beta1, t)));
-  bc2_sqrt = (float)sqrt(1.0 - pow(d.beta2, t));
-}
-
-// one element; g = the clipped gradient.  The statements follow torch's foreach calls one by one (lerp_; mul_ + addcmul_; sqrt, div_,
-// add_; addcdiv_): -ffp-contract=on fuses within a statement only.
-template <int ALGO>
-__device__ __forceinline__ void moments_elem(const nasrec_opt_moments_desc_t& d, float g, float& p, float& m, float& v, float lr,
-                                             float step_size, float bc2_sqrt) {
-  if (ALGO == NASREC_OPTIM_ADAM) {
-    const float w1 = (float)(1.0 - d.beta1), b2 = (float)d.beta2, w2 = (float)(1.0 - d.beta2);
-    m = w1 < 0.5f ? m + w1 * (g - m) : g - (g - m) * (1.f - w1);  // (torch's lerp)
-    v = v * b2;
-    v = v + w2 * (g * g);
-    float den = sqrtf(v) / bc2_sqrt;
-    den = den + d.eps;
-    p = p + (-step_size) * (m / den);
-  } else {
-    m = m * d.momentum;
-    m = m + g;
-    float dir = m;
-    if (d.nesterov) dir = g + d.momentum * m;
-    p = p + (-lr) * dir;
-  }
-}
-
 template <int ALGO>
 __device__ __forceinline__ void moments_vec(const nasrec_opt_moments_desc_t& d, const f32x4& g, f32x4& p, f32x4& m, f32x4& v, float lr,
                                             float ss, float bs) {

@@ -101,6 +101,47 @@ __device__ __forceinline__ float clip_coef_wave(const nasrec_clip_coef_desc_t& d
   return coef;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// One element of each optimizer, g = the clipped gradient: Adagrad (the apply launch, NASREC_OP_OPT_APPLY) and Adam / momentum SGD
+// (NASREC_OP_OPT_MOMENTS); NASREC_OP_LAST_LAYER_STEP calls the same functions.  D = a descriptor with beta1, beta2, eps, momentum,
+// nesterov.
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void adagrad_elem(float g, float& s, float& p, float lr, float eps) {
+  s = fmaf(g, g, s);
+  p = p - lr * (g / (sqrtf(s) + eps));
+}
+
+// Adam's per-parameter scalars of this step, from the step counter as torch computes them in Python doubles (torch/optim/adam.py,
+// _multi_tensor_adam): step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t), t = step + 1
+template <class D>
+__device__ __forceinline__ void adam_scalars(const D& d, float step, float lr, float& step_size, float& bc2_sqrt) {
+  const double t = (double)step + 1.0;
+  step_size = (float)((double)lr / (1.0 - pow(d.beta1, t)));
+  bc2_sqrt = (float)sqrt(1.0 - pow(d.beta2, t));
+}
+
+// one element; g = the clipped gradient.  The statements follow torch's foreach calls one by one (lerp_; mul_ + addcmul_; sqrt, div_,
+// add_; addcdiv_): -ffp-contract=on fuses within a statement only.
+template <int ALGO, class D>
+__device__ __forceinline__ void moments_elem(const D& d, float g, float& p, float& m, float& v, float lr,
+                                             float step_size, float bc2_sqrt) {
+  if (ALGO == NASREC_OPTIM_ADAM) {
+    const float w1 = (float)(1.0 - d.beta1), b2 = (float)d.beta2, w2 = (float)(1.0 - d.beta2);
+    m = w1 < 0.5f ? m + w1 * (g - m) : g - (g - m) * (1.f - w1);  // (torch's lerp)
+    v = v * b2;
+    v = v + w2 * (g * g);
+    float den = sqrtf(v) / bc2_sqrt;
+    den = den + d.eps;
+    p = p + (-step_size) * (m / den);
+  } else {
+    m = m * d.momentum;
+    m = m + g;
+    float dir = m;
+    if (d.nesterov) dir = g + d.momentum * m;
+    p = p + (-lr) * dir;
+  }
+}
+
 __device__ __forceinline__ void adagrad_dense_body(const nasrec_adagrad_dense_desc_t& d, int blk, int nblk, float lr, float coef) {
   if (d.chunks) {
     for (long c = blk; c < d.nchunks; c += nblk) {
@@ -113,27 +154,28 @@ __device__ __forceinline__ void adagrad_dense_body(const nasrec_adagrad_dense_de
         f32x4 s4 = *reinterpret_cast<const f32x4*>(sp + 4 * i), p4 = *reinterpret_cast<const f32x4*>(pp + 4 * i);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float g = g4[e] * coef;
-          s4[e] = fmaf(g, g, s4[e]);
-          p4[e] = p4[e] - lr * (g / (sqrtf(s4[e]) + d.eps));
+          float se = s4[e], pe = p4[e];
+          adagrad_elem(g4[e] * coef, se, pe, lr, d.eps);
+          s4[e] = se;
+          p4[e] = pe;
         }
         *reinterpret_cast<f32x4*>(sp + 4 * i) = s4;
         *reinterpret_cast<f32x4*>(pp + 4 * i) = p4;
       }
       for (long j = 4 * n4 + threadIdx.x; j < n; j += 256) {
-        const float g = gp[j] * coef;
-        const float s = fmaf(g, g, sp[j]);
+        float s = sp[j], p = pp[j];
+        adagrad_elem(gp[j] * coef, s, p, lr, d.eps);
         sp[j] = s;
-        pp[j] = pp[j] - lr * (g / (sqrtf(s) + d.eps));
+        pp[j] = p;
       }
     }
     return;
   }
   for (long i = (long)blk * 256 + threadIdx.x; i < d.n; i += (long)nblk * 256) {
-    const float g = d.g[i] * coef;
-    const float s = fmaf(g, g, d.state[i]);
+    float s = d.state[i], p = d.p[i];
+    adagrad_elem(d.g[i] * coef, s, p, lr, d.eps);
     d.state[i] = s;
-    d.p[i] = d.p[i] - lr * (g / (sqrtf(s) + d.eps));
+    d.p[i] = p;
   }
 }
 

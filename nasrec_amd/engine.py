@@ -1268,6 +1268,117 @@ class SupernetEngine:
             cp.opt.run(sp)
         return cp.loss
 
+    def ensure_last_layer_state(self, kind: str):
+        """Adam's exp_avg / exp_avg_sq or SGD's momentum_buffer of _final.{weight, bias} for the last-layer step (last_layer_step),
+        allocated on first use, zero, and its two step counters ll_steps [weight, bias].  -> {state key: (weight array, bias array)}.
+        (The whole-model moments of ensure_moments_state would hold two more copies of every table.)"""
+        keys = ("exp_avg", "exp_avg_sq") if kind == "adam" else ("momentum_buffer",)
+        st = self.__dict__.setdefault("ll_moments", {})
+        with torch.cuda.stream(self.stream):
+            for k in keys:
+                if k not in st:
+                    st[k] = (torch.zeros_like(self.params["_final.weight"]), torch.zeros_like(self.params["_final.bias"]))
+            if getattr(self, "ll_steps", None) is None:
+                self.ll_steps = torch.zeros(2, dtype=torch.float32, device=self.device)
+        self.stream.synchronize()
+        return {k: st[k] for k in keys}
+
+    def _last_layer_program(self, cp, clip, eps, weight_decay, no_reg_param_name, optim, graph):
+        """(staging launch + forward + final-logit backward with BCE folded in, d features skipped + NASREC_OP_LAST_LAYER_STEP,
+        the same without the staging launch) of a compiled training plan, built once per plan and optimizer setting"""
+        key = (clip, eps, weight_decay, no_reg_param_name, tuple(optim) if optim is not None else None, graph)
+        progs = cp.__dict__.setdefault("last_layer", {})
+        if key in progs:
+            return progs[key]
+        last = next(d for d in cp.bwd_final_only.descs if isinstance(d, L.FinalDesc))
+        fin = L.FinalDesc.from_buffer_copy(last)
+        fin.logits, fin.y, fin.loss, fin.dlogits_out = cp.logits.data_ptr(), cp.y.data_ptr(), cp.loss.data_ptr(), None
+        fin.grad_scale = cp.bce.grad_scale
+        K = int(self.params["_final.weight"].numel())
+        if K + 1 > L.LAST_LAYER_MAX:
+            raise L.EngineError("last-layer step: the final layer has %d inputs, the kernel takes at most %d" % (K, L.LAST_LAYER_MAX - 1))
+        d = L.LastLayerStepDesc()
+        d.kind, d.K, d.nsplit = L.OP_LAST_LAYER_STEP, K, max(1, int(fin.nsplit))
+        d.partial = fin.dw if fin.nsplit > 1 else None
+        d.dw, d.dbias = self.grads["_final.weight"].data_ptr(), self.grads["_final.bias"].data_ptr()
+        d.w, d.bias = self.params["_final.weight"].data_ptr(), self.params["_final.bias"].data_ptr()
+        d.max_norm = float(clip) if clip is not None else 0.0
+        d.wd = float(weight_decay)
+        d.decay_w = int(bool(weight_decay) and not (no_reg_param_name is not None and "_final.weight".startswith(no_reg_param_name)))
+        if optim is None:
+            d.algo, d.eps = L.OPTIM_ADAGRAD, float(eps)
+            d.s_w, d.s_b = self.state["_final.weight"].data_ptr(), self.state["_final.bias"].data_ptr()
+        else:
+            st = self.ensure_last_layer_state(optim.kind)
+            d.algo = L.OPTIM_ADAM if optim.kind == "adam" else L.OPTIM_SGD
+            d.eps, d.momentum, d.nesterov = float(optim.eps), float(optim.momentum), int(bool(optim.nesterov))
+            d.beta1, d.beta2 = float(optim.beta1), float(optim.beta2)
+            first = st["exp_avg"] if optim.kind == "adam" else st["momentum_buffer"]
+            d.s_w, d.s_b = first[0].data_ptr(), first[1].data_ptr()
+            if optim.kind == "adam":
+                d.v_w, d.v_b = st["exp_avg_sq"][0].data_ptr(), st["exp_avg_sq"][1].data_ptr()
+            d.step = self.ll_steps.data_ptr()
+        d.lr, d.norm_out = self.lr_dev.data_ptr(), self.clip_out.data_ptr()
+        cp.ll_keep = getattr(cp, "ll_keep", []) + [fin, d]  # (descriptors are passed by address: they live as long as the plan)
+        rest = Program(list(cp.fwd.descs) + [fin, d])
+        whole = None
+        if graph:
+            rest.capture(self.stream.cuda_stream)
+            self.stream.synchronize()
+        else:
+            whole = Program([cp.stage] + list(cp.fwd.descs) + [fin, d])
+        progs[key] = (whole, rest)
+        return progs[key]
+
+    @_on_device
+    def last_layer_step(self, int_x, cat_x, y, lr: float, choice=None, clip: Optional[float] = 5.0, eps: float = 1e-2,
+                        weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None, graph: bool = False):
+        """The training step of last-layer fine-tuning (SuperNet.set_mode_to_finelune_last_only): forward -> BCE -> d loss / d _final
+        (nothing else) -> [+ 2 wd W] -> clip_grad_norm_ over _final -> Adagrad (state: self.state) / Adam / SGD (optim, state:
+        ensure_last_layer_state) on _final.{weight, bias} alone.  Returns the (device) loss.  graph: replay a captured program (fixed
+        sub-networks).  The plan is the one the autograd route runs (compile(choice, B, train=True))."""
+        choice = choice if choice is not None else self.warm_choice
+        if self.host_embedding:
+            raise L.EngineError("the last-layer step needs the embedding tables on the device")
+        B = int(int_x.shape[0])
+        cp = self.compile(choice, B, train=True)
+        self.last_layer_plan = cp  # (its logits: SuperNet.engine_last_logits)
+        whole, rest = self._last_layer_program(cp, clip, eps, float(weight_decay or 0.0), no_reg_param_name, optim, bool(graph))
+        sp = self._sp()
+        if self._stage_inputs(sp, cp, int_x, cat_x, y, lr, launch=whole is None):
+            whole.run(sp)
+            return cp.loss
+        if graph:
+            rest.replay(sp)
+        else:
+            rest.run(sp)
+        return cp.loss
+
+    def close(self):
+        """Release what this engine holds outside torch's allocator now, not at the next garbage collection: captured graphs and the
+        uncached arenas of its plans (hipExtMallocWithFlags memory, freed when the last view of it goes).  The engine is unusable after."""
+        self.stream.synchronize()
+        for cp in list(self._plans.values()):
+            for prog in [getattr(cp, n, None) for n in ("step", "fwd", "whole")] + [p for pr in getattr(cp, "last_layer", {}).values() for p in pr]:
+                if prog is not None and prog.graph is not None:
+                    L.load().nasrec_graph_destroy(prog.graph)
+                    prog.graph = None
+            ctx = getattr(cp, "ctx", None)
+            if ctx is not None:
+                ctx.closures, ctx.deferred, ctx.mha_reduce, ctx.keep = [], [], [], []
+                ctx.sk_workspace = None
+                ctx.arena = None
+            cp.ctx = None
+            cp.arena = None
+            cp.__dict__.clear()
+        self._plans.clear()
+        self._pcache.clear()
+        self._spare_arenas = []
+        self._last_plan = None
+        self.last_layer_plan = None
+        self._uc_flat_arena = None
+        self._sk_ws = None
+
     @_on_device
     def run_forward(self, cp, int_x, cat_x, rows=None):
         """forward program of an already compiled (training) plan; logits land in cp.logits"""

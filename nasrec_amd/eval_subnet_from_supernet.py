@@ -19,22 +19,8 @@ from .utils.lr_schedule import ConstantWithWarmup, CosineAnnealingWarmupRestarts
 from .utils.train_utils import L2Loss, train_and_test_one_epoch, warmup_supernet_model
 
 
-def finetune_and_eval_one_model(model, args, checkpoint):
-    """eval_subnet_from_supernet.py:71-207 -> {"choice", "test_acc", "test_auroc", "test_loss"}"""
-    train_loader, test_loader = make_loaders(args)
-    model = model.to(args.gpu)
-    with torch.no_grad():
-        model = warmup_supernet_model(model, train_loader, args.gpu)  # full path: every lazy shape, every deleted projection
-    model.configure_path_sampling_strategy("fixed-path")
-    if args.loss_function != "bce":
-        raise NotImplementedError("Loss function {} is not implemented!".format(args.loss_function))
-    loss_fn = torch.nn.BCEWithLogitsLoss()
-    if args.finetune_whole_supernet == 0:
-        print("Finetune last only ...")
-        model.set_mode_to_finelune_last_only()
-    else:
-        print("Finetuning the whole supernet.")
-
+def make_optimizer_and_schedule(model, args):
+    """-> (L2 loss, optimizer, LR scheduler) of one candidate's fine-tune (eval_subnet_from_supernet.py:122-171)"""
     l2_loss_fn = L2Loss(args.wd, getattr(args, "no_reg_param_name", None), gpu=args.gpu)
 
     if args.optimizer == "adagrad":
@@ -56,6 +42,26 @@ def finetune_and_eval_one_model(model, args, checkpoint):
         lr_scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=[num_train_steps // 3, num_train_steps * 2 // 3], gamma=0.2)
     else:
         lr_scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=[num_train_steps * 10], gamma=0.1)
+    return l2_loss_fn, optimizer, lr_scheduler
+
+
+def finetune_and_eval_one_model(model, args, checkpoint):
+    """eval_subnet_from_supernet.py:71-207 -> {"choice", "test_acc", "test_auroc", "test_loss"}"""
+    train_loader, test_loader = make_loaders(args)
+    model = model.to(args.gpu)
+    with torch.no_grad():
+        model = warmup_supernet_model(model, train_loader, args.gpu)  # full path: every lazy shape, every deleted projection
+    model.configure_path_sampling_strategy("fixed-path")
+    if args.loss_function != "bce":
+        raise NotImplementedError("Loss function {} is not implemented!".format(args.loss_function))
+    loss_fn = torch.nn.BCEWithLogitsLoss()
+    if args.finetune_whole_supernet == 0:
+        print("Finetune last only ...")
+        model.set_mode_to_finelune_last_only()
+    else:
+        print("Finetuning the whole supernet.")
+
+    l2_loss_fn, optimizer, lr_scheduler = make_optimizer_and_schedule(model, args)
     if checkpoint is not None:
         model.load_state_dict(checkpoint["model_state_dict"], strict=True)  # (the optimizer state is deliberately not restored, :173-177)
     lr_scheduler.step(epoch=-1)  # back to the first step after reading the state_dict (:179)
@@ -89,6 +95,18 @@ def main(args):
         print("Evaluating {} subnets from record file: {}".format(len(all_choices), args.choice_from_pickle_file))
         all_results = []
         checkpoint = load_model_checkpoint(args.ckpt_path)
+        if getattr(args, "resident_candidates", 0) == 1:  # one supernet, set up once, scores every choice
+            from .searcher.resident import ResidentCandidateEvaluator
+            ev = ResidentCandidateEvaluator(args, checkpoint, gpu=args.gpu)
+            try:
+                for idx, rec in enumerate(all_choices):
+                    print("Evaluating {} of {} networks!".format(idx, len(all_choices)))
+                    print("GT performance: {:.5f}".format(rec["test_loss"]))
+                    print(rec["choice"])
+                    all_results.append(ev.evaluate(rec["choice"]))
+            finally:
+                ev.close()
+            all_choices = []
         for idx, rec in enumerate(all_choices):
             print("Evaluating {} of {} networks!".format(idx, len(all_choices)))
             print("GT performance: {:.5f}".format(rec["test_loss"]))
@@ -148,6 +166,9 @@ def build_parser():
     p.add_argument("--beta", type=float, default=0.0)
     p.add_argument("--target_latency", type=float, default=-1)
     p.add_argument("--latency_batch_size", type=int, default=512)
+    p.add_argument("--resident_candidates", type=int, default=0, choices=[0, 1],
+                   help="1: one long-lived supernet per GPU scores every candidate (set-up, checkpoint and batches kept between candidates; "
+                        "last-layer steps fused on the engine).  0: a fresh supernet per candidate, as the reference.")
     return p
 
 

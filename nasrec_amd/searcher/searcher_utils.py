@@ -25,6 +25,23 @@ def build_supernet(args, num_embeddings=None):
                     path_sampling_strategy="full-path")
 
 
+def fixed_model_latency(args, choice, gpu_id, kwargs):
+    """latency of the candidate as a fixed sub-network (searcher_utils.py:84-101)"""
+    from ..utils.train_utils import get_model_latency
+    tables = getattr(args, "num_embeddings", None)
+    n = kwargs["latency_batch_size"]
+    int_x = torch.rand((n, _num_dense_inputs_dict[args.dataset]), dtype=torch.float32)
+    cat_x = torch.zeros((n, _num_sparse_inputs_dict[args.dataset]), dtype=torch.int64)
+    print("Getting latency of fixed model...")
+    fixed = SuperNet(num_blocks=args.num_blocks, ops_config=ops_config_lib[args.config], use_layernorm=(args.use_layernorm == 1),
+                     activation="relu", num_embeddings=tables if tables is not None else _num_embedding_dict[args.dataset],
+                     sparse_input_size=_num_sparse_inputs_dict[args.dataset], path_sampling_strategy="fixed-path", fixed=True,
+                     fixed_choice=choice)
+    mean_lat, _ = get_model_latency(fixed, (int_x, cat_x), gpu_id)
+    print("Latency: {:.5f} s.".format(mean_lat))
+    return mean_lat
+
+
 def _create_model_train_and_get_results(args, gpu_id, eval_fn, tokenizer, choice, checkpoint, kwargs):
     """searcher_utils.py:57-104"""
     args.gpu = gpu_id
@@ -35,20 +52,9 @@ def _create_model_train_and_get_results(args, gpu_id, eval_fn, tokenizer, choice
     results = eval_fn(model, args, checkpoint)
     results["hash_token"] = tokenizer.hash_token(tokenizer.tokenize(model.choice))
     if kwargs.get("beta", 0.0) != 0.0:
-        from ..utils.train_utils import get_model_latency
         cur_choice = model.choice
         del model
-        n = kwargs["latency_batch_size"]
-        int_x = torch.rand((n, _num_dense_inputs_dict[args.dataset]), dtype=torch.float32)
-        cat_x = torch.zeros((n, _num_sparse_inputs_dict[args.dataset]), dtype=torch.int64)
-        print("Getting latency of fixed model...")
-        fixed = SuperNet(num_blocks=args.num_blocks, ops_config=ops_config_lib[args.config], use_layernorm=(args.use_layernorm == 1),
-                         activation="relu", num_embeddings=tables if tables is not None else _num_embedding_dict[args.dataset],
-                         sparse_input_size=_num_sparse_inputs_dict[args.dataset], path_sampling_strategy="fixed-path", fixed=True,
-                         fixed_choice=cur_choice)
-        mean_lat, _ = get_model_latency(fixed, (int_x, cat_x), gpu_id)
-        results["latency"] = mean_lat
-        print("Latency: {:.5f} s.".format(mean_lat))
+        results["latency"] = fixed_model_latency(args, cur_choice, gpu_id, kwargs)
     return results
 
 

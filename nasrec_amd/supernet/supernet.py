@@ -621,6 +621,7 @@ class SuperNet(nn.Module):
         d["_last_step_batch"] = int(int_feats.shape[0])
         weight_decay = float(weight_decay or 0.0)
         d["_last_step_key"] = (choice, clip, eps, graph)
+        d["_last_step_last_layer"] = False
         d["_last_step_wd"] = (weight_decay, no_reg_param_name)
         d["_last_step_optim"] = optim
         if weight_decay or optim is not None:
@@ -651,10 +652,44 @@ class SuperNet(nn.Module):
             return dp[1].step(int_feats, cat_feats, y, lr, choice=None if self._fixed else choice)
         return self._engine.train_step(int_feats, cat_feats, y, lr, choice, clip, eps, graph=graph)
 
+    def _last_layer_only(self):
+        """set_mode_to_finelune_last_only: every parameter outside _final is frozen"""
+        return all(n.startswith("_final.") or not p.requires_grad for n, p in self.named_parameters()) and \
+            all(p.requires_grad for n, p in self.named_parameters() if n.startswith("_final."))
+
+    def engine_last_layer_step(self, int_feats, cat_feats, y, lr: float, clip: Optional[float] = 5.0, eps: float = 1e-2,
+                               weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None):
+        """Fused step of last-layer fine-tuning (the searcher's candidate scoring, set_mode_to_finelune_last_only): forward, BCE,
+        d loss / d _final, clip_grad_norm_ and the optimizer — Adagrad (eps), or an OptimSpec of torch.optim.Adam / SGD — on
+        _final.{weight, bias} alone, in the engine (SupernetEngine.last_layer_step).  weight_decay: get_l2_loss's gradient on
+        _final.weight (the frozen parameters take none).  Returns the (device) loss.  One process with whole tables only;
+        engine_bind_optimizer(optimizer, last_layer=True) / engine_sync_optimizer_steps share the state with the torch optimizer."""
+        from .._lib import EngineError
+        if self._place_embedding_on_cpu:
+            raise EngineError("engine_last_layer_step needs the tables on the device; with place_embedding_on_cpu use forward / backward "
+                              "and a torch optimizer")
+        import torch.distributed as dist
+        if self._table_sharding == "row" or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            raise EngineError("the fused last-layer step covers one process with whole tables: row-sharded tables and data-parallel "
+                              "runs train the last layer through the torch route")
+        if not self._last_layer_only():
+            raise EngineError("engine_last_layer_step trains _final alone: every other parameter must be frozen "
+                              "(set_mode_to_finelune_last_only); use engine_train_step or the torch route")
+        choice = self._resolve_choice(None)
+        self._ensure_engine(int_feats)
+        d = self.__dict__
+        d["_last_layer_steps"] = d.get("_last_layer_steps", 0) + 1
+        d["_last_step_batch"] = int(int_feats.shape[0])
+        d["_last_step_last_layer"] = True  # (engine_last_logits: the plan the engine ran, SupernetEngine.last_layer_plan)
+        return self._engine.last_layer_step(int_feats, cat_feats, y, lr, choice, clip, eps, weight_decay=float(weight_decay or 0.0),
+                                            no_reg_param_name=no_reg_param_name, optim=optim, graph=self._fixed)
+
     def engine_last_logits(self):
         """logits [B, 1] of the most recent engine_train_step (what `model(int_x, cat_x)` returned inside that step)"""
-        choice, clip, eps, graph = self._last_step_key
         B = self._last_step_batch
+        if self.__dict__.get("_last_step_last_layer"):  # (engine_last_layer_step)
+            return self._engine.last_layer_plan.logits.view(B, 1)
+        choice, clip, eps, graph = self._last_step_key
         if self._table_sharding == "row":
             return self._sharded_ops.cp.logits.view(B, 1)
         dp = self.__dict__.get("_dp_step")
@@ -674,15 +709,20 @@ class SuperNet(nn.Module):
             return torch.zeros((), device=self._final.weight.device)
         return (eng.wd_l2_sumsq[0] * wd).to(torch.float32)
 
-    def engine_bind_optimizer(self, optimizer):
+    def engine_bind_optimizer(self, optimizer, last_layer: bool = False):
         """Share the Adagrad accumulators between a torch.optim.Adagrad and the engine: existing `sum` state (a resumed
         checkpoint) is copied into the engine's arenas, then `optimizer.state[p]["sum"]` aliases them, so
         `optimizer.state_dict()` stays a faithful checkpoint while the fused step does the updates.
-        torch.optim.Adam / SGD (OptimSpec.from_optimizer): _bind_moments."""
+        torch.optim.Adam / SGD (OptimSpec.from_optimizer): _bind_moments.  last_layer: the same for engine_last_layer_step, over
+        _final.{weight, bias} only (_bind_last_layer): the frozen parameters' state is left as it is."""
         eng = self._engine
         assert eng is not None, "run one forward first (lazy shapes)"
         from ..optim_spec import OptimSpec
         spec = OptimSpec.from_optimizer(optimizer) if type(optimizer) is not torch.optim.Adagrad else None
+        self.__dict__["_bound_last_layer"] = bool(last_layer)
+        if last_layer:
+            self.__dict__["_bound_moments"] = None
+            return self._bind_last_layer(optimizer, spec)
         self.__dict__["_bound_moments"] = spec
         if spec is not None:
             return self._bind_moments(optimizer, spec)
@@ -747,9 +787,77 @@ class SuperNet(nn.Module):
             if spec.kind == "adam":
                 st["step"] = torch.tensor(float(counts[k]), dtype=torch.float32)
 
+    _FINAL = ("_final.weight", "_final.bias")
+
+    def _bind_last_layer(self, optimizer, spec):
+        """engine_bind_optimizer(last_layer=True).  Adagrad: `sum` of _final.* aliases the engine's accumulators (the ones the
+        autograd route's plan shares).  Adam / SGD: the engine's last-layer moments and counters (ensure_last_layer_state) take the
+        optimizer's state of _final.* — none: zero — and alias it once a parameter has been stepped."""
+        eng = self._engine
+        params = dict(self.named_parameters())
+        self.__dict__["_bound_ll_spec"] = spec
+        if spec is None:
+            for name in self._FINAL:
+                st = optimizer.state[params[name]]
+                tgt = eng.state[name]
+                if "sum" in st and st["sum"].data_ptr() != tgt.data_ptr():
+                    tgt.copy_(st["sum"].to(tgt.device).view_as(tgt))
+                st["sum"] = tgt
+                st.setdefault("step", torch.tensor(0.0))
+            self._bound_optimizer_steps = getattr(self, "_last_layer_steps", 0)
+            return
+        arrays = eng.ensure_last_layer_state(spec.kind)
+        counts = torch.zeros(2, dtype=torch.float32)
+        with torch.cuda.stream(eng.stream):
+            for i, name in enumerate(self._FINAL):
+                st = optimizer.state.get(params[name])
+                for key in spec.state_keys:
+                    tgt = arrays[key][i]
+                    src = st.get(key) if st else None
+                    if src is None:
+                        tgt.zero_()
+                    elif src.data_ptr() != tgt.data_ptr():
+                        tgt.copy_(src.to(tgt.device).view_as(tgt))
+                if st:
+                    if spec.kind == "adam":
+                        counts[i] = float(st.get("step", 0.0))
+                    elif st.get("momentum_buffer") is not None:
+                        counts[i] = 1.0
+            eng.ll_steps.copy_(counts.to(eng.device))
+        eng.stream.synchronize()
+        self._alias_last_layer(optimizer, spec, counts)
+
+    def _alias_last_layer(self, optimizer, spec, counts):
+        arrays = self._engine.ll_moments
+        params = dict(self.named_parameters())
+        for i, name in enumerate(self._FINAL):
+            if counts[i] <= 0:
+                continue
+            st = optimizer.state[params[name]]
+            for key in spec.state_keys:
+                st[key] = arrays[key][i]
+            if spec.kind == "adam":
+                st["step"] = torch.tensor(float(counts[i]), dtype=torch.float32)
+
     def engine_sync_optimizer_steps(self, optimizer):
         """add the fused steps taken since engine_bind_optimizer to the optimizer's per-parameter step counters
         (Adam / SGD: the counters of the engine, and state entries for the parameters stepped for the first time)"""
+        if self.__dict__.get("_bound_last_layer"):
+            spec = self.__dict__.get("_bound_ll_spec")
+            if spec is not None:
+                self._engine.stream.synchronize()
+                torch.cuda.synchronize(self._engine.device)
+                self._alias_last_layer(optimizer, spec, self._engine.ll_steps.detach().cpu())
+                return
+            done = getattr(self, "_last_layer_steps", 0) - getattr(self, "_bound_optimizer_steps", 0)
+            if done:
+                params = dict(self.named_parameters())
+                for name in self._FINAL:
+                    st = optimizer.state.get(params[name])
+                    if st is not None and "step" in st:
+                        st["step"] = st["step"] + float(done)
+                self._bound_optimizer_steps = getattr(self, "_last_layer_steps", 0)
+            return
         spec = self.__dict__.get("_bound_moments")
         if spec is not None:
             eng = self._engine

@@ -107,6 +107,27 @@ def test_one_epoch(model, test_loader, loss_fn, gpu: Optional[int] = None, max_s
 test_one_epoch.__test__ = False  # not a pytest test
 
 
+def _last_layer_step_applies(model, optimizer, l2_loss_fn, use_amp):
+    """engine_last_layer_step stands in for the torch route's step: a SuperNet in last-layer mode (every parameter outside _final
+    frozen) of one process with whole tables on the device, an L2Loss, and torch.optim.Adagrad (lr_decay, weight_decay,
+    initial_accumulator_value 0, not maximize) or an Adam / SGD that OptimSpec.from_optimizer accepts, in one group"""
+    if use_amp or not hasattr(model, "engine_last_layer_step") or not isinstance(l2_loss_fn, L2Loss):
+        return False
+    from .dist import world_info
+    if world_info()[1] > 1 or getattr(model, "_table_sharding", None) == "row" or getattr(model, "_place_embedding_on_cpu", False):
+        return False
+    if len(optimizer.param_groups) != 1 or not model._last_layer_only():
+        return False
+    g = optimizer.param_groups[0]
+    if not {id(p) for p in model._final.parameters()} <= {id(p) for p in g["params"]}:
+        return False
+    if type(optimizer) is torch.optim.Adagrad:
+        return not (g.get("weight_decay", 0) != 0 or g.get("lr_decay", 0) != 0 or g.get("initial_accumulator_value", 0) != 0
+                    or g.get("maximize", False) or g.get("differentiable", False) or g.get("fused"))
+    from ..optim_spec import OptimSpec
+    return OptimSpec.from_optimizer(optimizer) is not None
+
+
 def _fused_step_applies(model, optimizer, l2_loss_fn, use_amp):
     if use_amp or not hasattr(model, "engine_train_step"):
         return False
@@ -177,13 +198,18 @@ def _agreed_batches(train_loader, train_batch_size: int, world: int, gpu):
 def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, train_loader, test_loader, loss_fn, l2_loss_fn,
                              train_batch_size: int, gpu: Union[int, None], display_interval: int = 100, test_interval: int = 2000,
                              max_train_steps: int = -1, max_eval_steps: int = -1, test_only_at_last_step: bool = False,
-                             grad_clip_value: float = None, tb_writer=None, use_amp: bool = False, use_engine_step: Optional[bool] = None):
+                             grad_clip_value: float = None, tb_writer=None, use_amp: bool = False, use_engine_step: Optional[bool] = None,
+                             last_layer_step: bool = False):
     """One epoch of training with tests in between; returns the reference's log dict (train_utils.py:181-390).
-    `use_engine_step`: None = fused engine step whenever it applies, False = always the torch route."""
+    `use_engine_step`: None = fused engine step whenever it applies, False = always the torch route.
+    `last_layer_step`: a model in last-layer mode (set_mode_to_finelune_last_only) with a qualifying optimizer trains every full batch
+    through SuperNet.engine_last_layer_step (_last_layer_step_applies); False (default) = as before."""
     _peek(test_loader)  # the reference peeks one test batch here (train_utils.py:224-225)
     model.train()
     logs = {k: [] for k in ("train_loss", "train_AUROC", "train_Accuracy", "test_loss", "test_AUROC", "test_Accuracy", "epoch", "iters")}
     fused = _fused_step_applies(model, optimizer, l2_loss_fn, use_amp) if use_engine_step is None else bool(use_engine_step)
+    last_only = bool(last_layer_step) and not fused and use_engine_step is not False and \
+        _last_layer_step_applies(model, optimizer, l2_loss_fn, use_amp)
     bound = False
     scaler = torch.amp.GradScaler("cuda") if use_amp else None
     best_model, best_test_loss = None, 9999.99
@@ -195,7 +221,10 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
     wd = l2_loss_fn.wd if (fused and isinstance(l2_loss_fn, L2Loss)) else 0.0
     no_reg = l2_loss_fn.no_reg_param_name if wd else None
     optim = None
-    if fused and type(optimizer) is not torch.optim.Adagrad:  # Adam / SGD: the group's hyperparameters (the learning rate per step)
+    if last_only:
+        wd = l2_loss_fn.wd
+        no_reg = l2_loss_fn.no_reg_param_name if wd else None
+    if (fused or last_only) and type(optimizer) is not torch.optim.Adagrad:  # Adam / SGD: the group's hyperparameters (the learning rate per step)
         from ..optim_spec import OptimSpec
         optim = OptimSpec.from_optimizer(optimizer)
     for batch_num, (int_x, cat_x, y) in enumerate(_agreed_batches(train_loader, train_batch_size, world, gpu)):
@@ -205,7 +234,21 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
             int_x, cat_x, y = int_x.to(gpu, non_blocking=True), cat_x.to(gpu, non_blocking=True), y.to(gpu, non_blocking=True)
         t_gpu0 = time.time()
         full = len(y) == train_batch_size  # a short last batch is evaluated but not trained on
-        if fused and full:
+        if last_only and full:
+            if not bound:
+                model._ensure_engine(int_x)
+                model.engine_bind_optimizer(optimizer, last_layer=True)
+                bound = True
+            group = optimizer.param_groups[0]
+            # the L2 term is only looked at on display steps: there it is get_l2_loss of the weights BEFORE the step, as the torch route has it
+            l2_loss = None
+            if batch_num % display_interval == 0 or batch_num == max_train_steps - 1:
+                with torch.no_grad():
+                    l2_loss = l2_loss_fn(model)
+            loss = model.engine_last_layer_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value,
+                                                eps=float(group.get("eps", 1e-2)), weight_decay=wd, no_reg_param_name=no_reg, optim=optim)
+            res = None
+        elif fused and full:
             if not bound:  # lazy shapes + engine, then share the Adagrad accumulators (a resumed optimizer keeps its state)
                 model._ensure_engine(int_x)
                 model.engine_bind_optimizer(optimizer)

@@ -12,7 +12,13 @@ Printed: per candidate the wall time of the whole call and of its phases (model 
 training steps; the 150 evaluation batches incl. AUROC on the host), candidates / hour / GPU; then the same three step kinds on batches
 already resident in HBM (no pipe, no Python harness): last-layer-only step, whole-network fine-tune step, evaluation forward.
 
-    python tools/search_operating_point.py [--candidates 3] [--train_steps 500] [--eval_steps 150]"""
+--resident: in the same call, on the same build, the same candidates kind scored by ONE ResidentCandidateEvaluator (`--resident_candidates 1`:
+set-up once, a restored snapshot per candidate, batches kept on the device, the fused last-layer step), with its per-phase breakdown
+and the fused last-layer step on resident batches.  --cli N: the real search CLI (`--method random --random_budget N
+--num_parallel_workers 1`, checkpoint on disk, full tables only) timed end to end as a child process, without and with
+`--resident_candidates 1`.
+
+    python tools/search_operating_point.py [--candidates 3] [--train_steps 500] [--eval_steps 150] [--resident] [--cli 8]"""
 import argparse
 import os
 import sys
@@ -34,6 +40,8 @@ def main():
     ap.add_argument("--test_batch_size", type=int, default=8192)
     ap.add_argument("--cap", type=int, default=0, help="cap the tables (0 = the full 33.76 M rows)")
     ap.add_argument("--profile", action="store_true", help="cProfile of the LAST candidate's call (host time by function)")
+    ap.add_argument("--resident", action="store_true", help="also score candidates with one resident evaluator (--resident_candidates 1)")
+    ap.add_argument("--cli", type=int, default=0, help="time the search CLI with this random budget, both ways (0 = skip)")
     a = ap.parse_args()
 
     from nasrec_amd import eval_subnet_from_supernet as E
@@ -70,7 +78,7 @@ def main():
 
     # phase timers: wrap the harness's own functions
     phase = {}
-    real_train, real_test = E.train_and_test_one_epoch, TU.test_one_epoch
+    real_train, real_test, real_auroc = E.train_and_test_one_epoch, TU.test_one_epoch, TU._auroc
 
     def timed_train(*x, **kw):
         torch.cuda.synchronize()
@@ -87,8 +95,14 @@ def main():
         torch.cuda.synchronize()
         phase["test"] = phase.get("test", 0.0) + time.perf_counter() - t
         return r
+    def timed_auroc(*x, **kw):  # (AUROC on the host, sklearn: part of the evaluation phase)
+        t = time.perf_counter()
+        r = real_auroc(*x, **kw)
+        phase["auroc"] = phase.get("auroc", 0.0) + time.perf_counter() - t
+        return r
     E.train_and_test_one_epoch = timed_train
     TU.test_one_epoch = timed_test
+    TU._auroc = timed_auroc
 
     searcher = S.Searcher(E.finetune_and_eval_one_model, args)
     tok = searcher._tokenizer
@@ -120,12 +134,71 @@ def main():
                   c, total, rows[-1][1], a.train_steps, tr, tr / a.train_steps * 1e3, a.train_batch_size * a.train_steps / max(tr, 1e-9),
                   a.eval_steps, rows[-1][3], rows[-1][3] / a.eval_steps * 1e3, a.test_batch_size * a.eval_steps / max(rows[-1][3], 1e-9) / 1e6,
                   rows[-1][4], rows[-1][5]))
-    E.train_and_test_one_epoch, TU.test_one_epoch = real_train, real_test
     if rows:
         use = rows[1:] if len(rows) > 1 else rows  # (the first candidate also pays one-off costs: kernels' first launches, allocator growth)
         mean = float(np.mean([r[0] for r in use]))
         print("steady state: %.2f s per candidate = %.0f candidates / hour / GPU  (reference, Tesla M40, from its own comment: 500 x 0.05 - 0.06 s = 25 - 30 s of "
               "training steps alone per candidate)" % (mean, 3600.0 / mean))
+
+    if a.resident:
+        from nasrec_amd.searcher import resident as R
+        real_rtrain = R.train_and_test_one_epoch
+        R.train_and_test_one_epoch = timed_train
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        ev = R.ResidentCandidateEvaluator(argparse.Namespace(**vars(args)), ckpt, gpu=0)
+        torch.cuda.synchronize()
+        setup = time.perf_counter() - t
+        print("resident evaluator: set-up once (build, full-path warm-up, checkpoint load, snapshot, %s batches on the device) %.2f s" % (
+            "first" if ev.resident else "NO", setup))
+        rrows = []
+        for c in range(a.candidates):
+            phase.clear()
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            res = R.evaluate_candidate(ev, tok, None, {"beta": 0.0})
+            torch.cuda.synchronize()
+            total = time.perf_counter() - t
+            tt = phase.get("train_and_test", 0.0)
+            te = phase.get("test", 0.0)
+            rrows.append(total)
+            print("resident candidate %d: %.2f s = restore + optimizer %.3f + %d fused last-layer steps %.2f (%.3f ms/step) + %d evaluation batches %.2f "
+                  "(%.2f ms/batch; AUROC on the host %.3f s = %.0f %% of the candidate);  test loss %.4f AUROC %.4f" % (
+                      c, total, total - tt, a.train_steps, tt - te, (tt - te) / a.train_steps * 1e3, a.eval_steps, te, te / a.eval_steps * 1e3,
+                      phase.get("auroc", 0.0), 100.0 * phase.get("auroc", 0.0) / total, res["test_loss"][-1], res["test_auroc"][-1]))
+        R.train_and_test_one_epoch = real_rtrain
+        use = rrows[1:] if len(rrows) > 1 else rrows
+        rmean = float(np.mean(use))
+        print("resident steady state: %.2f s per candidate = %.0f candidates / hour / GPU (set-up %.2f s once per search)" % (rmean, 3600.0 / rmean, setup))
+        if rows:
+            print("rebuild against resident, same call and build: %.2f s -> %.2f s per candidate (%.1fx)" % (mean, rmean, mean / rmean))
+        # the fused last-layer step alone, on batches already on the device
+        import bench
+        m = ev.model
+        tb = bench.synthetic_batches(8, a.train_batch_size, 13, tables, "cuda", 100)
+        opt = torch.optim.Adagrad(m.parameters(), lr=0.04, eps=1e-2)
+        m.engine_bind_optimizer(opt, last_layer=True)
+
+        def fused(i):
+            int_x, cat_x, y = tb[i % len(tb)]
+            m.engine_last_layer_step(int_x, cat_x, y.view(-1), 0.04)
+        for i in range(10):
+            fused(i)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for i in range(200):
+            fused(i)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t) / 200
+        print("resident batches, fused last-layer step (engine_last_layer_step, B = %d): %.3f ms = %.0f samples/s   (torch route, r06: 1.474 ms)" % (
+            a.train_batch_size, dt * 1e3, a.train_batch_size / dt))
+        del m, opt, tb
+        ev.close()
+        del ev
+    E.train_and_test_one_epoch, TU.test_one_epoch, TU._auroc = real_train, real_test, real_auroc
+
+    if a.cli:
+        cli_timings(a, args, ckpt, root)
 
     # ---- the same step kinds on batches resident in HBM: no pipe, no harness loop ----------------------------------------------
     import bench  # (synthetic_batches: the bench's input generator)
@@ -177,6 +250,44 @@ def main():
     dt = timeit(whole, 200)
     print("resident batches, whole-network fine-tune step, fused engine step (B = %d): %.3f ms = %.0f samples/s   (reference comment: 210 - 230 ms on a Tesla M40)" % (
         a.train_batch_size, dt * 1e3, a.train_batch_size / dt))
+
+
+def cli_timings(a, args, ckpt, root):
+    """the search CLI as a user runs it — `python -m nasrec_amd.eval_subnet_from_supernet --method random --random_budget N
+    --num_parallel_workers 1` with the checkpoint on disk — timed end to end, without and with --resident_candidates 1"""
+    import shutil
+    import subprocess
+    import tempfile
+    if a.cap:
+        print("--cli: the CLI has no table cap (full tables only): skipped")
+        return
+    d = tempfile.mkdtemp(prefix="nasrec_cli_")
+    try:
+        if shutil.disk_usage(d).free < 4 * 2.85e9:
+            print("--cli: not enough free disk space for the checkpoint in %s: skipped" % d)
+            return
+        path = os.path.join(d, "supernet.pt")
+        t = time.perf_counter()
+        torch.save({"model_state_dict": {k: v.cpu() for k, v in ckpt["model_state_dict"].items()}}, path)
+        print("checkpoint written in %.1f s (%.2f GB)" % (time.perf_counter() - t, os.path.getsize(path) / 1e9))
+        for flag in ("0", "1"):
+            cmd = [sys.executable, "-m", "nasrec_amd.eval_subnet_from_supernet", "--dataset", "criteo-kaggle", "--root_dir", root,
+                   "--logging_dir", os.path.join(d, "log" + flag), "--config", "xlarge", "--num_blocks", "7", "--use_layernorm", "1",
+                   "--learning_rate", "0.04", "--wd", "0", "--max_train_steps", str(a.train_steps), "--max_eval_steps", str(a.eval_steps),
+                   "--train_batch_size", str(a.train_batch_size), "--test_batch_size", str(a.test_batch_size), "--method", "random",
+                   "--random_budget", str(a.cli), "--num_parallel_workers", "1", "--test_only_at_last_step", "1", "--display_interval",
+                   "1000000", "--ckpt_path", path, "--resident_candidates", flag]
+            t = time.perf_counter()
+            r = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=1200)
+            dt = time.perf_counter() - t
+            if r.returncode != 0:
+                print("CLI --resident_candidates %s failed (exit %d): %s" % (flag, r.returncode, r.stderr.decode(errors="replace")[-2000:]))
+                return
+            print("CLI --method random --random_budget %d --num_parallel_workers 1 --resident_candidates %s: %.1f s end to end = %.2f s per "
+                  "candidate = %.0f candidates / hour / GPU (process start, imports and checkpoint reads included)" % (
+                      a.cli, flag, dt, dt / a.cli, 3600.0 * a.cli / dt))
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
 
 
 if __name__ == "__main__":
