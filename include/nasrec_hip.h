@@ -87,7 +87,8 @@ enum {
   NASREC_OP_WORKLIST_DEV = 38, /* (37 is taken by a layout-check slot of nasrec_desc_sizes) */
   NASREC_OP_WEIGHT_DECAY = 39,
   NASREC_OP_OPT_MOMENTS = 40,
-  NASREC_OP_LAST_LAYER_STEP = 41
+  NASREC_OP_LAST_LAYER_STEP = 41,
+  NASREC_OP_ROC_AUC = 42
 };
 
 /* algorithm of NASREC_OP_OPT_MOMENTS (ADAGRAD: NASREC_OP_LAST_LAYER_STEP only) */
@@ -589,6 +590,32 @@ typedef struct nasrec_last_layer_step_desc {
 } nasrec_last_layer_step_desc_t;
 
 /* ------------------------------------------------------------------------------------------------
+ * ROC AUC of binary labels and float32 scores, the same float64 bits as sklearn.metrics.roc_auc_score on numpy (DESIGN.md "ROC AUC
+ * on the device": the order of every sum is numpy's).  A chain of launches on `stream`, no synchronisation, no allocation:
+ *   (a) key = an order-preserving uint32 of the descending score order (+0 and -0 one key); the input checks into the status
+ *   (b) four stable 8-bit LSD radix passes over (key, label)
+ *   (c) cumulative positives tps and negatives fps at the end of every run of equal keys (int64 scans)
+ *   (d) sklearn's drop_intermediate: keep the first and last point and every point where (fps, tps) has a non-zero second difference
+ *   (e) terms (fpr[k] - fpr[k-1]) * (tpr[k] + tpr[k-1]) / 2.0 from (0, 0) on, fpr = fps / N, tpr = tps / P; summed in numpy's order:
+ *       chunks of 8192 terms, each summed pairwise (leaves of <= 128 with eight accumulators), the chunk sums in order from 0.0
+ * out (12 bytes, 8-byte aligned): double auc, int32 status.  status != 0 (bits NASREC_ROC_AUC_*): auc means nothing, the caller
+ * asks sklearn (which then raises or warns as it always did).  workspace: nasrec_roc_auc_workspace_bytes(n) bytes, 256-byte aligned.
+ * n <= NASREC_ROC_AUC_MAX_N.  Same inputs -> same bits.
+ * ---------------------------------------------------------------------------------------------- */
+#define NASREC_ROC_AUC_MAX_N (1ll << 30)
+enum { NASREC_ROC_AUC_TOO_FEW = 1, NASREC_ROC_AUC_BAD_LABEL = 2, NASREC_ROC_AUC_NOT_FINITE = 4, NASREC_ROC_AUC_ONE_CLASS = 8 };
+typedef struct nasrec_roc_auc_desc {
+  int32_t kind;            /* NASREC_OP_ROC_AUC */
+  int32_t _pad;
+  int64_t n;               /* samples; n < 2: status NASREC_ROC_AUC_TOO_FEW, nothing read */
+  const float* score;      /* [n] */
+  const float* label;      /* [n], each exactly 0 or 1 (else status NASREC_ROC_AUC_BAD_LABEL) */
+  void* workspace;         /* device memory of workspace_bytes */
+  int64_t workspace_bytes; /* >= nasrec_roc_auc_workspace_bytes(n) */
+  void* out;               /* device: double auc at byte 0, int32 status at byte 8 */
+} nasrec_roc_auc_desc_t;
+
+/* ------------------------------------------------------------------------------------------------
  * The row-sparse embedding backward in two halves (round 5).  NASREC_OP_EMB_DEDUP above does everything behind the backward pass;
  * but which sample leads a row, and which samples repeat it, depends on the IDS only — known before the forward pass starts (one
  * GPU: when the batch is staged; N GPUs: when the ids all-gather lands, nasrec_amd/parallel.py).  So:
@@ -877,6 +904,8 @@ int nasrec_final_fused(void* stream, const nasrec_final_desc_t* d);
 int nasrec_weight_decay(void* stream, const nasrec_weight_decay_desc_t* d);
 int nasrec_opt_moments(void* stream, const nasrec_opt_moments_desc_t* d);
 int nasrec_last_layer_step(void* stream, const nasrec_last_layer_step_desc_t* d);
+int nasrec_roc_auc(void* stream, const nasrec_roc_auc_desc_t* d);
+int64_t nasrec_roc_auc_workspace_bytes(int64_t n); /* 0 for n < 2 or n > NASREC_ROC_AUC_MAX_N */
 int nasrec_worklist(void* stream, const nasrec_worklist_desc_t* d);
 
 /* Uncached device memory (hipExtMallocWithFlags(hipDeviceMallocUncached)): the plan arena of a persistent step (NASREC_OP_PERSIST) —

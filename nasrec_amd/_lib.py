@@ -40,6 +40,9 @@ OP_OPT_MOMENTS = 40
 OP_LAST_LAYER_STEP = 41
 OPTIM_ADAGRAD, OPTIM_ADAM, OPTIM_SGD = 0, 1, 2  # NASREC_OPTIM_* (algorithm of NASREC_OP_OPT_MOMENTS / _LAST_LAYER_STEP)
 LAST_LAYER_MAX = 8192  # NASREC_LAST_LAYER_MAX: K + 1 of NASREC_OP_LAST_LAYER_STEP
+OP_ROC_AUC = 42
+ROC_AUC_MAX_N = 1 << 30  # NASREC_ROC_AUC_MAX_N
+ROC_AUC_TOO_FEW, ROC_AUC_BAD_LABEL, ROC_AUC_NOT_FINITE, ROC_AUC_ONE_CLASS = 1, 2, 4, 8  # NASREC_ROC_AUC_* status bits
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -257,6 +260,11 @@ class LastLayerStepDesc(C.Structure):
                 ("g_out", vp), ("norm_out", vp)]
 
 
+class RocAucDesc(C.Structure):
+    _fields_ = [("kind", i32), ("_pad", i32), ("n", i64), ("score", vp), ("label", vp), ("workspace", vp), ("workspace_bytes", i64),
+                ("out", vp)]
+
+
 DESC_BY_KIND = {
     OP_GEMM: GemmDesc, OP_EMBED_GATHER: EmbedDesc, OP_DOT_TRI_FWD: DotTriDesc, OP_DOT_TRI_BWD: DotTriDesc, OP_FM_FWD: FmDesc,
     OP_FM_BWD: FmDesc, OP_MHA_FWD: MhaDesc, OP_MHA_BWD: MhaDesc, OP_REDUCE_ROWS: ReduceRowsDesc, OP_COPY_SEGS: CopySegsDesc,
@@ -267,6 +275,7 @@ DESC_BY_KIND = {
     OP_WORKLIST: WorklistDesc, OP_CONST_I64: ConstI64Desc, OP_SPLITK_EPILOGUES: SplitkEpiloguesDesc, OP_DEDUP_IDS: DedupIdsDesc,
     OP_OPT_REDUCE2: OptReduce2Desc, OP_FINAL_FUSED: FinalDesc, OP_PERSIST: PersistDesc, OP_WORKLIST_DEV: WorklistDevDesc,
     OP_WEIGHT_DECAY: WeightDecayDesc, OP_OPT_MOMENTS: OptMomentsDesc, OP_LAST_LAYER_STEP: LastLayerStepDesc,
+    OP_ROC_AUC: RocAucDesc,
 }
 
 # every symbol include/nasrec_hip.h declares
@@ -277,7 +286,7 @@ SYMBOLS = [
     "nasrec_opt_apply", "nasrec_worklist", "nasrec_dedup_ids", "nasrec_opt_reduce2", "nasrec_final_fused", "nasrec_event_create",
     "nasrec_event_record", "nasrec_event_elapsed_ms", "nasrec_event_destroy", "nasrec_last_error", "nasrec_abi_version",
     "nasrec_desc_sizes", "nasrec_tsv_parse", "nasrec_alloc_uncached", "nasrec_free_uncached", "nasrec_persist_prepare", "nasrec_worklist_prepare",
-    "nasrec_weight_decay", "nasrec_opt_moments", "nasrec_last_layer_step",
+    "nasrec_weight_decay", "nasrec_opt_moments", "nasrec_last_layer_step", "nasrec_roc_auc", "nasrec_roc_auc_workspace_bytes",
 ]
 
 _lib = None
@@ -319,12 +328,14 @@ def load():
     for name in ("nasrec_gemm", "nasrec_embedding_gather", "nasrec_embedding_dedup", "nasrec_dot_tri", "nasrec_fm",
                  "nasrec_mha_ffn", "nasrec_layernorm", "nasrec_final_logit", "nasrec_bce_logits", "nasrec_adagrad_dense",
                  "nasrec_adagrad_rows", "nasrec_opt_reduce", "nasrec_opt_apply", "nasrec_worklist", "nasrec_dedup_ids", "nasrec_opt_reduce2", "nasrec_final_fused", "nasrec_weight_decay",
-                 "nasrec_opt_moments", "nasrec_last_layer_step"):
+                 "nasrec_opt_moments", "nasrec_last_layer_step", "nasrec_roc_auc"):
         getattr(lib, name).argtypes = [vp, vp]
+    lib.nasrec_roc_auc_workspace_bytes.argtypes = [i64]
+    lib.nasrec_roc_auc_workspace_bytes.restype = i64
     if lib.nasrec_abi_version() != 17:
         raise EngineError("ABI version mismatch: library %d, binding 17" % lib.nasrec_abi_version())
-    sizes = (i32 * 42)()
-    n = lib.nasrec_desc_sizes(sizes, 42)
+    sizes = (i32 * 43)()
+    n = lib.nasrec_desc_sizes(sizes, 43)
     for kind, cls in DESC_BY_KIND.items():
         if kind >= n or sizes[kind] != C.sizeof(cls):
             raise EngineError("struct layout mismatch for op kind %d: library %d bytes, binding %d bytes"

@@ -22,6 +22,7 @@ import sklearn.metrics
 import torch
 import torch.nn as nn
 
+from .. import metrics
 from ..supernet.supernet import SuperNet
 
 
@@ -77,6 +78,11 @@ def accuracy(gt, pred):
 
 
 def _auroc(y_true, y_prob):
+    """sklearn.metrics.roc_auc_score of the two tensors: on their GPU (metrics.roc_auc_score, the same float64 bits) when both are
+    contiguous float32 CUDA tensors of one device and equal length; anything else (CPU tensors, half scores under autocast, other
+    dtypes) on the host as before"""
+    if metrics.roc_auc_supported(y_true, y_prob):
+        return metrics.roc_auc_score(y_true.detach(), y_prob.detach())
     return sklearn.metrics.roc_auc_score(y_true.detach().cpu().numpy(), y_prob.detach().cpu().numpy())
 
 

@@ -9,7 +9,7 @@ The only timing the reference publishes for anything is a comment at this operat
 0.05 - 0.06 s per batch-512 step with last-layer-only fine-tuning, 0.21 - 0.23 s fine-tuning the whole network.
 
 Printed: per candidate the wall time of the whole call and of its phases (model build + full-path warm-up + checkpoint load; the 500
-training steps; the 150 evaluation batches incl. AUROC on the host), candidates / hour / GPU; then the same three step kinds on batches
+training steps; the 150 evaluation batches incl. the AUROC, on the GPU since NASREC_OP_ROC_AUC), candidates / hour / GPU; then the same three step kinds on batches
 already resident in HBM (no pipe, no Python harness): last-layer-only step, whole-network fine-tune step, evaluation forward.
 
 --resident: in the same call, on the same build, the same candidates kind scored by ONE ResidentCandidateEvaluator (`--resident_candidates 1`:
@@ -18,7 +18,10 @@ and the fused last-layer step on resident batches.  --cli N: the real search CLI
 --num_parallel_workers 1`, checkpoint on disk, full tables only) timed end to end as a child process, without and with
 `--resident_candidates 1`.
 
-    python tools/search_operating_point.py [--candidates 3] [--train_steps 500] [--eval_steps 150] [--resident] [--cli 8]"""
+--check_auroc: every AUROC call of the harness is recomputed by sklearn on host copies of its inputs (outside the timed phases) and
+compared bit for bit; the count of equal results is printed at the end.
+
+    python tools/search_operating_point.py [--candidates 3] [--train_steps 500] [--eval_steps 150] [--resident] [--cli 8] [--check_auroc]"""
 import argparse
 import os
 import sys
@@ -42,6 +45,7 @@ def main():
     ap.add_argument("--profile", action="store_true", help="cProfile of the LAST candidate's call (host time by function)")
     ap.add_argument("--resident", action="store_true", help="also score candidates with one resident evaluator (--resident_candidates 1)")
     ap.add_argument("--cli", type=int, default=0, help="time the search CLI with this random budget, both ways (0 = skip)")
+    ap.add_argument("--check_auroc", action="store_true", help="compare every AUROC of the harness with sklearn's, bit for bit")
     a = ap.parse_args()
 
     from nasrec_amd import eval_subnet_from_supernet as E
@@ -80,25 +84,41 @@ def main():
     phase = {}
     real_train, real_test, real_auroc = E.train_and_test_one_epoch, TU.test_one_epoch, TU._auroc
 
+    def checked(t):  # wall time since t, less the --check_auroc recomputations made meanwhile
+        return time.perf_counter() - t - phase.get("auroc_check", 0.0)
+
     def timed_train(*x, **kw):
         torch.cuda.synchronize()
-        t = time.perf_counter()
+        t = time.perf_counter() - phase.get("auroc_check", 0.0)
         r = real_train(*x, **kw)
         torch.cuda.synchronize()
-        phase["train_and_test"] = time.perf_counter() - t
+        phase["train_and_test"] = checked(t)
         return r
 
     def timed_test(*x, **kw):
         torch.cuda.synchronize()
-        t = time.perf_counter()
+        t = time.perf_counter() - phase.get("auroc_check", 0.0)
         r = real_test(*x, **kw)
         torch.cuda.synchronize()
-        phase["test"] = phase.get("test", 0.0) + time.perf_counter() - t
+        phase["test"] = phase.get("test", 0.0) + checked(t)
         return r
-    def timed_auroc(*x, **kw):  # (AUROC on the host, sklearn: part of the evaluation phase)
+    auroc_checks = []
+
+    def timed_auroc(*x, **kw):  # (part of the evaluation phase)
+        # the host reaches the AUROC while evaluation forwards are still queued: that wait is timed on its own ("auroc_wait"), so that
+        # the AUROC alone is "auroc" and wait + AUROC is what this phase measured when the AUROC ran on the host (its .cpu() waited)
+        t0 = time.perf_counter()
+        torch.cuda.synchronize()
         t = time.perf_counter()
+        phase["auroc_wait"] = phase.get("auroc_wait", 0.0) + t - t0
         r = real_auroc(*x, **kw)
-        phase["auroc"] = phase.get("auroc", 0.0) + time.perf_counter() - t
+        t1 = time.perf_counter()
+        phase["auroc"] = phase.get("auroc", 0.0) + t1 - t
+        if a.check_auroc:
+            import sklearn.metrics
+            want = sklearn.metrics.roc_auc_score(x[0].detach().cpu().numpy(), x[1].detach().cpu().numpy())
+            auroc_checks.append((float(r).hex() == float(want).hex(), x[1].is_cuda, x[1].numel()))
+            phase["auroc_check"] = phase.get("auroc_check", 0.0) + time.perf_counter() - t1
         return r
     E.train_and_test_one_epoch = timed_train
     TU.test_one_epoch = timed_test
@@ -126,7 +146,7 @@ def main():
             pstats.Stats(prof, stream=buf).sort_stats("cumulative").print_stats(45)
             print(buf.getvalue())
         torch.cuda.synchronize()
-        total = time.perf_counter() - t
+        total = checked(t)
         tr = phase.get("train_and_test", 0.0) - phase.get("test", 0.0)
         rows.append((total, total - phase.get("train_and_test", 0.0), tr, phase.get("test", 0.0), res["test_loss"][-1], res["test_auroc"][-1]))
         print("candidate %d: %.2f s = set-up (build, full-path warm-up, checkpoint load) %.2f + %d training steps %.2f (%.3f ms/step, %.0f samples/s) "
@@ -158,14 +178,15 @@ def main():
             t = time.perf_counter()
             res = R.evaluate_candidate(ev, tok, None, {"beta": 0.0})
             torch.cuda.synchronize()
-            total = time.perf_counter() - t
+            total = checked(t)
             tt = phase.get("train_and_test", 0.0)
             te = phase.get("test", 0.0)
             rrows.append(total)
             print("resident candidate %d: %.2f s = restore + optimizer %.3f + %d fused last-layer steps %.2f (%.3f ms/step) + %d evaluation batches %.2f "
-                  "(%.2f ms/batch; AUROC on the host %.3f s = %.0f %% of the candidate);  test loss %.4f AUROC %.4f" % (
+                  "(%.2f ms/batch; AUROC %.3f s = %.1f %% of the candidate, after %.3f s waiting for the queued forwards);  test loss %.4f AUROC %.4f" % (
                       c, total, total - tt, a.train_steps, tt - te, (tt - te) / a.train_steps * 1e3, a.eval_steps, te, te / a.eval_steps * 1e3,
-                      phase.get("auroc", 0.0), 100.0 * phase.get("auroc", 0.0) / total, res["test_loss"][-1], res["test_auroc"][-1]))
+                      phase.get("auroc", 0.0), 100.0 * phase.get("auroc", 0.0) / total, phase.get("auroc_wait", 0.0), res["test_loss"][-1],
+                      res["test_auroc"][-1]))
         R.train_and_test_one_epoch = real_rtrain
         use = rrows[1:] if len(rrows) > 1 else rrows
         rmean = float(np.mean(use))
@@ -196,6 +217,9 @@ def main():
         ev.close()
         del ev
     E.train_and_test_one_epoch, TU.test_one_epoch, TU._auroc = real_train, real_test, real_auroc
+    if a.check_auroc:
+        print("AUROC calls of the harness: %d (%d on the GPU, sizes %s); bit-identical to sklearn on host copies: %d" % (
+            len(auroc_checks), sum(c[1] for c in auroc_checks), sorted({c[2] for c in auroc_checks}), sum(c[0] for c in auroc_checks)))
 
     if a.cli:
         cli_timings(a, args, ckpt, root)
