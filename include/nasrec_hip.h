@@ -474,7 +474,7 @@ typedef struct nasrec_weight_decay_desc {
   uint32_t reg_mask; /* bit f: table f is regularised */
   const int64_t* idx;    /* [B,Fs] */
   const int32_t* leader; /* [B,Fs] */
-  float* gsum;           /* [B,Fs,16], contiguous: a leader's row holds its summed gradient */
+  float* gsum;           /* [B,Fs,16] (layout: rank_B below): a leader's row holds its summed gradient */
   float* table[NASREC_MAX_TABLES];
   float* state[NASREC_MAX_TABLES];
   int64_t rows[NASREC_MAX_TABLES];
@@ -492,6 +492,9 @@ typedef struct nasrec_weight_decay_desc {
   double* l2_sumsq;      /* [1] */
   const float* lr;       /* device scalars (phase 1) */
   const float* coef;
+  int32_t rank_B;        /* layout of `gsum` as in nasrec_adagrad_rows_desc_t: 0 = one contiguous [B,Fs,16] array; > 0 = the receive */
+  int32_t _pad;          /*   buffer of an all-gather, rank_B samples per rank chunk, chunks rank_stride floats apart (phase 0 reads and */
+  int64_t rank_stride;   /*   writes a leader's row where it lies: the same bits whichever layout holds the rows) */
 } nasrec_weight_decay_desc_t;
 
 /* ------------------------------------------------------------------------------------------------
@@ -533,7 +536,7 @@ typedef struct nasrec_opt_moments_desc {
   float* v;
   const int64_t* idx;    /* [B,Fs] */
   const int32_t* leader; /* [B,Fs] */
-  const float* gsum;     /* [B,Fs,16]: a leader's row holds its summed gradient */
+  const float* gsum;     /* [B,Fs,16] (layout: rank_B below): a leader's row holds its summed gradient */
   float* table[NASREC_MAX_TABLES];
   float* tm[NASREC_MAX_TABLES];
   float* tv[NASREC_MAX_TABLES];
@@ -548,6 +551,9 @@ typedef struct nasrec_opt_moments_desc {
   uint32_t* counter;
   const float* lr;       /* device scalars */
   const float* coef;     /* phase 1: clip.out of phase 0 */
+  int32_t rank_B;        /* layout of `gsum` (phase 0) as in nasrec_adagrad_rows_desc_t: 0 = contiguous [B,Fs,16]; > 0 = rank_B */
+  int32_t _pad2;         /*   samples per rank chunk of an all-gather's receive buffer, chunks rank_stride floats apart */
+  int64_t rank_stride;
 } nasrec_opt_moments_desc_t;
 
 /* ------------------------------------------------------------------------------------------------

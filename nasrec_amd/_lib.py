@@ -240,7 +240,7 @@ class WeightDecayDesc(C.Structure):
                 ("idx", vp), ("leader", vp), ("gsum", vp), ("table", vp * MAX_TABLES), ("state", vp * MAX_TABLES), ("rows", i64 * MAX_TABLES),
                 ("tile_off", i64 * (MAX_TABLES + 1)), ("bitmap", vp), ("p", vp), ("g", vp), ("add_chunks", vp), ("n_add", i64),
                 ("set_chunks", vp), ("n_set", i64), ("block_part", vp), ("counter", vp), ("clip_partial", vp), ("l2_sumsq", vp),
-                ("lr", vp), ("coef", vp)]
+                ("lr", vp), ("coef", vp), ("rank_B", i32), ("_pad", i32), ("rank_stride", i64)]
 
 
 class OptMomentsDesc(C.Structure):
@@ -250,7 +250,7 @@ class OptMomentsDesc(C.Structure):
                 ("g", vp), ("m", vp), ("v", vp), ("idx", vp), ("leader", vp), ("gsum", vp), ("table", vp * MAX_TABLES),
                 ("tm", vp * MAX_TABLES), ("tv", vp * MAX_TABLES), ("rows", i64 * MAX_TABLES), ("tile_off", i64 * (MAX_TABLES + 1)),
                 ("bitmap", vp), ("step", vp), ("inc", vp), ("n_inc", i64), ("zero_chunks", vp), ("n_zero", i64), ("counter", vp),
-                ("lr", vp), ("coef", vp)]
+                ("lr", vp), ("coef", vp), ("rank_B", i32), ("_pad2", i32), ("rank_stride", i64)]
 
 
 class LastLayerStepDesc(C.Structure):

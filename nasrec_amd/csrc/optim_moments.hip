@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void opt_moments_phase0_kernel(const nasrec_op
   const long row = d.idx[pair];
   if (row < 0 || row >= d.rows[f]) return;  // (flagged by the gather; never written outside a table)
   const long o = row * 16 + q * 4;
-  f32x4 g4 = *reinterpret_cast<const f32x4*>(d.gsum + pair * 16 + q * 4);
+  f32x4 g4 = *reinterpret_cast<const f32x4*>(d.gsum + gsum_row_offset(pair, d.Fs, d.rank_B, d.rank_stride) + q * 4);
   f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o), m4 = *reinterpret_cast<const f32x4*>(d.tm[f] + o), v4 = {};
   if (ALGO == NASREC_OPTIM_ADAM) v4 = *reinterpret_cast<const f32x4*>(d.tv[f] + o);
   g4 *= coef;
@@ -159,6 +159,8 @@ int launch_phases(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
     const int nrows = (int)((threads + 255) / 256);
     if (d->dense_blocks < 0 || d->dense_blocks + nrows < 1) return nasrec_set_error(-2, "opt_moments: empty launch");
     if (nrows > 0 && (!d->idx || !d->leader || !d->gsum || !d->bitmap)) return nasrec_set_error(-1, "opt_moments: row inputs missing");
+    if (d->rank_B < 0 || (d->rank_B > 0 && (d->rank_stride < (int64_t)d->rank_B * d->Fs * 16 || d->B % d->rank_B != 0)))
+      return nasrec_set_error(-2, "opt_moments: rank layout %d / %ld", d->rank_B, (long)d->rank_stride);
     hipLaunchKernelGGL(opt_moments_phase0_kernel<ALGO>, dim3((unsigned)(d->dense_blocks + nrows)), dim3(256), 0, st, *d);
   } else if (d->phase == 1) {
     if (d->nblocks <= 0) return nasrec_set_error(-1, "opt_moments: nblocks must be positive");

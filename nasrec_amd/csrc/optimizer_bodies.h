@@ -3,6 +3,16 @@
 #pragma once
 #include "common.h"
 
+// row of (sample, field) pair `pair` in per-sample row gradients: one contiguous [B,Fs,16] array (rank_B = 0), or the receive buffer
+// of an all-gather whose per-rank chunks of rank_B samples lie rank_stride floats apart (dd_row, dedup_bodies.h: the same mapping)
+__device__ __forceinline__ long gsum_row_offset(long pair, int Fs, int rank_B, long rank_stride) {
+  if (rank_B > 0) {
+    const long b = pair / Fs, f = pair - b * Fs, r = b / rank_B;
+    return r * rank_stride + ((b - r * rank_B) * Fs + f) * 16;
+  }
+  return pair * 16;
+}
+
 // sum of squares of x[0, n) (or of the chunk table's ranges): workgroup `blk` of `nblk` (256 threads), fixed-order tree -> partial[blk]
 __device__ __forceinline__ void sumsq_body(const nasrec_sumsq_desc_t& d, int blk, int nblk, float* red) {
   const int tid = threadIdx.x;

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void weight_decay_phase0_kernel(const nasrec_w
     const long row = d.idx[pair];
     if (row < 0 || row >= d.rows[f]) continue;  // (flagged by the gather; never read outside a table)
     const f32x4 w = *reinterpret_cast<const f32x4*>(d.table[f] + row * 16 + q * 4);
-    f32x4* gp = reinterpret_cast<f32x4*>(d.gsum + pair * 16 + q * 4);
+    f32x4* gp = reinterpret_cast<f32x4*>(d.gsum + gsum_row_offset(pair, d.Fs, d.rank_B, d.rank_stride) + q * 4);  // (read and written in place)
     const f32x4 g0 = *gp;
     f32x4 g1;
 #pragma unroll
@@ -173,6 +173,8 @@ int launch_weight_decay(hipStream_t st, const nasrec_weight_decay_desc_t* d) {
   if (d->Fs < 0 || d->Fs > NASREC_MAX_TABLES) return nasrec_set_error(-1, "weight_decay: Fs = %d", d->Fs);
   if (d->phase == 0) {
     if (!d->block_part || !d->counter || !d->clip_partial || !d->l2_sumsq) return nasrec_set_error(-1, "weight_decay: phase 0 outputs missing");
+    if (d->rank_B < 0 || (d->rank_B > 0 && (d->rank_stride < (int64_t)d->rank_B * d->Fs * 16 || d->B % d->rank_B != 0)))
+      return nasrec_set_error(-2, "weight_decay: rank layout %d / %ld", d->rank_B, (long)d->rank_stride);
     hipLaunchKernelGGL(weight_decay_phase0_kernel, dim3((unsigned)d->nblocks), dim3(256), 0, st, *d);
   } else if (d->phase == 1) {
     if ((d->Fs == 0 || d->tile_off[d->Fs] == 0) && d->n_set == 0) return 0;

@@ -368,15 +368,17 @@ class SupernetEngine:
         hands in the head of its all-gather send buffer: no copy between the backward and the exchange); local_optimizer = False: the
         plan gets no clip + Adagrad program of its own (a data-parallel step runs its optimizer over the GLOBAL batch).
         weight_decay != 0: the training step adds get_l2_loss(model, weight_decay, no_reg_param_name)'s gradient (_weight_decay_descs).
-        optim: None = Adagrad (eps); an OptimSpec (nasrec_amd/optim_spec.py) of kind adam / sgd = that optimizer (_moments_descs)"""
+        optim: None = Adagrad (eps); an OptimSpec (nasrec_amd/optim_spec.py) of kind adam / sgd = that optimizer (_moments_descs).
+        With local_optimizer = False both only shape the plan's chunk tables (_weight_decay_tables, _moments_tables), which the
+        data-parallel optimizer program reads (parallel.EngineDP.dp_optimizer)"""
         rgo = row_grad_out.data_ptr() if row_grad_out is not None else None
         weight_decay = float(weight_decay or 0.0)
         wd_key = (weight_decay, no_reg_param_name) if weight_decay else None
-        if weight_decay and not (train and local_optimizer):
-            raise L.EngineError("weight decay is part of the fused training step's optimizer: it needs train=True, local_optimizer=True")
+        if weight_decay and not train:
+            raise L.EngineError("weight decay is part of the fused training step's optimizer: it needs train=True")
         mom = tuple(optim) if optim is not None else None
-        if mom is not None and not (train and local_optimizer):
-            raise L.EngineError("Adam / SGD are the fused training step's optimizer: they need train=True, local_optimizer=True")
+        if mom is not None and not train:
+            raise L.EngineError("Adam / SGD are the fused training step's optimizer: they need train=True")
         fast = (id(choice), B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, wd_key, mom)
         hit = self._last_plan
         if self.cfg.fixed and hit is not None and hit[0] == fast and hit[1] is choice:  # fixed sub-network, same choice object: skip the JSON key
@@ -849,8 +851,9 @@ class SupernetEngine:
         cp.mom_inc = (tab.data_ptr() + 8 * len(trip), len(inc))
         cp.mom_names = names
 
-    def _moments_descs(self, cp, Bg, cat_x, gsum, clip_desc):
-        """the two NASREC_OP_OPT_MOMENTS launches of a plan with Adam / SGD: (phase 0 in place of the Adagrad apply launch, phase 1)"""
+    def _moments_descs(self, cp, Bg, cat_x, gsum, clip_desc, rank_layout=None):
+        """the two NASREC_OP_OPT_MOMENTS launches of a plan with Adam / SGD: (phase 0 in place of the Adagrad apply launch, phase 1).
+        rank_layout: (samples per rank, floats between the ranks' chunks) of `gsum` (_optimizer_descs)"""
         o = cp.mom
         st = self.moments
         m = L.OptMomentsDesc()
@@ -871,6 +874,8 @@ class SupernetEngine:
         m.v = second[0].data_ptr() if second is not None else None
         if gsum is not None:
             m.idx, m.leader, m.gsum = cat_x.data_ptr(), cp.leader.data_ptr(), gsum
+            if rank_layout:
+                m.rank_B, m.rank_stride = rank_layout
         mask, t = 0, 0
         for f in range(self.Fs):
             m.table[f], m.tm[f], m.rows[f] = self.tables[f].data_ptr(), first[1][f].data_ptr(), self.num_embeddings[f]
@@ -894,14 +899,17 @@ class SupernetEngine:
         m1.phase = 1
         return [m, m1]
 
-    def _weight_decay_descs(self, cp, Bg, cat_x, gsum, eps, clip_partial):
-        """the two NASREC_OP_WEIGHT_DECAY launches of a plan: (phase 0, in front of the clip; phase 1, behind the touched rows' Adagrad)"""
+    def _weight_decay_descs(self, cp, Bg, cat_x, gsum, eps, clip_partial, rank_layout=None):
+        """the two NASREC_OP_WEIGHT_DECAY launches of a plan: (phase 0, in front of the clip; phase 1, behind the touched rows' Adagrad).
+        rank_layout: (samples per rank, floats between the ranks' chunks) of `gsum` (_optimizer_descs)"""
         w = L.WeightDecayDesc()
         w.kind, w.phase, w.nblocks = L.OP_WEIGHT_DECAY, 0, self.WD_BLOCKS
         w.wd, w.eps = cp.wd, eps
         w.B, w.Fs = (Bg, self.Fs) if gsum is not None else (0, self.Fs)
         if gsum is not None:
             w.idx, w.leader, w.gsum = cat_x.data_ptr(), cp.leader.data_ptr(), gsum
+            if rank_layout:
+                w.rank_B, w.rank_stride = rank_layout
         mask, t = 0, 0
         for f in range(self.Fs):
             w.table[f], w.rows[f] = self.tables[f].data_ptr(), self.num_embeddings[f]
@@ -930,7 +938,9 @@ class SupernetEngine:
     def _optimizer_descs(self, cp, Bg, cat_x, sparse_grad, clip, eps, rank_layout=None):
         """clip_grad_norm_ + Adagrad (train_utils.py:285-286): row-sparse on the tables, flat on the dense arena.
         rank_layout (data-parallel step): (samples per rank, floats between the ranks' chunks) of `sparse_grad` when it is the receive
-        buffer of an all-gather that carries more than the rows (parallel.py); None = one contiguous [Bg, Fs, 16] array.
+        buffer of an all-gather that carries more than the rows (parallel.py); None = one contiguous [Bg, Fs, 16] array.  Weight decay and
+        Adam / SGD read and write the summed rows where the dedup left them: in that layout (Bg <= DEDUP_SPLIT_MAX_B, summed in place) or
+        in the contiguous gsum (the one-launch kernels).
         Leaves `cp.dedup_ids` (the id-only half of the row dedup, to be launched once the ids are in `cat_x`) or None."""
         descs = []
         cp.dedup_ids = None
@@ -969,11 +979,7 @@ class SupernetEngine:
         cc.partial_a, cc.partial_b, cc.out = cp.dense_partial.data_ptr(), cp.emb_partial.data_ptr(), self.clip_out.data_ptr()
         wd = getattr(cp, "wd", 0.0)
         mom = getattr(cp, "mom", None)
-        if mom is not None and rank_layout:
-            raise L.EngineError("Adam / SGD in the fused step cover one process (data-parallel runs take the torch route)")
         if wd:
-            if rank_layout:
-                raise L.EngineError("weight decay: the fused step covers one process (data-parallel runs take the torch route)")
             cc.n_a = nblk + 1  # partial_a[nblk]: what the L2 gradient adds to the norm's sum of squares (weight-decay phase 0)
             wd_part = cp.dense_partial.data_ptr() + 4 * nblk
         descs.append(cc)
@@ -1038,12 +1044,12 @@ class SupernetEngine:
                 app.rows.gsum = sparse_grad.data_ptr()  # summed in place: a leader's row holds its sum
                 app.rows.rank_B, app.rows.rank_stride = r2.rank_B, r2.rank_stride
                 if mom is not None:
-                    tail = self._moments_descs(cp, Bg, cat_x, sparse_grad.data_ptr(), app.clip)
+                    tail = self._moments_descs(cp, Bg, cat_x, sparse_grad.data_ptr(), app.clip, rank_layout)
                     if wd:
-                        return [r2, self._weight_decay_descs(cp, Bg, cat_x, sparse_grad.data_ptr(), eps, wd_part)[0]] + tail
+                        return [r2, self._weight_decay_descs(cp, Bg, cat_x, sparse_grad.data_ptr(), eps, wd_part, rank_layout)[0]] + tail
                     return [r2] + tail
                 if wd:
-                    w0, w1 = self._weight_decay_descs(cp, Bg, cat_x, sparse_grad.data_ptr(), eps, wd_part)
+                    w0, w1 = self._weight_decay_descs(cp, Bg, cat_x, sparse_grad.data_ptr(), eps, wd_part, rank_layout)
                     return [r2, w0, app, w1]
                 return [r2, app]
             if rank_layout:  # (the one-launch kernels read the rows where the all-gather left them; their sums go to the contiguous gsum)

@@ -168,9 +168,10 @@ def build_parser():
     p.add_argument("--gpu", type=int, default=None, help="GPU ID to use.")
     # not a reference flag: placement of the embedding tables under torchrun (nasrec_amd/sharded_tables.py)
     p.add_argument("--table-sharding", dest="table_sharding", type=str, default="none", choices=["none", "row"],
-                   help="none: every rank holds whole tables (replicated, row gradients all-gathered); row: every rank owns a row range "
-                        "of every table, ids / rows / row gradients travel by all-to-all (tables that outgrow one GPU).  Needs the fused "
-                        "step: --optimizer adagrad --wd 0")
+                   help="none: every rank holds whole tables (replicated, row gradients all-gathered; the fused step covers "
+                        "--optimizer adagrad / adam / sgd with any --wd); row: every rank owns a row range of every table, ids / rows / "
+                        "row gradients travel by all-to-all (tables that outgrow one GPU).  Row sharding needs the fused step's "
+                        "--optimizer adagrad --wd 0")
     return p
 
 

@@ -1,7 +1,8 @@
 """What the fused engine step needs to know about the torch optimizer it stands in for (main_train.py:150-160).
 
 `OptimSpec.from_optimizer` answers which torch optimizers the fused step reproduces: torch.optim.Adam and torch.optim.SGD with
-momentum, under the conditions listed there.  Adagrad keeps its own checks (utils/train_utils.py: _fused_step_applies)."""
+momentum, under the conditions listed there, in one process or in every rank of a data-parallel run with whole tables
+(nasrec_amd/parallel.py).  Adagrad keeps its own checks (utils/train_utils.py: _fused_step_applies)."""
 from typing import NamedTuple, Optional
 
 import torch

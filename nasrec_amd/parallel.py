@@ -12,7 +12,9 @@ local forward/backward:
     backward; parameters the path did not touch are zero on every rank and are not sent at all;
   * embedding gradients: all-gather of (ids [B,Fs] int64, per-sample row gradients [B,Fs,16]) — B_global·Fs·72 bytes,
     instead of all-reducing 2.16 GB of dense table gradient — then every rank runs the same row-sparse
-    dedup + clip + Adagrad over the global batch, so the replicated tables stay bit-identical across ranks;
+    dedup + clip + optimizer over the global batch, so the replicated tables stay bit-identical across ranks.  The optimizer is the
+    engine's fused one in every form it has: Adagrad, with or without L2 weight decay (`weight_decay`), or Adam / momentum SGD
+    (`optim`); weight decay's and the moments' passes over every table row run on every rank over the same bits;
   * the global-norm clip coefficient comes out identical on every rank because it is computed from identical data.
 Fixed sub-networks (batch 256, a 0.3 ms step): work handles cost ~40 us of host time per collective, more than the step can hide,
 so the WHOLE exchange step — launches, collectives on RCCL's stream and the event edges between the two streams — is captured
@@ -217,7 +219,8 @@ def tail_pieces(segments, budget: int) -> int:
 
 class DataParallelStep:
     def __init__(self, engine, choice, B_local: int, clip: Optional[float] = 5.0, eps: float = 1e-2, graph: Optional[bool] = True,
-                 force_exchange: bool = False, real_collectives: bool = False, paths: str = "shared"):
+                 force_exchange: bool = False, real_collectives: bool = False, paths: str = "shared", weight_decay: float = 0.0,
+                 no_reg_param_name: Optional[str] = None, optim=None):
         """choice: the fixed sub-network's choice, or None for a weight-sharing supernet (the path then comes with every step).
         force_exchange: take the multi-rank code path (all-reduce + all-gather + global-batch optimizer) even in a single-rank
         process group — lets one GPU exercise exactly what N GPUs run.
@@ -228,7 +231,9 @@ class DataParallelStep:
         EXTENSION of the reference) = every rank passes its OWN path to step(): the choices are exchanged first (one small
         all-gather), the dense gradients are all-reduced over the UNION of the ranks' parameter ranges — a parameter's gradient is the
         sum over the ranks whose path used it, the others contribute zeros — and clip + Adagrad run over that union on every rank
-        (replicas stay bit-identical); parameters no rank's path touched keep value and state, as `grad is None` does in the reference."""
+        (replicas stay bit-identical); parameters no rank's path touched keep value and state, as `grad is None` does in the reference.
+        weight_decay / no_reg_param_name / optim: the engine's fused optimizer over the global batch (engine.train_step's arguments:
+        get_l2_loss's gradient; an OptimSpec of Adam / SGD in place of Adagrad) — not with paths="per-rank"."""
         self.engine = engine
         self.dp = engine if hasattr(engine, "dp_plan") else EngineDP(engine)
         self.world = dist.get_world_size() if dist.is_initialized() else 1
@@ -245,12 +250,23 @@ class DataParallelStep:
         assert paths in ("shared", "per-rank"), paths
         self.per_rank = paths == "per-rank"
         assert not (self.per_rank and self.fixed), "a fixed sub-network has one path"
+        # the optimizer's options, handed to the engine protocol only when they are not the defaults (engines that implement the
+        # protocol without them — tests/test_data_parallel_cpu.py — keep working)
+        weight_decay = float(weight_decay or 0.0)
+        self.opt_kw = {}
+        if weight_decay:
+            self.opt_kw.update(weight_decay=weight_decay, no_reg_param_name=no_reg_param_name)
+        if optim is not None:
+            self.opt_kw["optim"] = optim
+        if self.per_rank and self.opt_kw:
+            from ._lib import EngineError
+            raise EngineError('paths="per-rank" runs Adagrad without weight decay: weight decay, Adam and SGD need every rank on the same path')
         self._last = None
         self._plans = {}
         self._last_key = None
         if not self.exchange:
             if self.fixed:
-                self.cp = engine.compile(choice, B_local, True, clip, eps, graph=self.graph)
+                self.cp = engine.compile(choice, B_local, True, clip, eps, graph=self.graph, **self.opt_kw)
             return
         Bg = B_local * self.world
         dev = engine.device
@@ -285,7 +301,7 @@ class DataParallelStep:
             kw = {}
             if self.fixed and self.sg_send.numel() > self.rows_n and getattr(self.dp, "accepts_row_grad_out", False):
                 kw["row_grad_out"] = self.sg_send[:self.rows_n]  # the backward writes the row gradients where the gather sends them from
-            hit = self.dp.dp_plan(choice, self.B, 1.0 / (self.B * self.world), self.clip, self.eps, False, **kw)
+            hit = self.dp.dp_plan(choice, self.B, 1.0 / (self.B * self.world), self.clip, self.eps, False, **kw, **self.opt_kw)
             self._layout(hit)
             self._plans[key] = hit
         return hit
@@ -307,6 +323,10 @@ class DataParallelStep:
             cpl = getattr(plan, "cp", None)
             if self.fixed and getattr(self.dp, "accepts_chunk_table", False) and getattr(cpl, "chunk_tab", None) is not None:
                 kw["chunk_table"] = (cpl.chunk_tab, cpl.nchunks)  # norm + Adagrad over the ranges the sub-network's backward reaches
+            if self.opt_kw:
+                kw.update(self.opt_kw)
+                if getattr(self.dp, "accepts_chunk_table", False):
+                    kw["plan_tables"] = cpl  # weight decay's / the moments' chunk tables of the first plan (a fixed sub-network's for good)
             self.recv = self.sg_recv[:self.world * stride]
             self.opt = self.dp.dp_optimizer(self.B * self.world, self.cat_all, self.recv, self.clip, self.eps, False, **kw)  # (graph: the whole exchange step is captured as one, _capture)
             self.ids_half = getattr(self.dp, "dp_dedup_ids", lambda: None)()
@@ -321,7 +341,7 @@ class DataParallelStep:
         eng = self.engine
         choice = choice if choice is not None else self.choice
         if not self.exchange:
-            loss = eng.train_step(int_x, cat_x, y, lr, choice, self.clip, self.eps, graph=self.graph)
+            loss = eng.train_step(int_x, cat_x, y, lr, choice, self.clip, self.eps, graph=self.graph, **self.opt_kw)
             self._last = ("plain", choice, int(int_x.shape[0]))
             return loss
         union = None
@@ -481,8 +501,8 @@ class DataParallelStep:
         and the engine launches on whatever stream is current — inside the capture that is the capturing stream).  Returns False when
         the platform refuses (the step then runs eagerly, same results)."""
         dev = self.engine.device
-        if dev.type != "cuda":
-            return False
+        if dev.type != "cuda" or dist.get_backend() != "nccl":
+            return False  # (gloo moves device tensors through the host: its collectives cannot be captured, the step runs eagerly)
         # communicators are created lazily by the first collective of each kind, which must not happen inside a capture
         w0 = torch.zeros(8, device=dev)
         w1 = torch.zeros(8 * self.world, device=dev)
@@ -511,7 +531,7 @@ class DataParallelStep:
         if self._last[0] == "dp":
             return self._last[1].cp
         _, choice, B = self._last
-        return self.engine.compile(choice, B, True, self.clip, self.eps, graph=self.graph)
+        return self.engine.compile(choice, B, True, self.clip, self.eps, graph=self.graph, **self.opt_kw)
 
 
 def _torch_tail_ops(flat_g, send, recv, rows_n, tail, world):
@@ -546,14 +566,31 @@ class EngineDP:
         self.engine = engine
         self._holder = None
 
-    def dp_optimizer(self, Bg, cat_all, sg_all, clip, eps, graph, rank_layout=None, chunk_table=None):
+    # what the optimizer program of a plan with weight decay / Adam / SGD reads off the plan (engine._weight_decay_tables, _moments_tables)
+    PLAN_TABLES = ("wd_add", "wd_set", "wd_union", "wd_tables", "wd_tab", "mom_chunks", "mom_inc", "mom_tables", "mom_tab")
+
+    @classmethod
+    def _take_plan_tables(cls, holder, cp, weight_decay, no_reg_param_name, optim):
+        holder.wd, holder.no_reg, holder.mom = float(weight_decay or 0.0), no_reg_param_name, optim
+        if holder.wd or optim is not None:
+            assert cp is not None and cp.wd == holder.wd and cp.mom == optim, "the plan was compiled for another optimizer"
+            for k in cls.PLAN_TABLES:
+                if hasattr(cp, k):
+                    setattr(holder, k, getattr(cp, k))
+
+    def dp_optimizer(self, Bg, cat_all, sg_all, clip, eps, graph, rank_layout=None, chunk_table=None, weight_decay=0.0,
+                     no_reg_param_name=None, optim=None, plan_tables=None):
+        """the optimizer over the global batch.  weight_decay / no_reg_param_name / optim: as engine.compile; plan_tables: the
+        CompiledPlan whose chunk tables they read (a fixed sub-network: its one plan; sampled paths: every step takes its own plan's)"""
         from .engine import Program
         eng = self.engine
         with torch.cuda.stream(eng.stream):
             holder = self._holder = _Holder()
             if chunk_table is not None:
                 holder.chunk_tab, holder.nchunks = chunk_table
-            eng._ensure_table_state()
+            self._take_plan_tables(holder, plan_tables, weight_decay, no_reg_param_name, optim)
+            if optim is None:  # (Adagrad's table state: Adam / SGD keep theirs in engine.moments)
+                eng._ensure_table_state()
             prog = Program(eng._optimizer_descs(holder, Bg, cat_all, sg_all, clip, eps, rank_layout=rank_layout))
             prog.holder = holder
             if graph:
@@ -593,6 +630,7 @@ class EngineDP:
                     if hasattr(holder, k):
                         setattr(h, k, getattr(holder, k))
                 h.chunk_tab, h.nchunks = plan.cp.chunk_tab, plan.cp.nchunks
+                self._take_plan_tables(h, plan.cp, weight_decay, no_reg_param_name, optim)
                 plan.opt_prog = Program(eng._optimizer_descs(h, Bg, cat_all, sg_all, clip, eps, rank_layout=rank_layout))
                 plan.opt_prog.holder = h
             plan.opt_prog.run(eng._sp())
@@ -641,14 +679,16 @@ class EngineDP:
         keep = (cs, rr)
         return (lambda: L.check(lib.nasrec_launch(eng._sp(), C.addressof(keep[0])))), (lambda: L.check(lib.nasrec_launch(eng._sp(), C.addressof(keep[1]))))
 
-    def dp_plan(self, choice, B, grad_scale, clip, eps, graph, row_grad_out=None) -> DPPlan:
+    def dp_plan(self, choice, B, grad_scale, clip, eps, graph, row_grad_out=None, weight_decay=0.0, no_reg_param_name=None,
+                optim=None) -> DPPlan:
         from .engine import Program
         eng = self.engine
         fixed = eng.cfg.fixed
         # weight-gradient products stay in backward order (never parked behind the backward): a block's gradients are complete when
         # its backward is, and can travel under the blocks that follow
         # (local_optimizer = False: clip + Adagrad of a data-parallel step run over the GLOBAL batch, dp_optimizer)
-        cp = eng.compile(choice, B, True, clip, eps, graph=False, grad_scale=grad_scale, defer_dw=False, row_grad_out=row_grad_out, local_optimizer=False)
+        cp = eng.compile(choice, B, True, clip, eps, graph=False, grad_scale=grad_scale, defer_dw=False, row_grad_out=row_grad_out, local_optimizer=False,
+                         weight_decay=weight_decay, no_reg_param_name=no_reg_param_name, optim=optim)
         plan = DPPlan()
         plan.cp = cp
         plan.cat_local, plan.loss = cp.cat_x, cp.loss

@@ -160,6 +160,10 @@ class ShardEmbedding(nn.Embedding):
 class SuperNet(nn.Module):
     """Top-level supernet (supernet.py:210-880)."""
 
+    # engine_train_step runs weight decay and Adam / SGD inside the data-parallel exchange step when the process group has several
+    # ranks (DataParallelStep's optimizer over the global batch): utils/train_utils._fused_step_applies may pick the fused route there
+    engine_dp_optimizers = True
+
     def __init__(self, num_blocks: int, ops_config: Any, use_layernorm: bool, activation: str = "relu",
                  num_embeddings: List[int] = NUM_EMBEDDINGS_CRITEO, sparse_input_size: int = 26, embedding_dim: int = 16,
                  last_n_blocks_out: int = 1, path_sampling_strategy: str = "default", fixed: bool = False, fixed_choice: Any = None,
@@ -495,6 +499,8 @@ class SuperNet(nn.Module):
 
     def __deepcopy__(self, memo):
         eng, names, sh = self._engine, self._param_names, (self._sharded, self._sharded_ops, self.__dict__.pop("_sharded_step", None))
+        # (the data-parallel step cached by engine_train_step drives THIS model's engine: the copy builds its own when it trains)
+        dp = self.__dict__.pop("_dp_step", None)
         self._engine, self._param_names, self._sharded, self._sharded_ops = None, [], None, None
         try:
             cls = self.__class__
@@ -506,6 +512,8 @@ class SuperNet(nn.Module):
             self._engine, self._param_names, self._sharded, self._sharded_ops = eng, names, sh[0], sh[1]
             if sh[2] is not None:
                 self.__dict__["_sharded_step"] = sh[2]
+            if dp is not None:
+                self.__dict__["_dp_step"] = dp
         return new  # the copy re-binds its own engine at its next forward
 
     def to(self, *args, **kwargs):
@@ -603,9 +611,10 @@ class SuperNet(nn.Module):
         """Fused step on the engine (forward, BCE, backward, clip_grad_norm_, Adagrad with row-sparse table update):
         the counterpart of train_utils.py:262-286 for optimizer == Adagrad (torch's own weight_decay == 0).  weight_decay != 0: the loss
         is BCE + get_l2_loss(self, weight_decay, no_reg_param_name) — every regularised parameter and every table row is decayed
-        (engine_last_l2 = that term on the pre-step weights); one process with whole tables only.  optim: an OptimSpec
-        (nasrec_amd/optim_spec.py) of torch.optim.Adam / SGD replaces Adagrad (eps unused) — every table row moves every step; one process
-        with whole tables only; engine_bind_optimizer / engine_sync_optimizer_steps share its state with the torch optimizer."""
+        (engine_last_l2 = that term on the pre-step weights).  optim: an OptimSpec (nasrec_amd/optim_spec.py) of torch.optim.Adam / SGD
+        replaces Adagrad (eps unused) — every table row moves every step; engine_bind_optimizer / engine_sync_optimizer_steps share its
+        state with the torch optimizer.  Both need whole tables; under data parallelism they run in the exchange step's optimizer over
+        the global batch (nasrec_amd/parallel.py)."""
         if self._place_embedding_on_cpu:
             from .._lib import EngineError
             raise EngineError("engine_train_step needs the tables on the device; with place_embedding_on_cpu use forward / backward "
@@ -624,14 +633,13 @@ class SuperNet(nn.Module):
         d["_last_step_last_layer"] = False
         d["_last_step_wd"] = (weight_decay, no_reg_param_name)
         d["_last_step_optim"] = optim
+        opt_kw = {}
         if weight_decay or optim is not None:
-            import torch.distributed as dist
-            if self._table_sharding == "row" or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            if self._table_sharding == "row":
                 from .._lib import EngineError
-                raise EngineError("weight decay, Adam and SGD in the fused step cover one process with whole tables: row-sharded tables "
-                                  "and data-parallel runs train them through the torch route")
-            return self._engine.train_step(int_feats, cat_feats, y, lr, choice, clip, eps, graph=graph, weight_decay=weight_decay,
-                                           no_reg_param_name=no_reg_param_name, optim=optim)
+                raise EngineError("weight decay, Adam and SGD in the fused step need whole tables: row-sharded tables train them "
+                                  "through the torch route")
+            opt_kw = dict(weight_decay=weight_decay, no_reg_param_name=no_reg_param_name, optim=optim)
         if self._table_sharding == "row":
             from ..sharded_tables import ShardedTableStep
             st = self.__dict__.get("_sharded_step")
@@ -645,12 +653,13 @@ class SuperNet(nn.Module):
             # one process per GPU (utils/dist.py): the batch is this rank's share of the global batch; same path on every rank
             from ..parallel import DataParallelStep
             dp = self.__dict__.get("_dp_step")
-            key = (id(self._engine), int(int_feats.shape[0]), clip, eps, graph)
+            key = (id(self._engine), int(int_feats.shape[0]), clip, eps, graph, weight_decay, no_reg_param_name, optim)
             if dp is None or dp[0] != key:
-                dp = (key, DataParallelStep(self._engine, choice if self._fixed else None, int(int_feats.shape[0]), clip=clip, eps=eps, graph=graph))
+                dp = (key, DataParallelStep(self._engine, choice if self._fixed else None, int(int_feats.shape[0]), clip=clip, eps=eps, graph=graph,
+                                            **opt_kw))
                 self.__dict__["_dp_step"] = dp
             return dp[1].step(int_feats, cat_feats, y, lr, choice=None if self._fixed else choice)
-        return self._engine.train_step(int_feats, cat_feats, y, lr, choice, clip, eps, graph=graph)
+        return self._engine.train_step(int_feats, cat_feats, y, lr, choice, clip, eps, graph=graph, **opt_kw)
 
     def _last_layer_only(self):
         """set_mode_to_finelune_last_only: every parameter outside _final is frozen"""

@@ -7,13 +7,14 @@ is `train_batch_size x world`, the path of a supernet step is drawn from an iden
 
 What keeps N replicas ONE model (each of these was a way to desynchronise silently):
   * `init_from_env` seeds torch (CPU + GPU generators) and np.random identically on every rank;
-  * `broadcast_replica_state` sends rank 0's parameters, tables and Adagrad accumulators to everybody after the weights are
-    initialised or loaded, and `assert_replicas_identical` checks a checksum of them before the first step;
+  * `broadcast_replica_state` sends rank 0's parameters, tables and optimizer state (Adagrad's accumulators; Adam's / SGD's moments
+    and step counters) to everybody after the weights are initialised or loaded, and `assert_replicas_identical` checks a checksum of
+    them before the first step;
   * `StepAgreement`: the ranks agree, one step ahead and off the compute stream, on whether EVERY rank holds a full batch for the
     next step — the epoch ends for all of them at the first step some rank cannot take (shards differ in length), so collectives
     never go unmatched;
-  * `allreduce_grads` averages the gradients on the torch route (weight decay, Adam / SGD, frozen-parameter modes), where the fused
-    engine step and its own exchange do not apply;
+  * `allreduce_grads` averages the gradients on the torch route (row-sharded tables with weight decay or Adam / SGD, frozen-parameter
+    modes, opaque loss terms), where the fused engine step and its own exchange do not apply;
   * `any_rank` makes the NaN exit collective."""
 import os
 
@@ -52,7 +53,8 @@ def world_info():
 
 
 def _replica_tensors(model):
-    """every tensor that defines a replica: parameters, buffers, and the engine's Adagrad accumulators once they exist"""
+    """every tensor that defines a replica: parameters, buffers, and the engine's optimizer state once it exists — Adagrad's
+    accumulators, Adam's / SGD's moments (flat arena and table arrays) and their step counters"""
     sharded = getattr(model, "_table_sharding", None) == "row"  # row-sharded tables: every rank owns DIFFERENT rows — not replica state
     out = [p.data for n, p in model.named_parameters() if not (sharded and n.startswith("_embedding."))] + [b.data for b in model.buffers()]
     eng = getattr(model, "_engine", None)
@@ -61,6 +63,12 @@ def _replica_tensors(model):
             out.append(eng.flat_s)
         for t in (getattr(eng, "table_state", None) or []):
             out.append(t)
+        for key in sorted(getattr(eng, "moments", None) or {}):
+            flat, tabs = eng.moments[key]
+            out.append(flat)
+            out.extend(tabs)
+        if getattr(eng, "opt_steps", None) is not None:
+            out.append(eng.opt_steps)
     return out
 
 
@@ -99,7 +107,7 @@ def assert_replicas_identical(model):
 def allreduce_grads(model):
     """torch route under data parallelism: average every existing gradient over the ranks (dense tensors, bucketed).  The ranks run
     the same path, so the `grad is None` sets agree.  The tables' dense gradients travel too — correct and slow (2.16 GB on Criteo):
-    the fused engine step (Adagrad, no weight decay) exchanges row gradients instead."""
+    the fused engine step (Adagrad, Adam or SGD, with or without weight decay, whole tables) exchanges row gradients instead."""
     rank, world = world_info()
     if world <= 1:
         return

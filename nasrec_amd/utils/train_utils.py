@@ -134,17 +134,26 @@ def _last_layer_step_applies(model, optimizer, l2_loss_fn, use_amp):
     return OptimSpec.from_optimizer(optimizer) is not None
 
 
+def _whole_table_optimizers_apply(model) -> bool:
+    """weight decay and Adam / SGD in the fused step: whole tables, and one process — or several, when the model's engine_train_step
+    runs them inside its data-parallel exchange step (`engine_dp_optimizers`, SuperNet: nasrec_amd/parallel.py).  A model whose fused
+    step has no exchange for them would train every rank on its own share of the batch: the replicas would drift apart silently."""
+    if getattr(model, "_table_sharding", None) == "row":
+        return False
+    from .dist import world_info
+    return world_info()[1] <= 1 or bool(getattr(model, "engine_dp_optimizers", False))
+
+
 def _fused_step_applies(model, optimizer, l2_loss_fn, use_amp):
     if use_amp or not hasattr(model, "engine_train_step"):
         return False
     moments = None
     if type(optimizer) is not torch.optim.Adagrad:
-        # torch.optim.Adam / SGD with momentum (main_train.py:150-160) under the conditions of OptimSpec.from_optimizer, for one
-        # process holding whole tables (row-sharded tables and data-parallel runs keep the torch route)
+        # torch.optim.Adam / SGD with momentum (main_train.py:150-160) under the conditions of OptimSpec.from_optimizer, with whole
+        # tables (_whole_table_optimizers_apply); row-sharded tables keep the torch route
         from ..optim_spec import OptimSpec
-        from .dist import world_info
         moments = OptimSpec.from_optimizer(optimizer)
-        if moments is None or world_info()[1] > 1 or getattr(model, "_table_sharding", None) == "row":
+        if moments is None or not _whole_table_optimizers_apply(model):
             return False
     if getattr(model, "_place_embedding_on_cpu", False):
         return False  # the tables stay on the host: torch's optimizer updates them there
@@ -162,10 +171,9 @@ def _fused_step_applies(model, optimizer, l2_loss_fn, use_amp):
     if {id(p) for p in params} != {id(p) for p in optimizer.param_groups[0]["params"]}:
         return False
     if isinstance(l2_loss_fn, L2Loss) and l2_loss_fn.wd != 0:
-        # the engine folds the L2 term into its step — for one process holding whole tables (row-sharded tables and data-parallel runs
-        # keep the torch route with weight decay, as before)
-        from .dist import world_info
-        return world_info()[1] <= 1 and getattr(model, "_table_sharding", None) != "row"
+        # the engine folds the L2 term into its step — with whole tables (_whole_table_optimizers_apply); row-sharded tables keep the
+        # torch route with weight decay
+        return _whole_table_optimizers_apply(model)
     with torch.no_grad():
         return float(l2_loss_fn(model)) == 0.0
 
