@@ -8,6 +8,7 @@ row-sparsely (identical to the dense reference update when weight_decay == 0).
 
 There is no CPU path here: everything below needs the HIP library and a GPU.
 """
+import copy
 import ctypes as C
 import json
 import os
@@ -18,6 +19,7 @@ import torch
 from . import _lib as L
 from . import plan as P
 from . import schedule as S
+from .optim_spec import OptimSpec
 
 E = 16
 # largest (global) batch whose row-gradient dedup runs in two halves (csrc/dedup_bodies.h; <= L.DEDUP_IDS_MAX_B); 0 = the one-launch kernels
@@ -75,7 +77,37 @@ class Program:
 
 
 class CompiledPlan:
-    pass
+    # (the dense chunk table of the plan's optimizer tail, for reports: bench.py)
+    chunk_tab = property(lambda self: self.tail.chunk_tab)
+    nchunks = property(lambda self: self.tail.nchunks)
+
+
+class TailBuffers:
+    """work buffers of the optimizer tail (_optimizer_descs), allocated on first use: a plan's own, or one set that every program of a
+    data-parallel run shares (parallel.EngineDP).  Never replaced once set: the programs built earlier hold their raw addresses."""
+    leader = gsum = emb_partial = dense_partial = dd_order = dd_lists = dd_counts = dd_heads = emb_partial2 = None
+
+
+class OptimizerTail:
+    """What the clip + optimizer launches of a plan read besides the engine's own arrays: the optimizer (an OptimSpec), the chunk table of
+    the dense ranges the norm and the update walk (None: the whole arena), the plan's weight-decay / moments chunk tables and the work
+    buffers.  compile builds one per plan; a data-parallel optimizer runs over a plan's (`over`).  _optimizer_descs leaves `dedup_ids`
+    (the id-only half of the row dedup) or None."""
+    wd_add = wd_set = wd_union = wd_tab = mom_chunks = mom_inc = mom_tab = None  # (_weight_decay_tables, _moments_tables)
+    wd_tables = mom_tables = mom_names = ()
+
+    def __init__(self, spec, arena=None, chunks=(None, 0), bufs=None):
+        self.spec, self.arena = spec, arena
+        self.chunk_tab, self.nchunks = chunks
+        self.bufs = bufs if bufs is not None else TailBuffers()
+        self.dedup_ids = None
+
+    def over(self, chunks, bufs):
+        """this plan's optimizer and chunk tables over another dense chunk table and a data-parallel run's work buffers"""
+        t = copy.copy(self)
+        t.arena, t.bufs, t.dedup_ids = None, bufs, None
+        t.chunk_tab, t.nchunks = chunks
+        return t
 
 
 _ITEMSIZE = {torch.float32: 4, torch.int64: 8, torch.int32: 4, torch.uint8: 1, torch.float64: 8}
@@ -362,36 +394,33 @@ class SupernetEngine:
     @_on_device
     def compile(self, choice, B: int, train: bool, clip: Optional[float] = 5.0, eps: float = 1e-2, graph: bool = False,
                 grad_scale: Optional[float] = None, defer_dw: bool = True, row_grad_out: Optional[torch.Tensor] = None,
-                local_optimizer: bool = True, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None,
-                optim=None) -> CompiledPlan:
+                local_optimizer: bool = True, spec: Optional[OptimSpec] = None) -> CompiledPlan:
         """row_grad_out: storage [B * Fs * 16] the backward writes the per-sample embedding-row gradients into (a data-parallel step
         hands in the head of its all-gather send buffer: no copy between the backward and the exchange); local_optimizer = False: the
         plan gets no clip + Adagrad program of its own (a data-parallel step runs its optimizer over the GLOBAL batch).
-        weight_decay != 0: the training step adds get_l2_loss(model, weight_decay, no_reg_param_name)'s gradient (_weight_decay_descs).
-        optim: None = Adagrad (eps); an OptimSpec (nasrec_amd/optim_spec.py) of kind adam / sgd = that optimizer (_moments_descs).
-        With local_optimizer = False both only shape the plan's chunk tables (_weight_decay_tables, _moments_tables), which the
-        data-parallel optimizer program reads (parallel.EngineDP.dp_optimizer)"""
+        spec: the optimizer (nasrec_amd/optim_spec.py, OptimSpec.of); None = Adagrad with `eps`.  Weight decay adds get_l2_loss's
+        gradient (_weight_decay_descs), Adam / SGD replace Adagrad (_moments_descs).  With local_optimizer = False the spec only shapes
+        the plan's chunk tables (_weight_decay_tables, _moments_tables), which the data-parallel optimizer program reads
+        (parallel.EngineDP.dp_optimizer)"""
         rgo = row_grad_out.data_ptr() if row_grad_out is not None else None
-        weight_decay = float(weight_decay or 0.0)
-        wd_key = (weight_decay, no_reg_param_name) if weight_decay else None
-        if weight_decay and not train:
+        spec = spec if spec is not None else OptimSpec.of(eps)
+        if spec.wd and not train:
             raise L.EngineError("weight decay is part of the fused training step's optimizer: it needs train=True")
-        mom = tuple(optim) if optim is not None else None
-        if mom is not None and not train:
+        if spec.moments and not train:
             raise L.EngineError("Adam / SGD are the fused training step's optimizer: they need train=True")
-        fast = (id(choice), B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, wd_key, mom)
+        fast = (id(choice), B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, spec)
         hit = self._last_plan
         if self.cfg.fixed and hit is not None and hit[0] == fast and hit[1] is choice:  # fixed sub-network, same choice object: skip the JSON key
             return hit[2]
-        key = json.dumps([choice, B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, wd_key, mom], sort_keys=True,
+        key = json.dumps([choice, B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, spec], sort_keys=True,
                          default=_jsonable)
         if key in self._plans:
             self._last_plan = (fast, choice, self._plans[key])
             return self._plans[key]
         arena = None
         # (weight decay: the default launches — the persistent step is an opt-in that has not been built for it)
-        persist = bool(self.persist and self.level_schedule and self.cfg.fixed and B <= 256 and train and local_optimizer and not weight_decay
-                       and mom is None)
+        persist = bool(self.persist and self.level_schedule and self.cfg.fixed and B <= 256 and train and local_optimizer and not spec.wd
+                       and not spec.moments)
         if self.cfg.fixed and B <= 256 and train and self.level_schedule and (_UC_ARENA or persist):
             arena = Arena(self.device, uncached=True)  # (see _UC_ARENA; the persistent step needs it whatever the knob says)
         if not self.cfg.fixed:
@@ -420,8 +449,7 @@ class SupernetEngine:
         with torch.cuda.stream(self.stream):
             cp = CompiledPlan()
             cp.arena, cp.evicted = arena, False
-            cp.wd, cp.no_reg = weight_decay, no_reg_param_name
-            cp.mom = optim
+            cp.tail = OptimizerTail(spec, arena)
             ctx = P.Ctx(B, self.device, self.params, self.grads, shape_only=False, train=train)
             ctx.sk_workspace = self._sk_workspace
             # parked weight-gradient batches are for one-launch-per-operator plans; the level scheduler places the products itself
@@ -486,7 +514,7 @@ class SupernetEngine:
             cp.fwd_levels = cp.bwd_levels = None
             cp.dead_forward = []
             if train:  # (the backward program decides which forward results are read: built further down, before the packing)
-                if optim is None:  # (Adagrad's table state: Adam / SGD keep theirs in `moments` instead)
+                if not spec.moments:  # (Adagrad's table state: Adam / SGD keep theirs in `moments` instead)
                     self._ensure_table_state()
                 self._build_training_tail(cp, ctx, w, bptr, fsegs, B, K, grad_scale)
             fwd_list = list(ctx.fwd)
@@ -515,21 +543,22 @@ class SupernetEngine:
                 # block output no later block reads, second passes) runs beside the first backward levels
                 # clip + Adagrad (built before the packing: the id-only half of its row dedup is an operator of the step like any other)
                 odescs = []
-                cp.dedup_ids, cp.ids_on_stage = None, False
+                cp.ids_on_stage = False
                 if local_optimizer:
-                    odescs = self._optimizer_descs(cp, B, cp.cat_x, sbuf.grad_tensor() if (sbuf.grad_written and not self.host_embedding)
+                    odescs = self._optimizer_descs(cp.tail, B, cp.cat_x, sbuf.grad_tensor() if (sbuf.grad_written and not self.host_embedding)
                                                    else None, clip, eps)
                 ids_in_program = []
-                if cp.dedup_ids is not None:
+                ids = cp.tail.dedup_ids
+                if ids is not None:
                     if scheduled and _IDS_AS_ITEM:
                         # ... which depends on nothing but the staged ids and is read by nothing before the optimizer: the level scheduler puts
                         # it where it costs least (beside a Transformer backward), off both the staging launch and the step's tail
-                        ids_in_program = [cp.dedup_ids]
+                        ids_in_program = [ids]
                     elif B <= 256:  # on the staging launch (which holds the caller's ids)
-                        cp.stage.dedup_ids = cp.dedup_ids
+                        cp.stage.dedup_ids = ids
                         cp.ids_on_stage = True
                     else:           # in-stream programs (large batch): in front of the launch that needs it
-                        odescs = [cp.dedup_ids] + odescs
+                        odescs = [ids] + odescs
                 cp.fb = None
                 if scheduled:
                     # (alloc: a forward product with several levels of slack may be re-cut into split-K items — only in the JOINT
@@ -691,7 +720,8 @@ class SupernetEngine:
 
         ctx.on_backward(final_bwd)
         ctx.build_backward()
-        cp.chunk_tab, cp.nchunks, cp.path_spans = None, 0, None
+        cp.path_spans = None
+        t = cp.tail
         if not cfg.fixed:
             # Paths differ from step to step.  torch skips parameters whose grad is None (everything outside the path),
             # so zero_grad, the norm and Adagrad touch ONLY the arena ranges this path trains — the same arithmetic on
@@ -700,12 +730,9 @@ class SupernetEngine:
             names = [n for n in list(ctx.grad_params) + ["_final.weight", "_final.bias"] if not n.startswith("_embedding.")]
             cp.path_spans = [(self.offsets[n], self.params[n].numel()) for n in dict.fromkeys(names)]
             flat = P.path_chunks(cp.path_spans)
-            cp.nchunks = len(flat) // 2
-            cp.chunk_tab = (arena.alloc(len(flat), torch.int64).tensor() if arena is not None
-                            else torch.empty(len(flat), dtype=torch.int64, device=self.device))
-            pre += P.const_i64_descs(cp.chunk_tab.data_ptr(), flat)
+            t.chunk_tab, t.nchunks = self._const_table(flat, arena, pre), len(flat) // 2
             ms = P.memset_desc(self.flat_g)
-            ms.chunks, ms.nchunks = cp.chunk_tab.data_ptr(), cp.nchunks
+            ms.chunks, ms.nchunks = t.chunk_tab.data_ptr(), t.nchunks
             pre.append(ms)
         elif _FIXED_OPT_TABLE:
             # A fixed sub-network can hold parameters no gradient ever reaches (the reference leaves their grad None: in
@@ -716,53 +743,54 @@ class SupernetEngine:
             spans = [(self.offsets[n], self.params[n].numel()) for n in dict.fromkeys(names)]
             if sum(n for _, n in spans) < 0.9 * self.flat_numel:
                 flat = P.path_chunks(spans, chunk=1024)  # (small pieces: a workgroup per piece keeps ~10^3 workgroups on the pass)
-                cp.nchunks = len(flat) // 2
-                cp.chunk_tab = torch.empty(len(flat), dtype=torch.int64, device=self.device)
-                lib = L.load()
-                for dsc in P.const_i64_descs(cp.chunk_tab.data_ptr(), flat):
-                    L.check(lib.nasrec_launch(self.stream.cuda_stream, C.addressof(dsc)))
-                self.stream.synchronize()  # (the descriptors carry the values: they must outlive their launches)
-        if cp.wd:
-            self._weight_decay_tables(cp, ctx, arena, pre)
-        if cp.mom is not None:
+                t.chunk_tab, t.nchunks = self._const_table(flat, arena, pre), len(flat) // 2
+        if t.spec.wd:
+            self._weight_decay_tables(t, ctx, arena, pre)
+        if t.spec.moments:
             self._moments_tables(cp, ctx, arena, pre)
         cp.bce, cp._pre = bd, pre
 
+    def _const_table(self, flat, arena, pre):
+        """an int64 table holding `flat`: a sampled path's lives in the plan slot's arena and is written by launches in front of every
+        step (`pre`: the slot is reused by other paths); a fixed sub-network's is written once, now"""
+        n = max(1, len(flat))
+        if not self.cfg.fixed:
+            tab = arena.alloc(n, torch.int64).tensor()
+            pre += P.const_i64_descs(tab.data_ptr(), flat)
+            return tab
+        tab = torch.empty(n, dtype=torch.int64, device=self.device)
+        lib = L.load()
+        for dsc in P.const_i64_descs(tab.data_ptr(), flat):
+            L.check(lib.nasrec_launch(self.stream.cuda_stream, C.addressof(dsc)))
+        self.stream.synchronize()  # (the descriptors carry the values: they must outlive their launches)
+        return tab
+
     WD_BLOCKS = 2048  # workgroups of the two weight-decay launches (8 per CU: the table pass is a stream over W and its state)
 
-    def _weight_decay_tables(self, cp, ctx, arena, pre):
+    def _weight_decay_tables(self, t, ctx, arena, pre):
         """Chunk tables of a plan with weight decay (csrc/weight_decay.hip): the regularised dense ranges the backward reaches (g += 2 wd W)
         and the ones it does not (g = 2 wd W: get_l2_loss walks named_parameters(), on the path or off it), and the union of the reached
         and the regularised ranges, over which Adagrad runs (torch skips grad = None: 1-D parameters off the path).  The clip's sum of
         squares keeps the reached ranges only — a fixed sub-network gets that table whatever its share of the arena."""
         names = [n for n in list(ctx.grad_params) + ["_final.weight", "_final.bias"] if not n.startswith("_embedding.")]
         reached = list(dict.fromkeys(names))
-        reg, cp.wd_tables = P.regularised(self.shapes, cp.no_reg)
+        reg, t.wd_tables = P.regularised(self.shapes, t.spec.no_reg)
         on = set(reached)
 
         def chunks(ns):
             return P.path_chunks([(self.offsets[n], self.params[n].numel()) for n in ns], chunk=1024)
         parts = [chunks([n for n in reg if n in on]), chunks([n for n in reg if n not in on]), chunks(list(dict.fromkeys(reached + reg)))]
-        if cp.chunk_tab is None:
+        if t.chunk_tab is None:
             parts.append(chunks(reached))
-        flat = [v for part in parts for v in part]
-        tab = (arena.alloc(max(1, len(flat)), torch.int64).tensor() if (arena is not None and not self.cfg.fixed)
-               else torch.empty(max(1, len(flat)), dtype=torch.int64, device=self.device))
-        if not self.cfg.fixed:
-            pre += P.const_i64_descs(tab.data_ptr(), flat)  # (the slot's arena is reused by other paths: written every step)
-        else:
-            lib = L.load()
-            for dsc in P.const_i64_descs(tab.data_ptr(), flat):
-                L.check(lib.nasrec_launch(self.stream.cuda_stream, C.addressof(dsc)))
-            self.stream.synchronize()
+        tab = self._const_table([v for part in parts for v in part], arena, pre)
         ptrs, off = [], 0
         for part in parts:
             ptrs.append((tab.data_ptr() + 8 * off, len(part) // 2))
             off += len(part)
-        cp.wd_add, cp.wd_set, cp.wd_union = ptrs[:3]
-        if cp.chunk_tab is None:
-            cp.chunk_tab, cp.nchunks = tab[off - len(parts[3]):off], ptrs[3][1]
-        cp.wd_tab = tab
+        t.wd_add, t.wd_set, t.wd_union = ptrs[:3]
+        if t.chunk_tab is None:
+            t.chunk_tab, t.nchunks = tab[off - len(parts[3]):off], ptrs[3][1]
+        t.wd_tab = tab
         self._row_bitmap()
         if getattr(self, "_wd_part", None) is None:
             with torch.cuda.stream(self.stream):
@@ -821,10 +849,12 @@ class SupernetEngine:
         no-op."""
         if self.host_embedding:
             raise L.EngineError("Adam / SGD in the fused step need the embedding tables on the device")
-        self.ensure_moments_state(cp.mom.kind)
+        t = cp.tail
+        spec = t.spec
+        self.ensure_moments_state(spec.kind)
         names = [n for n in list(ctx.grad_params) + ["_final.weight", "_final.bias"] if not n.startswith("_embedding.")]
-        if cp.wd:
-            names += P.regularised(self.shapes, cp.no_reg)[0]
+        if spec.wd:
+            names += P.regularised(self.shapes, spec.no_reg)[0]
         names = list(dict.fromkeys(names))
         trip = []
         for n in names:
@@ -832,102 +862,97 @@ class SupernetEngine:
             for o in range(0, cnt, self.MOM_CHUNK):
                 trip += [off + o, min(self.MOM_CHUNK, cnt - o), k]
         if cp.sparse0.grad_written:
-            cp.mom_tables = list(range(self.Fs))
+            t.mom_tables = list(range(self.Fs))
         else:
-            cp.mom_tables = sorted(cp.wd_tables) if cp.wd else []
-        inc = [self.param_index[n] for n in names] + [len(self.dense_names) + f for f in cp.mom_tables]
-        flat = trip + inc
-        tab = (arena.alloc(len(flat), torch.int64).tensor() if (arena is not None and not self.cfg.fixed)
-               else torch.empty(len(flat), dtype=torch.int64, device=self.device))
-        if not self.cfg.fixed:
-            pre += P.const_i64_descs(tab.data_ptr(), flat)  # (the slot's arena is reused by other paths: written every step)
-        else:
-            lib = L.load()
-            for dsc in P.const_i64_descs(tab.data_ptr(), flat):
-                L.check(lib.nasrec_launch(self.stream.cuda_stream, C.addressof(dsc)))
-            self.stream.synchronize()
-        cp.mom_tab = tab
-        cp.mom_chunks = (tab.data_ptr(), len(trip) // 3)
-        cp.mom_inc = (tab.data_ptr() + 8 * len(trip), len(inc))
-        cp.mom_names = names
+            t.mom_tables = sorted(t.wd_tables) if spec.wd else []
+        inc = [self.param_index[n] for n in names] + [len(self.dense_names) + f for f in t.mom_tables]
+        tab = t.mom_tab = self._const_table(trip + inc, arena, pre)
+        t.mom_chunks = (tab.data_ptr(), len(trip) // 3)
+        t.mom_inc = (tab.data_ptr() + 8 * len(trip), len(inc))
+        t.mom_names = names
 
-    def _moments_descs(self, cp, Bg, cat_x, gsum, clip_desc, rank_layout=None):
+    @staticmethod
+    def _optim_scalars(d, spec):
+        """algo and hyperparameters of an Adam / SGD spec on an OptMomentsDesc or a LastLayerStepDesc"""
+        d.algo = L.OPTIM_ADAM if spec.kind == "adam" else L.OPTIM_SGD
+        d.eps, d.momentum, d.nesterov = spec.eps, spec.momentum, int(bool(spec.nesterov))
+        d.beta1, d.beta2 = spec.beta1, spec.beta2
+
+    def _moments_descs(self, t, Bg, cat_x, gsum, clip_desc, rank_layout=None):
         """the two NASREC_OP_OPT_MOMENTS launches of a plan with Adam / SGD: (phase 0 in place of the Adagrad apply launch, phase 1).
         rank_layout: (samples per rank, floats between the ranks' chunks) of `gsum` (_optimizer_descs)"""
-        o = cp.mom
+        spec = t.spec
         st = self.moments
         m = L.OptMomentsDesc()
         m.kind, m.phase = L.OP_OPT_MOMENTS, 0
-        m.algo = L.OPTIM_ADAM if o.kind == "adam" else L.OPTIM_SGD
-        m.nesterov = int(bool(o.nesterov))
-        m.dense_blocks = min(2048, cp.mom_chunks[1])
-        m.nblocks = self.WD_BLOCKS if cp.mom_tables else 1  # (no table moves: phase 1 only counts the step and restores g)
+        self._optim_scalars(m, spec)
+        m.dense_blocks = min(2048, t.mom_chunks[1])
+        m.nblocks = self.WD_BLOCKS if t.mom_tables else 1  # (no table moves: phase 1 only counts the step and restores g)
         m.B, m.Fs = (Bg, self.Fs) if gsum is not None else (0, self.Fs)
         m.table_step0 = len(self.dense_names)
-        m.eps, m.momentum, m.wd = o.eps, o.momentum, cp.wd
-        m.beta1, m.beta2 = o.beta1, o.beta2
+        m.wd = spec.wd
         m.clip = clip_desc
-        m.chunks, m.nchunks = cp.mom_chunks
+        m.chunks, m.nchunks = t.mom_chunks
         m.p, m.g = self.flat_p.data_ptr(), self.flat_g.data_ptr()
-        first, second = (st["exp_avg"], st["exp_avg_sq"]) if o.kind == "adam" else (st["momentum_buffer"], None)
+        first, second = (st["exp_avg"], st["exp_avg_sq"]) if spec.kind == "adam" else (st["momentum_buffer"], None)
         m.m = first[0].data_ptr()
         m.v = second[0].data_ptr() if second is not None else None
         if gsum is not None:
-            m.idx, m.leader, m.gsum = cat_x.data_ptr(), cp.leader.data_ptr(), gsum
+            m.idx, m.leader, m.gsum = cat_x.data_ptr(), t.bufs.leader.data_ptr(), gsum
             if rank_layout:
                 m.rank_B, m.rank_stride = rank_layout
-        mask, t = 0, 0
+        mask, tile = 0, 0
         for f in range(self.Fs):
             m.table[f], m.tm[f], m.rows[f] = self.tables[f].data_ptr(), first[1][f].data_ptr(), self.num_embeddings[f]
             if second is not None:
                 m.tv[f] = second[1][f].data_ptr()
-            m.tile_off[f] = t
-            if f in cp.mom_tables:  # (a table that does not move owns no tile: phase 1 leaves it alone)
-                t += (self.num_embeddings[f] + 63) // 64
-            if cp.wd and f in cp.wd_tables:
+            m.tile_off[f] = tile
+            if f in t.mom_tables:  # (a table that does not move owns no tile: phase 1 leaves it alone)
+                tile += (self.num_embeddings[f] + 63) // 64
+            if spec.wd and f in t.wd_tables:
                 mask |= 1 << f
-        m.tile_off[self.Fs] = t
+        m.tile_off[self.Fs] = tile
         m.reg_mask = mask
         m.bitmap = self._row_bitmap().data_ptr()
         m.step = self.opt_steps.data_ptr()
-        m.inc, m.n_inc = cp.mom_inc
-        if cp.wd:
-            m.zero_chunks, m.n_zero = cp.wd_set
+        m.inc, m.n_inc = t.mom_inc
+        if spec.wd:
+            m.zero_chunks, m.n_zero = t.wd_set
         m.counter = self._mom_counter.data_ptr()
         m.lr, m.coef = self.lr_dev.data_ptr(), self.clip_out.data_ptr()
         m1 = L.OptMomentsDesc.from_buffer_copy(m)
         m1.phase = 1
-        return [m, m1]
+        return m, m1
 
-    def _weight_decay_descs(self, cp, Bg, cat_x, gsum, eps, clip_partial, rank_layout=None):
+    def _weight_decay_descs(self, t, Bg, cat_x, gsum, eps, clip_partial, rank_layout=None):
         """the two NASREC_OP_WEIGHT_DECAY launches of a plan: (phase 0, in front of the clip; phase 1, behind the touched rows' Adagrad).
         rank_layout: (samples per rank, floats between the ranks' chunks) of `gsum` (_optimizer_descs)"""
         w = L.WeightDecayDesc()
         w.kind, w.phase, w.nblocks = L.OP_WEIGHT_DECAY, 0, self.WD_BLOCKS
-        w.wd, w.eps = cp.wd, eps
+        w.wd, w.eps = t.spec.wd, eps
         w.B, w.Fs = (Bg, self.Fs) if gsum is not None else (0, self.Fs)
         if gsum is not None:
-            w.idx, w.leader, w.gsum = cat_x.data_ptr(), cp.leader.data_ptr(), gsum
+            w.idx, w.leader, w.gsum = cat_x.data_ptr(), t.bufs.leader.data_ptr(), gsum
             if rank_layout:
                 w.rank_B, w.rank_stride = rank_layout
-        mask, t = 0, 0
+        mask, tile = 0, 0
         for f in range(self.Fs):
             w.table[f], w.rows[f] = self.tables[f].data_ptr(), self.num_embeddings[f]
             if self.table_state is not None:  # (read by phase 1 only, which Adam / SGD plans do not launch)
                 w.state[f] = self.table_state[f].data_ptr()
-            w.tile_off[f] = t
-            if f in cp.wd_tables:
+            w.tile_off[f] = tile
+            if f in t.wd_tables:
                 mask |= 1 << f
-                t += (self.num_embeddings[f] + 63) // 64
-        w.tile_off[self.Fs] = t
+                tile += (self.num_embeddings[f] + 63) // 64
+        w.tile_off[self.Fs] = tile
         w.reg_mask = mask
         w.bitmap = self._row_bitmap().data_ptr()
-        if getattr(cp, "mom", None) is not None and mask != (1 << self.Fs) - 1:
+        if t.spec.moments and mask != (1 << self.Fs) - 1:
             # Adam / SGD mark the touched rows of EVERY table, in a layout over all tables: phase 0's marks (over the regularised
             # tables) would land on other rows' bits there, so they go to a bitmap nobody reads
             w.bitmap = self._row_bitmap(sink=True).data_ptr()
         w.p, w.g = self.flat_p.data_ptr(), self.flat_g.data_ptr()
-        (w.add_chunks, w.n_add), (w.set_chunks, w.n_set) = cp.wd_add, cp.wd_set
+        (w.add_chunks, w.n_add), (w.set_chunks, w.n_set) = t.wd_add, t.wd_set
         w.block_part, w.counter = self._wd_part.data_ptr(), self._wd_counter.data_ptr()
         w.clip_partial, w.l2_sumsq = clip_partial, self.wd_l2_sumsq.data_ptr()
         w.lr, w.coef = self.lr_dev.data_ptr(), self.clip_out.data_ptr()
@@ -935,54 +960,53 @@ class SupernetEngine:
         w1.phase = 1
         return w, w1
 
-    def _optimizer_descs(self, cp, Bg, cat_x, sparse_grad, clip, eps, rank_layout=None):
-        """clip_grad_norm_ + Adagrad (train_utils.py:285-286): row-sparse on the tables, flat on the dense arena.
+    def _optimizer_descs(self, t, Bg, cat_x, sparse_grad, clip, eps, rank_layout=None):
+        """clip_grad_norm_ + the optimizer of `t` (an OptimizerTail; train_utils.py:285-286): row-sparse on the tables, flat on the dense
+        arena.  One fixed sequence: the reduce stage (row dedup + the sums of squares), weight decay's phase 0, the apply stage (clip +
+        Adagrad, or phase 0 of Adam / SGD) and the phase-1 stage (weight decay's, or Adam / SGD's).  eps: Adagrad's.
         rank_layout (data-parallel step): (samples per rank, floats between the ranks' chunks) of `sparse_grad` when it is the receive
         buffer of an all-gather that carries more than the rows (parallel.py); None = one contiguous [Bg, Fs, 16] array.  Weight decay and
         Adam / SGD read and write the summed rows where the dedup left them: in that layout (Bg <= DEDUP_SPLIT_MAX_B, summed in place) or
         in the contiguous gsum (the one-launch kernels).
-        Leaves `cp.dedup_ids` (the id-only half of the row dedup, to be launched once the ids are in `cat_x`) or None."""
-        descs = []
-        cp.dedup_ids = None
+        Leaves `t.dedup_ids` (the id-only half of the row dedup, to be launched once the ids are in `cat_x`) or None."""
+        spec, b = t.spec, t.bufs
+        assert spec.moments or spec.eps == eps, "Adagrad's eps: the spec's and the argument disagree"
+        t.dedup_ids = None
         nb = (Bg + 255) // 256
-        new = getattr(cp, "arena", None)
-        new = (lambda n, dt=torch.float32: cp.arena.alloc(n, dt).tensor()) if new is not None else \
+        new = (lambda n, dt=torch.float32: t.arena.alloc(n, dt).tensor()) if t.arena is not None else \
             (lambda n, dt=torch.float32: torch.zeros(n, dtype=dt, device=self.device))
         nblk = max(1, min(256, (self.flat_numel + 256 * 8 - 1) // (256 * 8)))
-        tab, ntab = getattr(cp, "chunk_tab", None), getattr(cp, "nchunks", 0)
+        tab, ntab = t.chunk_tab, t.nchunks
         if tab is not None:
             nblk = max(1, min(256, ntab))
-        if getattr(cp, "leader", None) is None:  # (the data-parallel optimizer shares these across the plans of a run)
-            cp.leader = new(Bg * self.Fs, torch.int32)
-            cp.gsum = new(Bg * self.Fs * E)
-            cp.emb_partial = new(self.Fs * nb)
-            cp.dense_partial = new(256 + (1 if getattr(cp, "wd", 0.0) else 0))  # (weight decay: + phase 0's share of the norm)
-        if sparse_grad is not None:
+        if b.leader is None:
+            b.leader = new(Bg * self.Fs, torch.int32)
+            b.gsum = new(Bg * self.Fs * E)
+            b.emb_partial = new(self.Fs * nb)
+            b.dense_partial = new(256 + (1 if spec.wd else 0))  # (weight decay: + phase 0's share of the norm)
+        rows = sparse_grad is not None
+        if rows:
             dd = L.EmbDedupDesc()
             dd.kind = L.OP_EMB_DEDUP
             dd.B, dd.Fs = Bg, self.Fs
             dd.idx, dd.dout = cat_x.data_ptr(), sparse_grad.data_ptr()
-            dd.leader, dd.gsum, dd.sumsq_partial = cp.leader.data_ptr(), cp.gsum.data_ptr(), cp.emb_partial.data_ptr()
+            dd.leader, dd.gsum, dd.sumsq_partial = b.leader.data_ptr(), b.gsum.data_ptr(), b.emb_partial.data_ptr()
             dd.overflow = self.oob.data_ptr() + 4
-            descs.append(dd)
         sq = L.SumsqDesc()
         sq.kind = L.OP_SUMSQ
         sq.nblocks, sq.n = nblk, self.flat_numel
-        sq.x, sq.partial = self.flat_g.data_ptr(), cp.dense_partial.data_ptr()
+        sq.x, sq.partial = self.flat_g.data_ptr(), b.dense_partial.data_ptr()
         if tab is not None:
             sq.chunks, sq.nchunks = tab.data_ptr(), ntab
-        descs.append(sq)
         cc = L.ClipCoefDesc()
         cc.kind = L.OP_CLIP_COEF
-        cc.n_a, cc.n_b = nblk, (self.Fs * nb if sparse_grad is not None else 0)
+        cc.n_a, cc.n_b = nblk, (self.Fs * nb if rows else 0)
         cc.max_norm = float(clip) if clip is not None else 0.0
-        cc.partial_a, cc.partial_b, cc.out = cp.dense_partial.data_ptr(), cp.emb_partial.data_ptr(), self.clip_out.data_ptr()
-        wd = getattr(cp, "wd", 0.0)
-        mom = getattr(cp, "mom", None)
-        if wd:
+        cc.partial_a, cc.partial_b, cc.out = b.dense_partial.data_ptr(), b.emb_partial.data_ptr(), self.clip_out.data_ptr()
+        wd_part = None
+        if spec.wd:
             cc.n_a = nblk + 1  # partial_a[nblk]: what the L2 gradient adds to the norm's sum of squares (weight-decay phase 0)
-            wd_part = cp.dense_partial.data_ptr() + 4 * nblk
-        descs.append(cc)
+            wd_part = b.dense_partial.data_ptr() + 4 * nblk
         ad = L.AdagradDenseDesc()
         ad.kind = L.OP_ADAGRAD_DENSE
         ad.eps, ad.n = eps, self.flat_numel
@@ -990,103 +1014,80 @@ class SupernetEngine:
         ad.lr, ad.coef = self.lr_dev.data_ptr(), self.clip_out.data_ptr()
         if tab is not None:
             ad.chunks, ad.nchunks = tab.data_ptr(), ntab
-        if wd:  # Adagrad over the reached AND the regularised ranges
-            (ad.chunks, ad.nchunks), ntab = cp.wd_union, cp.wd_union[1]
-        descs.append(ad)
-        if sparse_grad is not None:
+        if spec.wd:  # Adagrad over the reached AND the regularised ranges
+            (ad.chunks, ad.nchunks), ntab = t.wd_union, t.wd_union[1]
+        if rows:
             ar = L.AdagradRowsDesc()
             ar.kind = L.OP_ADAGRAD_ROWS
             ar.B, ar.Fs, ar.eps = Bg, self.Fs, eps
-            ar.idx, ar.leader, ar.gsum = cat_x.data_ptr(), cp.leader.data_ptr(), cp.gsum.data_ptr()
+            ar.idx, ar.leader, ar.gsum = cat_x.data_ptr(), b.leader.data_ptr(), b.gsum.data_ptr()
             for f in range(self.Fs):
                 ar.table[f] = self.tables[f].data_ptr()
                 ar.state[f] = self.table_state[f].data_ptr() if self.table_state is not None else None  # (None: an Adam / SGD plan)
                 ar.rows[f] = self.num_embeddings[f]
             ar.lr, ar.coef = self.lr_dev.data_ptr(), self.clip_out.data_ptr()
-            descs.append(ar)
-        if sparse_grad is not None:
             app = L.OptApplyDesc()
             app.kind = L.OP_OPT_APPLY
             # (2.2 M parameters of the batch-256 bench network: 256 / 512 / 1024 / 2048 / 4096 workgroups -> 15.3 / 10.9 / 8.6 / 9.5 / 10.8 us)
             cap = 1024 if self.flat_numel <= (4 << 20) else 2048
             app.dense_blocks = min(cap, ntab if tab is not None else (self.flat_numel + 255) // 256)
             app.clip, app.dense, app.rows = cc, ad, ar
-            if Bg <= DEDUP_SPLIT_MAX_B:
-                # Two halves (csrc/dedup_bodies.h): leaders, duplicate lists and their order depend on the ids only — cp.dedup_ids runs
-                # as soon as the ids are there (B <= 256: on the staging launch; a data-parallel step: behind the ids all-gather, beside the
-                # forward) — and one launch behind the backward sums the duplicate rows IN PLACE and squares what the clip needs.
-                capn = 256
-                while capn < Bg:
-                    capn *= 2
-                if getattr(cp, "dd_order", None) is None:
-                    cp.dd_order = new(self.Fs * capn, torch.int32)
-                    cp.dd_lists = new(self.Fs * capn, torch.int32)
-                    cp.dd_counts = new(self.Fs * 2, torch.int32)
-                    cp.dd_heads = new(self.Fs * capn, torch.int32) if capn > 256 else None
-                row_blocks = max(1, min(512, (Bg * self.Fs * 4 + 255) // 256))
-                if getattr(cp, "emb_partial2", None) is None or cp.emb_partial2.numel() < self.Fs + row_blocks:
-                    cp.emb_partial2 = new(self.Fs + row_blocks)
-                ids = L.DedupIdsDesc()
-                ids.kind, ids.B, ids.Fs, ids.cap = L.OP_DEDUP_IDS, Bg, self.Fs, capn
-                ids.idx, ids.leader = cat_x.data_ptr(), cp.leader.data_ptr()
-                ids.order, ids.lists, ids.counts = cp.dd_order.data_ptr(), cp.dd_lists.data_ptr(), cp.dd_counts.data_ptr()
-                ids.heads = cp.dd_heads.data_ptr() if cp.dd_heads is not None else None
-                cp.dedup_ids = ids
-                r2 = L.OptReduce2Desc()
-                r2.kind, r2.B, r2.Fs, r2.cap = L.OP_OPT_REDUCE2, Bg, self.Fs, capn
-                r2.rank_B, r2.rank_stride = rank_layout if rank_layout else (0, 0)
-                r2.row_blocks = row_blocks
-                r2.rows, r2.leader = sparse_grad.data_ptr(), cp.leader.data_ptr()
-                r2.order, r2.lists, r2.counts, r2.heads = ids.order, ids.lists, ids.counts, ids.heads
-                r2.sumsq_partial = cp.emb_partial2.data_ptr()
-                r2.sumsq = sq
-                app.clip.partial_b, app.clip.n_b = cp.emb_partial2.data_ptr(), self.Fs + row_blocks
-                app.rows.gsum = sparse_grad.data_ptr()  # summed in place: a leader's row holds its sum
-                app.rows.rank_B, app.rows.rank_stride = r2.rank_B, r2.rank_stride
-                if mom is not None:
-                    tail = self._moments_descs(cp, Bg, cat_x, sparse_grad.data_ptr(), app.clip, rank_layout)
-                    if wd:
-                        return [r2, self._weight_decay_descs(cp, Bg, cat_x, sparse_grad.data_ptr(), eps, wd_part, rank_layout)[0]] + tail
-                    return [r2] + tail
-                if wd:
-                    w0, w1 = self._weight_decay_descs(cp, Bg, cat_x, sparse_grad.data_ptr(), eps, wd_part, rank_layout)
-                    return [r2, w0, app, w1]
-                return [r2, app]
+        # the reduce stage, and where the summed rows are for weight decay and Adam / SGD
+        if rows and Bg <= DEDUP_SPLIT_MAX_B:
+            # Two halves (csrc/dedup_bodies.h): leaders, duplicate lists and their order depend on the ids only — t.dedup_ids runs
+            # as soon as the ids are there (B <= 256: on the staging launch; a data-parallel step: behind the ids all-gather, beside the
+            # forward) — and one launch behind the backward sums the duplicate rows IN PLACE and squares what the clip needs.
+            capn = 256
+            while capn < Bg:
+                capn *= 2
+            if b.dd_order is None:
+                b.dd_order = new(self.Fs * capn, torch.int32)
+                b.dd_lists = new(self.Fs * capn, torch.int32)
+                b.dd_counts = new(self.Fs * 2, torch.int32)
+                b.dd_heads = new(self.Fs * capn, torch.int32) if capn > 256 else None
+            row_blocks = max(1, min(512, (Bg * self.Fs * 4 + 255) // 256))
+            if b.emb_partial2 is None:
+                b.emb_partial2 = new(self.Fs + row_blocks)
+            assert b.emb_partial2.numel() >= self.Fs + row_blocks, "the work buffers are sized by the first program that uses them"
+            ids = L.DedupIdsDesc()
+            ids.kind, ids.B, ids.Fs, ids.cap = L.OP_DEDUP_IDS, Bg, self.Fs, capn
+            ids.idx, ids.leader = cat_x.data_ptr(), b.leader.data_ptr()
+            ids.order, ids.lists, ids.counts = b.dd_order.data_ptr(), b.dd_lists.data_ptr(), b.dd_counts.data_ptr()
+            ids.heads = b.dd_heads.data_ptr() if b.dd_heads is not None else None
+            t.dedup_ids = ids
+            r2 = L.OptReduce2Desc()
+            r2.kind, r2.B, r2.Fs, r2.cap = L.OP_OPT_REDUCE2, Bg, self.Fs, capn
+            r2.rank_B, r2.rank_stride = rank_layout if rank_layout else (0, 0)
+            r2.row_blocks = row_blocks
+            r2.rows, r2.leader = sparse_grad.data_ptr(), b.leader.data_ptr()
+            r2.order, r2.lists, r2.counts, r2.heads = ids.order, ids.lists, ids.counts, ids.heads
+            r2.sumsq_partial = b.emb_partial2.data_ptr()
+            r2.sumsq = sq
+            app.clip.partial_b, app.clip.n_b = b.emb_partial2.data_ptr(), self.Fs + row_blocks
+            app.rows.gsum = sparse_grad.data_ptr()  # summed in place: a leader's row holds its sum
+            app.rows.rank_B, app.rows.rank_stride = r2.rank_B, r2.rank_stride
+            reduce, gsum, layout = [r2], sparse_grad.data_ptr(), rank_layout
+        elif rows:
             if rank_layout:  # (the one-launch kernels read the rows where the all-gather left them; their sums go to the contiguous gsum)
                 dd.rank_B, dd.rank_stride = rank_layout
-            if mom is not None:  # (the reduce launches as for Adagrad; Adam / SGD in place of the apply launch)
-                red = [dd, sq]
-                if Bg <= 256:
-                    red = L.OptReduceDesc()
-                    red.kind = L.OP_OPT_REDUCE
-                    red.dedup, red.sumsq = dd, sq
-                    red = [red]
-                if wd:
-                    red.append(self._weight_decay_descs(cp, Bg, cat_x, cp.gsum.data_ptr(), eps, wd_part)[0])
-                return red + self._moments_descs(cp, Bg, cat_x, cp.gsum.data_ptr(), app.clip)
-            if Bg <= 256:
-                # the five launches collapse into the two that the grid-wide dependencies require
+            reduce = [dd, sq]  # (global batch of a data-parallel step: chunked dedup + merge, two launches)
+            if Bg <= 256:  # (NASREC_DEDUP_SPLIT_MAX_B below 256) the five launches collapse into the two the grid-wide dependencies require
                 red = L.OptReduceDesc()
                 red.kind = L.OP_OPT_REDUCE
                 red.dedup, red.sumsq = dd, sq
-                if wd:
-                    w0, w1 = self._weight_decay_descs(cp, Bg, cat_x, cp.gsum.data_ptr(), eps, wd_part)
-                    return [red, w0, app, w1]
-                return [red, app]
-            if wd:
-                w0, w1 = self._weight_decay_descs(cp, Bg, cat_x, cp.gsum.data_ptr(), eps, wd_part)
-                return [dd, sq, w0, app, w1]
-            return [dd, sq, app]  # global batch of a data-parallel step: chunked dedup + merge (two launches), then the same apply
-        if mom is not None:  # (no gradient reaches the embedding stem: no touched rows)
-            descs = [sq]
-            if wd:
-                descs.append(self._weight_decay_descs(cp, Bg, cat_x, None, eps, wd_part)[0])
-            return descs + self._moments_descs(cp, Bg, cat_x, None, cc)
-        if wd:
-            w0, w1 = self._weight_decay_descs(cp, Bg, cat_x, cp.gsum.data_ptr() if sparse_grad is not None else None, eps, wd_part)
-            descs.insert(descs.index(cc), w0)
-            descs.append(w1)
-        return descs
+                reduce = [red]
+            gsum, layout = b.gsum.data_ptr(), None
+        else:  # (no gradient reaches the embedding stem: no touched rows)
+            reduce, gsum, layout = [sq], None, None
+        wd0, phase1 = None, None
+        if spec.wd:
+            wd0, phase1 = self._weight_decay_descs(t, Bg, cat_x, gsum, eps, wd_part, layout)
+        if spec.moments:
+            m0, phase1 = self._moments_descs(t, Bg, cat_x, gsum, app.clip if rows else cc, layout)
+            apply = [m0]
+        else:
+            apply = [app] if rows else [cc, ad]
+        return reduce + ([wd0] if wd0 is not None else []) + apply + ([phase1] if phase1 is not None else [])
 
     @_on_device
     def reserve(self, B: int, train: bool = True, choice=None, freeze_gc: bool = False):
@@ -1189,7 +1190,7 @@ class SupernetEngine:
             if not self.host_embedding:
                 L.check(L.load().nasrec_launch(sp, C.addressof(cp.gather)))
             if getattr(cp, "ids_on_stage", False):  # (the staging launch would have carried it)
-                L.check(L.load().nasrec_launch(sp, C.addressof(cp.dedup_ids)))
+                L.check(L.load().nasrec_launch(sp, C.addressof(cp.tail.dedup_ids)))
             return False
         d = cp.stage  # prebuilt per plan: only the sources change from step to step
         d.int_src, d.cat_src = int_x.data_ptr(), cat_x.data_ptr()
@@ -1247,8 +1248,7 @@ class SupernetEngine:
         else:  # pre-staged inputs: the batch size is the one of the plan they were staged into
             assert staged and self._last_plan is not None, "train_step without inputs needs a previously compiled plan holding them"
             B = int(self._last_plan[2].cat_x.shape[0])
-        cp = self.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, weight_decay=weight_decay, no_reg_param_name=no_reg_param_name,
-                          optim=optim)
+        cp = self.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, spec=OptimSpec.of(eps, weight_decay, no_reg_param_name, optim))
         sp = self._sp()
         if not staged:
             whole = not graph and getattr(cp, "fb", None) is not None and not self.host_embedding
@@ -1262,7 +1262,7 @@ class SupernetEngine:
             self.lr_dev.fill_(float(lr))
             L.check(L.load().nasrec_launch(sp, C.addressof(cp.gather)))
             if getattr(cp, "ids_on_stage", False):
-                L.check(L.load().nasrec_launch(sp, C.addressof(cp.dedup_ids)))
+                L.check(L.load().nasrec_launch(sp, C.addressof(cp.tail.dedup_ids)))
         if graph:
             cp.step.replay(sp)
         else:
@@ -1289,10 +1289,10 @@ class SupernetEngine:
         self.stream.synchronize()
         return {k: st[k] for k in keys}
 
-    def _last_layer_program(self, cp, clip, eps, weight_decay, no_reg_param_name, optim, graph):
+    def _last_layer_program(self, cp, clip, spec, graph):
         """(staging launch + forward + final-logit backward with BCE folded in, d features skipped + NASREC_OP_LAST_LAYER_STEP,
-        the same without the staging launch) of a compiled training plan, built once per plan and optimizer setting"""
-        key = (clip, eps, weight_decay, no_reg_param_name, tuple(optim) if optim is not None else None, graph)
+        the same without the staging launch) of a compiled training plan, built once per plan and optimizer (spec)"""
+        key = (clip, spec, graph)
         progs = cp.__dict__.setdefault("last_layer", {})
         if key in progs:
             return progs[key]
@@ -1309,19 +1309,17 @@ class SupernetEngine:
         d.dw, d.dbias = self.grads["_final.weight"].data_ptr(), self.grads["_final.bias"].data_ptr()
         d.w, d.bias = self.params["_final.weight"].data_ptr(), self.params["_final.bias"].data_ptr()
         d.max_norm = float(clip) if clip is not None else 0.0
-        d.wd = float(weight_decay)
-        d.decay_w = int(bool(weight_decay) and not (no_reg_param_name is not None and "_final.weight".startswith(no_reg_param_name)))
-        if optim is None:
-            d.algo, d.eps = L.OPTIM_ADAGRAD, float(eps)
+        d.wd = spec.wd
+        d.decay_w = int(bool(spec.wd) and not (spec.no_reg is not None and "_final.weight".startswith(spec.no_reg)))
+        if not spec.moments:
+            d.algo, d.eps = L.OPTIM_ADAGRAD, spec.eps
             d.s_w, d.s_b = self.state["_final.weight"].data_ptr(), self.state["_final.bias"].data_ptr()
         else:
-            st = self.ensure_last_layer_state(optim.kind)
-            d.algo = L.OPTIM_ADAM if optim.kind == "adam" else L.OPTIM_SGD
-            d.eps, d.momentum, d.nesterov = float(optim.eps), float(optim.momentum), int(bool(optim.nesterov))
-            d.beta1, d.beta2 = float(optim.beta1), float(optim.beta2)
-            first = st["exp_avg"] if optim.kind == "adam" else st["momentum_buffer"]
+            st = self.ensure_last_layer_state(spec.kind)
+            self._optim_scalars(d, spec)
+            first = st["exp_avg"] if spec.kind == "adam" else st["momentum_buffer"]
             d.s_w, d.s_b = first[0].data_ptr(), first[1].data_ptr()
-            if optim.kind == "adam":
+            if spec.kind == "adam":
                 d.v_w, d.v_b = st["exp_avg_sq"][0].data_ptr(), st["exp_avg_sq"][1].data_ptr()
             d.step = self.ll_steps.data_ptr()
         d.lr, d.norm_out = self.lr_dev.data_ptr(), self.clip_out.data_ptr()
@@ -1349,7 +1347,7 @@ class SupernetEngine:
         B = int(int_x.shape[0])
         cp = self.compile(choice, B, train=True)
         self.last_layer_plan = cp  # (its logits: SuperNet.engine_last_logits)
-        whole, rest = self._last_layer_program(cp, clip, eps, float(weight_decay or 0.0), no_reg_param_name, optim, bool(graph))
+        whole, rest = self._last_layer_program(cp, clip, OptimSpec.of(eps, weight_decay, no_reg_param_name, optim), bool(graph))
         sp = self._sp()
         if self._stage_inputs(sp, cp, int_x, cat_x, y, lr, launch=whole is None):
             whole.run(sp)

@@ -1,25 +1,44 @@
-"""What the fused engine step needs to know about the torch optimizer it stands in for (main_train.py:150-160).
+"""The optimizer of the fused engine step as one value: which torch optimizer it stands in for (main_train.py:150-160), that optimizer's
+hyperparameters, and the weight decay of get_l2_loss, whose gradient the step folds in.
 
-`OptimSpec.from_optimizer` answers which torch optimizers the fused step reproduces: torch.optim.Adam and torch.optim.SGD with
-momentum, under the conditions listed there, in one process or in every rank of a data-parallel run with whole tables
-(nasrec_amd/parallel.py).  Adagrad keeps its own checks (utils/train_utils.py: _fused_step_applies)."""
+`OptimSpec.for_step` decides which torch optimizers the fused step reproduces: torch.optim.Adagrad, and torch.optim.Adam / torch.optim.SGD
+with momentum under the conditions of `from_optimizer`, in one process or in every rank of a data-parallel run with whole tables
+(nasrec_amd/parallel.py).  The public entry points (SuperNet.engine_*, SupernetEngine.train_step / last_layer_step, DataParallelStep)
+normalise their arguments into one spec (`of`); everything below them passes that."""
 from typing import NamedTuple, Optional
 
 import torch
 
 
 class OptimSpec(NamedTuple):
-    kind: str               # "adam" | "sgd"
+    kind: str               # "adagrad" | "adam" | "sgd"
     beta1: float = 0.9      # Adam
     beta2: float = 0.999
-    eps: float = 1e-8
+    eps: float = 1e-8       # Adam's, or Adagrad's
     momentum: float = 0.0   # SGD
     nesterov: bool = False
+    wd: float = 0.0         # get_l2_loss(model, wd, no_reg): the step minimises BCE + that term
+    no_reg: Optional[str] = None
+
+    @property
+    def moments(self) -> bool:
+        """Adam / SGD: state in the engine's moment arrays and step counters (Adagrad: its accumulators)"""
+        return self.kind != "adagrad"
 
     @property
     def state_keys(self):
-        """the per-parameter moment tensors torch keeps in optimizer.state[p] (besides Adam's "step")"""
-        return ("exp_avg", "exp_avg_sq") if self.kind == "adam" else ("momentum_buffer",)
+        """the per-parameter tensors torch keeps in optimizer.state[p] (besides "step")"""
+        return {"adagrad": ("sum",), "adam": ("exp_avg", "exp_avg_sq")}.get(self.kind, ("momentum_buffer",))
+
+    @staticmethod
+    def of(eps: float = 1e-2, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None) -> "OptimSpec":
+        """the public entry points' optimizer arguments as one spec: optim None = Adagrad with `eps` (its only source: the default eps
+        of a spec is Adam's), else an Adam / SGD spec; no_reg_param_name only counts with weight decay"""
+        if optim is not None and not optim.moments:
+            raise ValueError("optim is an Adam / SGD spec; Adagrad is optim=None with its eps")
+        wd = float(weight_decay or 0.0)
+        base = optim if optim is not None else OptimSpec("adagrad", eps=float(eps))
+        return base._replace(wd=wd, no_reg=no_reg_param_name if wd else None)
 
     @staticmethod
     def from_optimizer(optimizer) -> Optional["OptimSpec"]:
@@ -43,3 +62,18 @@ class OptimSpec(NamedTuple):
                 return None
             return OptimSpec("sgd", momentum=float(g["momentum"]), nesterov=bool(g.get("nesterov", False)))
         return None
+
+    @staticmethod
+    def for_step(optimizer, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None) -> Optional["OptimSpec"]:
+        """the spec of the fused step that stands in for `optimizer.step()` on the loss + get_l2_loss(model, weight_decay,
+        no_reg_param_name), or None when the fused step does not reproduce the optimizer.  torch.optim.Adagrad: one group,
+        weight_decay, lr_decay and initial_accumulator_value 0, not maximize; Adam / SGD: from_optimizer."""
+        if type(optimizer) is not torch.optim.Adagrad:
+            optim = OptimSpec.from_optimizer(optimizer)
+            return OptimSpec.of(weight_decay=weight_decay, no_reg_param_name=no_reg_param_name, optim=optim) if optim is not None else None
+        if len(optimizer.param_groups) != 1:
+            return None
+        g = optimizer.param_groups[0]
+        if g.get("weight_decay", 0) != 0 or g.get("lr_decay", 0) != 0 or g.get("initial_accumulator_value", 0) != 0 or g.get("maximize", False):
+            return None
+        return OptimSpec.of(float(g["eps"]), weight_decay, no_reg_param_name)

@@ -35,6 +35,8 @@ from typing import Callable, List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from .optim_spec import OptimSpec
+
 BUCKET_GAP = 16384  # floats: arena ranges closer than this are sent as one all-reduce (fewer, larger collectives)
 
 
@@ -250,14 +252,12 @@ class DataParallelStep:
         assert paths in ("shared", "per-rank"), paths
         self.per_rank = paths == "per-rank"
         assert not (self.per_rank and self.fixed), "a fixed sub-network has one path"
-        # the optimizer's options, handed to the engine protocol only when they are not the defaults (engines that implement the
-        # protocol without them — tests/test_data_parallel_cpu.py — keep working)
-        weight_decay = float(weight_decay or 0.0)
-        self.opt_kw = {}
-        if weight_decay:
-            self.opt_kw.update(weight_decay=weight_decay, no_reg_param_name=no_reg_param_name)
-        if optim is not None:
-            self.opt_kw["optim"] = optim
+        # the optimizer, handed to the engine protocol only when it is not plain Adagrad (engines that implement the protocol without
+        # optimizer options — tests/test_data_parallel_cpu.py — keep working)
+        spec = OptimSpec.of(eps, weight_decay, no_reg_param_name, optim)
+        self.opt_kw = {"spec": spec} if (spec.wd or spec.moments) else {}
+        # (the plain step of one rank: SupernetEngine.train_step's own arguments)
+        self.step_kw = dict(weight_decay=spec.wd, no_reg_param_name=spec.no_reg, optim=optim) if self.opt_kw else {}
         if self.per_rank and self.opt_kw:
             from ._lib import EngineError
             raise EngineError('paths="per-rank" runs Adagrad without weight decay: weight decay, Adam and SGD need every rank on the same path')
@@ -320,13 +320,13 @@ class DataParallelStep:
             self.tail_n = tail_n
             stride = self.rows_n + tail_n
             kw = {"rank_layout": (self.B, stride)} if tail_n else {}
-            cpl = getattr(plan, "cp", None)
-            if self.fixed and getattr(self.dp, "accepts_chunk_table", False) and getattr(cpl, "chunk_tab", None) is not None:
-                kw["chunk_table"] = (cpl.chunk_tab, cpl.nchunks)  # norm + Adagrad over the ranges the sub-network's backward reaches
+            opt_tail = getattr(getattr(plan, "cp", None), "tail", None)
+            if self.fixed and getattr(self.dp, "accepts_chunk_table", False) and getattr(opt_tail, "chunk_tab", None) is not None:
+                kw["chunk_table"] = (opt_tail.chunk_tab, opt_tail.nchunks)  # norm + Adagrad over the ranges the sub-network's backward reaches
             if self.opt_kw:
                 kw.update(self.opt_kw)
                 if getattr(self.dp, "accepts_chunk_table", False):
-                    kw["plan_tables"] = cpl  # weight decay's / the moments' chunk tables of the first plan (a fixed sub-network's for good)
+                    kw["plan_tail"] = opt_tail  # weight decay's / the moments' chunk tables of the first plan (a fixed sub-network's for good)
             self.recv = self.sg_recv[:self.world * stride]
             self.opt = self.dp.dp_optimizer(self.B * self.world, self.cat_all, self.recv, self.clip, self.eps, False, **kw)  # (graph: the whole exchange step is captured as one, _capture)
             self.ids_half = getattr(self.dp, "dp_dedup_ids", lambda: None)()
@@ -341,7 +341,7 @@ class DataParallelStep:
         eng = self.engine
         choice = choice if choice is not None else self.choice
         if not self.exchange:
-            loss = eng.train_step(int_x, cat_x, y, lr, choice, self.clip, self.eps, graph=self.graph, **self.opt_kw)
+            loss = eng.train_step(int_x, cat_x, y, lr, choice, self.clip, self.eps, graph=self.graph, **self.step_kw)
             self._last = ("plain", choice, int(int_x.shape[0]))
             return loss
         union = None
@@ -564,41 +564,34 @@ class EngineDP:
 
     def __init__(self, engine):
         self.engine = engine
-        self._holder = None
+        self._tail = None
 
-    # what the optimizer program of a plan with weight decay / Adam / SGD reads off the plan (engine._weight_decay_tables, _moments_tables)
-    PLAN_TABLES = ("wd_add", "wd_set", "wd_union", "wd_tables", "wd_tab", "mom_chunks", "mom_inc", "mom_tables", "mom_tab")
-
-    @classmethod
-    def _take_plan_tables(cls, holder, cp, weight_decay, no_reg_param_name, optim):
-        holder.wd, holder.no_reg, holder.mom = float(weight_decay or 0.0), no_reg_param_name, optim
-        if holder.wd or optim is not None:
-            assert cp is not None and cp.wd == holder.wd and cp.mom == optim, "the plan was compiled for another optimizer"
-            for k in cls.PLAN_TABLES:
-                if hasattr(cp, k):
-                    setattr(holder, k, getattr(cp, k))
-
-    def dp_optimizer(self, Bg, cat_all, sg_all, clip, eps, graph, rank_layout=None, chunk_table=None, weight_decay=0.0,
-                     no_reg_param_name=None, optim=None, plan_tables=None):
-        """the optimizer over the global batch.  weight_decay / no_reg_param_name / optim: as engine.compile; plan_tables: the
-        CompiledPlan whose chunk tables they read (a fixed sub-network: its one plan; sampled paths: every step takes its own plan's)"""
-        from .engine import Program
+    def dp_optimizer(self, Bg, cat_all, sg_all, clip, eps, graph, rank_layout=None, chunk_table=None, spec=None, plan_tail=None):
+        """the optimizer over the global batch.  spec: as engine.compile (None: Adagrad with eps); plan_tail: the OptimizerTail of the
+        plan whose weight-decay / moments tables it reads (a fixed sub-network: its one plan; sampled paths: every step takes its own
+        plan's).  Every program of the run shares one set of work buffers (engine.TailBuffers)."""
+        from .engine import OptimizerTail, Program, TailBuffers
         eng = self.engine
+        spec = spec if spec is not None else OptimSpec.of(eps)
+        bufs = TailBuffers()
+
+        def over(plan_tail, chunks):
+            if plan_tail is None:
+                return OptimizerTail(spec, chunks=chunks, bufs=bufs)
+            assert plan_tail.spec == spec, "the plan was compiled for another optimizer"
+            return plan_tail.over(chunks, bufs)
+
         with torch.cuda.stream(eng.stream):
-            holder = self._holder = _Holder()
-            if chunk_table is not None:
-                holder.chunk_tab, holder.nchunks = chunk_table
-            self._take_plan_tables(holder, plan_tables, weight_decay, no_reg_param_name, optim)
-            if optim is None:  # (Adagrad's table state: Adam / SGD keep theirs in engine.moments)
+            base = self._tail = over(plan_tail, chunk_table or (None, 0))
+            if not spec.moments:  # (Adagrad's table state: Adam / SGD keep theirs in engine.moments)
                 eng._ensure_table_state()
-            prog = Program(eng._optimizer_descs(holder, Bg, cat_all, sg_all, clip, eps, rank_layout=rank_layout))
-            prog.holder = holder
+            prog = Program(eng._optimizer_descs(base, Bg, cat_all, sg_all, clip, eps, rank_layout=rank_layout))
+            prog.opt_tail = base
             if graph:
                 prog.capture(eng.stream.cuda_stream)
         eng.stream.synchronize()
         if eng.cfg.fixed:
             return (lambda plan: prog.replay(eng._sp())) if graph else (lambda plan: prog.run(eng._sp()))
-        shared = ("leader", "gsum", "emb_partial", "dense_partial", "dd_order", "dd_lists", "dd_counts", "dd_heads", "emb_partial2")
 
         def run(plan, spans=None):
             if spans is not None:
@@ -606,33 +599,24 @@ class EngineDP:
                 # by the program's first launches (stream-ordered, like the plan's)
                 from . import plan as P
                 flat = P.path_chunks(spans)
-                h = _Holder()
-                for k in shared:
-                    if hasattr(holder, k):
-                        setattr(h, k, getattr(holder, k))
                 # ONE table per plan, reused by every step (the union changes with the other ranks' paths: the table is rewritten in
                 # stream order by the program's first launches) and regrown only when a larger union arrives — never out of the plan's
                 # bump arena, which lives as long as the cached plan and would grow by a table per step
                 tab = getattr(plan, "union_tab", None)
                 if tab is None or tab.numel() < len(flat):
                     tab = plan.union_tab = torch.empty(max(len(flat), 2 * (tab.numel() if tab is not None else 0)), dtype=torch.int64, device=eng.device)
-                h.chunk_tab, h.nchunks = tab, len(flat) // 2
-                prog = Program(P.const_i64_descs(tab.data_ptr(), flat) + eng._optimizer_descs(h, Bg, cat_all, sg_all, clip, eps, rank_layout=rank_layout))
-                prog.holder = h
+                t = over(None, (tab, len(flat) // 2))
+                prog = Program(P.const_i64_descs(tab.data_ptr(), flat) + eng._optimizer_descs(t, Bg, cat_all, sg_all, clip, eps, rank_layout=rank_layout))
+                prog.opt_tail = t
                 plan.union_opt = prog  # (kept alive until the plan goes)
                 prog.run(eng._sp())
                 return
             # weight-sharing supernet: zero_grad / norm / Adagrad cover the arena ranges of the plan's path only (engine.compile),
-            # so the optimizer program is the plan's: same work buffers, the plan's chunk table
+            # so the optimizer program is the plan's: the run's work buffers, the plan's chunk tables
             if getattr(plan, "opt_prog", None) is None:
-                h = _Holder()
-                for k in shared:
-                    if hasattr(holder, k):
-                        setattr(h, k, getattr(holder, k))
-                h.chunk_tab, h.nchunks = plan.cp.chunk_tab, plan.cp.nchunks
-                self._take_plan_tables(h, plan.cp, weight_decay, no_reg_param_name, optim)
-                plan.opt_prog = Program(eng._optimizer_descs(h, Bg, cat_all, sg_all, clip, eps, rank_layout=rank_layout))
-                plan.opt_prog.holder = h
+                t = over(plan.cp.tail, (plan.cp.tail.chunk_tab, plan.cp.tail.nchunks))
+                plan.opt_prog = Program(eng._optimizer_descs(t, Bg, cat_all, sg_all, clip, eps, rank_layout=rank_layout))
+                plan.opt_prog.opt_tail = t
             plan.opt_prog.run(eng._sp())
 
         return run
@@ -648,7 +632,7 @@ class EngineDP:
         enqueued once the ids all-gather has landed, anywhere before the optimizer"""
         import ctypes as C
         from . import _lib as L
-        d = getattr(self._holder, "dedup_ids", None)
+        d = self._tail.dedup_ids if self._tail is not None else None
         if d is None:
             return None
         eng, lib = self.engine, L.load()
@@ -679,8 +663,7 @@ class EngineDP:
         keep = (cs, rr)
         return (lambda: L.check(lib.nasrec_launch(eng._sp(), C.addressof(keep[0])))), (lambda: L.check(lib.nasrec_launch(eng._sp(), C.addressof(keep[1]))))
 
-    def dp_plan(self, choice, B, grad_scale, clip, eps, graph, row_grad_out=None, weight_decay=0.0, no_reg_param_name=None,
-                optim=None) -> DPPlan:
+    def dp_plan(self, choice, B, grad_scale, clip, eps, graph, row_grad_out=None, spec=None) -> DPPlan:
         from .engine import Program
         eng = self.engine
         fixed = eng.cfg.fixed
@@ -688,7 +671,7 @@ class EngineDP:
         # its backward is, and can travel under the blocks that follow
         # (local_optimizer = False: clip + Adagrad of a data-parallel step run over the GLOBAL batch, dp_optimizer)
         cp = eng.compile(choice, B, True, clip, eps, graph=False, grad_scale=grad_scale, defer_dw=False, row_grad_out=row_grad_out, local_optimizer=False,
-                         weight_decay=weight_decay, no_reg_param_name=no_reg_param_name, optim=optim)
+                         spec=spec)
         plan = DPPlan()
         plan.cp = cp
         plan.cat_local, plan.loss = cp.cat_x, cp.loss
@@ -767,10 +750,6 @@ class EngineDP:
                 plan.segments = segs
         eng.stream.synchronize()
         return plan
-
-
-class _Holder:
-    pass
 
 
 def _jsonable(o):

@@ -628,18 +628,17 @@ class SuperNet(nn.Module):
         d = self.__dict__  # (plain bookkeeping: nn.Module.__setattr__ costs 2 us per assignment)
         d["_engine_steps"] = d.get("_engine_steps", 0) + 1
         d["_last_step_batch"] = int(int_feats.shape[0])
-        weight_decay = float(weight_decay or 0.0)
-        d["_last_step_key"] = (choice, clip, eps, graph)
+        from ..optim_spec import OptimSpec
+        spec = OptimSpec.of(eps, weight_decay, no_reg_param_name, optim)
+        d["_last_step_key"] = (choice, clip, eps, graph, spec)
         d["_last_step_last_layer"] = False
-        d["_last_step_wd"] = (weight_decay, no_reg_param_name)
-        d["_last_step_optim"] = optim
         opt_kw = {}
-        if weight_decay or optim is not None:
+        if spec.wd or spec.moments:
             if self._table_sharding == "row":
                 from .._lib import EngineError
                 raise EngineError("weight decay, Adam and SGD in the fused step need whole tables: row-sharded tables train them "
                                   "through the torch route")
-            opt_kw = dict(weight_decay=weight_decay, no_reg_param_name=no_reg_param_name, optim=optim)
+            opt_kw = dict(weight_decay=spec.wd, no_reg_param_name=spec.no_reg, optim=optim)
         if self._table_sharding == "row":
             from ..sharded_tables import ShardedTableStep
             st = self.__dict__.get("_sharded_step")
@@ -653,7 +652,7 @@ class SuperNet(nn.Module):
             # one process per GPU (utils/dist.py): the batch is this rank's share of the global batch; same path on every rank
             from ..parallel import DataParallelStep
             dp = self.__dict__.get("_dp_step")
-            key = (id(self._engine), int(int_feats.shape[0]), clip, eps, graph, weight_decay, no_reg_param_name, optim)
+            key = (id(self._engine), int(int_feats.shape[0]), clip, eps, graph, spec)
             if dp is None or dp[0] != key:
                 dp = (key, DataParallelStep(self._engine, choice if self._fixed else None, int(int_feats.shape[0]), clip=clip, eps=eps, graph=graph,
                                             **opt_kw))
@@ -698,130 +697,57 @@ class SuperNet(nn.Module):
         B = self._last_step_batch
         if self.__dict__.get("_last_step_last_layer"):  # (engine_last_layer_step)
             return self._engine.last_layer_plan.logits.view(B, 1)
-        choice, clip, eps, graph = self._last_step_key
+        choice, clip, eps, graph, spec = self._last_step_key
         if self._table_sharding == "row":
             return self._sharded_ops.cp.logits.view(B, 1)
         dp = self.__dict__.get("_dp_step")
         if dp is not None and dp[1].exchange:
             return dp[1].last_plan().logits.view(B, 1)
-        wd, no_reg = self.__dict__.get("_last_step_wd", (0.0, None))
-        cp = self._engine.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, weight_decay=wd, no_reg_param_name=no_reg,
-                                  optim=self.__dict__.get("_last_step_optim"))
+        cp = self._engine.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, spec=spec)
         return cp.logits.view(B, 1)
 
     def engine_last_l2(self):
         """(device) get_l2_loss(self, weight_decay, no_reg_param_name) of the pre-step weights of the most recent engine_train_step —
         the `L2:` the reference prints (train_utils.py:262-266); exactly 0 when that step had weight_decay == 0"""
-        wd, _ = self.__dict__.get("_last_step_wd", (0.0, None))
+        key = self.__dict__.get("_last_step_key")
+        wd = key[-1].wd if key is not None else 0.0
         eng = self._engine
         if not wd or getattr(eng, "wd_l2_sumsq", None) is None:
             return torch.zeros((), device=self._final.weight.device)
         return (eng.wd_l2_sumsq[0] * wd).to(torch.float32)
 
     def engine_bind_optimizer(self, optimizer, last_layer: bool = False):
-        """Share the Adagrad accumulators between a torch.optim.Adagrad and the engine: existing `sum` state (a resumed
-        checkpoint) is copied into the engine's arenas, then `optimizer.state[p]["sum"]` aliases them, so
-        `optimizer.state_dict()` stays a faithful checkpoint while the fused step does the updates.
-        torch.optim.Adam / SGD (OptimSpec.from_optimizer): _bind_moments.  last_layer: the same for engine_last_layer_step, over
-        _final.{weight, bias} only (_bind_last_layer): the frozen parameters' state is left as it is."""
+        """Share the optimizer state between a torch optimizer and the engine.  Adagrad: existing `sum` state (a resumed checkpoint) is
+        copied into the engine's accumulators, then `optimizer.state[p]["sum"]` aliases them, so `optimizer.state_dict()` stays a
+        faithful checkpoint while the fused step does the updates.  torch.optim.Adam / SGD (OptimSpec.for_step): the engine's moment
+        arrays and step counters take the optimizer's state — a parameter without state (never stepped) starts from zero — and the
+        state of every parameter that has some aliases them.  last_layer: the same for engine_last_layer_step, over _final.{weight,
+        bias} only: the frozen parameters' state is left as it is."""
         eng = self._engine
         assert eng is not None, "run one forward first (lazy shapes)"
         from ..optim_spec import OptimSpec
-        spec = OptimSpec.from_optimizer(optimizer) if type(optimizer) is not torch.optim.Adagrad else None
-        self.__dict__["_bound_last_layer"] = bool(last_layer)
-        if last_layer:
-            self.__dict__["_bound_moments"] = None
-            return self._bind_last_layer(optimizer, spec)
-        self.__dict__["_bound_moments"] = spec
-        if spec is not None:
-            return self._bind_moments(optimizer, spec)
-        eng._ensure_table_state()
-        for name, p in self.named_parameters():
-            if name.startswith("_embedding.") and self._table_sharding == "row":
-                tgt = self._sharded.state[int(name.split(".")[1])]
-            elif name.startswith("_embedding."):
-                tgt = eng.table_state[int(name.split(".")[1])]
-            elif name in eng.state:
-                tgt = eng.state[name]
-            else:
-                continue
-            st = optimizer.state[p]
-            if "sum" in st and st["sum"].data_ptr() != tgt.data_ptr():
-                tgt.copy_(st["sum"].to(tgt.device).view_as(tgt))
-            st["sum"] = tgt
-            st.setdefault("step", torch.tensor(0.0))
-        self._bound_optimizer_steps = getattr(self, "_engine_steps", 0)
-
-    def _bind_moments(self, optimizer, spec):
-        """Adam / SGD: the engine's step counters and moment arrays take the optimizer's state — a parameter without state (never
-        stepped) starts from zero — and `optimizer.state[p]` of every parameter that has state aliases the engine's arrays.
-        Parameters the fused steps reach later get their entries in engine_sync_optimizer_steps, as torch creates them on a
-        parameter's first step."""
-        eng = self._engine
-        if self._table_sharding == "row":
+        spec = OptimSpec.for_step(optimizer)
+        if spec is None or not spec.moments:  # (the Adagrad accumulators: also what an optimizer the fused step does not reproduce gets)
+            spec = OptimSpec.of()
+        if spec.moments and not last_layer and self._table_sharding == "row":
             from .._lib import EngineError
             raise EngineError("Adam / SGD in the fused step need whole tables on the device")
-        eng.ensure_moments_state(spec.kind)
-        counts = torch.zeros(eng.opt_steps.numel(), dtype=torch.float32)
-        with torch.cuda.stream(eng.stream):
-            for name, p in self.named_parameters():
-                if name not in eng.param_index:
-                    continue
-                st = optimizer.state.get(p)
-                for key in spec.state_keys:
-                    tgt = eng.moments_view(key, name)
-                    src = st.get(key) if st else None
-                    if src is None:
-                        tgt.zero_()
-                    elif src.data_ptr() != tgt.data_ptr():
-                        tgt.copy_(src.to(tgt.device).view_as(tgt))
-                if st:
-                    if spec.kind == "adam":
-                        counts[eng.param_index[name]] = float(st.get("step", 0.0))
-                    elif st.get("momentum_buffer") is not None:
-                        counts[eng.param_index[name]] = 1.0  # (SGD keeps no count: "has a buffer" is what the engine needs)
-            eng.opt_steps.copy_(counts.to(eng.device))
-        eng.stream.synchronize()
-        self._alias_moments(optimizer, spec, counts)
-
-    def _alias_moments(self, optimizer, spec, counts):
-        eng = self._engine
-        for name, p in self.named_parameters():
-            k = eng.param_index.get(name)
-            if k is None or counts[k] <= 0:
-                continue
-            st = optimizer.state[p]
-            for key in spec.state_keys:
-                st[key] = eng.moments_view(key, name)
-            if spec.kind == "adam":
-                st["step"] = torch.tensor(float(counts[k]), dtype=torch.float32)
-
-    _FINAL = ("_final.weight", "_final.bias")
-
-    def _bind_last_layer(self, optimizer, spec):
-        """engine_bind_optimizer(last_layer=True).  Adagrad: `sum` of _final.* aliases the engine's accumulators (the ones the
-        autograd route's plan shares).  Adam / SGD: the engine's last-layer moments and counters (ensure_last_layer_state) take the
-        optimizer's state of _final.* — none: zero — and alias it once a parameter has been stepped."""
-        eng = self._engine
-        params = dict(self.named_parameters())
-        self.__dict__["_bound_ll_spec"] = spec
-        if spec is None:
-            for name in self._FINAL:
-                st = optimizer.state[params[name]]
-                tgt = eng.state[name]
+        self.__dict__["_bound"] = (spec, bool(last_layer))
+        self._bound_optimizer_steps = getattr(self, "_last_layer_steps" if last_layer else "_engine_steps", 0)
+        slots, counters = self._state_slots(spec, last_layer)
+        if counters is None:
+            for p, views, _ in slots:
+                st, tgt = optimizer.state[p], views["sum"]
                 if "sum" in st and st["sum"].data_ptr() != tgt.data_ptr():
                     tgt.copy_(st["sum"].to(tgt.device).view_as(tgt))
                 st["sum"] = tgt
                 st.setdefault("step", torch.tensor(0.0))
-            self._bound_optimizer_steps = getattr(self, "_last_layer_steps", 0)
             return
-        arrays = eng.ensure_last_layer_state(spec.kind)
-        counts = torch.zeros(2, dtype=torch.float32)
+        counts = torch.zeros(counters.numel(), dtype=torch.float32)
         with torch.cuda.stream(eng.stream):
-            for i, name in enumerate(self._FINAL):
-                st = optimizer.state.get(params[name])
-                for key in spec.state_keys:
-                    tgt = arrays[key][i]
+            for p, views, k in slots:
+                st = optimizer.state.get(p)
+                for key, tgt in views.items():
                     src = st.get(key) if st else None
                     if src is None:
                         tgt.zero_()
@@ -829,57 +755,73 @@ class SuperNet(nn.Module):
                         tgt.copy_(src.to(tgt.device).view_as(tgt))
                 if st:
                     if spec.kind == "adam":
-                        counts[i] = float(st.get("step", 0.0))
+                        counts[k] = float(st.get("step", 0.0))
                     elif st.get("momentum_buffer") is not None:
-                        counts[i] = 1.0
-            eng.ll_steps.copy_(counts.to(eng.device))
+                        counts[k] = 1.0  # (SGD keeps no count: "has a buffer" is what the engine needs)
+            counters.copy_(counts.to(eng.device))
         eng.stream.synchronize()
-        self._alias_last_layer(optimizer, spec, counts)
+        self._alias_state(optimizer, spec, slots, counts)
 
-    def _alias_last_layer(self, optimizer, spec, counts):
-        arrays = self._engine.ll_moments
+    _FINAL = ("_final.weight", "_final.bias")
+
+    def _state_slots(self, spec, last_layer: bool):
+        """what engine_bind_optimizer / engine_sync_optimizer_steps share: [(parameter, {state key: engine array}, counter index)] for the
+        parameters the fused step updates (the whole model, or _final alone), and the engine's step counters (None: Adagrad)"""
+        eng = self._engine
         params = dict(self.named_parameters())
-        for i, name in enumerate(self._FINAL):
-            if counts[i] <= 0:
+        if not spec.moments:
+            if last_layer:
+                return [(params[n], {"sum": eng.state[n]}, None) for n in self._FINAL], None
+            eng._ensure_table_state()
+            slots = []
+            for name, p in params.items():
+                if name.startswith("_embedding."):
+                    f = int(name.split(".")[1])
+                    tgt = self._sharded.state[f] if self._table_sharding == "row" else eng.table_state[f]
+                elif name in eng.state:
+                    tgt = eng.state[name]
+                else:
+                    continue
+                slots.append((p, {"sum": tgt}, None))
+            return slots, None
+        if last_layer:
+            arrays = eng.ensure_last_layer_state(spec.kind)
+            return [(params[n], {k: arrays[k][i] for k in spec.state_keys}, i) for i, n in enumerate(self._FINAL)], eng.ll_steps
+        eng.ensure_moments_state(spec.kind)
+        return [(p, {k: eng.moments_view(k, n) for k in spec.state_keys}, eng.param_index[n]) for n, p in params.items()
+                if n in eng.param_index], eng.opt_steps
+
+    @staticmethod
+    def _alias_state(optimizer, spec, slots, counts):
+        """Adam / SGD: the state of every parameter the engine has stepped (counts > 0) aliases the engine's arrays, as torch creates it on
+        a parameter's first step"""
+        for p, views, k in slots:
+            if counts[k] <= 0:
                 continue
-            st = optimizer.state[params[name]]
-            for key in spec.state_keys:
-                st[key] = arrays[key][i]
+            st = optimizer.state[p]
+            st.update(views)
             if spec.kind == "adam":
-                st["step"] = torch.tensor(float(counts[i]), dtype=torch.float32)
+                st["step"] = torch.tensor(float(counts[k]), dtype=torch.float32)
 
     def engine_sync_optimizer_steps(self, optimizer):
         """add the fused steps taken since engine_bind_optimizer to the optimizer's per-parameter step counters
         (Adam / SGD: the counters of the engine, and state entries for the parameters stepped for the first time)"""
-        if self.__dict__.get("_bound_last_layer"):
-            spec = self.__dict__.get("_bound_ll_spec")
-            if spec is not None:
-                self._engine.stream.synchronize()
-                torch.cuda.synchronize(self._engine.device)
-                self._alias_last_layer(optimizer, spec, self._engine.ll_steps.detach().cpu())
-                return
-            done = getattr(self, "_last_layer_steps", 0) - getattr(self, "_bound_optimizer_steps", 0)
-            if done:
-                params = dict(self.named_parameters())
-                for name in self._FINAL:
-                    st = optimizer.state.get(params[name])
-                    if st is not None and "step" in st:
-                        st["step"] = st["step"] + float(done)
-                self._bound_optimizer_steps = getattr(self, "_last_layer_steps", 0)
+        spec, last_layer = self.__dict__.get("_bound", (None, False))
+        if spec is not None and spec.moments:
+            self._engine.stream.synchronize()
+            torch.cuda.synchronize(self._engine.device)
+            slots, counters = self._state_slots(spec, last_layer)
+            self._alias_state(optimizer, spec, slots, counters.detach().cpu())
             return
-        spec = self.__dict__.get("_bound_moments")
-        if spec is not None:
-            eng = self._engine
-            eng.stream.synchronize()
-            self._alias_moments(optimizer, spec, eng.opt_steps.detach().cpu())
-            return
-        done = getattr(self, "_engine_steps", 0) - getattr(self, "_bound_optimizer_steps", 0)
+        steps = getattr(self, "_last_layer_steps" if last_layer else "_engine_steps", 0)
+        done = steps - getattr(self, "_bound_optimizer_steps", 0)
         if done:
-            for p in self.parameters():
+            params = dict(self.named_parameters())
+            for p in ([params[n] for n in self._FINAL] if last_layer else self.parameters()):
                 st = optimizer.state.get(p)
                 if st is not None and "step" in st:
                     st["step"] = st["step"] + float(done)
-            self._bound_optimizer_steps = getattr(self, "_engine_steps", 0)
+            self._bound_optimizer_steps = steps
 
 
 class SuperNetBlock(nn.Module):

@@ -113,25 +113,30 @@ def test_one_epoch(model, test_loader, loss_fn, gpu: Optional[int] = None, max_s
 test_one_epoch.__test__ = False  # not a pytest test
 
 
+def _optim_spec(optimizer, l2_loss_fn):
+    """OptimSpec.for_step with the weight decay of an L2Loss (any other l2_loss_fn adds none: the callers check that it is zero)"""
+    from ..optim_spec import OptimSpec
+    if isinstance(l2_loss_fn, L2Loss):
+        return OptimSpec.for_step(optimizer, l2_loss_fn.wd, l2_loss_fn.no_reg_param_name)
+    return OptimSpec.for_step(optimizer)
+
+
 def _last_layer_step_applies(model, optimizer, l2_loss_fn, use_amp):
     """engine_last_layer_step stands in for the torch route's step: a SuperNet in last-layer mode (every parameter outside _final
-    frozen) of one process with whole tables on the device, an L2Loss, and torch.optim.Adagrad (lr_decay, weight_decay,
-    initial_accumulator_value 0, not maximize) or an Adam / SGD that OptimSpec.from_optimizer accepts, in one group"""
+    frozen) of one process with whole tables on the device, an L2Loss, and an optimizer OptimSpec.for_step accepts whose one group
+    holds _final — an Adagrad also neither differentiable nor fused"""
     if use_amp or not hasattr(model, "engine_last_layer_step") or not isinstance(l2_loss_fn, L2Loss):
         return False
     from .dist import world_info
     if world_info()[1] > 1 or getattr(model, "_table_sharding", None) == "row" or getattr(model, "_place_embedding_on_cpu", False):
         return False
-    if len(optimizer.param_groups) != 1 or not model._last_layer_only():
+    if _optim_spec(optimizer, l2_loss_fn) is None or not model._last_layer_only():
         return False
     g = optimizer.param_groups[0]
     if not {id(p) for p in model._final.parameters()} <= {id(p) for p in g["params"]}:
         return False
-    if type(optimizer) is torch.optim.Adagrad:
-        return not (g.get("weight_decay", 0) != 0 or g.get("lr_decay", 0) != 0 or g.get("initial_accumulator_value", 0) != 0
-                    or g.get("maximize", False) or g.get("differentiable", False) or g.get("fused"))
-    from ..optim_spec import OptimSpec
-    return OptimSpec.from_optimizer(optimizer) is not None
+    # (only this route refuses a differentiable / fused Adagrad: _fused_step_applies takes it)
+    return not (type(optimizer) is torch.optim.Adagrad and (g.get("differentiable", False) or g.get("fused")))
 
 
 def _whole_table_optimizers_apply(model) -> bool:
@@ -144,38 +149,33 @@ def _whole_table_optimizers_apply(model) -> bool:
     return world_info()[1] <= 1 or bool(getattr(model, "engine_dp_optimizers", False))
 
 
-def _fused_step_applies(model, optimizer, l2_loss_fn, use_amp):
+def _fused_step_spec(model, optimizer, l2_loss_fn, use_amp):
+    """the OptimSpec of the fused engine step that stands in for this model's torch step (OptimSpec.for_step), or None: the torch route"""
     if use_amp or not hasattr(model, "engine_train_step"):
-        return False
-    moments = None
-    if type(optimizer) is not torch.optim.Adagrad:
-        # torch.optim.Adam / SGD with momentum (main_train.py:150-160) under the conditions of OptimSpec.from_optimizer, with whole
-        # tables (_whole_table_optimizers_apply); row-sharded tables keep the torch route
-        from ..optim_spec import OptimSpec
-        moments = OptimSpec.from_optimizer(optimizer)
-        if moments is None or not _whole_table_optimizers_apply(model):
-            return False
-    if getattr(model, "_place_embedding_on_cpu", False):
-        return False  # the tables stay on the host: torch's optimizer updates them there
-    for g in optimizer.param_groups if moments is None else ():  # (Adagrad's own options)
-        if g.get("weight_decay", 0) != 0 or g.get("lr_decay", 0) != 0 or g.get("initial_accumulator_value", 0) != 0 or g.get("maximize", False):
-            return False
-    if len(optimizer.param_groups) != 1:
-        return False
+        return None
+    spec = _optim_spec(optimizer, l2_loss_fn)
+    if spec is None or getattr(model, "_place_embedding_on_cpu", False):
+        return None  # (the tables on the host: torch's optimizer updates them there)
     # the fused step updates the WHOLE dense arena and every touched embedding row: it only stands in for optimizer.step() when
     # every parameter trains and the optimizer's single group covers all of them (set_mode_to_finelune_last_only /
     # layernorm_calibrate / finetune_no_embedding, or an optimizer over a parameter subset, take the torch route)
     params = list(model.parameters())
     if not all(p.requires_grad for p in params):
-        return False
+        return None
     if {id(p) for p in params} != {id(p) for p in optimizer.param_groups[0]["params"]}:
-        return False
-    if isinstance(l2_loss_fn, L2Loss) and l2_loss_fn.wd != 0:
-        # the engine folds the L2 term into its step — with whole tables (_whole_table_optimizers_apply); row-sharded tables keep the
-        # torch route with weight decay
-        return _whole_table_optimizers_apply(model)
-    with torch.no_grad():
-        return float(l2_loss_fn(model)) == 0.0
+        return None
+    # weight decay, Adam and SGD need whole tables (_whole_table_optimizers_apply); row-sharded tables keep the torch route with them
+    if (spec.wd or spec.moments) and not _whole_table_optimizers_apply(model):
+        return None
+    if not spec.wd:
+        with torch.no_grad():
+            if float(l2_loss_fn(model)) != 0.0:
+                return None
+    return spec
+
+
+def _fused_step_applies(model, optimizer, l2_loss_fn, use_amp):
+    return _fused_step_spec(model, optimizer, l2_loss_fn, use_amp) is not None
 
 
 def _agreed_batches(train_loader, train_batch_size: int, world: int, gpu):
@@ -232,15 +232,21 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
     from .dist import StepAgreement, allreduce_grads, any_rank, world_info
     world = world_info()[1]
     zero_l2 = None
-    wd = l2_loss_fn.wd if (fused and isinstance(l2_loss_fn, L2Loss)) else 0.0
-    no_reg = l2_loss_fn.no_reg_param_name if wd else None
-    optim = None
-    if last_only:
-        wd = l2_loss_fn.wd
-        no_reg = l2_loss_fn.no_reg_param_name if wd else None
-    if (fused or last_only) and type(optimizer) is not torch.optim.Adagrad:  # Adam / SGD: the group's hyperparameters (the learning rate per step)
-        from ..optim_spec import OptimSpec
-        optim = OptimSpec.from_optimizer(optimizer)
+    # the fused steps' optimizer, once: Adagrad's eps or Adam / SGD's hyperparameters, and the L2 term's weight decay (the learning rate
+    # is read every step).  use_engine_step=True forces the fused step for an optimizer OptimSpec.for_step refuses: Adagrad with its eps.
+    from ..optim_spec import OptimSpec
+    spec = _optim_spec(optimizer, l2_loss_fn) if (fused or last_only) else None
+    if fused and spec is None:
+        wd = l2_loss_fn.wd if isinstance(l2_loss_fn, L2Loss) else 0.0
+        spec = OptimSpec.of(float(optimizer.param_groups[0]["eps"]), wd, getattr(l2_loss_fn, "no_reg_param_name", None))
+    opt_kw = {}
+    if spec is not None:
+        opt_kw = dict(weight_decay=spec.wd, no_reg_param_name=spec.no_reg)
+        if spec.moments:
+            opt_kw["optim"] = spec
+        else:
+            opt_kw["eps"] = spec.eps
+    wd = spec.wd if spec is not None else 0.0
     for batch_num, (int_x, cat_x, y) in enumerate(_agreed_batches(train_loader, train_batch_size, world, gpu)):
         t_data1 = time.time()
         on_dev = int_x.is_cuda and cat_x.is_cuda and y.is_cuda and (not isinstance(gpu, int) or int_x.device.index == gpu)
@@ -259,8 +265,7 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
             if batch_num % display_interval == 0 or batch_num == max_train_steps - 1:
                 with torch.no_grad():
                     l2_loss = l2_loss_fn(model)
-            loss = model.engine_last_layer_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value,
-                                                eps=float(group.get("eps", 1e-2)), weight_decay=wd, no_reg_param_name=no_reg, optim=optim)
+            loss = model.engine_last_layer_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value, **opt_kw)
             res = None
         elif fused and full:
             if not bound:  # lazy shapes + engine, then share the Adagrad accumulators (a resumed optimizer keeps its state)
@@ -268,14 +273,7 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                 model.engine_bind_optimizer(optimizer)
                 bound = True
             group = optimizer.param_groups[0]
-            if optim is not None:
-                loss = model.engine_train_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value, weight_decay=wd,
-                                               no_reg_param_name=no_reg, optim=optim)
-            elif wd:
-                loss = model.engine_train_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value, eps=float(group["eps"]),
-                                               weight_decay=wd, no_reg_param_name=no_reg)
-            else:
-                loss = model.engine_train_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value, eps=float(group["eps"]))
+            loss = model.engine_train_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value, **opt_kw)
             # the step's logits and the L2 term are only looked at on display steps: fetched there, not 3 900 times per epoch
             # (`torch.zeros` is a fill launch on the GPU, `engine_last_logits` a plan lookup)
             res = None

@@ -24,9 +24,8 @@ for cfgid, world in ((2, 8), (2, 4), (2, 2), (2, 1), (5, 8), (3, 8), (4, 8), (5,
     cat = bench.synthetic_ids(Bg, tables, g).cuda()
     sg = torch.randn(Bg * Fs * 16, device="cuda") * 1e-3
 
-    class H:
-        pass
     import nasrec_amd.engine as E
+    from nasrec_amd.optim_spec import OptimSpec
     sp = torch.cuda.current_stream().cuda_stream
     names = {getattr(L, n): n[3:] for n in dir(L) if n.startswith("OP_")}
     parts = []
@@ -35,7 +34,7 @@ for cfgid, world in ((2, 8), (2, 4), (2, 2), (2, 1), (5, 8), (3, 8), (4, 8), (5,
             continue
         keep = E.DEDUP_SPLIT_MAX_B
         E.DEDUP_SPLIT_MAX_B = cap
-        h = H()
+        h = E.OptimizerTail(OptimSpec.of(1e-2))
         sgc = sg.clone()  # (the two-halves launch sums in place)
         descs = eng._optimizer_descs(h, Bg, cat, sgc, 5.0, 1e-2)
         E.DEDUP_SPLIT_MAX_B = keep
