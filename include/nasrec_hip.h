@@ -705,7 +705,8 @@ typedef struct nasrec_const_i64_desc {
 typedef struct nasrec_layernorm_desc {
   int32_t kind; /* NASREC_OP_LAYERNORM_FWD / _BWD */
   int32_t mode, R, D;
-  int32_t ldx, ldy;
+  int32_t ldx, ldy;    /* row strides in floats (KC: per row; TOKR: per sample, i.e. per 16 rows): x AND dx use ldx, y AND dy
+                          use ldy, in both directions.  A consumer of dx must read it with ldx, not with D. */
   int32_t act, dims_in_use;
   int32_t accumulate;  /* fwd: y += ; bwd: dx += */
   float eps;

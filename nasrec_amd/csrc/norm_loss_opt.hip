@@ -167,12 +167,6 @@ int launch_const_i64(hipStream_t st, const nasrec_const_i64_desc_t* d) {
 // LayerNorm (supernet mode: every projection is followed by LN -> activation -> prefix mask,
 // modules.py:174-178).  Row r, element i:  KC: x[r*ld + i];  TOKR: x[(r>>4)*ld + (r&15) + i*16].
 // ---------------------------------------------------------------------------------------------------
-template <int MODE>
-__device__ __forceinline__ long ln_off(int r, int i, int ld) {
-  if (MODE == NASREC_AM_KC) return (long)r * ld + i;
-  return (long)(r >> 4) * ld + (r & 15) + (long)i * 16;
-}
-
 __device__ __forceinline__ float act_grad(float u, int act) {
   if (act == NASREC_ACT_RELU) return u > 0.f ? 1.f : 0.f;
   if (act == NASREC_ACT_SILU) {
@@ -211,30 +205,6 @@ __global__ __launch_bounds__(256) void ln_fwd_kc_kernel(const nasrec_layernorm_d
     u = act_apply(u, d.act);
     if (d.dims_in_use >= 0 && i >= d.dims_in_use) u = 0.f;
     y[i] = d.accumulate ? y[i] + u : u;
-  }
-}
-
-// token-axis rows: one thread per (b,e) row, D = N' <= 64 elements strided by 16 floats
-__global__ __launch_bounds__(256) void ln_fwd_tokr_kernel(const nasrec_layernorm_desc_t d) {
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= d.R) return;
-  float s = 0.f;
-  for (int i = 0; i < d.D; ++i) s += d.x[ln_off<NASREC_AM_TOKR>(r, i, d.ldx)];
-  const float mu = s / (float)d.D;
-  float v = 0.f;
-  for (int i = 0; i < d.D; ++i) {
-    const float c = d.x[ln_off<NASREC_AM_TOKR>(r, i, d.ldx)] - mu;
-    v = fmaf(c, c, v);
-  }
-  const float rstd = 1.f / sqrtf(v / (float)d.D + d.eps);
-  d.stats[2 * r] = mu;
-  d.stats[2 * r + 1] = rstd;
-  for (int i = 0; i < d.D; ++i) {
-    float u = fmaf((d.x[ln_off<NASREC_AM_TOKR>(r, i, d.ldx)] - mu) * rstd, d.w[i], d.b[i]);
-    u = act_apply(u, d.act);
-    if (d.dims_in_use >= 0 && i >= d.dims_in_use) u = 0.f;
-    float* y = d.y + ln_off<NASREC_AM_TOKR>(r, i, d.ldy);
-    *y = d.accumulate ? *y + u : u;
   }
 }
 
@@ -300,58 +270,13 @@ __global__ __launch_bounds__(256) void ln_bwd_kc_kernel(const nasrec_layernorm_d
   }
 }
 
-// backward, token-axis rows: thread = (b,e) row; dw/db reduced over the workgroup's 256 rows per element i
-__global__ __launch_bounds__(256) void ln_bwd_tokr_kernel(const nasrec_layernorm_desc_t d) {
-  __shared__ float red[4][2][64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  const bool live = r < d.R;
-  const float mu = live ? d.stats[2 * r] : 0.f, rstd = live ? d.stats[2 * r + 1] : 0.f;
-  float c1 = 0.f, c2 = 0.f;
-  if (live) {
-    for (int i = 0; i < d.D; ++i) {
-      const float xh = (d.x[ln_off<NASREC_AM_TOKR>(r, i, d.ldx)] - mu) * rstd;
-      float g = d.dy[ln_off<NASREC_AM_TOKR>(r, i, d.ldy)];
-      if (d.dims_in_use >= 0 && i >= d.dims_in_use) g = 0.f;
-      if (d.act != NASREC_ACT_NONE) g *= act_grad(fmaf(xh, d.w[i], d.b[i]), d.act);
-      const float gw = g * d.w[i];
-      c1 += gw;
-      c2 = fmaf(gw, xh, c2);
-    }
-    c1 /= (float)d.D;
-    c2 /= (float)d.D;
-  }
-  for (int i = 0; i < d.D; ++i) {
-    float g = 0.f, xh = 0.f;
-    if (live) {
-      xh = (d.x[ln_off<NASREC_AM_TOKR>(r, i, d.ldx)] - mu) * rstd;
-      g = d.dy[ln_off<NASREC_AM_TOKR>(r, i, d.ldy)];
-      if (d.dims_in_use >= 0 && i >= d.dims_in_use) g = 0.f;
-      if (d.act != NASREC_ACT_NONE) g *= act_grad(fmaf(xh, d.w[i], d.b[i]), d.act);
-      const float v = rstd * (g * d.w[i] - c1 - xh * c2);
-      float* dx = d.dx + ln_off<NASREC_AM_TOKR>(r, i, d.ldx);
-      *dx = d.accumulate ? *dx + v : v;
-    }
-    const float sw = wave_sum(g * xh), sb = wave_sum(g);
-    if (lane == 0) {
-      red[wave][0][i] = sw;
-      red[wave][1][i] = sb;
-    }
-  }
-  __syncthreads();
-  float* out = d.dwb_partial + (long)blockIdx.x * 2 * d.D;
-  for (int i = threadIdx.x; i < d.D; i += 256) {
-    out[i] = (red[0][0][i] + red[1][0][i]) + (red[2][0][i] + red[3][0][i]);
-    out[d.D + i] = (red[0][1][i] + red[1][1][i]) + (red[2][1][i] + red[3][1][i]);
-  }
-}
-
 // ---- register-resident rows ---------------------------------------------------------------------------------------------------
 // A LayerNorm row is read ONCE: dense rows (D <= 1024) live in 4 * NV registers of a wavefront's lanes (16-byte loads and
 // stores), token-axis rows (D = N' <= 64) in up to 64 registers of one thread.  Mean, variance, normalisation (forward) and
-// both reductions plus dx (backward) run on the registers; the general kernels above re-read the row from global memory for
-// every pass and serve unaligned rows (ld or D not a multiple of 4).  Bytes per row: forward 2 * 4D, backward 3 * 4D — the
-// HBM-streaming roofline these kernels are measured against.
+// both reductions plus dx (backward) run on the registers.  The general dense kernels above re-read the row from global memory
+// for every pass and serve unaligned dense rows (D or ld not a multiple of 4, or a pointer off a 16-byte boundary); unaligned
+// token-axis sample blocks are served by the tokr_reg kernels below, aligned ones by the wavefront-per-sample kernels after
+// them.  Bytes per row: forward 2 * 4D, backward 3 * 4D — the HBM-streaming roofline these kernels are measured against.
 template <int NV>
 __global__ __launch_bounds__(256) void ln_fwd_kc_vec_kernel(const nasrec_layernorm_desc_t d) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;

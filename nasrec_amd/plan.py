@@ -1293,7 +1293,8 @@ def emit_ln_dense(ctx, x: DV, D, lnname, tgt: Target, act, mask):
         d.kind = L.OP_COPY_SEGS
         d.B, d.nseg, d.ld_dst, d.accumulate, d.reverse = ctx.B, 1, x.ld, acc, 0
         d.dst = gp
-        d.seg[0], d.width[0], d.ld[0], d.off[0] = dx.data_ptr(), D, D, 0
+        # the LayerNorm backward writes dx with x's row stride (ldx = x.ld, the buffer is R * x.ld floats: _ln_numel), not densely
+        d.seg[0], d.width[0], d.ld[0], d.off[0] = dx.data_ptr(), D, x.ld, 0
         ctx.emit(d)
 
     emit_layernorm(ctx, L.AM_KC, x.ptr, x.ld, ctx.B, D, lnname, tgt.view.ptr, tgt.view.ld, act, mask, tgt.accumulate, tgt.view, xgrad)

@@ -130,3 +130,44 @@ def test_silu_and_sigmoid_epilogues_over_the_whole_range():
     ref = 1.0 / (1.0 + torch.exp(-zz))
     err = (sig - ref).abs()
     assert bool((err <= 4 * 1.2e-7 * (1 + zz.abs() / 8) * ref.abs() + 1e-38).all()), float((err / (ref.abs() + 1e-38)).max())
+
+
+@pytest.mark.parametrize("dims_in_use", [16, 9])
+@pytest.mark.parametrize("B", [256, 260])
+def test_sigmoid_gating_layernorm_without_projection_above_batch_256(B, dims_in_use):
+    """Inputs as wide as the output (no projection), so the operator's own LayerNorm reads the gated product directly — above batch
+    256 from a temporary whose rows are padded to 32 floats, and the LayerNorm backward writes dx with that stride.  fp64 torch of
+    op_sigmoid_gating's docstring: out = mask(LN(sigmoid(Linear_16x16(pad(left))) * pad(right)))."""
+    from nasrec_amd.supernet.modules import SigmoidGating
+    g = torch.Generator().manual_seed(260)
+    m = SigmoidGating(fixed=False, use_layernorm=True, max_dims_or_dims=16).cuda()
+    left, right, dout = torch.randn(B, 8, generator=g), torch.randn(B, 16, generator=g), torch.randn(B, 16, generator=g)
+    with torch.no_grad():
+        m(left.cuda(), right.cuda(), dims_in_use)  # first forward: lazy shapes, the projection is deleted
+    shapes = {"_left_self_linear._linear.weight": (16, 16), "_left_self_linear._linear.bias": (16,), "_layernorm.weight": (16,),
+              "_layernorm.bias": (16,)}
+    assert {k: tuple(v.shape) for k, v in m.state_dict().items()} == shapes
+    sd = {k: torch.randn(s, generator=g) * (0.3 if "_linear" in k else 0.1) + (1.0 if k == "_layernorm.weight" else 0.0) for k, s in shapes.items()}
+    m.load_state_dict(sd, strict=True)
+    m.train()
+    xl, xr = left.cuda().requires_grad_(True), right.cuda().requires_grad_(True)
+    out = m(xl, xr, dims_in_use)
+    (out * dout.cuda()).sum().backward()
+
+    p = {k: v.double().requires_grad_(True) for k, v in sd.items()}
+    l64, r64 = left.double().requires_grad_(True), right.double().requires_grad_(True)
+    gate = torch.sigmoid(torch.nn.functional.pad(l64, (0, 8)) @ p["_left_self_linear._linear.weight"].t() + p["_left_self_linear._linear.bias"])
+    ref = torch.nn.functional.layer_norm(gate * r64, (16,), p["_layernorm.weight"], p["_layernorm.bias"], 1e-5)
+    ref = ref * (torch.arange(16) < dims_in_use).double()
+    (ref * dout.double()).sum().backward()
+
+    ref = ref.detach()
+    err = float((out.detach().double().cpu() - ref).abs().max())
+    print("B=%d dims=%d out err %.3e" % (B, dims_in_use, err))
+    assert err <= 1e-5 * max(1.0, float(ref.abs().max())), ("out", err)
+    checks = [("left", xl.grad, l64.grad), ("right", xr.grad, r64.grad)] + [(k, dict(m.named_parameters())[k].grad, p[k].grad) for k in shapes]
+    for name, got, want in checks:
+        assert got is not None, name
+        err, tol = float((got.double().cpu() - want).abs().max()), 2e-5 * max(float(want.norm()), 1e-6)
+        print("B=%d dims=%d d%s err %.3e (tol %.3e)" % (B, dims_in_use, name, err, tol))
+        assert err <= tol, (name, err, tol)
