@@ -915,6 +915,25 @@ int nasrec_roc_auc(void* stream, const nasrec_roc_auc_desc_t* d);
 int64_t nasrec_roc_auc_workspace_bytes(int64_t n); /* 0 for n < 2 or n > NASREC_ROC_AUC_MAX_N */
 int nasrec_worklist(void* stream, const nasrec_worklist_desc_t* d);
 
+/* Which kernel family nasrec_gemm runs for `d`: the launcher switches on this very function, so a caller that sizes split-K
+ * workspaces or names kernels before it launches asks here.  Host only: it reads the descriptor's integers and whether its pointers
+ * are null, never what they point to, and needs no device.  -> a NASREC_GEMM_ROUTE_* family, or a negative NASREC_GEMM_ROUTE_BAD_*
+ * for what nasrec_gemm rejects.  *eligible_mask (optional) receives bit (1 << family) for every family whose own rule accepts `d`,
+ * whatever the precedence between them (GENERAL: every supported binding without NASREC_SPLITK_BALANCED). */
+enum {
+  NASREC_GEMM_ROUTE_GENERAL = 0,      /* the tiled template of gemm.hip, any binding, split-K through slabs + second pass */
+  NASREC_GEMM_ROUTE_KSLICE = 1,       /* gemm_kslice.hip: one large forward product at batch ~256, single pass */
+  NASREC_GEMM_ROUTE_SKINNY_N = 2,     /* gemm_skinny.hip: N <= 16 at large batch, single pass */
+  NASREC_GEMM_ROUTE_TINYK = 3,        /* gemm_skinny.hip: K <= 16 at large batch, single pass */
+  NASREC_GEMM_ROUTE_TOKEN_LINEAR = 4, /* token_linear.hip: token-axis Linear at large batch, single pass */
+  NASREC_GEMM_ROUTE_TOKEN_DW = 5,     /* token_linear.hip: token-axis weight gradient at large batch, split-K only */
+  NASREC_GEMM_ROUTE_FAST = 6,         /* gemm_fast.hip: 128x128 throughput tiles, split-K or NASREC_SPLITK_BALANCED */
+  NASREC_GEMM_ROUTE_BAD_NSEG = -1,
+  NASREC_GEMM_ROUTE_BAD_BINDING = -2,
+  NASREC_GEMM_ROUTE_BAD_BALANCED = -3 /* NASREC_SPLITK_BALANCED on a launch the throughput kernel does not take */
+};
+int nasrec_gemm_route(const nasrec_gemm_desc_t* d, unsigned* eligible_mask);
+
 /* Uncached device memory (hipExtMallocWithFlags(hipDeviceMallocUncached)): the plan arena of a persistent step (NASREC_OP_PERSIST) —
  * buffers that one workgroup of a launch writes and another workgroup of the SAME launch reads.  The caller owns the memory. */
 int nasrec_alloc_uncached(int64_t bytes, void** out);

@@ -149,6 +149,9 @@ class MemsetDesc(C.Structure):
 
 
 SPLITK_BALANCED = -1                  # NASREC_SPLITK_BALANCED
+(GEMM_ROUTE_GENERAL, GEMM_ROUTE_KSLICE, GEMM_ROUTE_SKINNY_N, GEMM_ROUTE_TINYK, GEMM_ROUTE_TOKEN_LINEAR, GEMM_ROUTE_TOKEN_DW,
+ GEMM_ROUTE_FAST) = range(7)          # NASREC_GEMM_ROUTE_* (nasrec_gemm_route)
+GEMM_ROUTE_BAD_NSEG, GEMM_ROUTE_BAD_BINDING, GEMM_ROUTE_BAD_BALANCED = -1, -2, -3
 SK_WORKSPACE_FLOATS = 512 * 3 * 128 * 128  # NASREC_SK_WORKSPACE_FLOATS
 CHUNK_ELEMS = 65536     # NASREC_CHUNK_ELEMS
 CONST_I64_MAX = 448     # NASREC_CONST_I64_MAX
@@ -286,7 +289,7 @@ SYMBOLS = [
     "nasrec_opt_apply", "nasrec_worklist", "nasrec_dedup_ids", "nasrec_opt_reduce2", "nasrec_final_fused", "nasrec_event_create",
     "nasrec_event_record", "nasrec_event_elapsed_ms", "nasrec_event_destroy", "nasrec_last_error", "nasrec_abi_version",
     "nasrec_desc_sizes", "nasrec_tsv_parse", "nasrec_alloc_uncached", "nasrec_free_uncached", "nasrec_persist_prepare", "nasrec_worklist_prepare",
-    "nasrec_weight_decay", "nasrec_opt_moments", "nasrec_last_layer_step", "nasrec_roc_auc", "nasrec_roc_auc_workspace_bytes",
+    "nasrec_weight_decay", "nasrec_opt_moments", "nasrec_last_layer_step", "nasrec_roc_auc", "nasrec_roc_auc_workspace_bytes", "nasrec_gemm_route",
 ]
 
 _lib = None
@@ -332,6 +335,7 @@ def load():
         getattr(lib, name).argtypes = [vp, vp]
     lib.nasrec_roc_auc_workspace_bytes.argtypes = [i64]
     lib.nasrec_roc_auc_workspace_bytes.restype = i64
+    lib.nasrec_gemm_route.argtypes = [vp, C.POINTER(C.c_uint)]
     if lib.nasrec_abi_version() != 17:
         raise EngineError("ABI version mismatch: library %d, binding 17" % lib.nasrec_abi_version())
     sizes = (i32 * 43)()

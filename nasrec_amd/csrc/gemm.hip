@@ -99,39 +99,18 @@ static void launch_ring(hipStream_t st, const nasrec_gemm_desc_t* d, int Mmax, i
     hipLaunchKernelGGL((gemm_ring_kernel<AM, BMODE, CM, NT, TK, TBM, TBN, false>), grid, dim3(NT), 0, st, *d, Mmax, Nmax);
 }
 
+// The general template on one operand binding.  Tile shape by the launch's LIVE workgroups of a 64x64 tiling (a zmode grid is padded to
+// Mmax x Nmax: the surplus workgroups exit at once) and by the depth of its k-segments.
 template <int AM, int BMODE, int CM>
-static int launch_gemm_t(hipStream_t st, const nasrec_gemm_desc_t* d) {
-  int Mmax = 0, Nmax = 0, Kmax = 0;
-  const int nprob = d->zmode ? d->nseg : 1;
-  for (int q = 0; q < nprob; ++q) {
-    if (d->seg[q].M > Mmax) Mmax = d->seg[q].M;
-    if (d->seg[q].N > Nmax) Nmax = d->seg[q].N;
-  }
+static void launch_general_t(hipStream_t st, const nasrec_gemm_desc_t* d, int Mmax, int Nmax, int nprob, int S) {
+  const int zdim = nprob * S;
+  int Kmax = 0;
   for (int q = 0; q < d->nseg; ++q)
     if (d->seg[q].A && d->seg[q].K > Kmax) Kmax = d->seg[q].K;
-  if (Mmax <= 0 || Nmax <= 0) return 0;
-  const int S = d->splitk > 1 ? d->splitk : 1;
-  if (S > 1 && d->workspace == nullptr) return nasrec_set_error(-3, "gemm: splitk=%d needs a workspace", S);
-  const int zdim = nprob * S;
-  // LIVE workgroups of a 64x64 tiling (a zmode grid is padded to Mmax x Nmax: the surplus workgroups exit at once)
   long wgs = 0;
   for (int q = 0; q < nprob; ++q) wgs += (long)((d->seg[q].M + 63) / 64) * ((d->seg[q].N + 63) / 64) * S;
   const bool deep = Kmax > 32;
-  if (AM == NASREC_AM_KC && BMODE == NASREC_AM_KC && CM == NASREC_CM_PLAIN && gemm_kslice_eligible(d)) {
-    return launch_gemm_kslice(st, d);  // batch-256 regime, one large forward product: K split inside the workgroup, single pass
-  } else if (AM == NASREC_AM_KC && (BMODE == NASREC_AM_KC || BMODE == NASREC_AM_RC) && CM == NASREC_CM_PLAIN && gemm_skinny_n_eligible(d)) {
-    return launch_gemm_skinny_n(st, d);  // large batch, N <= 16: a streaming read of x, K split inside the workgroup, single pass
-  } else if (AM == NASREC_AM_KC && (BMODE == NASREC_AM_KC || BMODE == NASREC_AM_RC) && CM == NASREC_CM_PLAIN && gemm_tinyk_eligible(d)) {
-    return launch_gemm_tinyk(st, d);  // large batch, K <= 16: a streaming write of y, weights in registers, no LDS
-  } else if (AM == NASREC_AM_TOKK && token_dw_eligible(d)) {
-    launch_token_dw(st, d, Mmax, Nmax);  // large batch: a wavefront per sample, operands straight to MFMA registers (token_linear.hip)
-  } else if (CM == NASREC_CM_PLAIN && gemm_fast_eligible(d, Mmax, Nmax)) {
-    // throughput regime: 128x128x32 tiles, 16-byte staging, LDS double buffer (gemm_fast.hip)
-    const int rc = launch_gemm_fast(st, d, Mmax, Nmax, zdim);
-    if (rc) return rc;
-  } else if (d->splitk == NASREC_SPLITK_BALANCED) {
-    return nasrec_set_error(-2, "gemm: the balanced schedule exists for throughput-regime launches only (plan.py decides both)");
-  } else if (wgs >= 1024) {
+  if (wgs >= 1024) {
     launch_cfg<AM, BMODE, CM, GEMM_BIG_NT, GEMM_BIG_TK, 64, 64>(st, d, Mmax, Nmax, zdim);
   } else if (wgs >= GEMM_SKINNY_BELOW) {
     if (GEMM_ZBATCH_TILE32 && d->zmode && nprob > 1 && deep) {
@@ -151,33 +130,94 @@ static int launch_gemm_t(hipStream_t st, const nasrec_gemm_desc_t* d) {
     if (deep) launch_ring<AM, BMODE, CM, 256, GEMM_TK_DEEP, 16, 64>(st, d, Mmax, Nmax, zdim);
     else launch_ring<AM, BMODE, CM, 256, 32, 16, 64>(st, d, Mmax, Nmax, zdim);
   }
-  if (S > 1 && !d->defer_second_pass) {
-    long elems = (long)Mmax * Nmax;
-    dim3 g2((unsigned)((elems + 255) / 256), 1, nprob);
-    hipLaunchKernelGGL((gemm_splitk_epilogue<CM>), g2, dim3(256), 0, st, *d, Mmax, Nmax);
+}
+
+static constexpr int binding_key(int am, int bm, int cm) { return am * 100 + bm * 10 + cm; }
+
+// THE routing rule of the family (include/nasrec_hip.h): launch_gemm switches on it, the planner asks it.  Each family's own rule
+// lives beside its kernel and checks its operand bindings itself; what is decided here is which bindings exist at all, the
+// precedence between families whose rules overlap, and that only the throughput kernel has a balanced schedule.
+int nasrec_gemm_route(const nasrec_gemm_desc_t* d, unsigned* eligible_mask) {
+  if (eligible_mask) *eligible_mask = 0;
+  if (d->nseg < 1 || d->nseg > NASREC_MAX_SEGS) return NASREC_GEMM_ROUTE_BAD_NSEG;
+  switch (binding_key(d->amode, d->bmode, d->cmode)) {
+    case binding_key(NASREC_AM_KC, NASREC_AM_KC, NASREC_CM_PLAIN):      // y = x Wᵀ
+    case binding_key(NASREC_AM_KC, NASREC_AM_RC, NASREC_CM_PLAIN):      // dx = dy W
+    case binding_key(NASREC_AM_RC, NASREC_AM_RC, NASREC_CM_PLAIN):      // dW = dyᵀ x
+    case binding_key(NASREC_AM_KC, NASREC_AM_TOKR, NASREC_CM_TOKJ):     // token-axis y = W x
+    case binding_key(NASREC_AM_RC, NASREC_AM_TOKR, NASREC_CM_TOKJ):     // token-axis dx = Wᵀ dy
+    case binding_key(NASREC_AM_TOKK, NASREC_AM_TOKK, NASREC_CM_PLAIN):  // token-axis dW = dy xᵀ
+      break;
+    default:
+      return NASREC_GEMM_ROUTE_BAD_BINDING;
   }
-  return nasrec_check_launch("gemm");
+  // in order of precedence
+  static const struct { int family; bool (*takes)(const nasrec_gemm_desc_t*); } ladder[] = {
+    {NASREC_GEMM_ROUTE_TOKEN_LINEAR, token_linear_eligible},  // large batch: weights in LDS, a wavefront per sample
+    {NASREC_GEMM_ROUTE_KSLICE, gemm_kslice_eligible},         // batch-256 regime, one large forward product: K split inside the workgroup
+    {NASREC_GEMM_ROUTE_SKINNY_N, gemm_skinny_n_eligible},     // large batch, N <= 16: a streaming read of x, K split inside the workgroup
+    {NASREC_GEMM_ROUTE_TINYK, gemm_tinyk_eligible},           // large batch, K <= 16: a streaming write of y, weights in registers, no LDS
+    {NASREC_GEMM_ROUTE_TOKEN_DW, token_dw_eligible},          // large batch: a wavefront per sample, operands straight to MFMA registers
+    {NASREC_GEMM_ROUTE_FAST, gemm_fast_eligible},             // throughput regime: 128x128x32 tiles, 16-byte staging, LDS double buffer
+  };
+  const bool balanced = d->splitk == NASREC_SPLITK_BALANCED;
+  int route = balanced ? NASREC_GEMM_ROUTE_BAD_BALANCED : NASREC_GEMM_ROUTE_GENERAL;
+  unsigned mask = balanced ? 0u : 1u << NASREC_GEMM_ROUTE_GENERAL;
+  bool taken = false;
+  for (const auto& f : ladder) {
+    if (!f.takes(d)) continue;
+    mask |= 1u << f.family;
+    if (!taken) route = f.family;
+    taken = true;
+    if (!eligible_mask) break;  // (the launcher only wants the winner)
+  }
+  if (eligible_mask) *eligible_mask = mask;
+  return route;
 }
 
 int launch_gemm(hipStream_t st, const nasrec_gemm_desc_t* d) {
-  if (d->nseg < 1 || d->nseg > NASREC_MAX_SEGS) return nasrec_set_error(-2, "gemm: nseg=%d out of range", d->nseg);
-  const int key = d->amode * 100 + d->bmode * 10 + d->cmode;
-  switch (key) {
-    case NASREC_AM_KC * 100 + NASREC_AM_KC * 10 + NASREC_CM_PLAIN:  // y = x Wᵀ
-      return launch_gemm_t<NASREC_AM_KC, NASREC_AM_KC, NASREC_CM_PLAIN>(st, d);
-    case NASREC_AM_KC * 100 + NASREC_AM_RC * 10 + NASREC_CM_PLAIN:  // dx = dy W
-      return launch_gemm_t<NASREC_AM_KC, NASREC_AM_RC, NASREC_CM_PLAIN>(st, d);
-    case NASREC_AM_RC * 100 + NASREC_AM_RC * 10 + NASREC_CM_PLAIN:  // dW = dyᵀ x
-      return launch_gemm_t<NASREC_AM_RC, NASREC_AM_RC, NASREC_CM_PLAIN>(st, d);
-    case NASREC_AM_KC * 100 + NASREC_AM_TOKR * 10 + NASREC_CM_TOKJ:  // token-axis y = W x
-      if (token_linear_eligible(d)) return launch_token_linear(st, d);  // large batch: weights in LDS, a wavefront per sample
-      return launch_gemm_t<NASREC_AM_KC, NASREC_AM_TOKR, NASREC_CM_TOKJ>(st, d);
-    case NASREC_AM_RC * 100 + NASREC_AM_TOKR * 10 + NASREC_CM_TOKJ:  // token-axis dx = Wᵀ dy
-      if (token_linear_eligible(d)) return launch_token_linear(st, d);
-      return launch_gemm_t<NASREC_AM_RC, NASREC_AM_TOKR, NASREC_CM_TOKJ>(st, d);
-    case NASREC_AM_TOKK * 100 + NASREC_AM_TOKK * 10 + NASREC_CM_PLAIN:  // token-axis dW = dy xᵀ
-      return launch_gemm_t<NASREC_AM_TOKK, NASREC_AM_TOKK, NASREC_CM_PLAIN>(st, d);
-    default:
-      return nasrec_set_error(-2, "gemm: unsupported operand binding a=%d b=%d c=%d", d->amode, d->bmode, d->cmode);
+  const int route = nasrec_gemm_route(d, nullptr);
+  if (route == NASREC_GEMM_ROUTE_BAD_NSEG) return nasrec_set_error(-2, "gemm: nseg=%d out of range", d->nseg);
+  if (route == NASREC_GEMM_ROUTE_BAD_BINDING)
+    return nasrec_set_error(-2, "gemm: unsupported operand binding a=%d b=%d c=%d", d->amode, d->bmode, d->cmode);
+  int Mmax = 0, Nmax = 0;
+  const int nprob = d->zmode ? d->nseg : 1;
+  for (int q = 0; q < nprob; ++q) {
+    if (d->seg[q].M > Mmax) Mmax = d->seg[q].M;
+    if (d->seg[q].N > Nmax) Nmax = d->seg[q].N;
   }
+  if (Mmax <= 0 || Nmax <= 0) return 0;
+  const int S = d->splitk > 1 ? d->splitk : 1;
+  if (S > 1 && d->workspace == nullptr) return nasrec_set_error(-3, "gemm: splitk=%d needs a workspace", S);
+  switch (route) {
+    // single-pass kernels
+    case NASREC_GEMM_ROUTE_TOKEN_LINEAR: return launch_token_linear(st, d);
+    case NASREC_GEMM_ROUTE_KSLICE: return launch_gemm_kslice(st, d);
+    case NASREC_GEMM_ROUTE_SKINNY_N: return launch_gemm_skinny_n(st, d);
+    case NASREC_GEMM_ROUTE_TINYK: return launch_gemm_tinyk(st, d);
+    case NASREC_GEMM_ROUTE_BAD_BALANCED:
+      return nasrec_set_error(-2, "gemm: the balanced schedule exists for throughput-regime launches only (the planner asks nasrec_gemm_route)");
+    // main passes: a split launch's slabs go through the second pass below
+    case NASREC_GEMM_ROUTE_TOKEN_DW: launch_token_dw(st, d, Mmax, Nmax); break;
+    case NASREC_GEMM_ROUTE_FAST: {
+      const int rc = launch_gemm_fast(st, d, Mmax, Nmax, nprob * S);
+      if (rc) return rc;
+      break;
+    }
+    default:  // NASREC_GEMM_ROUTE_GENERAL: one instantiation of the template per binding
+      switch (binding_key(d->amode, d->bmode, d->cmode)) {
+        case binding_key(NASREC_AM_KC, NASREC_AM_KC, NASREC_CM_PLAIN): launch_general_t<NASREC_AM_KC, NASREC_AM_KC, NASREC_CM_PLAIN>(st, d, Mmax, Nmax, nprob, S); break;
+        case binding_key(NASREC_AM_KC, NASREC_AM_RC, NASREC_CM_PLAIN): launch_general_t<NASREC_AM_KC, NASREC_AM_RC, NASREC_CM_PLAIN>(st, d, Mmax, Nmax, nprob, S); break;
+        case binding_key(NASREC_AM_RC, NASREC_AM_RC, NASREC_CM_PLAIN): launch_general_t<NASREC_AM_RC, NASREC_AM_RC, NASREC_CM_PLAIN>(st, d, Mmax, Nmax, nprob, S); break;
+        case binding_key(NASREC_AM_KC, NASREC_AM_TOKR, NASREC_CM_TOKJ): launch_general_t<NASREC_AM_KC, NASREC_AM_TOKR, NASREC_CM_TOKJ>(st, d, Mmax, Nmax, nprob, S); break;
+        case binding_key(NASREC_AM_RC, NASREC_AM_TOKR, NASREC_CM_TOKJ): launch_general_t<NASREC_AM_RC, NASREC_AM_TOKR, NASREC_CM_TOKJ>(st, d, Mmax, Nmax, nprob, S); break;
+        default: launch_general_t<NASREC_AM_TOKK, NASREC_AM_TOKK, NASREC_CM_PLAIN>(st, d, Mmax, Nmax, nprob, S); break;
+      }
+  }
+  if (S > 1 && !d->defer_second_pass) {
+    const dim3 g2((unsigned)(((long)Mmax * Nmax + 255) / 256), 1, nprob);
+    if (d->cmode == NASREC_CM_PLAIN) hipLaunchKernelGGL((gemm_splitk_epilogue<NASREC_CM_PLAIN>), g2, dim3(256), 0, st, *d, Mmax, Nmax);
+    else hipLaunchKernelGGL((gemm_splitk_epilogue<NASREC_CM_TOKJ>), g2, dim3(256), 0, st, *d, Mmax, Nmax);
+  }
+  return nasrec_check_launch("gemm");
 }

@@ -391,8 +391,8 @@ __global__ __launch_bounds__(1024) void gemm_kslice_kernel(const nasrec_gemm_des
 
 // Which launches take this kernel: one dense forward-type product (k-contiguous operands, plain output), no mask operands / virtual
 // column / row prefix, at most KS_SEGS segments, enough 32 x 32 tiles to cover most of the chip but not so many that 1024-thread
-// workgroups queue up, and a K deep enough that splitting it is what the general template would do anyway.  plan.py mirrors this
-// (`kslice_eligible`) and gives such launches splitk = 1.
+// workgroups queue up, and a K deep enough that splitting it is what the general template would do anyway.  The planner asks through
+// nasrec_gemm_route and gives such launches splitk = 1.
 bool gemm_kslice_eligible(const nasrec_gemm_desc_t* d) {
   if (d->amode != NASREC_AM_KC || d->bmode != NASREC_AM_KC || d->cmode != NASREC_CM_PLAIN || d->zmode || d->splitk > 1) return false;
   if (d->nseg > KS_SEGS) return false;

@@ -12,7 +12,7 @@
 //   * refills are unconditional: past the last tile of the workgroup they reload its last tile (never parked);
 //   * ReLU-mask operands are a template variant (AUX), not a run-time branch;
 //   * the segment cursor is advanced in a branch that contains no loads.
-// Row predicates (Mvalid, the virtual ones-column) are per workgroup: launch_gemm_t routes a launch whose k-segments disagree on
+// Row predicates (Mvalid, the virtual ones-column) are per workgroup: launch_ring (gemm.hip) routes a launch whose k-segments disagree on
 // them to gemm_tile.
 #pragma once
 #include <type_traits>

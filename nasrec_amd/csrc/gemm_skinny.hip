@@ -16,6 +16,7 @@
 //     bias, activation, saved planes, accumulation — reads first, one wait, stores).
 // The summation order is a fixed function of (segment list, NW); NW depends on M alone.
 #include <stdlib.h>
+#include <string.h>
 
 #include "gemm_tile.h"
 
@@ -118,8 +119,10 @@ __global__ __launch_bounds__(64 * NW) void gemm_skinny_n_kernel(const nasrec_gem
   }
 }
 
-// Which launches take this kernel (plan.py mirrors the rule — `skinny_n_eligible` — and gives them splitk = 1)
+// Which launches take this kernel (the planner asks through nasrec_gemm_route and gives them splitk = 1)
 bool gemm_skinny_n_eligible(const nasrec_gemm_desc_t* d) {
+  static const bool on = getenv("NASREC_SKINNY_N") == nullptr || strcmp(getenv("NASREC_SKINNY_N"), "0") != 0;  // A/B knob: 0 keeps these products on the general template (split-K + second pass)
+  if (!on) return false;
   if (d->amode != NASREC_AM_KC || (d->bmode != NASREC_AM_KC && d->bmode != NASREC_AM_RC) || d->cmode != NASREC_CM_PLAIN || d->splitk > 1) return false;
   if (d->zmode && d->nseg != 1) return false;
   const nasrec_gemm_seg_t& s0 = d->seg[0];

@@ -27,7 +27,9 @@
 #ifndef NASREC_GEMM_FAST_MIN_TILES
 #define NASREC_GEMM_FAST_MIN_TILES 120  // launches with at least this many 128x128 tiles (x split-K) take gemm_fast.hip
 #endif
-bool gemm_fast_eligible(const nasrec_gemm_desc_t* d, int Mmax, int Nmax);
+// Each family's rule stands beside its kernel; nasrec_gemm_route (gemm.hip) holds the precedence between them and is what the
+// launcher and the planner both ask.
+bool gemm_fast_eligible(const nasrec_gemm_desc_t* d);
 int launch_gemm_fast(hipStream_t st, const nasrec_gemm_desc_t* d, int Mmax, int Nmax, int zdim);
 bool gemm_kslice_eligible(const nasrec_gemm_desc_t* d);  // gemm_kslice.hip: large forward product at batch ~256, K split inside the workgroup
 int launch_gemm_kslice(hipStream_t st, const nasrec_gemm_desc_t* d);

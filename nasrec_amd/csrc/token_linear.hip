@@ -311,7 +311,7 @@ static void launch_token_dw_rb(hipStream_t st, const nasrec_gemm_desc_t* d, int 
   }
 }
 
-// main pass only: the caller (launch_gemm_t) runs the split-K second pass as for every other split launch
+// main pass only: the caller (launch_gemm) runs the split-K second pass as for every other split launch
 int launch_token_dw(hipStream_t st, const nasrec_gemm_desc_t* d, int Mmax, int Nmax) {
   const int rb = (Mmax + 15) / 16, cb = (Nmax + 15) / 16;
   const int grid = d->nseg * d->splitk;

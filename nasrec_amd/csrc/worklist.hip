@@ -134,13 +134,13 @@ static int wl_gemm_geometry(const nasrec_gemm_desc_t* g, nasrec_wl_item_t& it, i
       return 0;
     }
   }
-  // the tile choice of launch_gemm_t (gemm.hip) on 256-thread workgroups
+  // the tile choice of launch_general_t (gemm.hip) on 256-thread workgroups
   int tile, tbm, tbn;
   if (wgs >= GEMM_SKINNY_BELOW) {
     tile = WL_T32x32, tbm = 32, tbn = 32;
   } else {
     // skinny launches: the strip shape that pads the problems least (token-axis products have M = 8 .. 64 rows of weights against
-    // N = 4096 token columns: 64 x 16 strips compute up to 4x the rows that exist); ties go to launch_gemm_t's rule.  The order in
+    // N = 4096 token columns: 64 x 16 strips compute up to 4x the rows that exist); ties go to launch_general_t's rule.  The order in
     // which an output element accumulates over k does not depend on the tile shape, so results stay bit-identical.
     long pad64x16 = 0, pad16x64 = 0;
     for (int q = 0; q < nprob; ++q) {

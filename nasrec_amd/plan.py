@@ -357,9 +357,6 @@ def _splitk_for(tiles_mn, ktiles, nprob=1):
     return max(1, min(s, 32))
 
 
-GEMM_FAST_MIN_TILES = 120  # csrc/gemm_tile.h NASREC_GEMM_FAST_MIN_TILES
-_FAST_MIN_K = int(_os.environ.get("NASREC_FAST_MIN_K", "1"))     # A/B knobs (csrc/gemm_fast.hip reads the first one too).  64 -> 1 in round 4: a [B,16] x [16,1024] product is a streaming
-# write of B x 1024 floats, and the throughput kernel's epilogue (full 128-byte rows per store instruction) is the better store path whatever K is: cfg 5 +1.9 %, cfg 3 / 4 +1.1 % (A/B)
 _LN_NBLK = int(_os.environ.get("NASREC_LN_NBLK", "512"))          # workgroups (of four row-per-wave wavefronts) of the dense LayerNorm backward (A/B knob; 256 until round 4:
 # one workgroup per CU = four wavefronts per CU for a streaming kernel whose rows wait for the previous row's stores: cfg 5 +1.6 %, cfg 3 +0.7 %; 1024 = 512)
 _TOKDW_CAP = int(_os.environ.get("NASREC_TOKDW_CAP", "128"))     # workgroups per problem of the token-axis weight gradient (A/B knob; 32 until round 4: a launch of two problems ran on 64 of
@@ -367,88 +364,34 @@ _TOKDW_CAP = int(_os.environ.get("NASREC_TOKDW_CAP", "128"))     # workgroups pe
 _FAST_MIN_KT = int(_os.environ.get("NASREC_FAST_MIN_KT", "4"))   # k-tiles of 32 per split of the throughput kernel (8 -> 4, round 4: a 4096x128x1024 product ran on 128 of 256 CUs; cfg 3 5.957 -> 5.930 ms, A/B)
 
 
-def _fast_gemm_splitk(amode, bmode, cmode, segs, zmode):
-    """Mirror of csrc/gemm_fast.hip `gemm_fast_eligible`: does this launch take the throughput-regime kernel (128x128x32
-    tiles), and with which split-K?  -> S (>= 1) or None.  A product with few output tiles but a deep K (the weight gradients
-    of a large batch: K = B) is split so that tiles x S fills the chip, >= 8 k-tiles of 32 per split."""
-    if cmode != L.CM_PLAIN or (amode, bmode) not in _FAST_BINDINGS:
+def gemm_route(d):
+    """-> (family, eligible mask) of nasrec_gemm_route (csrc/gemm.hip): the rule by which the launcher itself picks the kernel of this
+    descriptor.  family is an L.GEMM_ROUTE_* (negative: the launcher rejects the descriptor); bit (1 << family) of the mask says that
+    family's own rule accepts it, whatever wins.  Host only, no device needed."""
+    mask = C.c_uint()
+    return L.load().nasrec_gemm_route(C.addressof(d), C.byref(mask)), mask.value
+
+
+_KSLICE_BIT, _SKINNY_N_BIT, _FAST_BIT = 1 << L.GEMM_ROUTE_KSLICE, 1 << L.GEMM_ROUTE_SKINNY_N, 1 << L.GEMM_ROUTE_FAST
+
+
+def _fast_gemm_splitk(d, tiles, kt, mask1):
+    """Does this launch take the throughput-regime kernel (128x128x32 tiles), and with which split-K?  -> S (>= 1) or None.  A product
+    with few output tiles but a deep K (the weight gradients of a large batch: K = B) is split so that tiles x S fills the chip,
+    >= _FAST_MIN_KT k-tiles of 32 per split.  tiles: 128x128 tiles of the launch, kt: k-tiles of its live segments (deepest problem of
+    a zmode launch), mask1: the launcher's answer for d at splitk = 1.  Leaves d.splitk = 1."""
+    if tiles <= 0:
         return None
-    kmax = 0
-    kt_max = kt_sum = 0
-    any_live = False
-    for sd in segs:
-        if sd.get("Aaux") or sd.get("Baux"):
-            return None
-        if not sd.get("A"):
-            continue
-        any_live = True
-        K = sd["K"]
-        if K > kmax:
-            kmax = K
-        # 31-bit byte offsets of the staging loads: operand extents stay below 2^29 floats (gemm_fast.hip:623-625)
-        r, ld = max(sd["M"], sd["N"]), max(sd.get("lda", 0), sd.get("ldb", 0))
-        if r * ld + K >= (1 << 29) or K * ld + r >= (1 << 29):
-            return None
-        kt = (K + 31) // 32
-        kt_sum += kt
-        if kt > kt_max:
-            kt_max = kt
-    if not any_live or kmax < _FAST_MIN_K:
-        return None
-    tiles = area = 0
-    for sd in (segs if zmode else segs[:1]):
-        tiles += ((sd["M"] + 127) // 128) * ((sd["N"] + 127) // 128)
-        area += sd["M"] * sd["N"]
-    if 2 * area < tiles * 128 * 128:
-        return None  # skinny problems: the small-tile kernel
-    kt = kt_max if zmode else kt_sum
     S = 1
     if tiles < 256:
         S = max(1, min(-(-256 // tiles), kt // _FAST_MIN_KT, 32))
-    return S if tiles * S >= GEMM_FAST_MIN_TILES else None
+    if S > 1:
+        d.splitk = S
+        mask1 = gemm_route(d)[1]
+        d.splitk = 1
+    return S if mask1 & _FAST_BIT else None
 
 
-_FAST_BINDINGS = ((L.AM_KC, L.AM_KC), (L.AM_KC, L.AM_RC), (L.AM_RC, L.AM_RC))
-def kslice_eligible(amode, bmode, cmode, segs, zmode):
-    """mirror of csrc/gemm_kslice.hip `gemm_kslice_eligible`: one large forward product of the batch-256 regime runs as a single pass
-    with K split inside the workgroup (no split-K workspace, no second launch)"""
-    if (amode, bmode, cmode) != (L.AM_KC, L.AM_KC, L.CM_PLAIN) or zmode:
-        return False
-    M, N = segs[0]["M"], segs[0]["N"]
-    K = 0
-    for sd in segs:
-        if sd.get("Aaux") or sd.get("Baux") or sd.get("ones_col") or (0 < sd.get("Mvalid", M) < M):
-            return False
-        if sd.get("A") and sd["K"] > 0:
-            K += sd["K"]
-            if M * sd["lda"] >= (1 << 29) or N * sd["ldb"] >= (1 << 29):
-                return False
-    if len(segs) > 4:  # KS_SEGS (csrc/gemm_kslice.hip)
-        return False
-    tiles = ((M + 31) // 32) * ((N + 31) // 32)
-    return M <= 512 and 128 <= tiles <= 512 and K >= 512
-
-
-def skinny_n_eligible(amode, bmode, cmode, segs, zmode):
-    """mirror of csrc/gemm_skinny.hip `gemm_skinny_n_eligible`: a forward Linear with <= 16 outputs at large batch streams x once, K split
-    inside the workgroup (no split-K workspace, no second launch)"""
-    if amode != L.AM_KC or bmode not in (L.AM_KC, L.AM_RC) or cmode != L.CM_PLAIN or (zmode and len(segs) != 1):
-        return False
-    M, N = segs[0]["M"], segs[0]["N"]
-    if N < 1 or N > 16 or M < 1024:
-        return False
-    K = 0
-    for sd in segs:
-        if sd.get("Aaux") or sd.get("Baux") or sd.get("ones_col") or (0 < sd.get("Mvalid", M) < M):
-            return False
-        if sd.get("A") and sd["K"] > 0:
-            K += sd["K"]
-            if M * sd.get("lda", 0) >= (1 << 29) or (sd["K"] if bmode == L.AM_RC else N) * sd.get("ldb", 0) >= (1 << 29):
-                return False
-    return K >= 256 and _SKINNY_N
-
-
-_SKINNY_N = _os.environ.get("NASREC_SKINNY_N", "1") != "0"  # A/B knob: 0 keeps these products on the general template (split-K + second pass)
 BALANCED_MIN_SAVING_US = float(_os.environ.get("NASREC_BALANCED_MIN_US", "80.0"))  # (env: A/B knob)
 
 
@@ -479,51 +422,17 @@ def _balanced_schedule_pays(segs, zmode):
     return (rounds - tiles / 512.0) * T * 3.8 >= BALANCED_MIN_SAVING_US
 
 
-_TINYK = _os.environ.get("NASREC_TINYK", "1") != "0"  # A/B knob (csrc/gemm_skinny.hip reads the same variable)
-_TINYK_RC = _os.environ.get("NASREC_TINYK", "1") == "2"  # the input-gradient form too (measured no faster than the throughput tile: off)
-
-
-def tinyk_eligible(d) -> bool:
-    """mirror of csrc/gemm_skinny.hip `gemm_tinyk_eligible`: K <= 16 at large batch with a wide output (a streaming write)"""
-    if not _TINYK or d.amode != L.AM_KC or d.bmode not in (L.AM_KC, L.AM_RC) or d.cmode != L.CM_PLAIN or d.splitk > 1:
-        return False
-    if d.bmode == L.AM_RC and not _TINYK_RC:
-        return False
-    if not d.zmode and d.nseg != 1:
-        return False
-    for q in range(d.nseg):
-        s = d.seg[q]
-        if s.Aaux or s.Baux or s.ones_col or (0 < s.Mvalid < s.M):
-            return False
-        if s.M < 1024 or s.N < 256 or s.K < 0 or s.K > 16:
-            return False
-    return True
+_ROUTE_KERNEL = {L.GEMM_ROUTE_GENERAL: "gemm_kernel", L.GEMM_ROUTE_KSLICE: "gemm_kslice_kernel", L.GEMM_ROUTE_SKINNY_N: "gemm_skinny_n_kernel",
+                 L.GEMM_ROUTE_TINYK: "gemm_tinyk_kernel", L.GEMM_ROUTE_TOKEN_LINEAR: "token_linear_kernel",
+                 L.GEMM_ROUTE_TOKEN_DW: "token_dw_kernel", L.GEMM_ROUTE_FAST: "gemm_fast_kernel"}
 
 
 def gemm_kernel_name(d) -> str:
-    """which kernel family launch_gemm picks for this descriptor (mirror of csrc/gemm.hip / gemm_fast.hip)"""
-    segs = [dict(A=d.seg[q].A, Aaux=d.seg[q].Aaux, Baux=d.seg[q].Baux, M=d.seg[q].M, N=d.seg[q].N, K=d.seg[q].K) for q in range(d.nseg)]
-    live = [sd for sd in segs if sd["A"]]
-    if d.splitk <= 1 and kslice_eligible(d.amode, d.bmode, d.cmode, [dict(sd, ones_col=d.seg[q].ones_col, Mvalid=d.seg[q].Mvalid, lda=d.seg[q].lda,
-                                                                          ldb=d.seg[q].ldb) for q, sd in enumerate(segs)], d.zmode):
-        return "gemm_kslice_kernel"
-    if d.splitk <= 1 and skinny_n_eligible(d.amode, d.bmode, d.cmode, [dict(sd, ones_col=d.seg[q].ones_col, Mvalid=d.seg[q].Mvalid, lda=d.seg[q].lda,
-                                                                            ldb=d.seg[q].ldb) for q, sd in enumerate(segs)], d.zmode):
-        return "gemm_skinny_n_kernel"
-    if tinyk_eligible(d):
-        return "gemm_tinyk_kernel"
-    if (d.cmode == L.CM_TOKJ and d.bmode == L.AM_TOKR and d.amode in (L.AM_KC, L.AM_RC) and d.splitk <= 1 and not d.pre_add
-            and not d.save_act and d.mul_nseg == 0 and all(sd["M"] <= 80 and sd["N"] >= 16 * 1024 and not sd["Aaux"] and not sd["Baux"] for sd in segs)):
-        return "token_linear_kernel"  # (csrc/token_linear.hip `token_linear_eligible` has the complete rule)
-    if d.cmode != L.CM_PLAIN or (d.amode, d.bmode) not in ((L.AM_KC, L.AM_KC), (L.AM_KC, L.AM_RC), (L.AM_RC, L.AM_RC)) or not live:
-        return "gemm_kernel"
-    if any(sd["Aaux"] or sd["Baux"] for sd in segs) or max(sd["K"] for sd in live) < _FAST_MIN_K:
-        return "gemm_kernel"
-    probs = segs if d.zmode else segs[:1]
-    tiles = sum(((sd["M"] + 127) // 128) * ((sd["N"] + 127) // 128) for sd in probs)
-    if 2 * sum(sd["M"] * sd["N"] for sd in probs) < tiles * 128 * 128:
-        return "gemm_kernel"
-    return "gemm_fast_kernel" if tiles * max(1, d.splitk) >= GEMM_FAST_MIN_TILES else "gemm_kernel"
+    """the kernel launch_gemm runs for this descriptor, as the profiler names it"""
+    family = gemm_route(d)[0]
+    if family < 0:
+        raise ValueError("nasrec_gemm rejects this descriptor (nasrec_gemm_route: %d)" % family)
+    return _ROUTE_KERNEL[family]
 
 
 def gemm_descs(ctx, amode, bmode, cmode, segs, zmode, act=0, bias_on_rows=0, mask_on_rows=0, dims=-1, beta=0, bias=None, save_z=None,
@@ -563,6 +472,7 @@ def gemm_descs(ctx, amode, bmode, cmode, segs, zmode, act=0, bias_on_rows=0, mas
             d.mul_ptr[q], d.mul_off[q], d.mul_width[q], d.mul_ld[q] = ptr, off, width, ld
     M = N = 0
     kt_max = kt_sum = live_tiles = 0
+    fast_tiles = fast_kt_max = fast_kt_sum = 0  # 128x128 tiles of the problems, k-tiles of the live segments (_fast_gemm_splitk)
     dseg = d.seg
     for q in range(nseg):
         sdict = segs[q]
@@ -580,13 +490,23 @@ def gemm_descs(ctx, amode, bmode, cmode, segs, zmode, act=0, bias_on_rows=0, mas
         kt_sum += kt
         if kt > kt_max:
             kt_max = kt
+        if sdict.get("A"):
+            fast_kt_sum += kt
+            if kt > fast_kt_max:
+                fast_kt_max = kt
+        if zmode or q == 0:
+            fast_tiles += ((m + 127) // 128) * ((n + 127) // 128)
         live_tiles += ((m + 63) // 64) * ((n + 63) // 64)  # (a zmode grid is padded to Mmax x Nmax)
     B = ctx.B
     if zmode:
         S = _splitk_for(live_tiles, kt_max)
     else:
         S = _splitk_for(((M + 63) // 64) * ((N + 63) // 64), kt_sum)
-    fast = _fast_gemm_splitk(amode, bmode, cmode, segs, zmode) if B > 128 else None  # (a throughput-regime launch needs >= 120 128x128 tiles)
+    # which kernels would take the launch is the launcher's own rule (the descriptor is complete but for its split-K fields); how far
+    # to split, and on which batch sizes, is policy and stays here
+    d.splitk = 1
+    mask1 = gemm_route(d)[1]
+    fast = _fast_gemm_splitk(d, fast_tiles, fast_kt_max if zmode else fast_kt_sum, mask1) if B > 128 else None  # (a throughput-regime launch needs >= 120 128x128 tiles)
     if fast is not None:
         S = fast
     if amode == L.AM_TOKK and zmode and B >= 1024:
@@ -601,11 +521,10 @@ def gemm_descs(ctx, amode, bmode, cmode, segs, zmode, act=0, bias_on_rows=0, mas
             S = max(4, min(_TOKDW_CAP, 256 // nseg, B // 64))
     if splitk is not None:
         S = splitk
-    elif B <= 512 and S > 1 and kslice_eligible(amode, bmode, cmode, segs, zmode):
+    elif B <= 512 and S > 1 and mask1 & _KSLICE_BIT:
         S = 1  # csrc/gemm_kslice.hip: K is split inside the workgroup
-    elif B >= 1024 and skinny_n_eligible(amode, bmode, cmode, segs, zmode):
+    elif B >= 1024 and mask1 & _SKINNY_N_BIT:
         S = 1  # csrc/gemm_skinny.hip: likewise
-    d.splitk = 1
     if fast == 1 and S == 1 and B > 256 and ctx.sk_workspace is not None and _balanced_schedule_pays(segs, zmode):
         d.splitk = L.SPLITK_BALANCED
         d.workspace = ctx.sk_workspace().data_ptr()

@@ -497,7 +497,7 @@ def resplit_slack_solos(descs, alloc, min_slack=None):
         d = nd.desc
         if nd.part != "whole" or not isinstance(d, L.GemmDesc) or d.splitk > 1 or alap[i] - nd.level < (RESPLIT_MIN_SLACK if min_slack is None else min_slack):
             continue
-        if P.gemm_kernel_name(d) != "gemm_kslice_kernel":
+        if P.gemm_route(d)[0] != L.GEMM_ROUTE_KSLICE:
             continue
         s0 = d.seg[0]
         kt = sum((d.seg[q].K + 31) // 32 for q in range(d.nseg) if d.seg[q].A)
@@ -554,11 +554,14 @@ def gemm_capable(d) -> bool:
     S = d.splitk if d.splitk > 1 else 1
     if nprob == 1 and ((d.seg[0].M + 63) // 64) * ((d.seg[0].N + 63) // 64) * S >= SOLO_TILES:
         return False
-    from . import plan as P
-    if not getattr(d, "_wl_force", False) and P.kslice_eligible(d.amode, d.bmode, d.cmode, [dict(A=d.seg[q].A, Aaux=d.seg[q].Aaux, Baux=d.seg[q].Baux, ones_col=d.seg[q].ones_col,
-                                                           Mvalid=d.seg[q].Mvalid, M=d.seg[q].M, N=d.seg[q].N, K=d.seg[q].K, lda=d.seg[q].lda,
-                                                           ldb=d.seg[q].ldb) for q in range(d.nseg)], d.zmode):
-        return False  # csrc/gemm_kslice.hip: a kernel of its own (1024-thread workgroups, 133 KB of LDS)
+    if not getattr(d, "_wl_force", False):
+        from . import plan as P
+        one = d
+        if d.splitk > 1:  # the single-pass rule with this launch's split-K disregarded, as the planner asked it when it chose S
+            one = L.GemmDesc.from_buffer_copy(d)
+            one.splitk = 1
+        if P.gemm_route(one)[1] & (1 << L.GEMM_ROUTE_KSLICE):
+            return False  # csrc/gemm_kslice.hip: a kernel of its own (1024-thread workgroups, 133 KB of LDS)
     s0 = d.seg[0]
     if not d.zmode:
         for q in range(d.nseg):

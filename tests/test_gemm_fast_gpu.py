@@ -296,3 +296,27 @@ def test_token_weight_gradient_batch_at_large_batch(lib, S):
     g = dz[:, 1:1 + nout].double().clone()
     g[:, kd:] = 0
     _close(db, g.sum((0, 2)), tol=5e-5)
+
+
+def test_token_weight_gradient_smallest_launch_the_large_batch_kernel_takes(lib):
+    """two problems of M, N <= 80 over exactly 1024 samples (K = 1024 x 16) at splitk = 4: the launcher's own rule must send the
+    launch to token_dw_kernel (csrc/token_linear.hip), and the slabs summed by the second pass must be the fp64 product"""
+    torch.manual_seed(8)
+    B, S = 1024, 4
+    dz = _rand(B, 45, 16, scale=0.3)
+    xs = [_rand(B, 72, 16), _rand(B, 9, 16)]
+    dWs = [torch.full((45, x.shape[1]), float("nan"), device="cuda") for x in xs]
+    d = L.GemmDesc()
+    d.kind = L.OP_GEMM
+    d.amode, d.bmode, d.cmode, d.nseg, d.zmode, d.dims_in_use = L.AM_TOKK, L.AM_TOKK, L.CM_PLAIN, 2, 1, -1
+    for q, (x, dW) in enumerate(zip(xs, dWs)):
+        for k, v in dict(A=dz.data_ptr(), B=x.data_ptr(), C=dW.data_ptr(), M=45, N=x.shape[1], K=B * 16, lda=dz.stride(0), ldb=x.stride(0),
+                         ldc=x.shape[1], Mvalid=45).items():
+            setattr(d.seg[q], k, v)
+    ws = torch.full((S * 45 * 72 * 2,), float("nan"), device="cuda")
+    d.splitk, d.workspace = S, ws.data_ptr()
+    assert P.gemm_route(d)[0] == L.GEMM_ROUTE_TOKEN_DW and P.gemm_kernel_name(d) == "token_dw_kernel"
+    L.check(lib.nasrec_gemm(None, C.addressof(d)))
+    torch.cuda.synchronize()
+    for x, dW in zip(xs, dWs):
+        _close(dW, torch.einsum("boe,bne->on", dz.double(), x.double()), tol=5e-5)

@@ -90,6 +90,20 @@ def test_gemm_dense_forward_segments(lib, splitk, act, dims):
     close(gy, ref)
 
 
+def test_gemm_small_product_runs_on_the_general_template(lib):
+    """2 x 2 ragged 64 x 64 tiles, an odd K: the launcher's own rule (nasrec_gemm_route) names the general template, nasrec_gemm runs it"""
+    from nasrec_amd import plan as P
+    torch.manual_seed(0)
+    B, N, K = 70, 77, 45
+    x, W = torch.randn(B, K), torch.randn(N, K) * 0.1
+    gx, gW, gy = dev(x), dev(W), dev(torch.full((B, N), float("nan")))
+    d = gemm_desc(L.AM_KC, L.AM_KC, L.CM_PLAIN, [dict(A=gx.data_ptr(), B=gW.data_ptr(), C=gy.data_ptr(), M=B, N=N, K=K, lda=K, ldb=K, ldc=N)], 0)
+    assert P.gemm_route(d)[0] == L.GEMM_ROUTE_GENERAL and P.gemm_kernel_name(d) == "gemm_kernel"
+    L.check(lib.nasrec_gemm(None, C.addressof(d)))
+    torch.cuda.synchronize()
+    close(gy, x.double() @ W.double().t())
+
+
 @pytest.mark.parametrize("splitk", [1, 3])
 def test_gemm_zmode_batch_of_unequal_weight_gradients_every_tile_configuration(lib, splitk):
     """A parked-weight-gradient style launch: independent dW = (dy ⊙ [y>0])ᵀ x products of very different sizes in ONE zmode
