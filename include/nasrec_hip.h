@@ -152,7 +152,22 @@ typedef struct nasrec_gemm_desc {
   const float* pre_add; /* optional, addressed like C: added to the accumulator BEFORE bias/activation — lets a
                            K-range longer than NASREC_MAX_SEGS segments be chained over several launches */
   nasrec_gemm_seg_t seg[NASREC_MAX_SEGS];
+  int32_t precision; /* NASREC_PRECISION_*: what the matrix cores may be fed (below).  0 = HIGHEST, so a zero-initialised descriptor
+                        keeps fp32 arithmetic.  Appended behind seg[]: nothing that addresses the head of a descriptor moves */
+  int32_t _pad_precision;
 } nasrec_gemm_desc_t;
+
+/* Matrix-product precision of a GEMM descriptor — PERMISSION, not obligation, as torch.set_float32_matmul_precision: operands,
+ * results and accumulation stay fp32 in memory; the value allows the kernel to round the OPERANDS of the products on their way to the
+ * matrix cores.  Only throughput-regime launches (NASREC_GEMM_ROUTE_FAST) have a reduced body (gemm_fast_bf16_kernel); every other
+ * family ignores the field and computes in fp32.  The field never changes the route or the split-K the planner picks.
+ *   HIGHEST  fp32 operands (v_mfma_f32_32x32x2_f32), exact fp32 FMA chain
+ *   HIGH     bf16 x 3: a = hi + lo with hi = bf16(a), lo = bf16(a - hi); lo*hi + hi*lo + hi*hi per k, fp32 accumulation
+ *   MEDIUM   bf16: bf16(a) * bf16(b) per k (round to nearest even), fp32 accumulation
+ * Any other value is rejected (NASREC_GEMM_ROUTE_BAD_PRECISION).
+ * The field was added WITHOUT a new nasrec_abi_version(): a binding's layout check (nasrec_desc_sizes: the descriptor and every
+ * container that embeds it grew by 8 bytes) is what catches a stale struct definition. */
+enum { NASREC_PRECISION_HIGHEST = 0, NASREC_PRECISION_HIGH = 1, NASREC_PRECISION_MEDIUM = 2 };
 
 /* ------------------------------------------------------------------------------------------------
  * Embedding stem.  out[b,f,:] = table_f[idx[b,f],:]  — replaces Fs × nn.Embedding + torch.stack
@@ -927,10 +942,12 @@ enum {
   NASREC_GEMM_ROUTE_TINYK = 3,        /* gemm_skinny.hip: K <= 16 at large batch, single pass */
   NASREC_GEMM_ROUTE_TOKEN_LINEAR = 4, /* token_linear.hip: token-axis Linear at large batch, single pass */
   NASREC_GEMM_ROUTE_TOKEN_DW = 5,     /* token_linear.hip: token-axis weight gradient at large batch, split-K only */
-  NASREC_GEMM_ROUTE_FAST = 6,         /* gemm_fast.hip: 128x128 throughput tiles, split-K or NASREC_SPLITK_BALANCED */
+  NASREC_GEMM_ROUTE_FAST = 6,         /* gemm_fast.hip: 128x128 throughput tiles, split-K or NASREC_SPLITK_BALANCED; with
+                                         precision != HIGHEST its bf16 body (gemm_fast_bf16.hip) — same family, same mask */
   NASREC_GEMM_ROUTE_BAD_NSEG = -1,
   NASREC_GEMM_ROUTE_BAD_BINDING = -2,
-  NASREC_GEMM_ROUTE_BAD_BALANCED = -3 /* NASREC_SPLITK_BALANCED on a launch the throughput kernel does not take */
+  NASREC_GEMM_ROUTE_BAD_BALANCED = -3, /* NASREC_SPLITK_BALANCED on a launch the throughput kernel does not take */
+  NASREC_GEMM_ROUTE_BAD_PRECISION = -4 /* nasrec_gemm_desc_t.precision is no NASREC_PRECISION_* */
 };
 int nasrec_gemm_route(const nasrec_gemm_desc_t* d, unsigned* eligible_mask);
 

@@ -57,7 +57,8 @@ class GemmDesc(C.Structure):
                 ("bias_on_rows", i32), ("mask_on_rows", i32), ("dims_in_use", i32), ("beta", i32), ("splitk", i32),
                 ("bias", vp), ("save_z", vp), ("save_act", vp), ("mul_ptr", vp * MAX_SEGS), ("mul_off", i32 * MAX_SEGS),
                 ("mul_width", i32 * MAX_SEGS), ("mul_ld", i32 * MAX_SEGS), ("mul_nseg", i32), ("defer_second_pass", i32),
-                ("workspace", vp), ("counters", vp), ("rowsum_out", vp), ("pre_add", vp), ("seg", GemmSeg * MAX_SEGS)]
+                ("workspace", vp), ("counters", vp), ("rowsum_out", vp), ("pre_add", vp), ("seg", GemmSeg * MAX_SEGS),
+                ("precision", i32), ("_pad_precision", i32)]
 
 
 EPILOGUES_MAX = 3  # NASREC_EPILOGUES_MAX
@@ -151,7 +152,22 @@ class MemsetDesc(C.Structure):
 SPLITK_BALANCED = -1                  # NASREC_SPLITK_BALANCED
 (GEMM_ROUTE_GENERAL, GEMM_ROUTE_KSLICE, GEMM_ROUTE_SKINNY_N, GEMM_ROUTE_TINYK, GEMM_ROUTE_TOKEN_LINEAR, GEMM_ROUTE_TOKEN_DW,
  GEMM_ROUTE_FAST) = range(7)          # NASREC_GEMM_ROUTE_* (nasrec_gemm_route)
-GEMM_ROUTE_BAD_NSEG, GEMM_ROUTE_BAD_BINDING, GEMM_ROUTE_BAD_BALANCED = -1, -2, -3
+GEMM_ROUTE_BAD_NSEG, GEMM_ROUTE_BAD_BINDING, GEMM_ROUTE_BAD_BALANCED, GEMM_ROUTE_BAD_PRECISION = -1, -2, -3, -4
+PRECISION_HIGHEST, PRECISION_HIGH, PRECISION_MEDIUM = 0, 1, 2  # NASREC_PRECISION_* (nasrec_gemm_desc_t.precision)
+PRECISION_BY_NAME = {"highest": PRECISION_HIGHEST, "high": PRECISION_HIGH, "medium": PRECISION_MEDIUM}
+MATMUL_PRECISION_ENV = "NASREC_MATMUL_PRECISION"
+
+
+def matmul_precision_name(value=None) -> str:
+    """"highest" | "high" | "medium" from an explicit value, else from the environment variable NASREC_MATMUL_PRECISION, else
+    "highest".  Raises ValueError on anything else (also from the environment: a typo must not silently run fp32)."""
+    src = "matmul_precision"
+    if value is None:
+        value = os.environ.get(MATMUL_PRECISION_ENV) or "highest"
+        src = MATMUL_PRECISION_ENV
+    if not isinstance(value, str) or value not in PRECISION_BY_NAME:
+        raise ValueError("%s must be one of 'highest', 'high', 'medium' (got %r)" % (src, value))
+    return value
 SK_WORKSPACE_FLOATS = 512 * 3 * 128 * 128  # NASREC_SK_WORKSPACE_FLOATS
 CHUNK_ELEMS = 65536     # NASREC_CHUNK_ELEMS
 CONST_I64_MAX = 448     # NASREC_CONST_I64_MAX

@@ -140,6 +140,7 @@ static constexpr int binding_key(int am, int bm, int cm) { return am * 100 + bm 
 int nasrec_gemm_route(const nasrec_gemm_desc_t* d, unsigned* eligible_mask) {
   if (eligible_mask) *eligible_mask = 0;
   if (d->nseg < 1 || d->nseg > NASREC_MAX_SEGS) return NASREC_GEMM_ROUTE_BAD_NSEG;
+  if (d->precision < NASREC_PRECISION_HIGHEST || d->precision > NASREC_PRECISION_MEDIUM) return NASREC_GEMM_ROUTE_BAD_PRECISION;
   switch (binding_key(d->amode, d->bmode, d->cmode)) {
     case binding_key(NASREC_AM_KC, NASREC_AM_KC, NASREC_CM_PLAIN):      // y = x Wᵀ
     case binding_key(NASREC_AM_KC, NASREC_AM_RC, NASREC_CM_PLAIN):      // dx = dy W
@@ -180,6 +181,8 @@ int launch_gemm(hipStream_t st, const nasrec_gemm_desc_t* d) {
   if (route == NASREC_GEMM_ROUTE_BAD_NSEG) return nasrec_set_error(-2, "gemm: nseg=%d out of range", d->nseg);
   if (route == NASREC_GEMM_ROUTE_BAD_BINDING)
     return nasrec_set_error(-2, "gemm: unsupported operand binding a=%d b=%d c=%d", d->amode, d->bmode, d->cmode);
+  if (route == NASREC_GEMM_ROUTE_BAD_PRECISION)
+    return nasrec_set_error(-2, "gemm: precision=%d is no NASREC_PRECISION_* (0 highest, 1 high, 2 medium)", d->precision);
   int Mmax = 0, Nmax = 0;
   const int nprob = d->zmode ? d->nseg : 1;
   for (int q = 0; q < nprob; ++q) {

@@ -32,19 +32,11 @@
 //     covers a whole tile finishes it; partial runs dump their accumulators to the workspace and gemm_fast_fixup_kernel sums
 //     the pieces of each split tile in ascending k order (fixed association: results do not depend on timing) and applies the
 //     epilogue.  No inter-workgroup signalling.
-// fp32 in, fp32 accumulate: v_mfma_f32_32x32x2_f32 is an exact fp32 FMA chain (no reduced-precision path exists on gfx950).
+// fp32 in, fp32 accumulate: v_mfma_f32_32x32x2_f32 is an exact fp32 FMA chain (no fp32-INPUT reduced-precision path — xf32 / tf32 —
+// exists on gfx950).  The reduced path is a second body, gemm_fast_bf16.hip: the same tiles, schedules and epilogue (gemm_fast_common.h)
+// on v_mfma_f32_32x32x16_bf16, taken only by descriptors that ask for it (nasrec_gemm_desc_t.precision != NASREC_PRECISION_HIGHEST).
 #include <stdlib.h>
-#include "gemm_tile.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-#define FT_BM 128
-#define FT_BN 128
-#define FT_BK 32
-#define FT_KC_LD 36                        // [row][32 + 4]
-#define FT_TILE_FLOATS (FT_BM * FT_KC_LD)  // 4608 >= 32 * 128 (the [k][row] form)
-#define FT_FENCE() __builtin_amdgcn_sched_barrier(0)
+#include "gemm_fast_common.h"
 
 template <int MODE>
 __device__ __forceinline__ void ft_slot(int tid, int it, int& row, int& k) {
@@ -55,228 +47,6 @@ __device__ __forceinline__ void ft_slot(int tid, int it, int& row, int& k) {
   } else {                     // 32 float4 along rows per k
     k = idx >> 5;
     row = (idx & 31) << 2;
-  }
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ft_rsrc(const float* base, long extent_floats) {
-  const long bytes = extent_floats * 4;
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes > 0x7fffffffL ? 0x7fffffff : (int)bytes, 0x00020000);
-}
-
-#define FT_SK_WGS 512            // workgroups that share the odd tiles' iterations (2 per CU)
-#define FT_SK_PIECES 3           // a share of < 2 tiles touches at most 3 tiles
-#define FT_PIECE_FLOATS (FT_BM * FT_BN)
-
-// Order of the tiles of one problem: groups of FT_GROUP_M tile rows, inside a group column by column.  The ~64 workgroups an
-// XCD runs at a time then cover 8 rows x 8 columns (8 A panels + 8 B panels in its 4 MB L2) instead of 1.5 rows x 41 columns,
-// and an XCD's contiguous run re-reads the B panels once per group instead of once per row: fabric reads of the
-// 4096 x 5133 x 1024 product 634 MB -> (see profiles/) against 122 MB of operands.
-#define FT_GROUP_M 8
-__device__ __forceinline__ void ft_grouped(int t, int tm, int tn, int& by, int& bx) {
-  const int per_group = FT_GROUP_M * tn;
-  const int grp = t / per_group, first = grp * FT_GROUP_M;
-  const int rows = tm - first < FT_GROUP_M ? tm - first : FT_GROUP_M;
-  const int r = t - grp * per_group;
-  bx = r / rows;
-  by = first + (r - bx * rows);
-}
-
-// tile index (live tiles, problem-major, then k-split, grouped (m, n) order) -> problem z, k-split ks, tile row / column; false: no such tile
-__device__ __forceinline__ bool ft_decode(const nasrec_gemm_desc_t& d, int lin, int S, int tiles_m, int tiles_n, int& z, int& ks, int& by,
-                                          int& bx) {
-  z = 0;
-  if (d.zmode) {
-    // a batch of independent problems: the grid holds exactly their LIVE tiles, so the eight contiguous runs the XCDs get
-    // carry equal work whatever the mix of problem sizes (a grid padded to Mmax x Nmax handed six XCDs 72 tiles each — more
-    // than their 64 workgroup slots — and two XCDs 8)
-    int rem = lin, tn = 1, per = 1;
-    for (;; ++z) {
-      if (z >= d.nseg) return false;
-      tn = (d.seg[z].N + FT_BN - 1) / FT_BN;
-      per = ((d.seg[z].M + FT_BM - 1) / FT_BM) * tn;
-      if (rem < per * S) break;
-      rem -= per * S;
-    }
-    ks = rem / per;
-    ft_grouped(rem - ks * per, per / tn, tn, by, bx);
-  } else {
-    const int per_z = tiles_m * tiles_n;
-    ks = lin / per_z;
-    ft_grouped(lin - ks * per_z, tiles_m, tiles_n, by, bx);
-  }
-  return true;
-}
-
-// XCD-aware order: ids are dealt round-robin to the 8 XCDs; give every XCD one contiguous run of [0, total) (bijective)
-__device__ __forceinline__ int ft_xcd_run(int id, int total) {
-  const int xcd = id & 7, q = id >> 3;
-  const int chunk = total >> 3, rem = total & 7;
-  return xcd * chunk + (xcd < rem ? xcd : rem) + q;
-}
-
-// first global k-iteration of share w of W iterations split over FT_SK_WGS workgroups
-__device__ __host__ __forceinline__ long ft_share_begin(long W, int w) { return W * w / FT_SK_WGS; }
-
-// epilogue of one finished 128 x 128 tile held in the D layout of v_mfma_f32_32x32x2_f32:
-// col = lane & 31, row = 8 * (reg >> 2) + 4 * (lane >> 5) + (reg & 3)
-__device__ __forceinline__ void ft_epilogue(const nasrec_gemm_desc_t& d, const nasrec_gemm_seg_t& s0, int m0, int n0, int wm, int wn, int fr,
-                                            int fg, const f32x16 (&acc)[2][2], bool acc_in_tile) {
-  const int M = s0.M, N = s0.N;
-  const int Mv = (s0.Mvalid > 0 && s0.Mvalid < M) ? s0.Mvalid : M;
-  // plain product (the common case of the large launches: LayerNorm / the split-K pass own the epilogue): straight stores
-  // (acc_in_tile: the accumulators were started from the output tile — the accumulation is already in them)
-  const bool plain = acc_in_tile || (!d.bias && !d.pre_add && !d.save_z && !d.save_act && d.act == NASREC_ACT_NONE && d.mul_nseg == 0 &&
-                                     d.dims_in_use < 0 && !(d.zmode ? s0.accumulate : d.beta) && !s0.ones_col);
-  if (plain) {
-    float* Cp = s0.C;
-    const int ldc = s0.ldc;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int i = m0 + wm * 64 + a * 32 + 8 * (r >> 2) + 4 * fg + (r & 3), j = n0 + wn * 64 + b * 32 + fr;
-          if (i < M && j < N) Cp[(long)i * ldc + j] = i < Mv ? acc[a][b][r] : 0.f;
-        }
-    return;
-  }
-  // general epilogue == epilogue_store<NASREC_CM_PLAIN> element by element (gemm_tile.h), with everything that depends on the
-  // column alone looked up once per lane and column: a lane owns 2 columns x 32 rows, and the gating product's segment search
-  // (mul_lookup: a scalar loop over up to 8 k-segments) used to run for each of its 64 elements
-  const bool acc_c = d.zmode ? s0.accumulate != 0 : d.beta != 0;
-  const bool has_pre = d.pre_add != nullptr;
-  float* rs = s0.rowsum ? s0.rowsum : d.rowsum_out;
-  // per column of the lane: the gating operand's pointer / stride, the bias, the dead-column flag
-  const float* mp[2] = {nullptr, nullptr};
-  int mld[2] = {0, 0};
-  float bias_c[2];
-  bool dead_c[2];
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    const int j = min(n0 + wn * 64 + b * 32 + fr, N - 1);
-    if (d.mul_nseg > 0) {
-      for (int q = 0; q < d.mul_nseg; ++q) {
-        const int jj = j - d.mul_off[q];
-        if (jj >= 0 && jj < d.mul_width[q]) {
-          mp[b] = d.mul_ptr[q] ? d.mul_ptr[q] + jj : nullptr;
-          mld[b] = d.mul_ld[q];
-          break;
-        }
-      }
-    }
-    bias_c[b] = d.bias ? d.bias[j] : 0.f;  // (a bias over rows belongs to the token-axis layout: gemm_fast_eligible)
-    dead_c[b] = d.dims_in_use >= 0 && !d.mask_on_rows && j >= d.dims_in_use;
-  }
-  // one element from accumulator to memory: the same operations in the same order whichever way its operands were fetched.  NO load
-  // in here: vmcnt counts loads and stores in one in-order queue, so a load between two stores makes the wave wait for every earlier
-  // store to be acknowledged — once per element
-  float* const Cp = s0.C;
-  float* const zp = d.save_z;
-  float* const ap = d.save_act;
-  const long ldc = s0.ldc;
-  const int act = d.act;
-  const bool has_bias = d.bias != nullptr, has_mulv = d.mul_nseg > 0;
-  const int dead_rows = (d.dims_in_use >= 0 && d.mask_on_rows) ? d.dims_in_use : 0x7fffffff;
-  auto finish = [&](int i, int j, int b, float v, float prevv, float mulv, float cvv) {
-    const long o = (long)i * ldc + j;
-    if (has_pre) v += prevv;
-    if (has_bias) v += bias_c[b];
-    if (zp) zp[o] = v;
-    v = act_apply(v, act);
-    if (ap) ap[o] = v;
-    if (has_mulv) v *= mulv;
-    if (dead_c[b] || i >= dead_rows) v = 0.f;
-    if (acc_c) v += cvv;
-    Cp[o] = v;
-  };
-  const int nread = (d.mul_nseg > 0 ? 1 : 0) + (has_pre ? 1 : 0) + (acc_c ? 1 : 0);
-  if (nread <= 1 && !s0.ones_col) {
-    // ONE array is read (the accumulation target of a dx product, the gating operand, or the residual): all 64 of the lane's values are
-    // in flight before its first store.  Sixteen at a time — load, wait, store, and vmcnt counts loads and stores in one queue, so the next
-    // sixteen loads wait for the previous stores to be acknowledged — a 4096 x 1024 x 128 dx product took 39.7 us with accumulation against
-    // 18.2 us without; a tile alone on its CU (256-tile launches) has nothing to hide four such round trips behind.
-    float rd[2][2][16] = {};
-    bool live_c[2] = {false, false};
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      if (nread == 0) break;  // (bias / activation / saved planes only: nothing to read)
-      const int j = min(n0 + wn * 64 + b * 32 + fr, N - 1);
-      const float* base = acc_c ? s0.C + j : has_pre ? d.pre_add + j : mp[b];
-      const bool live = base != nullptr;  // (a column outside every gating segment: the loads go to C — unconditional, no branch — and count as 0)
-      live_c[b] = live;
-      const float* bp = live ? base : s0.C + j;
-      const long ld = (acc_c || has_pre || !live) ? s0.ldc : mld[b];
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int i = min(m0 + wm * 64 + a * 32 + 8 * (r >> 2) + 4 * fg + (r & 3), M - 1);  // (clamped: rows >= M are never stored)
-          rd[a][b][r] = bp[(long)i * ld];  // (straight into its register: a select here and the compiler loads one element at a time)
-        }
-    }
-    // ONE wait for the whole batch, spelled out: the stores below sit behind uniform branches (saved planes present or not), the
-    // compiler cannot count them, and without this it waits with vmcnt(0) — every earlier store acknowledged — at the first use of each
-    // of the 64 loaded registers
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt / lgkmcnt untouched
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int j = n0 + wn * 64 + b * 32 + fr;
-      if (j >= N) continue;
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int i = m0 + wm * 64 + a * 32 + 8 * (r >> 2) + 4 * fg + (r & 3);
-          if (i >= M) continue;
-          const float x = live_c[b] ? rd[a][b][r] : 0.f;
-          finish(i, j, b, i < Mv ? acc[a][b][r] : 0.f, x, x, x);
-        }
-    }
-    return;
-  }
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    const int j = n0 + wn * 64 + b * 32 + fr;
-    if (j >= N) continue;
-    const bool ones_j = s0.ones_col && j == N - 1;
-    // Everything the 16 rows of a fragment READ (the gating operand, the residual, the accumulation target) is loaded before the first of
-    // their stores (round 4): element by element — load, use, store, and the next load may not pass that store, the arrays could
-    // alias — a lane paid a dependent memory round trip per element, 64 per tile (the gated 4096 x 5133 x 1024 product: 96 TFLOP/s
-    // against 131 for the plain product of the same shape).  Same arithmetic per element: same bits.
-    const bool has_mul = d.mul_nseg > 0 && mp[b] != nullptr;
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      float mulv[16] = {}, prev[16] = {}, cv[16] = {};
-      long off[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) off[r] = min(m0 + wm * 64 + a * 32 + 8 * (r >> 2) + 4 * fg + (r & 3), M - 1);  // (clamped: rows >= M are never stored)
-      // (one uniform branch per ARRAY, sixteen loads inside: a branch per element makes the compiler wait for element r before it issues r + 1)
-      if (has_mul) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mulv[r] = mp[b][off[r] * mld[b]];
-      }
-      if (has_pre) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) prev[r] = d.pre_add[off[r] * ldc + j];
-      }
-      if (acc_c) {  // (the ones-column's lanes read a real element too and drop it)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) cv[r] = Cp[off[r] * ldc + j];
-      }
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): one wait per batch of sixteen (see above)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int i = m0 + wm * 64 + a * 32 + 8 * (r >> 2) + 4 * fg + (r & 3);
-        if (i >= M) continue;
-        const float v = i < Mv ? acc[a][b][r] : 0.f;
-        if (ones_j) {
-          rs[i] = v;
-          continue;
-        }
-        finish(i, j, b, v, prev[r], mulv[r], cv[r]);
-      }
-    }
   }
 }
 
@@ -684,6 +454,7 @@ __global__ __launch_bounds__(256) void gemm_fast_fixup_kernel(const nasrec_gemm_
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
   for (; w < FT_SK_WGS && ft_share_begin(W, w) < hi; ++w) {
+    if (ft_share_begin(W, w + 1) == ft_share_begin(W, w)) continue;  // (fewer than 512 iterations in all: an empty share wrote no piece)
     const int piece = t - (int)(ft_share_begin(W, w) / sk_T);  // tiles this workgroup touched before tile t
     const float* slot = d.workspace + ((long)w * FT_SK_PIECES + piece) * FT_PIECE_FLOATS;
 #pragma unroll
@@ -696,45 +467,22 @@ __global__ __launch_bounds__(256) void gemm_fast_fixup_kernel(const nasrec_gemm_
   ft_epilogue(d, s0, m0, n0, wm, wn, fr, fg, acc, false);
 }
 
+void launch_gemm_fast_fixup(hipStream_t st, const nasrec_gemm_desc_t* d, int tiles_m, int tiles_n, int sk_tiles, int sk_T) {
+  hipLaunchKernelGGL(gemm_fast_fixup_kernel, dim3((unsigned)sk_tiles), dim3(256), 0, st, *d, tiles_m, tiles_n, sk_tiles, sk_T);
+}
+
 template <int AM, int BMODE>
 static int launch_fast_t(hipStream_t st, const nasrec_gemm_desc_t* d, int Mmax, int Nmax, int zdim, bool ones) {
-  const int tm = (Mmax + FT_BM - 1) / FT_BM, tn = (Nmax + FT_BN - 1) / FT_BN;
-  long blocks = (long)tm * tn * zdim;
-  if (d->zmode) {  // live tiles only (zdim = problems x split-K)
-    const int S = d->splitk > 1 ? d->splitk : 1;
-    blocks = 0;
-    for (int q = 0; q < d->nseg; ++q)
-      blocks += (long)((d->seg[q].M + FT_BM - 1) / FT_BM) * ((d->seg[q].N + FT_BN - 1) / FT_BN) * S;
-  }
-  int sk_tiles = 0, sk_T = 0;
-  if (d->splitk == NASREC_SPLITK_BALANCED) {
-    // every tile of the launch must have the same number of k-iterations
-    int T = 0;
-    if (d->zmode) {
-      for (int q = 0; q < d->nseg; ++q) {
-        const int tq = d->seg[q].A ? (d->seg[q].K + FT_BK - 1) / FT_BK : 0;
-        if (q > 0 && tq != T) return nasrec_set_error(-2, "gemm: balanced schedule needs equal K over the batch (problem %d)", q);
-        T = tq;
-      }
-    } else {
-      for (int q = 0; q < d->nseg; ++q)
-        if (d->seg[q].A) T += (d->seg[q].K + FT_BK - 1) / FT_BK;
-    }
-    if (T < 1) return nasrec_set_error(-2, "gemm: balanced schedule on an empty product");
-    if (!d->workspace) return nasrec_set_error(-3, "gemm: balanced schedule needs a workspace of NASREC_SK_WORKSPACE_FLOATS floats");
-    const long tiles = blocks;
-    if (tiles % FT_SK_WGS != 0) {
-      sk_tiles = (int)(tiles >= FT_SK_WGS ? FT_SK_WGS + tiles % FT_SK_WGS : tiles);
-      sk_T = T;
-      blocks = FT_SK_WGS + (tiles - sk_tiles);
-    }
-  }
+  int tm, tn, sk_tiles, sk_T;
+  long blocks;
+  const int rc = ft_schedule(d, Mmax, Nmax, zdim, tm, tn, blocks, sk_tiles, sk_T);
+  if (rc) return rc;
   const dim3 grid((unsigned)blocks);
   if (ones)
     hipLaunchKernelGGL((gemm_fast_kernel<AM, BMODE, true>), grid, dim3(256), 0, st, *d, Mmax, Nmax, tm, tn, sk_tiles, sk_T);
   else
     hipLaunchKernelGGL((gemm_fast_kernel<AM, BMODE, false>), grid, dim3(256), 0, st, *d, Mmax, Nmax, tm, tn, sk_tiles, sk_T);
-  if (sk_tiles > 0) hipLaunchKernelGGL(gemm_fast_fixup_kernel, dim3((unsigned)sk_tiles), dim3(256), 0, st, *d, tm, tn, sk_tiles, sk_T);
+  if (sk_tiles > 0) launch_gemm_fast_fixup(st, d, tm, tn, sk_tiles, sk_T);
   return 0;
 }
 
@@ -771,6 +519,7 @@ bool gemm_fast_eligible(const nasrec_gemm_desc_t* d) {
 }
 
 int launch_gemm_fast(hipStream_t st, const nasrec_gemm_desc_t* d, int Mmax, int Nmax, int zdim) {
+  if (d->precision != NASREC_PRECISION_HIGHEST) return launch_gemm_fast_bf16(st, d, Mmax, Nmax, zdim);  // (gemm_fast_bf16.hip)
   bool ones = false;
   for (int q = 0; q < d->nseg; ++q) ones = ones || d->seg[q].ones_col != 0;
   if (d->amode == NASREC_AM_KC && d->bmode == NASREC_AM_KC) return launch_fast_t<NASREC_AM_KC, NASREC_AM_KC>(st, d, Mmax, Nmax, zdim, ones);

@@ -244,11 +244,17 @@ def _on_device(fn):
 
 class SupernetEngine:
     def __init__(self, cfg: P.NetConfig, Fd: int, Fs: int, num_embeddings: List[int], device="cuda:0", warm_choice=None,
-                 world_size: int = 1, tables: Optional[List[torch.Tensor]] = None, host_embedding: bool = False):
-        """host_embedding: the tables live in host memory (SuperNet(place_embedding_on_cpu=True), supernet.py:231,418-428): the engine
+                 world_size: int = 1, tables: Optional[List[torch.Tensor]] = None, host_embedding: bool = False,
+                 matmul_precision: Optional[str] = None):
+        """matmul_precision: "highest" | "high" | "medium" (None: the environment variable NASREC_MATMUL_PRECISION, else "highest") —
+        what torch.set_float32_matmul_precision is to torch: tensors, accumulation and results stay fp32, the value PERMITS the
+        throughput-regime GEMM launches of every plan to feed the matrix cores bf16 operands ("medium") or bf16 x 3 ("high"); every
+        other launch stays fp32 (include/nasrec_hip.h NASREC_PRECISION_*).  "highest" is bit for bit the arithmetic without it.
+        host_embedding: the tables live in host memory (SuperNet(place_embedding_on_cpu=True), supernet.py:231,418-428): the engine
         holds no table, the caller hands the looked-up rows [B, Fs, 16] to every forward and receives their gradient; only the
         forward / backward programs are available in this mode (the fused optimizer step needs the tables on the device)."""
         L.load()
+        self.matmul_precision = L.matmul_precision_name(matmul_precision)
         if not torch.cuda.is_available():
             raise L.EngineError("SupernetEngine needs a GPU: there is no CPU fallback")
         self.cfg, self.Fd, self.Fs = cfg, Fd, Fs
@@ -452,6 +458,7 @@ class SupernetEngine:
             cp.tail = OptimizerTail(spec, arena)
             ctx = P.Ctx(B, self.device, self.params, self.grads, shape_only=False, train=train)
             ctx.sk_workspace = self._sk_workspace
+            ctx.matmul_precision = L.PRECISION_BY_NAME[self.matmul_precision]
             # parked weight-gradient batches are for one-launch-per-operator plans; the level scheduler places the products itself
             ctx.defer_dw = defer_dw and getattr(self, "park_weight_grads", True) and not (self.level_schedule and cfg.fixed and B <= 256)
             ctx.arena = arena
@@ -602,6 +609,8 @@ class SupernetEngine:
                     cp.step.capture(self.stream.cuda_stream)
             elif graph:
                 cp.fwd.capture(self.stream.cuda_stream)
+        # launches of the plan's programs that run the bf16 body (0 at "highest"; forward + backward, each launch once)
+        cp.bf16_launches = P.bf16_launches(cp.fwd.descs) + (P.bf16_launches(cp.bwd.descs) if train else 0)
         if graph or arena is None or cfg.fixed:
             self.stream.synchronize()  # these plans are built (zero-filled, captured) on the private stream, and replayed on the caller's
         self._plans[key] = cp

@@ -61,6 +61,7 @@ def train_and_eval_one_model(model, args):
 
 
 def main(args):
+    print("Matmul precision: {}".format(args.matmul_precision))
     np.random.seed(args.random_seed)  # the candidates come from the global stream (supernet.py `fixed-path`)
     if args.choice_from_pickle_file is not None:
         all_choices = load_pickle_data(args.choice_from_pickle_file)
@@ -76,7 +77,8 @@ def main(args):
         print("Evaluating {:d} out of {:d} subnetworks!".format(i, num_subnets))
         model = SuperNet(sparse_input_size=_num_sparse_inputs_dict[args.dataset], num_blocks=args.num_blocks, ops_config=ops_config_lib[args.config],
                          use_layernorm=(args.use_layernorm == 1), activation=args.activation, num_embeddings=tables,
-                         path_sampling_strategy="fixed-path", fixed=True, fixed_choice=choice)
+                         path_sampling_strategy="fixed-path", fixed=True, fixed_choice=choice,
+                         matmul_precision=args.matmul_precision)
         model = model.to(args.gpu)
         logs = train_and_eval_one_model(model, args)
         print("Trained model with the following choice...")
@@ -123,6 +125,9 @@ def build_parser():
     p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "rmsprop"])
     p.add_argument("--loss_function", type=str, default="bce", choices=["bce"])
     p.add_argument("--gpu", type=int, default=0, help="GPU ID to use.")
+    p.add_argument("--matmul-precision", dest="matmul_precision", type=str, default="highest", choices=["highest", "high", "medium"],
+                   help="what the large-batch matrix products may feed the matrix cores (SuperNet(matmul_precision=...), as "
+                        "torch.set_float32_matmul_precision): highest = fp32; high = bf16 x 3; medium = bf16. Tensors and accumulation stay fp32")
     return p
 
 

@@ -75,6 +75,7 @@ def finetune_and_eval_one_model(model, args, checkpoint):
 
 def main(args):
     print("Logging dir: {}".format(args.logging_dir))
+    print("Matmul precision: {}".format(args.matmul_precision))
     create_dir(args.logging_dir)
     if args.method == "random":
         searcher = Searcher(finetune_and_eval_one_model, args)
@@ -169,6 +170,9 @@ def build_parser():
     p.add_argument("--resident_candidates", type=int, default=0, choices=[0, 1],
                    help="1: one long-lived supernet per GPU scores every candidate (set-up, checkpoint and batches kept between candidates; "
                         "last-layer steps fused on the engine).  0: a fresh supernet per candidate, as the reference.")
+    p.add_argument("--matmul-precision", dest="matmul_precision", type=str, default="highest", choices=["highest", "high", "medium"],
+                   help="what the large-batch matrix products may feed the matrix cores (SuperNet(matmul_precision=...), as "
+                        "torch.set_float32_matmul_precision): highest = fp32; high = bf16 x 3; medium = bf16. Tensors and accumulation stay fp32")
     return p
 
 

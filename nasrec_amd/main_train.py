@@ -115,7 +115,8 @@ def get_model(args):
     if args.net == "supernet":
         return SuperNet(sparse_input_size=_num_sparse_inputs_dict[args.dataset], num_blocks=7, ops_config=ops_config_lib["xlarge"],
                         use_layernorm=True, activation=args.activation, num_embeddings=_num_embedding_dict[args.dataset],
-                        path_sampling_strategy="full-path", table_sharding=args.table_sharding)
+                        path_sampling_strategy="full-path", table_sharding=args.table_sharding,
+                        matmul_precision=args.matmul_precision)
     if args.net == "supernet-config":
         choice = load_json(args.supernet_config)
         print(choice)
@@ -123,7 +124,7 @@ def get_model(args):
         return SuperNet(sparse_input_size=_num_sparse_inputs_dict[args.dataset], num_blocks=choice["num_blocks"],
                         ops_config=ops_config_lib[choice["config"]], use_layernorm=False, activation=args.activation,
                         num_embeddings=_num_embedding_dict[args.dataset], path_sampling_strategy="fixed-path", fixed=True,
-                        fixed_choice=choice, table_sharding=args.table_sharding)
+                        fixed_choice=choice, table_sharding=args.table_sharding, matmul_precision=args.matmul_precision)
     raise NotImplementedError("Model {} is not implemented!".format(args.net))
 
 
@@ -131,6 +132,7 @@ def main(args):
     from nasrec_amd.utils.dist import init_from_env
     rank, world = init_from_env(args)  # torchrun: one process per GPU, args.gpu = the local rank
     create_dir(args.logging_dir)
+    print("Matmul precision: {}".format(args.matmul_precision))
     model = get_model(args).to(args.gpu)
     return train_and_eval_one_model(model, args)
 
@@ -172,6 +174,9 @@ def build_parser():
                         "--optimizer adagrad / adam / sgd with any --wd); row: every rank owns a row range of every table, ids / rows / "
                         "row gradients travel by all-to-all (tables that outgrow one GPU).  Row sharding needs the fused step's "
                         "--optimizer adagrad --wd 0")
+    p.add_argument("--matmul-precision", dest="matmul_precision", type=str, default="highest", choices=["highest", "high", "medium"],
+                   help="what the large-batch matrix products may feed the matrix cores (SuperNet(matmul_precision=...), as "
+                        "torch.set_float32_matmul_precision): highest = fp32; high = bf16 x 3; medium = bf16. Tensors and accumulation stay fp32")
     return p
 
 

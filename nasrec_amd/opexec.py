@@ -113,14 +113,16 @@ def _as_strided(buf_t, view, B):
 class OpPlan:
     """compiled single-operator plan: static input buffers, forward / backward programs, gradient buffers"""
 
-    def __init__(self, emit, inputs: List[torch.Tensor], params: Dict[str, torch.Tensor], train: bool):
+    def __init__(self, emit, inputs: List[torch.Tensor], params: Dict[str, torch.Tensor], train: bool, matmul_precision: str = "highest"):
         dev = inputs[0].device
+        self.matmul_precision = matmul_precision
         self.B = B = int(inputs[0].shape[0])
         self.train = train
         self.generation = 0
         self.names = list(params.keys())
         ctx = P.Ctx(B, dev, {"op." + k: v for k, v in params.items()},
                     {"op." + k: torch.zeros_like(v) for k, v in params.items()} if train else {}, shape_only=False, train=train)
+        ctx.matmul_precision = L.PRECISION_BY_NAME[matmul_precision]
         self.ctx = ctx
         self.ins = [torch.empty(tuple(x.shape), dtype=torch.float32, device=dev) for x in inputs]
         self.in_views = [_in_view(ctx, t, t.shape) for t in self.ins]
@@ -138,6 +140,8 @@ class OpPlan:
             self.bwd = Program(ctx.bwd)
             self.grad_names = [n[3:] for n in ctx.grad_params]
             self.grads = {k[3:]: v for k, v in ctx.grads.items()}
+        # launches of this plan that run the bf16 body (engine.CompiledPlan.bf16_launches)
+        self.bf16_launches = P.bf16_launches(ctx.fwd) + (P.bf16_launches(ctx.bwd) if train else 0)
 
     def run_forward(self, inputs, stream_ptr):
         for dst, src in zip(self.ins, inputs):
@@ -198,14 +202,16 @@ def run(module: nn.Module, emit, inputs: List[torch.Tensor], key_extra=()):
         if p.device != inputs[0].device:
             raise L.EngineError("parameter %s lives on %s, the inputs on %s" % (n, p.device, inputs[0].device))
     train = torch.is_grad_enabled() and (any(p.requires_grad for p in params.values()) or any(x.requires_grad for x in inputs))
-    key = (tuple(tuple(x.shape) for x in inputs), train, tuple(p.data_ptr() for p in params.values()), key_extra)
+    # the module's owner (SuperNet(matmul_precision=...) marks its operators) or the environment: nasrec_amd/_lib.py
+    precision = L.matmul_precision_name(module.__dict__.get("_matmul_precision"))
+    key = (tuple(tuple(x.shape) for x in inputs), train, tuple(p.data_ptr() for p in params.values()), key_extra, precision)
     cache = module.__dict__.setdefault("_op_plans", {})
     plan = cache.get(key)
     if plan is None:
         if len(cache) >= 8:
             cache.pop(next(iter(cache)))
         with torch.cuda.device(inputs[0].device):
-            plan = OpPlan(emit, inputs, {n: p.data for n, p in params.items()}, train)
+            plan = OpPlan(emit, inputs, {n: p.data for n, p in params.items()}, train, precision)
         cache[key] = plan
     with torch.cuda.device(inputs[0].device):
         if train:

@@ -179,6 +179,7 @@ class Ctx:
         self.sk_workspace = None  # optional callable -> tensor of L.SK_WORKSPACE_FLOATS floats shared by the plan's balanced GEMM launches
         self.mha_bwd_form = 0  # nasrec_mha_desc_t.bwd_form of the Transformer backward launches (4: the form worklist launches run)
         self.block_marks: List = []  # (block index, length of the backward program once that block's gradients are complete)
+        self.matmul_precision = L.PRECISION_HIGHEST  # L.PRECISION_* written into every GEMM descriptor of the plan (gemm_descs)
 
     # -- memory -----------------------------------------------------------------------------------------------
     def alloc(self, numel):
@@ -432,7 +433,19 @@ def gemm_kernel_name(d) -> str:
     family = gemm_route(d)[0]
     if family < 0:
         raise ValueError("nasrec_gemm rejects this descriptor (nasrec_gemm_route: %d)" % family)
+    if family == L.GEMM_ROUTE_FAST and d.precision != L.PRECISION_HIGHEST:
+        return "gemm_fast_bf16_kernel"  # csrc/gemm_fast_bf16.hip: the throughput launch's bf16 body (same family, same mask)
     return _ROUTE_KERNEL[family]
+
+
+def bf16_launches(descs) -> int:
+    """how many launches of a program run the bf16 body: the precision on a descriptor is a permission that only throughput-regime
+    launches take up (csrc/gemm_fast_bf16.hip) — every other GEMM family, and every launch of a worklist, computes in fp32"""
+    n = 0
+    for d in descs:
+        if isinstance(d, L.GemmDesc) and d.precision != L.PRECISION_HIGHEST and gemm_route(d)[0] == L.GEMM_ROUTE_FAST:
+            n += 1
+    return n
 
 
 def gemm_descs(ctx, amode, bmode, cmode, segs, zmode, act=0, bias_on_rows=0, mask_on_rows=0, dims=-1, beta=0, bias=None, save_z=None,
@@ -455,6 +468,9 @@ def gemm_descs(ctx, amode, bmode, cmode, segs, zmode, act=0, bias_on_rows=0, mas
     if mask_on_rows:
         d.mask_on_rows = mask_on_rows
     d.dims_in_use = dims
+    precision = getattr(ctx, "matmul_precision", 0)  # (a caller's own minimal context — tools, tests — has none: fp32)
+    if precision:  # permission for the throughput kernel's bf16 body; never part of the routing or split-K decisions below
+        d.precision = precision
     if beta:
         d.beta = beta
     if bias:

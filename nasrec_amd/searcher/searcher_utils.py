@@ -22,7 +22,7 @@ def build_supernet(args, num_embeddings=None):
     return SuperNet(sparse_input_size=_num_sparse_inputs_dict[args.dataset], num_blocks=args.num_blocks, ops_config=ops_config_lib[args.config],
                     use_layernorm=(args.use_layernorm == 1), activation="relu",
                     num_embeddings=num_embeddings if num_embeddings is not None else _num_embedding_dict[args.dataset],
-                    path_sampling_strategy="full-path")
+                    path_sampling_strategy="full-path", matmul_precision=getattr(args, "matmul_precision", None))
 
 
 def fixed_model_latency(args, choice, gpu_id, kwargs):
@@ -36,7 +36,7 @@ def fixed_model_latency(args, choice, gpu_id, kwargs):
     fixed = SuperNet(num_blocks=args.num_blocks, ops_config=ops_config_lib[args.config], use_layernorm=(args.use_layernorm == 1),
                      activation="relu", num_embeddings=tables if tables is not None else _num_embedding_dict[args.dataset],
                      sparse_input_size=_num_sparse_inputs_dict[args.dataset], path_sampling_strategy="fixed-path", fixed=True,
-                     fixed_choice=choice)
+                     fixed_choice=choice, matmul_precision=getattr(args, "matmul_precision", None))
     mean_lat, _ = get_model_latency(fixed, (int_x, cat_x), gpu_id)
     print("Latency: {:.5f} s.".format(mean_lat))
     return mean_lat

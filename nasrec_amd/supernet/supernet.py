@@ -168,8 +168,17 @@ class SuperNet(nn.Module):
                  num_embeddings: List[int] = NUM_EMBEDDINGS_CRITEO, sparse_input_size: int = 26, embedding_dim: int = 16,
                  last_n_blocks_out: int = 1, path_sampling_strategy: str = "default", fixed: bool = False, fixed_choice: Any = None,
                  place_embedding_on_cpu: bool = False, anypath_choice: str = "uniform", supernet_training_steps: int = 0,
-                 candidate_choices: Optional[List] = None, use_final_sigmoid: bool = False, table_sharding: Optional[str] = None):
-        """table_sharding (not a reference argument): None = every process holds whole tables (the reference's layout); "row" = the
+                 candidate_choices: Optional[List] = None, use_final_sigmoid: bool = False, table_sharding: Optional[str] = None,
+                 matmul_precision: Optional[str] = None):
+        """matmul_precision (not a reference argument): "highest" | "high" | "medium"; None = the environment variable
+        NASREC_MATMUL_PRECISION, else "highest".  What torch.set_float32_matmul_precision is to torch, for the engine: parameters,
+        activations, optimizer state and checkpoints stay fp32 and products accumulate in fp32; "medium" permits the large-batch
+        (throughput-regime) products of the Linear family — forward, input gradient, weight gradient — to round their operands to bf16
+        on the way to the matrix cores, "high" to bf16 x 3 (hi + lo split, three products).  Every other kernel, and every plan at batch
+        <= 256, computes in fp32 whatever the value; "highest" is bit for bit the arithmetic without the argument.
+        Under data parallelism every rank must pass the same value (utils/dist.py checks it at start-up).  use_amp=True keeps the torch
+        route.
+        table_sharding (not a reference argument): None = every process holds whole tables (the reference's layout); "row" = the
         rows of every table are split over the ranks of the process group (nasrec_amd/sharded_tables.py) — for tables that outgrow
         one GPU.  `_embedding[f]` then holds THIS rank's row range; `state_dict()` returns whole tables (a collective when world > 1);
         training goes through the fused engine step (Adagrad, weight decay 0), evaluation through the ordinary no-grad forward."""
@@ -189,6 +198,8 @@ class SuperNet(nn.Module):
         self._fixed = fixed
         assert table_sharding in (None, "none", "row"), "table_sharding must be None or 'row'"
         self._table_sharding = "row" if table_sharding == "row" else None
+        from .._lib import matmul_precision_name
+        self._matmul_precision = matmul_precision_name(matmul_precision)  # (ValueError on anything else)
         self._sharded = self._sharded_ops = None
         self._embedding = self._embedding_layers(sparse_input_size, num_embeddings, embedding_dim)
         self._final = nn.LazyLinear(1)
@@ -216,6 +227,8 @@ class SuperNet(nn.Module):
                 fixed_micro_choice=None if (fixed_choice is None) or (not fixed) else fixed_choice["micro"][idx],
                 anypath_choice=anypath_choice, supernet_training_steps=supernet_training_steps, sparse_input_size=sparse_input_size))
         self._blocks = nn.ModuleList(blocks)
+        for m in self.modules():  # operators run on their own (opexec.run) take their owner's precision
+            m.__dict__["_matmul_precision"] = self._matmul_precision
         # engine state (not part of the reference API)
         self._engine = None
         self._materialized = False
@@ -455,7 +468,7 @@ class SuperNet(nn.Module):
         Fd = self._Fd
         host = bool(self._place_embedding_on_cpu) or self._table_sharding == "row"
         eng = SupernetEngine(self._net_config(), Fd, self._sparse_input_size, self._num_embeddings, device=device,
-                             warm_choice=self._warm_choice(), host_embedding=host,
+                             warm_choice=self._warm_choice(), host_embedding=host, matmul_precision=self._matmul_precision,
                              tables=None if host else [params["_embedding.%d.weight" % f].data for f in range(self._sparse_input_size)])
         eng.load_params({k: v.data for k, v in params.items() if not k.startswith("_embedding.")})
         # re-point every dense nn.Parameter at the engine's flat arena (optimizers update in place; kernels read the

@@ -76,11 +76,12 @@ def train_and_eval_one_model(model, args):
 def main(args):
     from nasrec_amd.utils.dist import init_from_env
     rank, world = init_from_env(args)  # torchrun: one process per GPU, args.gpu = the local rank; same path seed on every rank
+    print("Matmul precision: {}".format(args.matmul_precision))
     model = SuperNet(sparse_input_size=_num_sparse_inputs_dict[args.dataset], num_blocks=args.num_blocks,
                      ops_config=ops_config_lib[args.config], use_layernorm=(args.use_layernorm == 1), activation="relu",
                      num_embeddings=_num_embedding_dict[args.dataset], path_sampling_strategy=args.strategy,
                      anypath_choice=args.anypath_choice, supernet_training_steps=args.supernet_training_steps, candidate_choices=None,
-                     table_sharding=args.table_sharding)
+                     table_sharding=args.table_sharding, matmul_precision=args.matmul_precision)
     return train_and_eval_one_model(model.to(args.gpu), args)
 
 
@@ -120,6 +121,9 @@ def build_parser():
     # not a reference flag: placement of the embedding tables under torchrun (nasrec_amd/sharded_tables.py)
     p.add_argument("--table-sharding", dest="table_sharding", type=str, default="none", choices=["none", "row"],
                    help="none: whole tables on every rank; row: every rank owns a row range of every table (all-to-all of ids / rows / row gradients)")
+    p.add_argument("--matmul-precision", dest="matmul_precision", type=str, default="highest", choices=["highest", "high", "medium"],
+                   help="what the large-batch matrix products may feed the matrix cores (SuperNet(matmul_precision=...), as "
+                        "torch.set_float32_matmul_precision): highest = fp32; high = bf16 x 3; medium = bf16. Tensors and accumulation stay fp32")
     return p
 
 

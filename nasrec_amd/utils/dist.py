@@ -96,6 +96,16 @@ def assert_replicas_identical(model):
     if world <= 1:
         return
     mine = replica_checksum(model)
+    # the matmul precision is a constructor argument / environment variable of every rank: ranks that disagree would compute different
+    # gradients from identical weights and drift apart silently — compared with the checksum
+    prec = getattr(model, "_matmul_precision", "highest")
+    code = torch.tensor([float({"highest": 0, "high": 1, "medium": 2}[prec])], dtype=mine.dtype, device=mine.device)
+    lo, hi = code.clone(), code.clone()
+    dist.all_reduce(lo, op=dist.ReduceOp.MIN)
+    dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+    if not torch.equal(lo, hi):
+        raise RuntimeError("data-parallel ranks disagree on the matmul precision (rank %d: %r): pass the same SuperNet(matmul_precision=...) / "
+                           "NASREC_MATMUL_PRECISION to every rank" % (rank, prec))
     lo, hi = mine.clone(), mine.clone()
     dist.all_reduce(lo, op=dist.ReduceOp.MIN)
     dist.all_reduce(hi, op=dist.ReduceOp.MAX)
