@@ -159,9 +159,11 @@ typedef struct nasrec_gemm_desc {
 
 /* Matrix-product precision of a GEMM descriptor — PERMISSION, not obligation, as torch.set_float32_matmul_precision: operands,
  * results and accumulation stay fp32 in memory; the value allows the kernel to round the OPERANDS of the products on their way to the
- * matrix cores.  Only throughput-regime launches (NASREC_GEMM_ROUTE_FAST) have a reduced body (gemm_fast_bf16_kernel); every other
- * family ignores the field and computes in fp32.  The field never changes the route or the split-K the planner picks.
- *   HIGHEST  fp32 operands (v_mfma_f32_32x32x2_f32), exact fp32 FMA chain
+ * matrix cores.  Three families have a reduced body: throughput-regime launches (NASREC_GEMM_ROUTE_FAST: gemm_fast_bf16_kernel, HIGH
+ * and MEDIUM), the large-batch token-axis weight gradient (NASREC_GEMM_ROUTE_TOKEN_DW: token_dw_bf16_kernel, HIGH and MEDIUM) and the
+ * large-batch token-axis Linear (NASREC_GEMM_ROUTE_TOKEN_LINEAR: token_linear_bf16_kernel, MEDIUM only — HIGH runs its fp32 body);
+ * every other family ignores the field and computes in fp32.  The field never changes the route or the split-K the planner picks.
+ *   HIGHEST  fp32 operands (v_mfma_f32_32x32x2_f32 / v_mfma_f32_16x16x4_f32), exact fp32 FMA chain
  *   HIGH     bf16 x 3: a = hi + lo with hi = bf16(a), lo = bf16(a - hi); lo*hi + hi*lo + hi*hi per k, fp32 accumulation
  *   MEDIUM   bf16: bf16(a) * bf16(b) per k (round to nearest even), fp32 accumulation
  * Any other value is rejected (NASREC_GEMM_ROUTE_BAD_PRECISION).
@@ -940,8 +942,10 @@ enum {
   NASREC_GEMM_ROUTE_KSLICE = 1,       /* gemm_kslice.hip: one large forward product at batch ~256, single pass */
   NASREC_GEMM_ROUTE_SKINNY_N = 2,     /* gemm_skinny.hip: N <= 16 at large batch, single pass */
   NASREC_GEMM_ROUTE_TINYK = 3,        /* gemm_skinny.hip: K <= 16 at large batch, single pass */
-  NASREC_GEMM_ROUTE_TOKEN_LINEAR = 4, /* token_linear.hip: token-axis Linear at large batch, single pass */
-  NASREC_GEMM_ROUTE_TOKEN_DW = 5,     /* token_linear.hip: token-axis weight gradient at large batch, split-K only */
+  NASREC_GEMM_ROUTE_TOKEN_LINEAR = 4, /* token_linear.hip: token-axis Linear at large batch, single pass; with precision == MEDIUM its
+                                         bf16 body (token_linear_bf16.hip) — same family, same mask */
+  NASREC_GEMM_ROUTE_TOKEN_DW = 5,     /* token_linear.hip: token-axis weight gradient at large batch, split-K only; with precision !=
+                                         HIGHEST its bf16 body (token_linear_bf16.hip) — same family, same mask */
   NASREC_GEMM_ROUTE_FAST = 6,         /* gemm_fast.hip: 128x128 throughput tiles, split-K or NASREC_SPLITK_BALANCED; with
                                          precision != HIGHEST its bf16 body (gemm_fast_bf16.hip) — same family, same mask */
   NASREC_GEMM_ROUTE_BAD_NSEG = -1,

@@ -213,11 +213,14 @@ __device__ __forceinline__ void ft_epilogue(const nasrec_gemm_desc_t& d, const n
 #pragma unroll
         for (int r = 0; r < 16; ++r) mulv[r] = mp[b][off[r] * mld[b]];
       }
-      if (has_pre) {
+      // (The virtual ones column j = N - 1 has no element in C or pre_add: (i, N - 1) is (i + 1, 0) of a dense [M, N - 1] array, and for
+      // the last row the float BEHIND it — an illegal access when the array ends where a mapping ends.  Its lanes read nothing; their
+      // values were never used.  Still one branch per array, sixteen loads inside.)
+      if (has_pre && !ones_j) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) prev[r] = d.pre_add[off[r] * ldc + j];
       }
-      if (acc_c) {  // (the ones-column's lanes read a real element too and drop it)
+      if (acc_c && !ones_j) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) cv[r] = Cp[off[r] * ldc + j];
       }

@@ -16,17 +16,10 @@
 //     to out[b][i][e] (64-byte segments) through the same epilogue as the general kernel (bias on rows, activation, prefix
 //     mask on rows, saved pre-activation, accumulation).
 // Exact fp32 FMA chains; the k order inside a sample is the natural one, so results do not depend on the launch geometry.
-#include "gemm_tile.h"
-
-#define TL_WAVES 16
-#define TL_CHUNK 8        // k-steps (of 4 k) loaded before their MFMAs
-#define TL_MAX_LDS 147456  // bytes of staged weights per workgroup (one 16-wave workgroup per CU; 160 KB LDS)
-#define TL_BIAS_FLOATS 80  // the row biases sit in front of the weights (M <= 80)
-
-template <int RB>
-struct TlPad {
-  static constexpr int v = RB == 1 ? 16 : (RB <= 3 ? 48 : 80);
-};
+// (This file holds the fp32 bodies; a descriptor that permits bf16 products — MEDIUM for the forward / input-gradient kernel, HIGH or
+// MEDIUM for the weight gradient — runs token_linear_bf16.hip on the same eligibility rule, geometry and LDS image size:
+// token_linear_common.h.)
+#include "token_linear_common.h"
 
 template <int AM, int RB>
 __global__ __launch_bounds__(1024) void token_linear_kernel(const nasrec_gemm_desc_t d, int wgs) {
@@ -201,7 +194,9 @@ int launch_token_linear(hipStream_t st, const nasrec_gemm_desc_t* d) {
   const int need = (Bs + TL_WAVES - 1) / TL_WAVES;
   if (wgs > need) wgs = need;
   const size_t lds = (size_t)(kp_max > 0 ? kp_max : 4) * mp * 4 + TL_BIAS_FLOATS * 4;
-  if (d->amode == NASREC_AM_KC)
+  if (d->precision == NASREC_PRECISION_MEDIUM)
+    launch_token_linear_bf16(st, d, rb, wgs * nprob, wgs, lds);  // (token_linear_bf16.hip; HIGH stays here: DESIGN.md "Matmul precision")
+  else if (d->amode == NASREC_AM_KC)
     launch_token_linear_t<NASREC_AM_KC>(st, d, rb, wgs * nprob, wgs, lds);
   else
     launch_token_linear_t<NASREC_AM_RC>(st, d, rb, wgs * nprob, wgs, lds);
@@ -218,8 +213,6 @@ int launch_token_linear(hipStream_t st, const nasrec_gemm_desc_t* d) {
 // slab and the general second pass (gemm_splitk_epilogue: fixed-order sum over the S slabs, row mask, accumulation, bias column)
 // finishes — desc.splitk = S workgroups per problem, chosen by the plan.
 // ---------------------------------------------------------------------------------------------------------------------------------
-#define TDW_WAVES 16
-
 template <int RB, int CB>
 __global__ __launch_bounds__(64 * TDW_WAVES) void token_dw_kernel(const nasrec_gemm_desc_t d, int Mmax, int Nmax) {
   __shared__ __attribute__((aligned(16))) float red[4 * RB * CB * 4 * 64];
@@ -315,6 +308,10 @@ static void launch_token_dw_rb(hipStream_t st, const nasrec_gemm_desc_t* d, int 
 int launch_token_dw(hipStream_t st, const nasrec_gemm_desc_t* d, int Mmax, int Nmax) {
   const int rb = (Mmax + 15) / 16, cb = (Nmax + 15) / 16;
   const int grid = d->nseg * d->splitk;
+  if (d->precision != NASREC_PRECISION_HIGHEST) {
+    launch_token_dw_bf16(st, d, rb, cb, grid, Mmax, Nmax);  // (token_linear_bf16.hip)
+    return 0;
+  }
   switch (rb) {
     case 1: launch_token_dw_rb<1>(st, d, cb, grid, Mmax, Nmax); break;
     case 2: launch_token_dw_rb<2>(st, d, cb, grid, Mmax, Nmax); break;

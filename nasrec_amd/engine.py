@@ -611,6 +611,8 @@ class SupernetEngine:
                 cp.fwd.capture(self.stream.cuda_stream)
         # launches of the plan's programs that run the bf16 body (0 at "highest"; forward + backward, each launch once)
         cp.bf16_launches = P.bf16_launches(cp.fwd.descs) + (P.bf16_launches(cp.bwd.descs) if train else 0)
+        # ... and the large-batch token-axis launches among them that run theirs (csrc/token_linear_bf16.hip), counted apart
+        cp.bf16_token_launches = P.bf16_token_launches(cp.fwd.descs) + (P.bf16_token_launches(cp.bwd.descs) if train else 0)
         if graph or arena is None or cfg.fixed:
             self.stream.synchronize()  # these plans are built (zero-filled, captured) on the private stream, and replayed on the caller's
         self._plans[key] = cp

@@ -142,6 +142,7 @@ class OpPlan:
             self.grads = {k[3:]: v for k, v in ctx.grads.items()}
         # launches of this plan that run the bf16 body (engine.CompiledPlan.bf16_launches)
         self.bf16_launches = P.bf16_launches(ctx.fwd) + (P.bf16_launches(ctx.bwd) if train else 0)
+        self.bf16_token_launches = P.bf16_token_launches(ctx.fwd) + (P.bf16_token_launches(ctx.bwd) if train else 0)
 
     def run_forward(self, inputs, stream_ptr):
         for dst, src in zip(self.ins, inputs):

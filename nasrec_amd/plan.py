@@ -428,23 +428,45 @@ _ROUTE_KERNEL = {L.GEMM_ROUTE_GENERAL: "gemm_kernel", L.GEMM_ROUTE_KSLICE: "gemm
                  L.GEMM_ROUTE_TOKEN_DW: "token_dw_kernel", L.GEMM_ROUTE_FAST: "gemm_fast_kernel"}
 
 
+# the bf16 body of a family that has one, by the precisions at which the launcher takes it (csrc/gemm_fast_bf16.hip,
+# csrc/token_linear_bf16.hip): same family, same mask.  token_linear has a MEDIUM body only (DESIGN.md "Matmul precision")
+_ROUTE_KERNEL_BF16 = {L.GEMM_ROUTE_FAST: ("gemm_fast_bf16_kernel", (L.PRECISION_HIGH, L.PRECISION_MEDIUM)),
+                      L.GEMM_ROUTE_TOKEN_LINEAR: ("token_linear_bf16_kernel", (L.PRECISION_MEDIUM,)),
+                      L.GEMM_ROUTE_TOKEN_DW: ("token_dw_bf16_kernel", (L.PRECISION_HIGH, L.PRECISION_MEDIUM))}
+_TOKEN_FAMILIES = (L.GEMM_ROUTE_TOKEN_LINEAR, L.GEMM_ROUTE_TOKEN_DW)
+
+
 def gemm_kernel_name(d) -> str:
     """the kernel launch_gemm runs for this descriptor, as the profiler names it"""
     family = gemm_route(d)[0]
     if family < 0:
         raise ValueError("nasrec_gemm rejects this descriptor (nasrec_gemm_route: %d)" % family)
-    if family == L.GEMM_ROUTE_FAST and d.precision != L.PRECISION_HIGHEST:
-        return "gemm_fast_bf16_kernel"  # csrc/gemm_fast_bf16.hip: the throughput launch's bf16 body (same family, same mask)
+    bf16 = _ROUTE_KERNEL_BF16.get(family)
+    if bf16 is not None and d.precision in bf16[1]:
+        return bf16[0]
     return _ROUTE_KERNEL[family]
 
 
 def bf16_launches(descs) -> int:
-    """how many launches of a program run the bf16 body: the precision on a descriptor is a permission that only throughput-regime
-    launches take up (csrc/gemm_fast_bf16.hip) — every other GEMM family, and every launch of a worklist, computes in fp32"""
+    """how many THROUGHPUT-regime launches of a program run the bf16 body (csrc/gemm_fast_bf16.hip).  The precision on a descriptor is
+    a permission: throughput launches and the large-batch token-axis launches (bf16_token_launches) take it up — every other GEMM
+    family, and every launch of a worklist, computes in fp32"""
     n = 0
     for d in descs:
         if isinstance(d, L.GemmDesc) and d.precision != L.PRECISION_HIGHEST and gemm_route(d)[0] == L.GEMM_ROUTE_FAST:
             n += 1
+    return n
+
+
+def bf16_token_launches(descs) -> int:
+    """how many large-batch token-axis launches of a program run their bf16 body (csrc/token_linear_bf16.hip): token_dw at "high" and
+    "medium", token_linear at "medium" only"""
+    n = 0
+    for d in descs:
+        if isinstance(d, L.GemmDesc) and d.precision != L.PRECISION_HIGHEST:
+            family = gemm_route(d)[0]
+            if family in _TOKEN_FAMILIES and d.precision in _ROUTE_KERNEL_BF16[family][1]:
+                n += 1
     return n
 
 

@@ -173,8 +173,10 @@ class SuperNet(nn.Module):
         """matmul_precision (not a reference argument): "highest" | "high" | "medium"; None = the environment variable
         NASREC_MATMUL_PRECISION, else "highest".  What torch.set_float32_matmul_precision is to torch, for the engine: parameters,
         activations, optimizer state and checkpoints stay fp32 and products accumulate in fp32; "medium" permits the large-batch
-        (throughput-regime) products of the Linear family — forward, input gradient, weight gradient — to round their operands to bf16
-        on the way to the matrix cores, "high" to bf16 x 3 (hi + lo split, three products).  Every other kernel, and every plan at batch
+        products of the Linear family — forward, input gradient, weight gradient; the throughput-regime GEMMs and, at batch >= 1024,
+        the token-axis Linears (ElasticLinear3D, the token projections, _sparse_inp_proj) — to round their operands to bf16 on the way
+        to the matrix cores, "high" to bf16 x 3 (hi + lo split, three products; the throughput GEMMs and the token-axis weight
+        gradients take it, the token-axis forward and input-gradient products stay fp32).  Every other kernel, and every plan at batch
         <= 256, computes in fp32 whatever the value; "highest" is bit for bit the arithmetic without the argument.
         Under data parallelism every rank must pass the same value (utils/dist.py checks it at start-up).  use_amp=True keeps the torch
         route.

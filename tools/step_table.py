@@ -42,8 +42,9 @@ with torch.cuda.stream(eng.stream):
                 M, N = segs[0][0], segs[0][1]
                 Kt = sum(s[2] for s in segs)
                 fl = bench.gemm_flops(d)
-                info = "am=%d bm=%d cm=%d z=%d M=%d N=%d K=%s splitk=%d act=%d  %.1f TF/s" % (
-                    d.amode, d.bmode, d.cmode, d.zmode, M, N, "+".join(str(s[2]) for s in segs) if not d.zmode else "%dx%d" % (len(segs), segs[0][2]),
+                # (the body by name: a family with a bf16 body runs it where the descriptor's precision permits — plan.gemm_kernel_name)
+                info = "%s am=%d bm=%d cm=%d z=%d M=%d N=%d K=%s splitk=%d act=%d  %.1f TF/s" % (
+                    P.gemm_kernel_name(d), d.amode, d.bmode, d.cmode, d.zmode, M, N, "+".join(str(s[2]) for s in segs) if not d.zmode else "%dx%d" % (len(segs), segs[0][2]),
                     d.splitk, d.act, fl / us / 1e6)
             if isinstance(d, L.WorklistDesc):
                 info = "worklist of " + " || ".join(names.get(n.desc.kind, "?") + ("[%s]" % n.part if n.part != "whole" else "") for n in d.nodes)
