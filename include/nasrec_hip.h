@@ -531,6 +531,14 @@ typedef struct nasrec_weight_decay_desc {
  *     regularised ranges).  The workgroup that finishes last adds 1 to the counters step[inc[i]] (counter: zero before, left zero).
  * Tables are walked in tiles of 64 rows, tile_off over ALL tables: table f's bits are the words [2 tile_off[f], 2 tile_off[f+1]).
  * Table f's step counter is step[table_step0 + f].  SGD: m = the momentum buffer, v / tv unused.
+ *
+ * sparse_rows != 0 (Adam only; appended WITHOUT a new nasrec_abi_version(), as nasrec_gemm_desc_t.precision was: a binding's layout
+ * check catches a stale structure): row-sparse Adam.  The dense chunks are updated as above; a table moves only in the rows of the
+ * batch, as torch.optim.SparseAdam moves them, t = step[table_step0 + f] + 1, g = a leader's summed gradient * coef (zero or not):
+ *   m = m + (1 - b1) (g - m);  v = v + (1 - b2) (g^2 - v);  p = p - (lr sqrt(1 - b2^t) / (1 - b1^t)) * m / (sqrt(v) + eps)
+ * Phase 0 does not mark `bitmap`, and every other row of table / tm / tv keeps its bits.  With n_zero == 0 there is no phase 1: the
+ * workgroup of phase 0 that finishes last adds 1 to step[inc[i]] (every workgroup has read its counters by then) and leaves
+ * `counter` zero.  With n_zero > 0 phase 0 does not count, and phase 1 runs as above with tile_off all zero (no table row moves).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct nasrec_opt_moments_desc {
   int32_t kind;  /* NASREC_OP_OPT_MOMENTS */
@@ -571,6 +579,8 @@ typedef struct nasrec_opt_moments_desc {
   int32_t rank_B;        /* layout of `gsum` (phase 0) as in nasrec_adagrad_rows_desc_t: 0 = contiguous [B,Fs,16]; > 0 = rank_B */
   int32_t _pad2;         /*   samples per rank chunk of an all-gather's receive buffer, chunks rank_stride floats apart */
   int64_t rank_stride;
+  int32_t sparse_rows;   /* 0 = every table row moves every step; != 0 = row-sparse Adam (above) */
+  int32_t _pad3;
 } nasrec_opt_moments_desc_t;
 
 /* ------------------------------------------------------------------------------------------------

@@ -269,7 +269,7 @@ class OptMomentsDesc(C.Structure):
                 ("g", vp), ("m", vp), ("v", vp), ("idx", vp), ("leader", vp), ("gsum", vp), ("table", vp * MAX_TABLES),
                 ("tm", vp * MAX_TABLES), ("tv", vp * MAX_TABLES), ("rows", i64 * MAX_TABLES), ("tile_off", i64 * (MAX_TABLES + 1)),
                 ("bitmap", vp), ("step", vp), ("inc", vp), ("n_inc", i64), ("zero_chunks", vp), ("n_zero", i64), ("counter", vp),
-                ("lr", vp), ("coef", vp), ("rank_B", i32), ("_pad2", i32), ("rank_stride", i64)]
+                ("lr", vp), ("coef", vp), ("rank_B", i32), ("_pad2", i32), ("rank_stride", i64), ("sparse_rows", i32), ("_pad3", i32)]
 
 
 class LastLayerStepDesc(C.Structure):

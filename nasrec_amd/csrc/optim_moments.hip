@@ -3,6 +3,8 @@
 // coefficient, dense chunks, the batch's touched rows, which it marks in a bitmap); phase 1 streams the untouched rows of every table
 // (a zero gradient still moves a row whose moments are non-zero: W and its one or two moment arrays, read and written once) and,
 // in the workgroup that finishes last, counts the step of every parameter it updated.
+// Row-sparse Adam (sparse_rows, include/nasrec_hip.h) is a phase 0 of its own, opt_moments_sparse_phase0_kernel: the same clip and dense
+// chunks, torch.optim.SparseAdam on the touched rows, no bitmap, and no phase 1 unless weight decay has gradients to restore.
 #include "optimizer_bodies.h"
 
 namespace {
@@ -27,54 +29,67 @@ __device__ __forceinline__ void table_scalars(const nasrec_opt_moments_desc_t& d
   if (ALGO == NASREC_OPTIM_ADAM && f >= 0 && f < d.Fs) adam_scalars(d, d.step[d.table_step0 + f], lr, ss[f], bs[f]);
 }
 
+// phase 0's head: wavefront 0 of every workgroup computes the clip coefficient into *sh_coef (workgroup 0 writes clip.out); the caller
+// synchronises
+__device__ __forceinline__ void clip_head(const nasrec_opt_moments_desc_t& d, float* sh_coef) {
+  const int tid = threadIdx.x;
+  if (tid < 64) {
+    float total;
+    const float c = clip_coef_wave(d.clip, tid, &total);
+    if (tid == 0) {
+      *sh_coef = c;
+      if (blockIdx.x == 0) {
+        d.clip.out[0] = c;
+        d.clip.out[1] = total;
+      }
+    }
+  }
+}
+
+// phase 0's dense arena (workgroups [0, dense_blocks)): one parameter per chunk (its step counter), float4 pieces, then the chunk's tail
+template <int ALGO>
+__device__ __forceinline__ void dense_chunks(const nasrec_opt_moments_desc_t& d, float coef, float lr) {
+  const int tid = threadIdx.x, blk = blockIdx.x;
+  for (long c = blk; c < d.nchunks; c += d.dense_blocks) {
+    const long off = d.chunks[3 * c], n = d.chunks[3 * c + 1], k = d.chunks[3 * c + 2], n4 = n >> 2;
+    float ss = 0.f, bs = 1.f;
+    if (ALGO == NASREC_OPTIM_ADAM) adam_scalars(d, d.step[k], lr, ss, bs);
+    float* pp = d.p + off;
+    float* mp = d.m + off;
+    float* vp = ALGO == NASREC_OPTIM_ADAM ? d.v + off : nullptr;
+    const float* gp = d.g + off;
+    for (long i = tid; i < n4; i += 256) {
+      f32x4 g4 = *reinterpret_cast<const f32x4*>(gp + 4 * i);
+      f32x4 p4 = *reinterpret_cast<const f32x4*>(pp + 4 * i), m4 = *reinterpret_cast<const f32x4*>(mp + 4 * i), v4 = {};
+      if (ALGO == NASREC_OPTIM_ADAM) v4 = *reinterpret_cast<const f32x4*>(vp + 4 * i);
+      g4 *= coef;
+      moments_vec<ALGO>(d, g4, p4, m4, v4, lr, ss, bs);
+      *reinterpret_cast<f32x4*>(pp + 4 * i) = p4;
+      *reinterpret_cast<f32x4*>(mp + 4 * i) = m4;
+      if (ALGO == NASREC_OPTIM_ADAM) *reinterpret_cast<f32x4*>(vp + 4 * i) = v4;
+    }
+    for (long j = 4 * n4 + tid; j < n; j += 256) {
+      float pe = pp[j], me = mp[j], ve = ALGO == NASREC_OPTIM_ADAM ? vp[j] : 0.f;
+      moments_elem<ALGO>(d, gp[j] * coef, pe, me, ve, lr, ss, bs);
+      pp[j] = pe;
+      mp[j] = me;
+      if (ALGO == NASREC_OPTIM_ADAM) vp[j] = ve;
+    }
+  }
+}
+
 template <int ALGO>
 __global__ __launch_bounds__(256) void opt_moments_phase0_kernel(const nasrec_opt_moments_desc_t d) {
   __shared__ float sh_coef;
   __shared__ float t_ss[NASREC_MAX_TABLES], t_bs[NASREC_MAX_TABLES];
   const int tid = threadIdx.x, blk = blockIdx.x;
   const float lr = *d.lr;
-  if (tid < 64) {
-    float total;
-    const float c = clip_coef_wave(d.clip, tid, &total);
-    if (tid == 0) {
-      sh_coef = c;
-      if (blk == 0) {
-        d.clip.out[0] = c;
-        d.clip.out[1] = total;
-      }
-    }
-  }
+  clip_head(d, &sh_coef);
   if (blk >= d.dense_blocks) table_scalars<ALGO>(d, 64, lr, t_ss, t_bs);
   __syncthreads();
   const float coef = sh_coef;
   if (blk < d.dense_blocks) {
-    // dense arena: one parameter per chunk (its step counter), float4 pieces, then the chunk's tail
-    for (long c = blk; c < d.nchunks; c += d.dense_blocks) {
-      const long off = d.chunks[3 * c], n = d.chunks[3 * c + 1], k = d.chunks[3 * c + 2], n4 = n >> 2;
-      float ss = 0.f, bs = 1.f;
-      if (ALGO == NASREC_OPTIM_ADAM) adam_scalars(d, d.step[k], lr, ss, bs);
-      float* pp = d.p + off;
-      float* mp = d.m + off;
-      float* vp = ALGO == NASREC_OPTIM_ADAM ? d.v + off : nullptr;
-      const float* gp = d.g + off;
-      for (long i = tid; i < n4; i += 256) {
-        f32x4 g4 = *reinterpret_cast<const f32x4*>(gp + 4 * i);
-        f32x4 p4 = *reinterpret_cast<const f32x4*>(pp + 4 * i), m4 = *reinterpret_cast<const f32x4*>(mp + 4 * i), v4 = {};
-        if (ALGO == NASREC_OPTIM_ADAM) v4 = *reinterpret_cast<const f32x4*>(vp + 4 * i);
-        g4 *= coef;
-        moments_vec<ALGO>(d, g4, p4, m4, v4, lr, ss, bs);
-        *reinterpret_cast<f32x4*>(pp + 4 * i) = p4;
-        *reinterpret_cast<f32x4*>(mp + 4 * i) = m4;
-        if (ALGO == NASREC_OPTIM_ADAM) *reinterpret_cast<f32x4*>(vp + 4 * i) = v4;
-      }
-      for (long j = 4 * n4 + tid; j < n; j += 256) {
-        float pe = pp[j], me = mp[j], ve = ALGO == NASREC_OPTIM_ADAM ? vp[j] : 0.f;
-        moments_elem<ALGO>(d, gp[j] * coef, pe, me, ve, lr, ss, bs);
-        pp[j] = pe;
-        mp[j] = me;
-        if (ALGO == NASREC_OPTIM_ADAM) vp[j] = ve;
-      }
-    }
+    dense_chunks<ALGO>(d, coef, lr);
     return;
   }
   // touched rows: 4 lanes x float4 per (sample, field) pair; the leader of a row id carries the row's summed gradient
@@ -96,6 +111,63 @@ __global__ __launch_bounds__(256) void opt_moments_phase0_kernel(const nasrec_op
   *reinterpret_cast<f32x4*>(d.tm[f] + o) = m4;
   if (ALGO == NASREC_OPTIM_ADAM) *reinterpret_cast<f32x4*>(d.tv[f] + o) = v4;
   if (q == 0) atomicOr(d.bitmap + 2 * d.tile_off[f] + (row >> 5), 1u << (row & 31));  // (a set of bits: no value depends on the order)
+}
+
+// Row-sparse Adam's phase 0 (sparse_rows): clip and dense chunks as above; a touched row takes torch.optim.SparseAdam's update with its
+// summed gradient, zero or not; no bit is marked.  Without weight decay's zero_chunks there is no phase 1, and the workgroup that finishes
+// last counts the steps: every workgroup has read its counters (dense_chunks, the tables' step sizes) when it arrives at d.counter.
+__global__ __launch_bounds__(256) void opt_moments_sparse_phase0_kernel(const nasrec_opt_moments_desc_t d) {
+  __shared__ float sh_coef;
+  __shared__ float t_ss[NASREC_MAX_TABLES];
+  __shared__ int last;
+  const int tid = threadIdx.x, blk = blockIdx.x;
+  const float lr = *d.lr;
+  clip_head(d, &sh_coef);
+  if (blk >= d.dense_blocks && tid >= 64 && tid - 64 < d.Fs) t_ss[tid - 64] = sparse_adam_step_size(d, d.step[d.table_step0 + tid - 64], lr);
+  __syncthreads();
+  const float coef = sh_coef;
+  if (blk < d.dense_blocks) {
+    dense_chunks<NASREC_OPTIM_ADAM>(d, coef, lr);
+  } else {
+    // touched rows: 4 lanes x float4 per (sample, field) pair; the leader of a row id carries the row's summed gradient
+    const long t = (long)(blk - d.dense_blocks) * 256 + tid;
+    const long pair = t >> 2;
+    const int q = (int)(t & 3);
+    if (pair < (long)d.B * d.Fs && d.leader[pair]) {
+      const int f = (int)(pair % d.Fs);
+      const long row = d.idx[pair];
+      if (row >= 0 && row < d.rows[f]) {  // (flagged by the gather; never written outside a table)
+        const long o = row * 16 + q * 4;
+        f32x4 g4 = *reinterpret_cast<const f32x4*>(d.gsum + gsum_row_offset(pair, d.Fs, d.rank_B, d.rank_stride) + q * 4);
+        f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o), m4 = *reinterpret_cast<const f32x4*>(d.tm[f] + o);
+        f32x4 v4 = *reinterpret_cast<const f32x4*>(d.tv[f] + o);
+        g4 *= coef;
+        const float ss = t_ss[f];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float pe = p4[e], me = m4[e], ve = v4[e];
+          sparse_adam_elem(d, g4[e], pe, me, ve, ss);
+          p4[e] = pe;
+          m4[e] = me;
+          v4[e] = ve;
+        }
+        *reinterpret_cast<f32x4*>(d.table[f] + o) = p4;
+        *reinterpret_cast<f32x4*>(d.tm[f] + o) = m4;
+        *reinterpret_cast<f32x4*>(d.tv[f] + o) = v4;
+      }
+    }
+  }
+  if (d.n_zero > 0) return;  // (phase 1 restores g over zero_chunks and counts)
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence();
+    last = atomicAdd(d.counter, 1u) == gridDim.x - 1u;
+  }
+  __syncthreads();
+  if (!last) return;
+  __threadfence();
+  for (long i = tid; i < d.n_inc; i += 256) d.step[d.inc[i]] += 1.f;
+  if (tid == 0) *d.counter = 0u;
 }
 
 // phase 1's row update: the optimizer with g = 0, or g = 2 wd W * coef on a regularised table (untouched_rows_pass, optimizer_bodies.h)
@@ -158,13 +230,20 @@ int launch_phases(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
     const long threads = (long)d->B * d->Fs * 4;
     const int nrows = (int)((threads + 255) / 256);
     if (d->dense_blocks < 0 || d->dense_blocks + nrows < 1) return nasrec_set_error(-2, "opt_moments: empty launch");
-    if (nrows > 0 && (!d->idx || !d->leader || !d->gsum || !d->bitmap)) return nasrec_set_error(-1, "opt_moments: row inputs missing");
+    if (nrows > 0 && (!d->idx || !d->leader || !d->gsum || (!d->bitmap && !d->sparse_rows))) return nasrec_set_error(-1, "opt_moments: row inputs missing");
     if (d->rank_B < 0 || (d->rank_B > 0 && (d->rank_stride < (int64_t)d->rank_B * d->Fs * 16 || d->B % d->rank_B != 0)))
       return nasrec_set_error(-2, "opt_moments: rank layout %d / %ld", d->rank_B, (long)d->rank_stride);
-    hipLaunchKernelGGL(opt_moments_phase0_kernel<ALGO>, dim3((unsigned)(d->dense_blocks + nrows)), dim3(256), 0, st, *d);
+    if (d->sparse_rows) {
+      if (d->n_zero <= 0 && (!d->counter || (d->n_inc > 0 && !d->inc))) return nasrec_set_error(-1, "opt_moments: sparse_rows without zero_chunks counts the steps: counter / inc missing");
+      hipLaunchKernelGGL(opt_moments_sparse_phase0_kernel, dim3((unsigned)(d->dense_blocks + nrows)), dim3(256), 0, st, *d);
+    } else {
+      hipLaunchKernelGGL(opt_moments_phase0_kernel<ALGO>, dim3((unsigned)(d->dense_blocks + nrows)), dim3(256), 0, st, *d);
+    }
   } else if (d->phase == 1) {
     if (d->nblocks <= 0) return nasrec_set_error(-1, "opt_moments: nblocks must be positive");
     if (!d->bitmap || !d->counter || !d->coef) return nasrec_set_error(-1, "opt_moments: phase 1 inputs missing");
+    if (d->sparse_rows && (d->n_zero <= 0 || d->tile_off[d->Fs] != 0))
+      return nasrec_set_error(-1, "opt_moments: sparse_rows has a phase 1 only to restore zero_chunks, and no table owns a tile");
     hipLaunchKernelGGL(opt_moments_phase1_kernel<ALGO>, dim3((unsigned)d->nblocks), dim3(256), 0, st, *d);
   } else {
     return nasrec_set_error(-1, "opt_moments: phase %d", d->phase);
@@ -177,6 +256,7 @@ int launch_phases(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
 int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
   if (d->Fs < 0 || d->Fs > NASREC_MAX_TABLES) return nasrec_set_error(-1, "opt_moments: Fs = %d", d->Fs);
   if (!d->lr || !d->step) return nasrec_set_error(-1, "opt_moments: lr / step missing");
+  if (d->sparse_rows && d->algo != NASREC_OPTIM_ADAM) return nasrec_set_error(-1, "opt_moments: sparse_rows is row-sparse Adam (algo %d)", d->algo);
   if (d->algo == NASREC_OPTIM_ADAM) return launch_phases<NASREC_OPTIM_ADAM>(st, d);
   if (d->algo == NASREC_OPTIM_SGD) return launch_phases<NASREC_OPTIM_SGD>(st, d);
   return nasrec_set_error(-1, "opt_moments: algo %d", d->algo);

@@ -152,6 +152,33 @@ __device__ __forceinline__ void moments_elem(const D& d, float g, float& p, floa
   }
 }
 
+// Row-sparse Adam on a touched table row (torch.optim.SparseAdam, torch/optim/_functional.py sparse_adam): the step size carries both
+// bias corrections, in Python doubles: lr sqrt(1 - b2^t) / (1 - b1^t), t = step + 1; eps is added to sqrt(v) itself
+template <class D>
+__device__ __forceinline__ float sparse_adam_step_size(const D& d, float step, float lr) {
+  const double t = (double)step + 1.0;
+  return (float)((double)lr * sqrt(1.0 - pow(d.beta2, t)) / (1.0 - pow(d.beta1, t)));
+}
+
+// one element; g = the clipped summed gradient.  One statement per torch call (sub, mul_, add_; pow, sub_, mul_, add_; sqrt_, add_; div_,
+// mul, add_), as in moments_elem
+template <class D>
+__device__ __forceinline__ void sparse_adam_elem(const D& d, float g, float& p, float& m, float& v, float step_size) {
+  const float w1 = (float)(1.0 - d.beta1), w2 = (float)(1.0 - d.beta2);
+  float mu = g - m;
+  mu = mu * w1;
+  m = m + mu;
+  float vu = g * g;
+  vu = vu - v;
+  vu = vu * w2;
+  v = v + vu;
+  float den = sqrtf(v);
+  den = den + d.eps;
+  float u = m / den;
+  u = (-step_size) * u;
+  p = p + u;
+}
+
 __device__ __forceinline__ void adagrad_dense_body(const nasrec_adagrad_dense_desc_t& d, int blk, int nblk, float lr, float coef) {
   if (d.chunks) {
     for (long c = blk; c < d.nchunks; c += nblk) {

@@ -857,11 +857,14 @@ class SupernetEngine:
         step updates — the reached ones (torch skips grad = None) plus, with weight decay, the regularised ones — then the step-counter
         indices of those parameters and of the tables that move: all of them when the path's backward reaches the embedding stem, else
         (grad None in torch) only the regularised ones with weight decay, none without.  Always a table: unlike Adagrad, g = 0 is not a
-        no-op."""
+        no-op.  Row-sparse Adam (spec.sparse_rows) counts the same steps; its tables move in the batch's rows only (_moments_descs)."""
         if self.host_embedding:
             raise L.EngineError("Adam / SGD in the fused step need the embedding tables on the device")
         t = cp.tail
         spec = t.spec
+        if spec.sparse_rows and spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
+            raise L.EngineError("row-sparse Adam with a regularised table: the L2 term puts a gradient on every row; leave the tables out "
+                                "(no_reg_param_name='_embedding') or use weight_decay=0")
         self.ensure_moments_state(spec.kind)
         names = [n for n in list(ctx.grad_params) + ["_final.weight", "_final.bias"] if not n.startswith("_embedding.")]
         if spec.wd:
@@ -891,14 +894,18 @@ class SupernetEngine:
 
     def _moments_descs(self, t, Bg, cat_x, gsum, clip_desc, rank_layout=None):
         """the two NASREC_OP_OPT_MOMENTS launches of a plan with Adam / SGD: (phase 0 in place of the Adagrad apply launch, phase 1).
-        rank_layout: (samples per rank, floats between the ranks' chunks) of `gsum` (_optimizer_descs)"""
+        rank_layout: (samples per rank, floats between the ranks' chunks) of `gsum` (_optimizer_descs).
+        Row-sparse Adam: no table owns a tile, and phase 1 is None unless weight decay left unreached ranges of g to restore — phase 0
+        then counts the steps itself; with them phase 1 runs in its no-table-moves form on all its workgroups (the ranges of a supernet
+        are millions of floats)."""
         spec = t.spec
         st = self.moments
         m = L.OptMomentsDesc()
         m.kind, m.phase = L.OP_OPT_MOMENTS, 0
         self._optim_scalars(m, spec)
         m.dense_blocks = min(2048, t.mom_chunks[1])
-        m.nblocks = self.WD_BLOCKS if t.mom_tables else 1  # (no table moves: phase 1 only counts the step and restores g)
+        m.sparse_rows = int(bool(spec.sparse_rows))
+        m.nblocks = self.WD_BLOCKS if (t.mom_tables or spec.sparse_rows) else 1  # (no table moves: phase 1 only counts the step and restores g)
         m.B, m.Fs = (Bg, self.Fs) if gsum is not None else (0, self.Fs)
         m.table_step0 = len(self.dense_names)
         m.wd = spec.wd
@@ -918,7 +925,7 @@ class SupernetEngine:
             if second is not None:
                 m.tv[f] = second[1][f].data_ptr()
             m.tile_off[f] = tile
-            if f in t.mom_tables:  # (a table that does not move owns no tile: phase 1 leaves it alone)
+            if f in t.mom_tables and not spec.sparse_rows:  # (a table that does not move owns no tile: phase 1 leaves it alone)
                 tile += (self.num_embeddings[f] + 63) // 64
             if spec.wd and f in t.wd_tables:
                 mask |= 1 << f
@@ -931,6 +938,8 @@ class SupernetEngine:
             m.zero_chunks, m.n_zero = t.wd_set
         m.counter = self._mom_counter.data_ptr()
         m.lr, m.coef = self.lr_dev.data_ptr(), self.clip_out.data_ptr()
+        if spec.sparse_rows and not m.n_zero:
+            return m, None
         m1 = L.OptMomentsDesc.from_buffer_copy(m)
         m1.phase = 1
         return m, m1
@@ -1247,7 +1256,8 @@ class SupernetEngine:
         weight_decay != 0: the step minimises BCE + get_l2_loss(model, weight_decay, no_reg_param_name) (train_utils.py:91-115,262-266):
         every regularised parameter and EVERY table row is decayed; wd_l2_sumsq then holds sum ||W||^2 of the pre-step weights.
         optim: an OptimSpec of kind adam / sgd replaces Adagrad (eps is then unused): torch.optim.Adam / SGD over the parameters the step
-        reaches and EVERY table row, state in `moments` and `opt_steps` (ensure_moments_state)."""
+        reaches and EVERY table row, state in `moments` and `opt_steps` (ensure_moments_state); with sparse_rows the tables move in the
+        batch's rows only (utils/optim.RowSparseAdam), and weight decay must leave them out."""
         choice = choice if choice is not None else self.warm_choice
         if graph is None:
             graph = self.cfg.fixed and self.prefers_graph(int(int_x.shape[0]) if int_x is not None else int(self._last_plan[2].cat_x.shape[0]))

@@ -122,7 +122,7 @@ def build_parser():
     p.add_argument("--choice_from_pickle_file", type=str, default=None,
                    help="Pre-sampled cached choices from a pickle file; the number of records overrides 'num_subnets'.")
     p.add_argument("--no-reg-param-name", type=str, default=None, help="Name of the parameters that do not need to be regularized.")
-    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "rmsprop"])
+    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rmsprop"])
     p.add_argument("--loss_function", type=str, default="bce", choices=["bce"])
     p.add_argument("--gpu", type=int, default=0, help="GPU ID to use.")
     p.add_argument("--matmul-precision", dest="matmul_precision", type=str, default="highest", choices=["highest", "high", "medium"],

@@ -44,13 +44,20 @@ def summary_writer(logging_dir):
 
 
 def build_optimizer(name, model, lr):
-    """main_train.py:150-160 (Adagrad eps 1e-2; Adam eps 1e-8; SGD nesterov momentum 0.9)"""
+    """main_train.py:150-160 (Adagrad eps 1e-2; Adam eps 1e-8; SGD nesterov momentum 0.9); row-sparse-adam: Adam's lr and eps, the
+    tables moving in the batch's rows only (utils/optim.RowSparseAdam)"""
     if name == "adagrad":
         return torch.optim.Adagrad(model.parameters(), lr=lr, eps=1e-2)
     if name == "adam":
         return torch.optim.Adam(model.parameters(), lr=lr, eps=1e-8)
     if name == "sgd":
         return torch.optim.SGD(model.parameters(), lr=lr, nesterov=True, momentum=0.9)
+    if name == "row-sparse-adam":
+        from nasrec_amd.utils.optim import RowSparseAdam
+        if getattr(model, "_table_sharding", None) == "row":
+            raise ValueError("--optimizer row-sparse-adam needs whole tables: a row-sharded table holds one rank's rows under local ids; "
+                             "use --optimizer adam with --table-sharding row")
+        return RowSparseAdam(model.parameters(), list(model._embedding.parameters()), lr=lr, eps=1e-8)
     raise KeyError(name)
 
 
@@ -85,7 +92,7 @@ def train_and_eval_one_model(model, args):
     model.apply(init_weights)
     from nasrec_amd.utils.dist import assert_replicas_identical, broadcast_replica_state
     broadcast_replica_state(model)  # data parallel: rank 0's weights, tables and accumulators are THE model
-    assert_replicas_identical(model)
+    assert_replicas_identical(model, optimizer)
     print(model)
     create_dir(args.logging_dir)
     with open(os.path.join(args.logging_dir, "configs_args.json"), "w") as f:
@@ -154,7 +161,7 @@ def build_parser():
                    help="Data split for validation (evaluation). Can be one of ['val', 'test']")
     p.add_argument("--train_batch_size", type=int, default=200, help="Training batch size.")
     p.add_argument("--test_batch_size", type=int, default=16368, help="Testing batch size.")
-    p.add_argument("--optimizer", type=str, default="adagrad", help="Optimizer", choices=["adagrad", "sgd", "adam", "rmsprop", "ds-optimizer"])
+    p.add_argument("--optimizer", type=str, default="adagrad", help="Optimizer", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rmsprop", "ds-optimizer"])
     # Criteo: train 36672495 / val 4584061 / test 4584061 / trainval 41256556; Avazu: 32343175 / 4042896 / 4042896 / 36386071;
     # KDD: 119711284 / 14963910 / 14963910 / 134675194
     p.add_argument("--train_limit", type=int, default=41256556, help="Maximum number of training examples.")

@@ -2,7 +2,7 @@
 hyperparameters, and the weight decay of get_l2_loss, whose gradient the step folds in.
 
 `OptimSpec.for_step` decides which torch optimizers the fused step reproduces: torch.optim.Adagrad, and torch.optim.Adam / torch.optim.SGD
-with momentum under the conditions of `from_optimizer`, in one process or in every rank of a data-parallel run with whole tables
+with momentum / RowSparseAdam (nasrec_amd/utils/optim.py) under the conditions of `from_optimizer`, in one process or in every rank of a data-parallel run with whole tables
 (nasrec_amd/parallel.py).  The public entry points (SuperNet.engine_*, SupernetEngine.train_step / last_layer_step, DataParallelStep)
 normalise their arguments into one spec (`of`); everything below them passes that."""
 from typing import NamedTuple, Optional
@@ -19,6 +19,7 @@ class OptimSpec(NamedTuple):
     nesterov: bool = False
     wd: float = 0.0         # get_l2_loss(model, wd, no_reg): the step minimises BCE + that term
     no_reg: Optional[str] = None
+    sparse_rows: bool = False  # Adam: row-sparse on the tables (utils/optim.RowSparseAdam: torch.optim.SparseAdam on the batch's rows)
 
     @property
     def moments(self) -> bool:
@@ -44,19 +45,21 @@ class OptimSpec(NamedTuple):
     def from_optimizer(optimizer) -> Optional["OptimSpec"]:
         """the spec of a torch.optim.Adam / torch.optim.SGD the fused step reproduces, else None.
         Adam: one group, amsgrad, weight_decay, maximize, capturable, differentiable and fused all off.
-        SGD: one group, momentum != 0 (plain SGD keeps the torch route), dampening 0, weight_decay 0, not maximize / differentiable / fused."""
+        SGD: one group, momentum != 0 (plain SGD keeps the torch route), dampening 0, weight_decay 0, not maximize / differentiable / fused.
+        RowSparseAdam: Adam's conditions (its one group carries Adam's keys) -> sparse_rows."""
+        from .utils.optim import RowSparseAdam
         if len(optimizer.param_groups) != 1:
             return None
         g = optimizer.param_groups[0]
         if g.get("weight_decay", 0) != 0 or g.get("maximize", False) or g.get("differentiable", False) or g.get("fused"):
             return None
-        if type(optimizer) is torch.optim.Adam:
+        if type(optimizer) in (torch.optim.Adam, RowSparseAdam):
             if g.get("amsgrad", False) or g.get("capturable", False):
                 return None
             b1, b2 = g["betas"]
             if torch.is_tensor(b1) or torch.is_tensor(b2):
                 return None
-            return OptimSpec("adam", beta1=float(b1), beta2=float(b2), eps=float(g["eps"]))
+            return OptimSpec("adam", beta1=float(b1), beta2=float(b2), eps=float(g["eps"]), sparse_rows=type(optimizer) is RowSparseAdam)
         if type(optimizer) is torch.optim.SGD:
             if g.get("dampening", 0) != 0 or not g.get("momentum", 0):
                 return None
@@ -67,9 +70,12 @@ class OptimSpec(NamedTuple):
     def for_step(optimizer, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None) -> Optional["OptimSpec"]:
         """the spec of the fused step that stands in for `optimizer.step()` on the loss + get_l2_loss(model, weight_decay,
         no_reg_param_name), or None when the fused step does not reproduce the optimizer.  torch.optim.Adagrad: one group,
-        weight_decay, lr_decay and initial_accumulator_value 0, not maximize; Adam / SGD: from_optimizer."""
+        weight_decay, lr_decay and initial_accumulator_value 0, not maximize; Adam / SGD / RowSparseAdam: from_optimizer.  Row-sparse
+        Adam with a regularised table is None too (`regularises_tables`): the L2 term puts a gradient on every row."""
         if type(optimizer) is not torch.optim.Adagrad:
             optim = OptimSpec.from_optimizer(optimizer)
+            if optim is not None and optim.sparse_rows and regularises_tables(weight_decay, no_reg_param_name):
+                return None
             return OptimSpec.of(weight_decay=weight_decay, no_reg_param_name=no_reg_param_name, optim=optim) if optim is not None else None
         if len(optimizer.param_groups) != 1:
             return None
@@ -77,3 +83,9 @@ class OptimSpec(NamedTuple):
         if g.get("weight_decay", 0) != 0 or g.get("lr_decay", 0) != 0 or g.get("initial_accumulator_value", 0) != 0 or g.get("maximize", False):
             return None
         return OptimSpec.of(float(g["eps"]), weight_decay, no_reg_param_name)
+
+
+def regularises_tables(weight_decay, no_reg_param_name: Optional[str]) -> bool:
+    """get_l2_loss(model, weight_decay, no_reg_param_name) reaches an embedding table: it leaves out the names that START with
+    no_reg_param_name (utils/train_utils.py), so every table "_embedding.<f>.weight" is left out exactly by a prefix of "_embedding." """
+    return bool(weight_decay) and not (no_reg_param_name is not None and "_embedding.".startswith(no_reg_param_name))

@@ -627,7 +627,8 @@ class SuperNet(nn.Module):
         the counterpart of train_utils.py:262-286 for optimizer == Adagrad (torch's own weight_decay == 0).  weight_decay != 0: the loss
         is BCE + get_l2_loss(self, weight_decay, no_reg_param_name) — every regularised parameter and every table row is decayed
         (engine_last_l2 = that term on the pre-step weights).  optim: an OptimSpec (nasrec_amd/optim_spec.py) of torch.optim.Adam / SGD
-        replaces Adagrad (eps unused) — every table row moves every step; engine_bind_optimizer / engine_sync_optimizer_steps share its
+        replaces Adagrad (eps unused) — every table row moves every step, or with sparse_rows (utils/optim.RowSparseAdam) only the
+        batch's rows, which weight decay must then leave out; engine_bind_optimizer / engine_sync_optimizer_steps share its
         state with the torch optimizer.  Both need whole tables; under data parallelism they run in the exchange step's optimizer over
         the global batch (nasrec_amd/parallel.py)."""
         if self._place_embedding_on_cpu:

@@ -48,7 +48,7 @@ def train_and_eval_one_model(model, args):
         model.apply(init_weights)
     from nasrec_amd.utils.dist import assert_replicas_identical, broadcast_replica_state
     broadcast_replica_state(model)  # data parallel: rank 0's weights, tables and accumulators are THE model
-    assert_replicas_identical(model)
+    assert_replicas_identical(model, optimizer)
     print(model)
     strategy_name = args.strategy if args.strategy == "single-path" else args.strategy + "-" + args.anypath_choice
     logging_dir = os.path.join(args.logging_dir, "supernet_{}blocks_layernorm{:d}_{}_lr{:.2f}_supernetwarmup_{}".format(
@@ -115,7 +115,7 @@ def build_parser():
     p.add_argument("--validate_split", type=str, default="test", choices=["val", "test"])
     p.add_argument("--no-reg-param-name", type=str, default=None, help="Name of the parameters that do not need to be regularized.")
     p.add_argument("--loss_function", type=str, default="bce", choices=["bce"])
-    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "rmsprop", "ds-optimizer"])
+    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rmsprop", "ds-optimizer"])
     p.add_argument("--pretrained_dlrm_emb_path", type=str, default=None, help="Pretrained embedding path from DLRM model.")
     p.add_argument("--gpu", type=int, default=0, help="GPU ID to use.")
     # not a reference flag: placement of the embedding tables under torchrun (nasrec_amd/sharded_tables.py)

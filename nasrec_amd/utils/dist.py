@@ -90,8 +90,9 @@ def replica_checksum(model) -> torch.Tensor:
     return acc
 
 
-def assert_replicas_identical(model):
-    """raise unless every rank holds the same weights (checked before the first step of a data-parallel run)"""
+def assert_replicas_identical(model, optimizer=None):
+    """raise unless every rank holds the same weights (checked before the first step of a data-parallel run); optimizer: also unless
+    every rank runs the same table semantic (OptimSpec.sparse_rows: row-sparse Adam on some ranks and Adam on others would drift)"""
     rank, world = world_info()
     if world <= 1:
         return
@@ -106,6 +107,17 @@ def assert_replicas_identical(model):
     if not torch.equal(lo, hi):
         raise RuntimeError("data-parallel ranks disagree on the matmul precision (rank %d: %r): pass the same SuperNet(matmul_precision=...) / "
                            "NASREC_MATMUL_PRECISION to every rank" % (rank, prec))
+    if optimizer is not None:
+        from ..optim_spec import OptimSpec
+        spec = OptimSpec.from_optimizer(optimizer)
+        sparse = bool(spec is not None and spec.sparse_rows)
+        lo = torch.tensor([float(sparse)], dtype=mine.dtype, device=mine.device)
+        hi = lo.clone()
+        dist.all_reduce(lo, op=dist.ReduceOp.MIN)
+        dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+        if not torch.equal(lo, hi):
+            raise RuntimeError("data-parallel ranks disagree on the optimizer's table rows (rank %d: sparse_rows=%r): pass the same "
+                               "--optimizer to every rank" % (rank, sparse))
     lo, hi = mine.clone(), mine.clone()
     dist.all_reduce(lo, op=dist.ReduceOp.MIN)
     dist.all_reduce(hi, op=dist.ReduceOp.MAX)

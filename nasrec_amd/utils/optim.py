@@ -1,0 +1,111 @@
+"""Row-sparse ("lazy") Adam over a whole model: torch.optim.Adam on the dense parameters, torch.optim.SparseAdam on the embedding tables.
+
+A table moves only in the rows whose ids are in the batch — weights and both moments — and every other row keeps its bits: what
+recommendation models with tables of 10^7 rows train with.  The tables' gradients stay dense tensors (nn.Embedding(sparse=False), as the
+reference builds them), so the optimizer cannot see which rows the batch touched: the training loop tells it (`touch`).  A touched row
+whose summed gradient is exactly zero still decays its moments and moves, as a row of a coalesced sparse gradient does.
+
+`step()` is the torch route; the fused engine step reproduces it (OptimSpec.sparse_rows, csrc/optim_moments.hip) and shares its state
+through SuperNet.engine_bind_optimizer, as with torch.optim.Adam."""
+import math
+from typing import Iterable
+
+import torch
+from torch.optim.adam import adam as _adam
+
+
+class RowSparseAdam(torch.optim.Optimizer):
+    """params: every parameter of the model, the tables included; table_params: the tables, table f first ... (model._embedding's
+    parameters in order): column f of the ids given to `touch` belongs to table_params[f].  One param group with torch.optim.Adam's
+    keys; state per parameter: step, exp_avg, exp_avg_sq (Adam's key set: a checkpoint has Adam's shape)."""
+
+    def __init__(self, params, table_params: Iterable[torch.Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8):
+        if lr < 0.0 or eps < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+            raise ValueError("RowSparseAdam: lr %r, betas %r, eps %r" % (lr, betas, eps))
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0, amsgrad=False, maximize=False, capturable=False,
+                        differentiable=False, fused=None)
+        super().__init__(params, defaults)
+        if len(self.param_groups) != 1:
+            raise ValueError("RowSparseAdam keeps one param group")
+        self._tables = list(table_params)
+        own = {id(p) for p in self.param_groups[0]["params"]}
+        if not all(id(t) in own for t in self._tables):
+            raise ValueError("RowSparseAdam: every table must be one of params")
+        self._table_index = {id(t): f for f, t in enumerate(self._tables)}
+        self._ids = None
+
+    def touch(self, cat_feats: torch.Tensor):
+        """the ids [B, Fs] of the batch whose gradients the next step() applies: column f = the rows of table f it touches.  In a
+        process group of several ranks the torch route averages the tables' dense gradients over the ranks, so the touched rows are
+        those of every rank's batch: the ids are gathered (a collective: every rank calls touch)."""
+        if cat_feats.dim() != 2 or cat_feats.shape[1] != len(self._tables):
+            raise ValueError("touch: ids of shape [B, %d] expected, got %s" % (len(self._tables), tuple(cat_feats.shape)))
+        ids = cat_feats.detach().long()
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            parts = [torch.empty_like(ids) for _ in range(dist.get_world_size())]
+            dist.all_gather(parts, ids.contiguous())
+            ids = torch.cat(parts)
+        # an id must name a row of its table: a row-sharded table (SuperNet(table_sharding="row")) holds one rank's rows under local
+        # ids, which the batch's global ids do not address (one comparison on the device, one flag read back per step)
+        sizes = torch.tensor([t.shape[0] for t in self._tables], device=ids.device)
+        if ids.numel() and bool(((ids < 0) | (ids >= sizes)).any()):
+            raise ValueError("touch: an id lies outside its table (%s rows): RowSparseAdam needs whole tables under the batch's ids, "
+                             "not row-sharded ones" % [int(t.shape[0]) for t in self._tables])
+        self._ids = ids
+
+    def _init_state(self, p):
+        st = self.state[p]
+        if len(st) == 0:
+            st["step"] = torch.tensor(0.0, dtype=torch.float32)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        group = self.param_groups[0]
+        beta1, beta2 = group["betas"]
+        lr, eps = group["lr"], group["eps"]
+        dense = ([], [], [], [], [])
+        tables = []
+        for p in group["params"]:
+            if p.grad is None:
+                continue  # (a parameter the sampled path does not reach; a table when the backward stops short of the stem)
+            if p.grad.is_sparse:
+                raise RuntimeError("RowSparseAdam reads dense gradients (nn.Embedding(sparse=False)) and the ids of touch()")
+            st = self._init_state(p)
+            if id(p) in self._table_index:
+                tables.append((p, st))
+                continue
+            for lst, v in zip(dense, (p, p.grad, st["exp_avg"], st["exp_avg_sq"], st["step"])):
+                lst.append(v)
+        if tables and self._ids is None:
+            raise RuntimeError("RowSparseAdam.step: a table has a gradient and no ids were given since the last step: call "
+                               "optimizer.touch(cat_feats) before step() (touched rows are never guessed from non-zero gradients)")
+        if dense[0]:
+            # torch.optim.Adam itself, per-parameter step counters included
+            _adam(dense[0], dense[1], dense[2], dense[3], [], dense[4], amsgrad=False, beta1=beta1, beta2=beta2, lr=lr, weight_decay=0,
+                  eps=eps, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None, has_complex=False)
+        for p, st in tables:
+            # torch.optim.SparseAdam on the rows of the batch (torch/optim/_functional.py sparse_adam, statement by statement)
+            st["step"] += 1
+            t = float(st["step"])
+            rows = torch.unique(self._ids[:, self._table_index[id(p)]]).to(p.device)
+            g = p.grad.index_select(0, rows)
+            m_old, v_old = st["exp_avg"].index_select(0, rows), st["exp_avg_sq"].index_select(0, rows)
+            m_upd = g.sub(m_old).mul_(1 - beta1)
+            v_upd = g.pow(2).sub_(v_old).mul_(1 - beta2)
+            numer = m_upd.add(m_old)
+            v_new = v_upd.add(v_old)
+            st["exp_avg"].index_copy_(0, rows, numer)
+            st["exp_avg_sq"].index_copy_(0, rows, v_new)
+            denom = v_new.sqrt().add_(eps)
+            step_size = lr * math.sqrt(1 - beta2 ** t) / (1 - beta1 ** t)
+            p.index_add_(0, rows, numer.div(denom).mul_(-step_size))
+        self._ids = None  # consumed: the next gradients need their own ids
+        return loss

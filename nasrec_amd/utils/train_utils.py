@@ -121,6 +121,15 @@ def _optim_spec(optimizer, l2_loss_fn):
     return OptimSpec.for_step(optimizer)
 
 
+def _refuse_regularised_tables(optimizer, l2_loss_fn):
+    """row-sparse Adam moves a table in the batch's rows only; an L2 term over a table puts a gradient on every row, on either route"""
+    from ..optim_spec import OptimSpec, regularises_tables
+    spec = OptimSpec.from_optimizer(optimizer) if isinstance(optimizer, torch.optim.Optimizer) else None
+    if spec is not None and spec.sparse_rows and isinstance(l2_loss_fn, L2Loss) and regularises_tables(l2_loss_fn.wd, l2_loss_fn.no_reg_param_name):
+        raise ValueError("row-sparse Adam cannot train a regularised embedding table (weight decay %g reaches every row): pass "
+                         "--no-reg-param-name _embedding to leave the tables out of the L2 term, or --wd 0" % l2_loss_fn.wd)
+
+
 def _last_layer_step_applies(model, optimizer, l2_loss_fn, use_amp):
     """engine_last_layer_step stands in for the torch route's step: a SuperNet in last-layer mode (every parameter outside _final
     frozen) of one process with whole tables on the device, an L2Loss, and an optimizer OptimSpec.for_step accepts whose one group
@@ -218,6 +227,7 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
     `use_engine_step`: None = fused engine step whenever it applies, False = always the torch route.
     `last_layer_step`: a model in last-layer mode (set_mode_to_finelune_last_only) with a qualifying optimizer trains every full batch
     through SuperNet.engine_last_layer_step (_last_layer_step_applies); False (default) = as before."""
+    _refuse_regularised_tables(optimizer, l2_loss_fn)
     _peek(test_loader)  # the reference peeks one test batch here (train_utils.py:224-225)
     model.train()
     logs = {k: [] for k in ("train_loss", "train_AUROC", "train_Accuracy", "test_loss", "test_AUROC", "test_Accuracy", "epoch", "iters")}
@@ -298,6 +308,8 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                     scaler.unscale_(optimizer)
                     if grad_clip_value is not None:
                         torch.nn.utils.clip_grad_norm_(model.parameters(), grad_clip_value)
+                    if hasattr(optimizer, "touch"):
+                        optimizer.touch(cat_x)
                     scaler.step(optimizer)
                     scaler.update()
                 else:
@@ -306,6 +318,8 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                         allreduce_grads(model)
                     if grad_clip_value is not None:
                         torch.nn.utils.clip_grad_norm_(model.parameters(), grad_clip_value)
+                    if hasattr(optimizer, "touch"):  # (RowSparseAdam: the rows this batch touches)
+                        optimizer.touch(cat_x)
                     optimizer.step()
         t_gpu1 = time.time()
         last = batch_num == max_train_steps - 1

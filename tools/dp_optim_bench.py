@@ -5,10 +5,10 @@ alternating rounds:
   plain     DataParallelStep without a process group: the single-process fused step (engine.train_step);
   exchange  DataParallelStep(force_exchange=True, real_collectives=True) in a single-rank RCCL group: the captured exchange step with
             RCCL's all-reduce / all-gather kernels and the optimizer over the gathered batch — what each of N ranks runs.
-Optimizers: Adagrad (eps 1e-2) with wd 0 and 1e-8, Adam (eps 1e-8), Nesterov SGD (momentum 0.9); lr 1e-3.
+Optimizers: Adagrad (eps 1e-2) with wd 0 and 1e-8, Adam (eps 1e-8), Nesterov SGD (momentum 0.9), row-sparse Adam (eps 1e-8); lr 1e-3.
 
     python tools/dp_optim_bench.py --optimizer adam --wd 0     # one optimizer: one JSON line
-    python tools/dp_optim_bench.py --all                       # the four of them, each in a child process of its own"""
+    python tools/dp_optim_bench.py --all                       # every configuration, each in a child process of its own"""
 import argparse
 import json
 import os
@@ -18,12 +18,12 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-CONFIGS = [("adagrad", 0.0), ("adagrad", 1e-8), ("adam", 0.0), ("sgd", 0.0)]
+CONFIGS = [("adagrad", 0.0), ("adagrad", 1e-8), ("adam", 0.0), ("sgd", 0.0), ("row-sparse-adam", 0.0)]
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--optimizer", choices=["adagrad", "adam", "sgd"], default="adagrad")
+    ap.add_argument("--optimizer", choices=["adagrad", "adam", "sgd", "row-sparse-adam"], default="adagrad")
     ap.add_argument("--wd", type=float, default=0.0)
     ap.add_argument("--B", type=int, default=256)
     ap.add_argument("--steps", type=int, default=20, help="steps per round")
@@ -64,8 +64,10 @@ def main():
     with torch.no_grad():
         m(batches[0][0], batches[0][1])
     eng, choice = m._engine, m._resolve_choice(None)
-    optim = {"adam": OptimSpec("adam", eps=1e-8), "sgd": OptimSpec("sgd", momentum=0.9, nesterov=True)}.get(a.optimizer)
-    kw = dict(clip=5.0, eps=1e-2, weight_decay=a.wd, optim=optim)
+    optim = {"adam": OptimSpec("adam", eps=1e-8), "sgd": OptimSpec("sgd", momentum=0.9, nesterov=True),
+             "row-sparse-adam": OptimSpec("adam", eps=1e-8, sparse_rows=True)}.get(a.optimizer)
+    no_reg = "_embedding" if (a.optimizer == "row-sparse-adam" and a.wd) else None  # (row-sparse Adam: the L2 term leaves the tables out)
+    kw = dict(clip=5.0, eps=1e-2, weight_decay=a.wd, no_reg_param_name=no_reg, optim=optim)
     plain = DataParallelStep(eng, choice, a.B, graph=None, **kw)  # (no process group yet: the plain step)
     s = socket.socket()
     s.bind(("127.0.0.1", 0))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Cost of the optimizer choice (`--optimizer adagrad | adam | sgd`, main_train.py:150-160) on the bench cfg-2 network: the Criteo
-best-1shot sub-network, full tables (33.76 M rows), batch 256, clip 5.0; Adagrad(eps 1e-2), Adam(eps 1e-8), SGD(momentum 0.9,
-Nesterov).  Prints one JSON line per measured (route, optimizer, wd):
+"""Cost of the optimizer choice (`--optimizer adagrad | adam | sgd | row-sparse-adam`, main_train.py:150-160) on the bench cfg-2 network:
+the Criteo best-1shot sub-network, full tables (33.76 M rows), batch 256, clip 5.0; Adagrad(eps 1e-2), Adam(eps 1e-8), SGD(momentum 0.9,
+Nesterov), row-sparse Adam (Adam's lr and eps; with --wd the L2 term leaves the tables out, as the optimizer requires).  Prints one JSON line per measured (route, optimizer, wd):
 
     python tools/optim_step_bench.py --route fused --optimizer adam --wd 0     # the fused engine step
     python tools/optim_step_bench.py --route torch --optimizer adam --wd 0     # forward / autograd / clip_grad_norm_ / torch.optim
@@ -20,13 +20,13 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-LR = {"adagrad": 1e-3, "adam": 1e-3, "sgd": 1e-3}
+LR = {"adagrad": 1e-3, "adam": 1e-3, "sgd": 1e-3, "row-sparse-adam": 1e-3}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--route", choices=["fused", "torch"], default="fused")
-    ap.add_argument("--optimizer", choices=["adagrad", "adam", "sgd"], default="adam")
+    ap.add_argument("--optimizer", choices=["adagrad", "adam", "sgd", "row-sparse-adam"], default="adam")
     ap.add_argument("--wd", type=float, default=0.0)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
@@ -45,7 +45,7 @@ def main():
         return
     if a.all:
         for route in ("fused", "torch"):
-            for opt in ("adagrad", "adam", "sgd"):
+            for opt in ("adagrad", "adam", "sgd", "row-sparse-adam"):
                 for wd in (0.0, 1e-8):
                     steps = a.steps if route == "fused" else min(a.steps, 20)
                     cmd = [sys.executable, os.path.abspath(__file__), "--route", route, "--optimizer", opt, "--wd", str(wd), "--steps", str(steps),
@@ -75,6 +75,7 @@ def main():
     lr = LR[a.optimizer]
     opt = MT.build_optimizer(a.optimizer, m, lr)
     spec = OptimSpec.from_optimizer(opt) if a.optimizer != "adagrad" else None
+    no_reg = "_embedding" if (a.optimizer == "row-sparse-adam" and a.wd) else None
     loss_fn = torch.nn.BCEWithLogitsLoss()
     if a.route == "fused":
         m.engine_bind_optimizer(opt)
@@ -83,14 +84,16 @@ def main():
         int_x, cat_x, y = batches[i % len(batches)]
         if a.route == "fused":
             if spec is not None:
-                m.engine_train_step(int_x, cat_x, y.view(-1), lr=lr, clip=5.0, weight_decay=a.wd, optim=spec)
+                m.engine_train_step(int_x, cat_x, y.view(-1), lr=lr, clip=5.0, weight_decay=a.wd, no_reg_param_name=no_reg, optim=spec)
             else:
                 m.engine_train_step(int_x, cat_x, y.view(-1), lr=lr, clip=5.0, eps=1e-2, weight_decay=a.wd)
             return
         opt.zero_grad()
-        loss = loss_fn(m(int_x, cat_x), y.view(-1, 1)) + get_l2_loss(m, a.wd, None, gpu=0)
+        loss = loss_fn(m(int_x, cat_x), y.view(-1, 1)) + get_l2_loss(m, a.wd, no_reg, gpu=0)
         loss.backward()
         torch.nn.utils.clip_grad_norm_(m.parameters(), 5.0)
+        if hasattr(opt, "touch"):
+            opt.touch(cat_x)
         opt.step()
 
     for i in range(a.warmup):
