@@ -180,7 +180,7 @@ def test_balanced_schedule_is_refused_where_it_does_not_apply(lib, sk_ws):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# token-axis Linear at large batch (csrc/token_linear.hip): weights in LDS, a wavefront per sample
+# token-axis Linear at large batch (csrc/token_linear.hip, its body in csrc/token_linear_common.h): weights in LDS, a wavefront per sample
 # ---------------------------------------------------------------------------------------------------------------------------------
 def _tok_desc(am, segs, zmode, **kw):
     d = L.GemmDesc()

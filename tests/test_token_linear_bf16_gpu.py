@@ -1,9 +1,15 @@
-"""The bf16 bodies of the large-batch token-axis kernels (csrc/token_linear_bf16.hip: token_linear_bf16_kernel at
-nasrec_gemm_desc_t.precision = MEDIUM, token_dw_bf16_kernel at HIGH / MEDIUM) through the C-ABI, held to the arithmetic contract of
-DESIGN.md "Matmul precision":
+"""The large-batch token-axis kernels at every matmul precision through the C-ABI.  One body each for the forward / input-gradient
+kernel and the weight gradient (csrc/token_linear_common.h: token_linear_body, token_dw_body), entered with the fp32 products
+(csrc/token_linear.hip: token_linear_kernel, token_dw_kernel — HIGHEST, what every default run uses) or the bf16 products
+(csrc/token_linear_bf16.hip: token_linear_bf16_kernel at nasrec_gemm_desc_t.precision = MEDIUM, token_dw_bf16_kernel at HIGH / MEDIUM),
+held to the arithmetic contract of DESIGN.md "Matmul precision":
 
+    HIGHEST |C - sum_k a b| <= (Kt + 8) u S,                   S = sum_k |a| |b|
     MEDIUM  |C - sum_k â b̂| <= (Kt + 8) u S,                  S = sum_k |â| |b̂|
     HIGH    |C - sum_k a b| <= (2^-16 + (3 Kt + 8) u) S,       S = sum_k |a| |b|
+
+(HIGHEST: an fp32 FMA chain of Kt terms with unit roundoff 2^-24 stays within Kt 2^-23 S; the + 8 is the allowance for the epilogue
+and the second pass, as at MEDIUM)
 
 with â = bf16(a) (round to nearest even), u = 2^-23, Kt the total k of the product, everything on the right in fp64; an fp32 term t
 the epilogue adds (bias, the accumulation target) widens the bound by 8 u |t|.  Exact-integer products (|W| <= 2, |x| <= 3, integer
@@ -11,10 +17,11 @@ bias; dW: |dz|, |x| <= 2, every sum < 2^24) need no tolerance and catch any frag
 
 Shapes: B = 1024 (the routes' minimum) and 1031 (a ragged last workgroup); M over every row-block count and its edges; K segments
 with ragged k-steps and ragged 32-k chunks, [32] and [33] (a chunk exactly full / one k over), and the > 64 KB LDS image at M = 64.
+Weight gradient: 45 x 73 (3 x 5 blocks of 16) and 72 x 73 (5 x 5 blocks: the instantiation at the register limit).
 
 The forward / input-gradient kernel has no HIGH body: measured, it was slower than the fp32 kernel on one of the launches of
-DESIGN.md's table, so HIGH keeps the fp32 body there and its cases left with the kernel (the fp32 body's own tests are in
-tests/test_gemm_fast_gpu.py); test_high_keeps_the_fp32_body_of_the_forward_kernel pins that."""
+DESIGN.md's table, so HIGH keeps the fp32 products there and its cases left with the kernel (further cases of the fp32 kernels, at a
+flat tolerance, are in tests/test_gemm_fast_gpu.py); test_high_keeps_the_fp32_body_of_the_forward_kernel pins that."""
 import ctypes as C
 
 import pytest
@@ -25,19 +32,19 @@ from nasrec_amd import plan as P
 
 pytestmark = pytest.mark.gpu
 
-PRECISIONS = [L.PRECISION_HIGH, L.PRECISION_MEDIUM]  # of token_dw_bf16_kernel
-LINEAR_PRECISIONS = [L.PRECISION_MEDIUM]             # of token_linear_bf16_kernel
+PRECISIONS = [L.PRECISION_HIGHEST, L.PRECISION_HIGH, L.PRECISION_MEDIUM]  # token_dw_kernel; token_dw_bf16_kernel
+LINEAR_PRECISIONS = [L.PRECISION_HIGHEST, L.PRECISION_MEDIUM]             # token_linear_kernel; token_linear_bf16_kernel
 U = 2.0 ** -23
 K3 = [26, 72, 9]
 KBIG = [72, 72, 72, 72, 21]  # at M = 64: 99 KB of staged weights (> the default dynamic-LDS limit)
 
 
 def _coef(prec, Kt):
-    return (Kt + 8) * U if prec == L.PRECISION_MEDIUM else 2.0 ** -16 + (3 * Kt + 8) * U
+    return 2.0 ** -16 + (3 * Kt + 8) * U if prec == L.PRECISION_HIGH else (Kt + 8) * U
 
 
 def _seen(prec, t):
-    """the operand as the product sees it, in fp64: bf16-rounded for MEDIUM, itself for HIGH"""
+    """the operand as the product sees it, in fp64: bf16-rounded for MEDIUM, itself for HIGH and HIGHEST"""
     return t.bfloat16().double() if prec == L.PRECISION_MEDIUM else t.double()
 
 
@@ -85,7 +92,8 @@ def _tok_desc(am, segs, zmode, prec, **kw):
             setattr(d.seg[q], k, v)
         d.seg[q].Mvalid = sd["M"]
     d.precision = prec
-    assert P.gemm_kernel_name(d) == "token_linear_bf16_kernel", "the case must be sized for the token-axis kernel"
+    name = "token_linear_bf16_kernel" if prec == L.PRECISION_MEDIUM else "token_linear_kernel"
+    assert P.gemm_kernel_name(d) == name, "the case must be sized for the token-axis kernel"
     return d
 
 
@@ -278,8 +286,7 @@ def test_input_gradient_batch(lib, prec, integers):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # weight gradient: dW[n', n] = sum_{b,e} dz[b, n', e] x[b, n, e], S workgroups per problem -> S slabs -> the fixed-order second pass
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _dw(lib, prec, B, S, integers):
-    nout, kd, widths = 45, 40, [72, 26, 9, 72]
+def _dw(lib, prec, B, S, nout, kd, widths, integers):
     Ntot = sum(widths)
     if integers:
         dz, dW = _ints(-2, 2, B, nout + 2, 16), _ints(-3, 3, nout, Ntot)
@@ -293,7 +300,7 @@ def _dw(lib, prec, B, S, integers):
     for q, w in enumerate(widths):
         slab = _ints(-2, 2, B, w + 4, 16) if integers else _rand(B, w + 4, 16)
         slabs.append(slab)
-        ones, acc = int(q == 0), int(q == 3)
+        ones, acc = int(q == 0), int(q == len(widths) - 1)
         segs.append(dict(A=dz.data_ptr() + 4 * 16, B=slab.data_ptr() + 4 * 3 * 16, C=dW.data_ptr() + 4 * koff, M=nout, N=w + ones, K=B * 16,
                          lda=dz.stride(0), ldb=slab.stride(0), ldc=Ntot, Mvalid=kd, accumulate=acc, ones_col=ones, rowsum=db.data_ptr() if ones else None))
         xs = _seen(prec, slab[:, 3:3 + w])
@@ -308,10 +315,11 @@ def _dw(lib, prec, B, S, integers):
     for q, sd in enumerate(segs):
         for k, v in sd.items():
             setattr(d.seg[q], k, v)
-    ws = torch.full((S * nout * 73 * len(segs),), float("nan"), device="cuda")
+    ws = torch.full((S * nout * (max(widths) + 1) * len(segs),), float("nan"), device="cuda")
     d.splitk, d.workspace = S, ws.data_ptr()
     d.precision = prec
-    assert P.gemm_route(d)[0] == L.GEMM_ROUTE_TOKEN_DW and P.gemm_kernel_name(d) == "token_dw_bf16_kernel"
+    name = "token_dw_kernel" if prec == L.PRECISION_HIGHEST else "token_dw_bf16_kernel"
+    assert P.gemm_route(d)[0] == L.GEMM_ROUTE_TOKEN_DW and P.gemm_kernel_name(d) == name
     _launch(lib, d)
 
     def again():
@@ -323,14 +331,18 @@ def _dw(lib, prec, B, S, integers):
     return dW, db, checks, g.sum((0, 2)), _coef(prec, B * 16) * g.abs().sum((0, 2)), again, (dz, slabs)
 
 
-DW_SHAPES = [(1024, 4), (1280, 8), (1280, 37)]  # the smallest launch the family takes; the shapes of the fp32 test
+# (B, S, nout, kd, widths).  45 x (72 + ones column): 3 x 5 blocks — the smallest launch the family takes, then the shapes of the fp32
+# test; 72 x (72 + ones column): 5 x 5 blocks (integer sums <= 1024 * 16 * 4)
+DW45 = (45, 40, [72, 26, 9, 72])
+DW_SHAPES = [pytest.param(1024, 4, *DW45, id="1024-4"), pytest.param(1280, 8, *DW45, id="1280-8"), pytest.param(1280, 37, *DW45, id="1280-37"),
+             pytest.param(1024, 4, 72, 64, [72, 72], id="1024-4-5x5")]
 
 
 @pytest.mark.parametrize("prec", PRECISIONS)
-@pytest.mark.parametrize("B,S", DW_SHAPES)
-def test_weight_gradient_integer_products_are_exact(lib, prec, B, S):
+@pytest.mark.parametrize("B,S,nout,kd,widths", DW_SHAPES)
+def test_weight_gradient_integer_products_are_exact(lib, prec, B, S, nout, kd, widths):
     torch.manual_seed(29)
-    dW, db, checks, db_want, _, _, _keep = _dw(lib, prec, B, S, integers=True)
+    dW, db, checks, db_want, _, _, _keep = _dw(lib, prec, B, S, nout, kd, widths, integers=True)
     for koff, w, want, _ in checks:
         assert float(want.abs().max()) < 2 ** 24
         assert torch.equal(dW[:, koff:koff + w].double(), want), "columns %d..%d" % (koff, koff + w)
@@ -338,10 +350,10 @@ def test_weight_gradient_integer_products_are_exact(lib, prec, B, S):
 
 
 @pytest.mark.parametrize("prec", PRECISIONS)
-@pytest.mark.parametrize("B,S", DW_SHAPES)
-def test_weight_gradient_within_the_derived_bound(lib, prec, B, S):
+@pytest.mark.parametrize("B,S,nout,kd,widths", DW_SHAPES)
+def test_weight_gradient_within_the_derived_bound(lib, prec, B, S, nout, kd, widths):
     torch.manual_seed(30)
-    dW, db, checks, db_want, db_bound, again, _keep = _dw(lib, prec, B, S, integers=False)
+    dW, db, checks, db_want, db_bound, again, _keep = _dw(lib, prec, B, S, nout, kd, widths, integers=False)
     for koff, w, want, bound in checks:
         _within(dW[:, koff:koff + w], want, bound, "dW columns %d..%d B=%d S=%d prec=%d" % (koff, koff + w, B, S, prec))
     _within(db, db_want, db_bound, "bias gradient (ones column) B=%d S=%d prec=%d" % (B, S, prec))

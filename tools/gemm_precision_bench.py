@@ -130,7 +130,8 @@ def main():
               ("DX", 4096, 1024, 1024), ("DW", 1024, 1024, 4096)]
     # (kind, B, M, Ks): launches of the config-3 step (B = 4096) and one of config 5's (B = 8192, about 10 tokens)
     token_shapes = [("TF", 4096, 64, [72, 72, 72, 72]), ("TF", 4096, 45, [26, 72, 72]), ("TDX", 4096, 72, [64] * 4), ("TDW", 4096, 64, [72] * 8),
-                    ("TF", 8192, 10, [10, 10])]
+                    ("TF", 8192, 10, [10, 10]),
+                    ("TDW", 4096, 72, [72] * 8)]  # 5 x 5 blocks of 16: the token_dw instantiations at the register limit
     lines = ["# %s, one process, %d alternating rounds of %d launches per mode after a clock-settling warm-up; median window (min .. max)"
              % (torch.cuda.get_device_name(dev), ROUNDS, ITERS),
              "# binding F: y = x W^T (KC/KC), DX: dx = dy W (KC/RC), DW: dW = dy^T x (RC/RC); TF = 2 M N K / time; speed-up against `highest` of the same run",
