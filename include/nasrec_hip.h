@@ -92,7 +92,7 @@ enum {
 };
 
 /* algorithm of NASREC_OP_OPT_MOMENTS (ADAGRAD: NASREC_OP_LAST_LAYER_STEP only) */
-enum { NASREC_OPTIM_ADAGRAD = 0, NASREC_OPTIM_ADAM = 1, NASREC_OPTIM_SGD = 2 };
+enum { NASREC_OPTIM_ADAGRAD = 0, NASREC_OPTIM_ADAM = 1, NASREC_OPTIM_SGD = 2, NASREC_OPTIM_RMSPROP = 3 };
 
 /* ------------------------------------------------------------------------------------------------
  * GEMM family.  C(i,j) = epilogue( sum_k A(i,k) * B(j,k) ).   Replaces every nn.Linear / LazyLinear
@@ -539,11 +539,26 @@ typedef struct nasrec_weight_decay_desc {
  * Phase 0 does not mark `bitmap`, and every other row of table / tm / tv keeps its bits.  With n_zero == 0 there is no phase 1: the
  * workgroup of phase 0 that finishes last adds 1 to step[inc[i]] (every workgroup has read its counters by then) and leaves
  * `counter` zero.  With n_zero > 0 phase 0 does not count, and phase 1 runs as above with tile_off all zero (no table row moves).
+ *
+ * algo = NASREC_OPTIM_RMSPROP: torch.optim.RMSprop(lr, alpha, eps) with momentum 0, not centered, on every element, the tables' rows
+ * decayed lazily.  alpha travels in `beta2` (beta1, momentum and nesterov are unused; momentum must be 0); v / tv hold square_avg, m is
+ * unused, and the slots of `tm` carry the per-row stamps instead (`stamp`, the same storage: the structure does not grow): stamp[f][row]
+ * = the step count of table f at which v of that row is current, one 32-bit word per row.  Per element, g = the clipped gradient:
+ *   v = v alpha;  v = v + (1 - alpha) g^2;  p = p - lr g / (sqrt(v) + eps)
+ * A row with a zero gradient does not move, and its v only decays by alpha per step: that factor is paid when the row is next touched.
+ *   phase 0: clip and dense chunks as above (over p / g / v).  A leader row of table f with its id in range: t = step[table_step0 + f]
+ *     + 1, n = t - 1 - stamp[f][row]; n > 0: v_row = (float)((double)v_row * pow(alpha, n)) (one rounding; n = 0 skips the multiply, so
+ *     the bits are the dense statements'); then the three statements with g = the summed gradient * coef, and stamp[f][row] = t.  No
+ *     bit is marked; every other row keeps its bits in table, tv and stamp.  Steps are counted as with sparse_rows: by the workgroup
+ *     of phase 0 that finishes last when n_zero == 0, else by phase 1, which runs with tile_off all zero.
+ *   phase 2 (flush; RMSprop only): every row of every table, in the tiles of tile_off (here over ALL tables; `bitmap` all zero, read
+ *     only): n = step[table_step0 + f] - stamp; n > 0: v_row *= alpha^n as above and stamp = step.  Idempotent.  nblocks workgroups.
+ * Refused (-1, nothing launched): stamps missing, momentum != 0, sparse_rows != 0, a table owning a tile in phase 1.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct nasrec_opt_moments_desc {
   int32_t kind;  /* NASREC_OP_OPT_MOMENTS */
-  int32_t phase; /* 0 / 1 (above) */
-  int32_t algo;  /* NASREC_OPTIM_ADAM / NASREC_OPTIM_SGD */
+  int32_t phase; /* 0 / 1 (above); 2 = RMSprop's flush */
+  int32_t algo;  /* NASREC_OPTIM_ADAM / NASREC_OPTIM_SGD / NASREC_OPTIM_RMSPROP */
   int32_t nesterov;
   int32_t dense_blocks; /* phase 0: workgroups on the dense chunks */
   int32_t nblocks;      /* phase 1: workgroups */
@@ -563,7 +578,10 @@ typedef struct nasrec_opt_moments_desc {
   const int32_t* leader; /* [B,Fs] */
   const float* gsum;     /* [B,Fs,16] (layout: rank_B below): a leader's row holds its summed gradient */
   float* table[NASREC_MAX_TABLES];
-  float* tm[NASREC_MAX_TABLES];
+  union {
+    float* tm[NASREC_MAX_TABLES];
+    uint32_t* stamp[NASREC_MAX_TABLES]; /* NASREC_OPTIM_RMSPROP: per-row stamps (above); that algorithm has no first moment */
+  };
   float* tv[NASREC_MAX_TABLES];
   int64_t rows[NASREC_MAX_TABLES];
   int64_t tile_off[NASREC_MAX_TABLES + 1];

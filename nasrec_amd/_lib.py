@@ -38,7 +38,7 @@ OP_WORKLIST_DEV = 38  # (37: a layout-check slot of nasrec_desc_sizes)
 OP_WEIGHT_DECAY = 39
 OP_OPT_MOMENTS = 40
 OP_LAST_LAYER_STEP = 41
-OPTIM_ADAGRAD, OPTIM_ADAM, OPTIM_SGD = 0, 1, 2  # NASREC_OPTIM_* (algorithm of NASREC_OP_OPT_MOMENTS / _LAST_LAYER_STEP)
+OPTIM_ADAGRAD, OPTIM_ADAM, OPTIM_SGD, OPTIM_RMSPROP = 0, 1, 2, 3  # NASREC_OPTIM_* (algorithm of NASREC_OP_OPT_MOMENTS / _LAST_LAYER_STEP)
 LAST_LAYER_MAX = 8192  # NASREC_LAST_LAYER_MAX: K + 1 of NASREC_OP_LAST_LAYER_STEP
 OP_ROC_AUC = 42
 ROC_AUC_MAX_N = 1 << 30  # NASREC_ROC_AUC_MAX_N
@@ -263,6 +263,7 @@ class WeightDecayDesc(C.Structure):
 
 
 class OptMomentsDesc(C.Structure):
+    # (OPTIM_RMSPROP keeps no first moment: the slots of `tm` carry its per-row stamps, `stamp` in the header's union, and beta2 its alpha)
     _fields_ = [("kind", i32), ("phase", i32), ("algo", i32), ("nesterov", i32), ("dense_blocks", i32), ("nblocks", i32), ("B", i32),
                 ("Fs", i32), ("table_step0", i32), ("reg_mask", C.c_uint32), ("eps", f32), ("momentum", f32), ("wd", f32), ("_pad", f32),
                 ("beta1", C.c_double), ("beta2", C.c_double), ("clip", ClipCoefDesc), ("chunks", vp), ("nchunks", i64), ("p", vp),

@@ -5,20 +5,29 @@
 // in the workgroup that finishes last, counts the step of every parameter it updated.
 // Row-sparse Adam (sparse_rows, include/nasrec_hip.h) is a phase 0 of its own, opt_moments_sparse_phase0_kernel: the same clip and dense
 // chunks, torch.optim.SparseAdam on the touched rows, no bitmap, and no phase 1 unless weight decay has gradients to restore.
+// RMSprop (NASREC_OPTIM_RMSPROP: momentum 0, not centered) has a phase 0 of its own too, opt_moments_rmsprop_phase0_kernel: a row whose
+// gradient is zero does not move and its square_avg only decays, so the touched rows pay the decay they owe (per-row stamps) and take
+// torch.optim.RMSprop's update; opt_moments_flush_kernel (phase 2) brings every row's square_avg current for whoever reads the state.
 #include "optimizer_bodies.h"
 
 namespace {
+
+// which moment arrays an algorithm keeps: m = exp_avg / momentum_buffer (not RMSprop), v = exp_avg_sq / square_avg (not SGD)
+template <int ALGO>
+constexpr bool HAS_M = ALGO != NASREC_OPTIM_RMSPROP;
+template <int ALGO>
+constexpr bool HAS_V = ALGO != NASREC_OPTIM_SGD;
 
 template <int ALGO>
 __device__ __forceinline__ void moments_vec(const nasrec_opt_moments_desc_t& d, const f32x4& g, f32x4& p, f32x4& m, f32x4& v, float lr,
                                             float ss, float bs) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    float pe = p[e], me = m[e], ve = ALGO == NASREC_OPTIM_ADAM ? v[e] : 0.f;
+    float pe = p[e], me = HAS_M<ALGO> ? m[e] : 0.f, ve = HAS_V<ALGO> ? v[e] : 0.f;
     moments_elem<ALGO>(d, g[e], pe, me, ve, lr, ss, bs);
     p[e] = pe;
-    m[e] = me;
-    if (ALGO == NASREC_OPTIM_ADAM) v[e] = ve;
+    if (HAS_M<ALGO>) m[e] = me;
+    if (HAS_V<ALGO>) v[e] = ve;
   }
 }
 
@@ -55,25 +64,26 @@ __device__ __forceinline__ void dense_chunks(const nasrec_opt_moments_desc_t& d,
     float ss = 0.f, bs = 1.f;
     if (ALGO == NASREC_OPTIM_ADAM) adam_scalars(d, d.step[k], lr, ss, bs);
     float* pp = d.p + off;
-    float* mp = d.m + off;
-    float* vp = ALGO == NASREC_OPTIM_ADAM ? d.v + off : nullptr;
+    float* mp = HAS_M<ALGO> ? d.m + off : nullptr;
+    float* vp = HAS_V<ALGO> ? d.v + off : nullptr;
     const float* gp = d.g + off;
     for (long i = tid; i < n4; i += 256) {
       f32x4 g4 = *reinterpret_cast<const f32x4*>(gp + 4 * i);
-      f32x4 p4 = *reinterpret_cast<const f32x4*>(pp + 4 * i), m4 = *reinterpret_cast<const f32x4*>(mp + 4 * i), v4 = {};
-      if (ALGO == NASREC_OPTIM_ADAM) v4 = *reinterpret_cast<const f32x4*>(vp + 4 * i);
+      f32x4 p4 = *reinterpret_cast<const f32x4*>(pp + 4 * i), m4 = {}, v4 = {};
+      if (HAS_M<ALGO>) m4 = *reinterpret_cast<const f32x4*>(mp + 4 * i);
+      if (HAS_V<ALGO>) v4 = *reinterpret_cast<const f32x4*>(vp + 4 * i);
       g4 *= coef;
       moments_vec<ALGO>(d, g4, p4, m4, v4, lr, ss, bs);
       *reinterpret_cast<f32x4*>(pp + 4 * i) = p4;
-      *reinterpret_cast<f32x4*>(mp + 4 * i) = m4;
-      if (ALGO == NASREC_OPTIM_ADAM) *reinterpret_cast<f32x4*>(vp + 4 * i) = v4;
+      if (HAS_M<ALGO>) *reinterpret_cast<f32x4*>(mp + 4 * i) = m4;
+      if (HAS_V<ALGO>) *reinterpret_cast<f32x4*>(vp + 4 * i) = v4;
     }
     for (long j = 4 * n4 + tid; j < n; j += 256) {
-      float pe = pp[j], me = mp[j], ve = ALGO == NASREC_OPTIM_ADAM ? vp[j] : 0.f;
+      float pe = pp[j], me = HAS_M<ALGO> ? mp[j] : 0.f, ve = HAS_V<ALGO> ? vp[j] : 0.f;
       moments_elem<ALGO>(d, gp[j] * coef, pe, me, ve, lr, ss, bs);
       pp[j] = pe;
-      mp[j] = me;
-      if (ALGO == NASREC_OPTIM_ADAM) vp[j] = ve;
+      if (HAS_M<ALGO>) mp[j] = me;
+      if (HAS_V<ALGO>) vp[j] = ve;
     }
   }
 }
@@ -170,6 +180,84 @@ __global__ __launch_bounds__(256) void opt_moments_sparse_phase0_kernel(const na
   if (tid == 0) *d.counter = 0u;
 }
 
+// RMSprop's phase 0: clip and dense chunks as above (p / g / v); a touched row first pays the decay its square_avg owes since its stamp
+// (lazy_decay, optimizer_bodies.h), then takes torch.optim.RMSprop's update with its summed gradient, and is stamped with this step; no
+// bit is marked.  The four lanes of a row read its stamp before lane 0 writes it: they sit in one wavefront, and the store follows the
+// loads in program order.  Steps are counted as in opt_moments_sparse_phase0_kernel.
+__global__ __launch_bounds__(256) void opt_moments_rmsprop_phase0_kernel(const nasrec_opt_moments_desc_t d) {
+  __shared__ float sh_coef;
+  __shared__ int last;
+  const int tid = threadIdx.x, blk = blockIdx.x;
+  const float lr = *d.lr;
+  clip_head(d, &sh_coef);
+  __syncthreads();
+  const float coef = sh_coef;
+  if (blk < d.dense_blocks) {
+    dense_chunks<NASREC_OPTIM_RMSPROP>(d, coef, lr);
+  } else {
+    // touched rows: 4 lanes x float4 per (sample, field) pair; the leader of a row id carries the row's summed gradient
+    const long t = (long)(blk - d.dense_blocks) * 256 + tid;
+    const long pair = t >> 2;
+    const int q = (int)(t & 3);
+    if (pair < (long)d.B * d.Fs && d.leader[pair]) {
+      const int f = (int)(pair % d.Fs);
+      const long row = d.idx[pair];
+      if (row >= 0 && row < d.rows[f]) {  // (flagged by the gather; never written outside a table)
+        const long o = row * 16 + q * 4;
+        const long step = (long)d.step[d.table_step0 + f] + 1;
+        const long n = step - 1 - (long)d.stamp[f][row];
+        f32x4 g4 = *reinterpret_cast<const f32x4*>(d.gsum + gsum_row_offset(pair, d.Fs, d.rank_B, d.rank_stride) + q * 4);
+        f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o), v4 = *reinterpret_cast<const f32x4*>(d.tv[f] + o), m4 = {};
+        g4 *= coef;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v4[e] = lazy_decay(v4[e], d.beta2, n);
+        moments_vec<NASREC_OPTIM_RMSPROP>(d, g4, p4, m4, v4, lr, 0.f, 1.f);
+        *reinterpret_cast<f32x4*>(d.table[f] + o) = p4;
+        *reinterpret_cast<f32x4*>(d.tv[f] + o) = v4;
+        if (q == 0) d.stamp[f][row] = (uint32_t)step;
+      }
+    }
+  }
+  if (d.n_zero > 0) return;  // (phase 1 restores g over zero_chunks and counts)
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence();
+    last = atomicAdd(d.counter, 1u) == gridDim.x - 1u;
+  }
+  __syncthreads();
+  if (!last) return;
+  __threadfence();
+  for (long i = tid; i < d.n_inc; i += 256) d.step[d.inc[i]] += 1.f;
+  if (tid == 0) *d.counter = 0u;
+}
+
+// RMSprop's flush (phase 2): every row of every table whose stamp lies behind its table's step count pays the decay it owes and is
+// stamped current; a second flush finds nothing to do.  The bitmap is all zero and only read (untouched_rows_pass hands over every row).
+struct FlushRows {
+  const nasrec_opt_moments_desc_t& d;
+  long n[TABLE_PASS_UNROLL];
+  uint32_t now[TABLE_PASS_UNROLL];
+  f32x4 v[TABLE_PASS_UNROLL];
+  __device__ __forceinline__ void load(int u, int f, long off) {
+    now[u] = (uint32_t)d.step[d.table_step0 + f];
+    n[u] = (long)now[u] - (long)d.stamp[f][off >> 4];
+    if (n[u] > 0) v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(d.tv[f] + off));
+  }
+  __device__ __forceinline__ void update(int u, int f, long off) {
+    if (n[u] <= 0) return;
+    const double k = pow(d.beta2, (double)n[u]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[u][e] = (float)((double)v[u][e] * k);
+    __builtin_nontemporal_store(v[u], reinterpret_cast<f32x4*>(d.tv[f] + off));
+    if ((off & 15) == 0) d.stamp[f][off >> 4] = now[u];
+  }
+};
+
+__global__ __launch_bounds__(256) void opt_moments_flush_kernel(const nasrec_opt_moments_desc_t d) {
+  FlushRows r{d};
+  untouched_rows_pass(d.tile_off, d.rows, d.Fs, d.bitmap, blockIdx.x, d.nblocks, r);
+}
+
 // phase 1's row update: the optimizer with g = 0, or g = 2 wd W * coef on a regularised table (untouched_rows_pass, optimizer_bodies.h)
 template <int ALGO>
 struct MomentRows {
@@ -180,8 +268,8 @@ struct MomentRows {
   f32x4 w[TABLE_PASS_UNROLL], m[TABLE_PASS_UNROLL], v[TABLE_PASS_UNROLL];
   __device__ __forceinline__ void load(int u, int f, long off) {
     w[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(d.table[f] + off));
-    m[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(d.tm[f] + off));
-    if (ALGO == NASREC_OPTIM_ADAM) v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(d.tv[f] + off));
+    if (HAS_M<ALGO>) m[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(d.tm[f] + off));
+    if (HAS_V<ALGO>) v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(d.tv[f] + off));
   }
   __device__ __forceinline__ void update(int u, int f, long off) {
     f32x4 g = {0.f, 0.f, 0.f, 0.f};
@@ -191,8 +279,8 @@ struct MomentRows {
     }
     moments_vec<ALGO>(d, g, w[u], m[u], v[u], lr, ALGO == NASREC_OPTIM_ADAM ? ss[f] : 0.f, ALGO == NASREC_OPTIM_ADAM ? bs[f] : 1.f);
     __builtin_nontemporal_store(w[u], reinterpret_cast<f32x4*>(d.table[f] + off));
-    __builtin_nontemporal_store(m[u], reinterpret_cast<f32x4*>(d.tm[f] + off));
-    if (ALGO == NASREC_OPTIM_ADAM) __builtin_nontemporal_store(v[u], reinterpret_cast<f32x4*>(d.tv[f] + off));
+    if (HAS_M<ALGO>) __builtin_nontemporal_store(m[u], reinterpret_cast<f32x4*>(d.tm[f] + off));
+    if (HAS_V<ALGO>) __builtin_nontemporal_store(v[u], reinterpret_cast<f32x4*>(d.tv[f] + off));
   }
 };
 
@@ -230,10 +318,13 @@ int launch_phases(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
     const long threads = (long)d->B * d->Fs * 4;
     const int nrows = (int)((threads + 255) / 256);
     if (d->dense_blocks < 0 || d->dense_blocks + nrows < 1) return nasrec_set_error(-2, "opt_moments: empty launch");
-    if (nrows > 0 && (!d->idx || !d->leader || !d->gsum || (!d->bitmap && !d->sparse_rows))) return nasrec_set_error(-1, "opt_moments: row inputs missing");
+    if (nrows > 0 && (!d->idx || !d->leader || !d->gsum || (!d->bitmap && !d->sparse_rows && ALGO != NASREC_OPTIM_RMSPROP))) return nasrec_set_error(-1, "opt_moments: row inputs missing");
     if (d->rank_B < 0 || (d->rank_B > 0 && (d->rank_stride < (int64_t)d->rank_B * d->Fs * 16 || d->B % d->rank_B != 0)))
       return nasrec_set_error(-2, "opt_moments: rank layout %d / %ld", d->rank_B, (long)d->rank_stride);
-    if (d->sparse_rows) {
+    if constexpr (ALGO == NASREC_OPTIM_RMSPROP) {
+      if (d->n_zero <= 0 && (!d->counter || (d->n_inc > 0 && !d->inc))) return nasrec_set_error(-1, "opt_moments: RMSprop without zero_chunks counts the steps: counter / inc missing");
+      hipLaunchKernelGGL(opt_moments_rmsprop_phase0_kernel, dim3((unsigned)(d->dense_blocks + nrows)), dim3(256), 0, st, *d);
+    } else if (d->sparse_rows) {
       if (d->n_zero <= 0 && (!d->counter || (d->n_inc > 0 && !d->inc))) return nasrec_set_error(-1, "opt_moments: sparse_rows without zero_chunks counts the steps: counter / inc missing");
       hipLaunchKernelGGL(opt_moments_sparse_phase0_kernel, dim3((unsigned)(d->dense_blocks + nrows)), dim3(256), 0, st, *d);
     } else {
@@ -251,11 +342,27 @@ int launch_phases(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
   return nasrec_check_launch("opt_moments");
 }
 
+// RMSprop: what the lazily decayed rows need, checked before anything is launched; phase 2 = the flush
+int launch_rmsprop(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
+  if (d->momentum != 0.f) return nasrec_set_error(-1, "opt_moments: RMSprop with momentum %g moves untouched rows", (double)d->momentum);
+  if (d->sparse_rows) return nasrec_set_error(-1, "opt_moments: sparse_rows is row-sparse Adam (algo %d)", d->algo);
+  for (int f = 0; f < d->Fs; ++f)
+    if (!d->stamp[f] || !d->tv[f]) return nasrec_set_error(-1, "opt_moments: RMSprop without the stamps / square_avg of table %d", f);
+  if (d->phase == 1 && (d->n_zero <= 0 || d->tile_off[d->Fs] != 0))
+    return nasrec_set_error(-1, "opt_moments: RMSprop has a phase 1 only to restore zero_chunks, and no table owns a tile");
+  if (d->phase != 2) return launch_phases<NASREC_OPTIM_RMSPROP>(st, d);
+  if (d->nblocks <= 0 || !d->bitmap) return nasrec_set_error(-1, "opt_moments: flush needs nblocks > 0 and the (all-zero) bitmap");
+  if (d->tile_off[d->Fs] <= 0) return 0;
+  hipLaunchKernelGGL(opt_moments_flush_kernel, dim3((unsigned)d->nblocks), dim3(256), 0, st, *d);
+  return nasrec_check_launch("opt_moments");
+}
+
 }  // namespace
 
 int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
   if (d->Fs < 0 || d->Fs > NASREC_MAX_TABLES) return nasrec_set_error(-1, "opt_moments: Fs = %d", d->Fs);
   if (!d->lr || !d->step) return nasrec_set_error(-1, "opt_moments: lr / step missing");
+  if (d->algo == NASREC_OPTIM_RMSPROP) return launch_rmsprop(st, d);
   if (d->sparse_rows && d->algo != NASREC_OPTIM_ADAM) return nasrec_set_error(-1, "opt_moments: sparse_rows is row-sparse Adam (algo %d)", d->algo);
   if (d->algo == NASREC_OPTIM_ADAM) return launch_phases<NASREC_OPTIM_ADAM>(st, d);
   if (d->algo == NASREC_OPTIM_SGD) return launch_phases<NASREC_OPTIM_SGD>(st, d);

@@ -131,7 +131,8 @@ __device__ __forceinline__ void adam_scalars(const D& d, float step, float lr, f
 }
 
 // one element; g = the clipped gradient.  The statements follow torch's foreach calls one by one (lerp_; mul_ + addcmul_; sqrt, div_,
-// add_; addcdiv_): -ffp-contract=on fuses within a statement only.
+// add_; addcdiv_): -ffp-contract=on fuses within a statement only.  RMSprop (momentum 0, not centered; alpha travels in beta2): mul_,
+// addcmul_; sqrt, add_; addcdiv_ — m is unused.
 template <int ALGO, class D>
 __device__ __forceinline__ void moments_elem(const D& d, float g, float& p, float& m, float& v, float lr,
                                              float step_size, float bc2_sqrt) {
@@ -143,6 +144,13 @@ __device__ __forceinline__ void moments_elem(const D& d, float g, float& p, floa
     float den = sqrtf(v) / bc2_sqrt;
     den = den + d.eps;
     p = p + (-step_size) * (m / den);
+  } else if (ALGO == NASREC_OPTIM_RMSPROP) {
+    const float a = (float)d.beta2, w = (float)(1.0 - d.beta2);
+    v = v * a;
+    v = v + w * (g * g);
+    float den = sqrtf(v);
+    den = den + d.eps;
+    p = p + (-lr) * (g / den);
   } else {
     m = m * d.momentum;
     m = m + g;
@@ -177,6 +185,12 @@ __device__ __forceinline__ void sparse_adam_elem(const D& d, float g, float& p, 
   float u = m / den;
   u = (-step_size) * u;
   p = p + u;
+}
+
+// RMSprop's lazily decayed table rows: a row whose gradient was zero for n steps owes its square_avg the factor alpha^n; power and
+// product in fp64, rounded once (n = 0: v as it is, so a row touched every step has the bits of the dense statements)
+__device__ __forceinline__ float lazy_decay(float v, double alpha, long n) {
+  return n > 0 ? (float)((double)v * pow(alpha, (double)n)) : v;
 }
 
 __device__ __forceinline__ void adagrad_dense_body(const nasrec_adagrad_dense_desc_t& d, int blk, int nblk, float lr, float coef) {

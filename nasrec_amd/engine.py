@@ -826,13 +826,17 @@ class SupernetEngine:
     def ensure_moments_state(self, kind: str):
         """Adam's exp_avg / exp_avg_sq or SGD's momentum_buffer for the dense arena (flat, the layout of flat_p) and for every table,
         allocated on first use, zero; and the per-parameter step counters (dense parameters in dense_names order, then the tables).
+        "rmsprop": square_avg, and `lazy_stamps` — per table one int32 per row, the table's step count at which that row's square_avg
+        is current (csrc/optim_moments.hip); engine-private, never part of optimizer.state.
         -> {state key: (flat arena, [table arrays])}"""
-        keys = ("exp_avg", "exp_avg_sq") if kind == "adam" else ("momentum_buffer",)
+        keys = {"adam": ("exp_avg", "exp_avg_sq"), "rmsprop": ("square_avg",)}.get(kind, ("momentum_buffer",))
         st = self.__dict__.setdefault("moments", {})
         with torch.cuda.stream(self.stream):
             for k in keys:
                 if k not in st:
                     st[k] = (torch.zeros(self.flat_numel, dtype=torch.float32, device=self.device), [torch.zeros_like(t) for t in self.tables])
+            if kind == "rmsprop" and getattr(self, "lazy_stamps", None) is None:
+                self.lazy_stamps = [torch.zeros(n, dtype=torch.int32, device=self.device) for n in self.num_embeddings]
             if getattr(self, "opt_steps", None) is None:
                 self.opt_steps = torch.zeros(len(self.dense_names) + self.Fs, dtype=torch.float32, device=self.device)
                 self._mom_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -850,6 +854,33 @@ class SupernetEngine:
         o, n = self.offsets[name], self.params[name].numel()
         return flat[o:o + n].view(self.params[name].shape)
 
+    def _flush_desc(self):
+        """RMSprop's flush launch (phase 2): every row of every table, in 64-row tiles"""
+        m = L.OptMomentsDesc()
+        m.kind, m.phase, m.algo = L.OP_OPT_MOMENTS, 2, L.OPTIM_RMSPROP
+        m.nblocks, m.Fs, m.table_step0 = self.WD_BLOCKS, self.Fs, len(self.dense_names)
+        m.beta2 = self._lazy_alpha
+        tile = 0
+        for f in range(self.Fs):
+            m.table[f], m.rows[f] = self.tables[f].data_ptr(), self.num_embeddings[f]
+            m.tv[f], m.tm[f] = self.moments["square_avg"][1][f].data_ptr(), self.lazy_stamps[f].data_ptr()
+            m.tile_off[f] = tile
+            tile += (self.num_embeddings[f] + 63) // 64
+        m.tile_off[self.Fs] = tile
+        m.bitmap = self._row_bitmap().data_ptr()
+        m.step, m.lr = self.opt_steps.data_ptr(), self.lr_dev.data_ptr()
+        return m
+
+    def flush_lazy_rows(self):
+        """RMSprop: bring square_avg of every table row current (a row outside the batches owes it alpha^n since its stamp) — what a
+        reader of the state needs: optimizer.state_dict(), a torch step on the aliased state, the broadcast to replicas.  One streaming
+        launch on the engine's stream, waited for; a no-op before the first RMSprop plan and when nothing is owed."""
+        if getattr(self, "lazy_stamps", None) is None or getattr(self, "_lazy_alpha", None) is None:
+            return
+        m = self._flush_desc()
+        L.check(L.load().nasrec_opt_moments(self.stream.cuda_stream, C.addressof(m)))
+        self.stream.synchronize()  # (the reader may sit on another stream)
+
     MOM_CHUNK = 1024  # elements per dense chunk of the Adam / SGD launch (one parameter per chunk)
 
     def _moments_tables(self, cp, ctx, arena, pre):
@@ -862,6 +893,9 @@ class SupernetEngine:
             raise L.EngineError("Adam / SGD in the fused step need the embedding tables on the device")
         t = cp.tail
         spec = t.spec
+        if spec.kind == "rmsprop" and spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
+            raise L.EngineError("lazy RMSprop with a regularised table: the L2 term puts a gradient on every row; leave the tables out "
+                                "(no_reg_param_name='_embedding') or use weight_decay=0")
         if spec.sparse_rows and spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
             raise L.EngineError("row-sparse Adam with a regularised table: the L2 term puts a gradient on every row; leave the tables out "
                                 "(no_reg_param_name='_embedding') or use weight_decay=0")
@@ -888,32 +922,38 @@ class SupernetEngine:
     @staticmethod
     def _optim_scalars(d, spec):
         """algo and hyperparameters of an Adam / SGD spec on an OptMomentsDesc or a LastLayerStepDesc"""
-        d.algo = L.OPTIM_ADAM if spec.kind == "adam" else L.OPTIM_SGD
+        d.algo = {"adam": L.OPTIM_ADAM, "rmsprop": L.OPTIM_RMSPROP}.get(spec.kind, L.OPTIM_SGD)
         d.eps, d.momentum, d.nesterov = spec.eps, spec.momentum, int(bool(spec.nesterov))
-        d.beta1, d.beta2 = spec.beta1, spec.beta2
+        d.beta1, d.beta2 = spec.beta1, (spec.alpha if spec.kind == "rmsprop" else spec.beta2)  # (RMSprop's alpha travels in beta2)
 
     def _moments_descs(self, t, Bg, cat_x, gsum, clip_desc, rank_layout=None):
         """the two NASREC_OP_OPT_MOMENTS launches of a plan with Adam / SGD: (phase 0 in place of the Adagrad apply launch, phase 1).
         rank_layout: (samples per rank, floats between the ranks' chunks) of `gsum` (_optimizer_descs).
         Row-sparse Adam: no table owns a tile, and phase 1 is None unless weight decay left unreached ranges of g to restore — phase 0
         then counts the steps itself; with them phase 1 runs in its no-table-moves form on all its workgroups (the ranges of a supernet
-        are millions of floats)."""
+        are millions of floats).  RMSprop: the same shape of launches (its rows rest too, owing only a decay); m is unused and the
+        slots of `tm` carry the stamps."""
         spec = t.spec
         st = self.moments
+        lazy = spec.sparse_rows or spec.kind == "rmsprop"  # (the tables move in the batch's rows only)
         m = L.OptMomentsDesc()
         m.kind, m.phase = L.OP_OPT_MOMENTS, 0
         self._optim_scalars(m, spec)
         m.dense_blocks = min(2048, t.mom_chunks[1])
         m.sparse_rows = int(bool(spec.sparse_rows))
-        m.nblocks = self.WD_BLOCKS if (t.mom_tables or spec.sparse_rows) else 1  # (no table moves: phase 1 only counts the step and restores g)
+        m.nblocks = self.WD_BLOCKS if (t.mom_tables or lazy) else 1  # (no table moves: phase 1 only counts the step and restores g)
         m.B, m.Fs = (Bg, self.Fs) if gsum is not None else (0, self.Fs)
         m.table_step0 = len(self.dense_names)
         m.wd = spec.wd
         m.clip = clip_desc
         m.chunks, m.nchunks = t.mom_chunks
         m.p, m.g = self.flat_p.data_ptr(), self.flat_g.data_ptr()
-        first, second = (st["exp_avg"], st["exp_avg_sq"]) if spec.kind == "adam" else (st["momentum_buffer"], None)
-        m.m = first[0].data_ptr()
+        if spec.kind == "rmsprop":
+            first, second = (None, self.lazy_stamps), st["square_avg"]
+            self._lazy_alpha = float(spec.alpha)
+        else:
+            first, second = (st["exp_avg"], st["exp_avg_sq"]) if spec.kind == "adam" else (st["momentum_buffer"], None)
+        m.m = first[0].data_ptr() if first[0] is not None else None
         m.v = second[0].data_ptr() if second is not None else None
         if gsum is not None:
             m.idx, m.leader, m.gsum = cat_x.data_ptr(), t.bufs.leader.data_ptr(), gsum
@@ -925,7 +965,7 @@ class SupernetEngine:
             if second is not None:
                 m.tv[f] = second[1][f].data_ptr()
             m.tile_off[f] = tile
-            if f in t.mom_tables and not spec.sparse_rows:  # (a table that does not move owns no tile: phase 1 leaves it alone)
+            if f in t.mom_tables and not lazy:  # (a table that does not move owns no tile: phase 1 leaves it alone)
                 tile += (self.num_embeddings[f] + 63) // 64
             if spec.wd and f in t.wd_tables:
                 mask |= 1 << f
@@ -938,7 +978,7 @@ class SupernetEngine:
             m.zero_chunks, m.n_zero = t.wd_set
         m.counter = self._mom_counter.data_ptr()
         m.lr, m.coef = self.lr_dev.data_ptr(), self.clip_out.data_ptr()
-        if spec.sparse_rows and not m.n_zero:
+        if lazy and not m.n_zero:
             return m, None
         m1 = L.OptMomentsDesc.from_buffer_copy(m)
         m1.phase = 1
@@ -1365,6 +1405,8 @@ class SupernetEngine:
         choice = choice if choice is not None else self.warm_choice
         if self.host_embedding:
             raise L.EngineError("the last-layer step needs the embedding tables on the device")
+        if optim is not None and optim.kind == "rmsprop":
+            raise L.EngineError("the last-layer step has no RMSprop: the fine-tune keeps the torch route with it")
         B = int(int_x.shape[0])
         cp = self.compile(choice, B, train=True)
         self.last_layer_plan = cp  # (its logits: SuperNet.engine_last_logits)

@@ -45,7 +45,8 @@ def summary_writer(logging_dir):
 
 def build_optimizer(name, model, lr):
     """main_train.py:150-160 (Adagrad eps 1e-2; Adam eps 1e-8; SGD nesterov momentum 0.9); row-sparse-adam: Adam's lr and eps, the
-    tables moving in the batch's rows only (utils/optim.RowSparseAdam)"""
+    tables moving in the batch's rows only (utils/optim.RowSparseAdam); rmsprop: torch's defaults (alpha 0.99, eps 1e-8) as
+    utils/optim.LazyRMSprop, which is torch.optim.RMSprop and the type the fused step takes"""
     if name == "adagrad":
         return torch.optim.Adagrad(model.parameters(), lr=lr, eps=1e-2)
     if name == "adam":
@@ -58,6 +59,9 @@ def build_optimizer(name, model, lr):
             raise ValueError("--optimizer row-sparse-adam needs whole tables: a row-sharded table holds one rank's rows under local ids; "
                              "use --optimizer adam with --table-sharding row")
         return RowSparseAdam(model.parameters(), list(model._embedding.parameters()), lr=lr, eps=1e-8)
+    if name == "rmsprop":
+        from nasrec_amd.utils.optim import LazyRMSprop
+        return LazyRMSprop(model.parameters(), lr=lr)
     raise KeyError(name)
 
 

@@ -2,7 +2,7 @@
 hyperparameters, and the weight decay of get_l2_loss, whose gradient the step folds in.
 
 `OptimSpec.for_step` decides which torch optimizers the fused step reproduces: torch.optim.Adagrad, and torch.optim.Adam / torch.optim.SGD
-with momentum / RowSparseAdam (nasrec_amd/utils/optim.py) under the conditions of `from_optimizer`, in one process or in every rank of a data-parallel run with whole tables
+with momentum / RowSparseAdam / LazyRMSprop (nasrec_amd/utils/optim.py) under the conditions of `from_optimizer`, in one process or in every rank of a data-parallel run with whole tables
 (nasrec_amd/parallel.py).  The public entry points (SuperNet.engine_*, SupernetEngine.train_step / last_layer_step, DataParallelStep)
 normalise their arguments into one spec (`of`); everything below them passes that."""
 from typing import NamedTuple, Optional
@@ -11,25 +11,26 @@ import torch
 
 
 class OptimSpec(NamedTuple):
-    kind: str               # "adagrad" | "adam" | "sgd"
+    kind: str               # "adagrad" | "adam" | "sgd" | "rmsprop"
     beta1: float = 0.9      # Adam
     beta2: float = 0.999
-    eps: float = 1e-8       # Adam's, or Adagrad's
+    eps: float = 1e-8       # Adam's / RMSprop's, or Adagrad's
     momentum: float = 0.0   # SGD
     nesterov: bool = False
     wd: float = 0.0         # get_l2_loss(model, wd, no_reg): the step minimises BCE + that term
     no_reg: Optional[str] = None
     sparse_rows: bool = False  # Adam: row-sparse on the tables (utils/optim.RowSparseAdam: torch.optim.SparseAdam on the batch's rows)
+    alpha: float = 0.99     # RMSprop's smoothing constant (utils/optim.LazyRMSprop: momentum 0, not centered)
 
     @property
     def moments(self) -> bool:
-        """Adam / SGD: state in the engine's moment arrays and step counters (Adagrad: its accumulators)"""
+        """Adam / SGD / RMSprop: state in the engine's moment arrays and step counters (Adagrad: its accumulators)"""
         return self.kind != "adagrad"
 
     @property
     def state_keys(self):
         """the per-parameter tensors torch keeps in optimizer.state[p] (besides "step")"""
-        return {"adagrad": ("sum",), "adam": ("exp_avg", "exp_avg_sq")}.get(self.kind, ("momentum_buffer",))
+        return {"adagrad": ("sum",), "adam": ("exp_avg", "exp_avg_sq"), "rmsprop": ("square_avg",)}.get(self.kind, ("momentum_buffer",))
 
     @staticmethod
     def of(eps: float = 1e-2, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None) -> "OptimSpec":
@@ -46,8 +47,10 @@ class OptimSpec(NamedTuple):
         """the spec of a torch.optim.Adam / torch.optim.SGD the fused step reproduces, else None.
         Adam: one group, amsgrad, weight_decay, maximize, capturable, differentiable and fused all off.
         SGD: one group, momentum != 0 (plain SGD keeps the torch route), dampening 0, weight_decay 0, not maximize / differentiable / fused.
-        RowSparseAdam: Adam's conditions (its one group carries Adam's keys) -> sparse_rows."""
-        from .utils.optim import RowSparseAdam
+        RowSparseAdam: Adam's conditions (its one group carries Adam's keys) -> sparse_rows.
+        LazyRMSprop (that type exactly: a hand-built torch.optim.RMSprop keeps the torch route): one group, momentum 0, not centered,
+        weight_decay 0, not maximize / capturable / differentiable."""
+        from .utils.optim import LazyRMSprop, RowSparseAdam
         if len(optimizer.param_groups) != 1:
             return None
         g = optimizer.param_groups[0]
@@ -60,6 +63,12 @@ class OptimSpec(NamedTuple):
             if torch.is_tensor(b1) or torch.is_tensor(b2):
                 return None
             return OptimSpec("adam", beta1=float(b1), beta2=float(b2), eps=float(g["eps"]), sparse_rows=type(optimizer) is RowSparseAdam)
+        if type(optimizer) is LazyRMSprop:
+            if g.get("momentum", 0) != 0 or g.get("centered", False) or g.get("capturable", False):
+                return None
+            if torch.is_tensor(g["alpha"]) or torch.is_tensor(g["eps"]):
+                return None
+            return OptimSpec("rmsprop", alpha=float(g["alpha"]), eps=float(g["eps"]))
         if type(optimizer) is torch.optim.SGD:
             if g.get("dampening", 0) != 0 or not g.get("momentum", 0):
                 return None
@@ -71,10 +80,11 @@ class OptimSpec(NamedTuple):
         """the spec of the fused step that stands in for `optimizer.step()` on the loss + get_l2_loss(model, weight_decay,
         no_reg_param_name), or None when the fused step does not reproduce the optimizer.  torch.optim.Adagrad: one group,
         weight_decay, lr_decay and initial_accumulator_value 0, not maximize; Adam / SGD / RowSparseAdam: from_optimizer.  Row-sparse
-        Adam with a regularised table is None too (`regularises_tables`): the L2 term puts a gradient on every row."""
+        Adam and RMSprop with a regularised table are None too (`regularises_tables`): the L2 term puts a gradient on every row, and
+        RMSprop's rows rest only while their gradient is zero."""
         if type(optimizer) is not torch.optim.Adagrad:
             optim = OptimSpec.from_optimizer(optimizer)
-            if optim is not None and optim.sparse_rows and regularises_tables(weight_decay, no_reg_param_name):
+            if optim is not None and (optim.sparse_rows or optim.kind == "rmsprop") and regularises_tables(weight_decay, no_reg_param_name):
                 return None
             return OptimSpec.of(weight_decay=weight_decay, no_reg_param_name=no_reg_param_name, optim=optim) if optim is not None else None
         if len(optimizer.param_groups) != 1:

@@ -735,16 +735,18 @@ class SuperNet(nn.Module):
     def engine_bind_optimizer(self, optimizer, last_layer: bool = False):
         """Share the optimizer state between a torch optimizer and the engine.  Adagrad: existing `sum` state (a resumed checkpoint) is
         copied into the engine's accumulators, then `optimizer.state[p]["sum"]` aliases them, so `optimizer.state_dict()` stays a
-        faithful checkpoint while the fused step does the updates.  torch.optim.Adam / SGD (OptimSpec.for_step): the engine's moment
+        faithful checkpoint while the fused step does the updates.  torch.optim.Adam / SGD / LazyRMSprop (OptimSpec.for_step): the engine's moment
         arrays and step counters take the optimizer's state — a parameter without state (never stepped) starts from zero — and the
         state of every parameter that has some aliases them.  last_layer: the same for engine_last_layer_step, over _final.{weight,
-        bias} only: the frozen parameters' state is left as it is."""
+        bias} only: the frozen parameters' state is left as it is.  LazyRMSprop: every row of an existing square_avg is current (torch
+        keeps it so), so a table's row stamps start at that table's step count; the optimizer gets the engine's flush as its hook
+        (utils/optim.LazyRMSprop), and last_layer keeps the Adagrad accumulators: that step has no RMSprop."""
         eng = self._engine
         assert eng is not None, "run one forward first (lazy shapes)"
         from ..optim_spec import OptimSpec
         spec = OptimSpec.for_step(optimizer)
-        if spec is None or not spec.moments:  # (the Adagrad accumulators: also what an optimizer the fused step does not reproduce gets)
-            spec = OptimSpec.of()
+        if spec is None or not spec.moments or (last_layer and spec.kind == "rmsprop"):
+            spec = OptimSpec.of()  # (the Adagrad accumulators: also what an optimizer the fused step does not reproduce gets)
         if spec.moments and not last_layer and self._table_sharding == "row":
             from .._lib import EngineError
             raise EngineError("Adam / SGD in the fused step need whole tables on the device")
@@ -770,12 +772,18 @@ class SuperNet(nn.Module):
                     elif src.data_ptr() != tgt.data_ptr():
                         tgt.copy_(src.to(tgt.device).view_as(tgt))
                 if st:
-                    if spec.kind == "adam":
+                    if spec.kind in ("adam", "rmsprop"):
                         counts[k] = float(st.get("step", 0.0))
                     elif st.get("momentum_buffer") is not None:
                         counts[k] = 1.0  # (SGD keeps no count: "has a buffer" is what the engine needs)
             counters.copy_(counts.to(eng.device))
+            if spec.kind == "rmsprop":
+                eng._lazy_alpha = float(spec.alpha)
+                for f, stamp in enumerate(eng.lazy_stamps):
+                    stamp.fill_(int(counts[eng.param_index["_embedding.%d.weight" % f]]))
         eng.stream.synchronize()
+        if spec.kind == "rmsprop":
+            optimizer._lazy_flush = eng.flush_lazy_rows
         self._alias_state(optimizer, spec, slots, counts)
 
     _FINAL = ("_final.weight", "_final.bias")
@@ -816,7 +824,7 @@ class SuperNet(nn.Module):
                 continue
             st = optimizer.state[p]
             st.update(views)
-            if spec.kind == "adam":
+            if spec.kind in ("adam", "rmsprop"):
                 st["step"] = torch.tensor(float(counts[k]), dtype=torch.float32)
 
     def engine_sync_optimizer_steps(self, optimizer):
@@ -824,6 +832,7 @@ class SuperNet(nn.Module):
         (Adam / SGD: the counters of the engine, and state entries for the parameters stepped for the first time)"""
         spec, last_layer = self.__dict__.get("_bound", (None, False))
         if spec is not None and spec.moments:
+            self._engine.flush_lazy_rows()  # (RMSprop: the state about to be aliased is read with every row current; else a no-op)
             self._engine.stream.synchronize()
             torch.cuda.synchronize(self._engine.device)
             slots, counters = self._state_slots(spec, last_layer)

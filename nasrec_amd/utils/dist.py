@@ -54,7 +54,7 @@ def world_info():
 
 def _replica_tensors(model):
     """every tensor that defines a replica: parameters, buffers, and the engine's optimizer state once it exists — Adagrad's
-    accumulators, Adam's / SGD's moments (flat arena and table arrays) and their step counters"""
+    accumulators, Adam's / SGD's / RMSprop's moments (flat arena and table arrays), their step counters and RMSprop's row stamps"""
     sharded = getattr(model, "_table_sharding", None) == "row"  # row-sharded tables: every rank owns DIFFERENT rows — not replica state
     out = [p.data for n, p in model.named_parameters() if not (sharded and n.startswith("_embedding."))] + [b.data for b in model.buffers()]
     eng = getattr(model, "_engine", None)
@@ -69,6 +69,7 @@ def _replica_tensors(model):
             out.extend(tabs)
         if getattr(eng, "opt_steps", None) is not None:
             out.append(eng.opt_steps)
+        out.extend(getattr(eng, "lazy_stamps", None) or [])  # (RMSprop: the step at which each table row's square_avg is current)
     return out
 
 

@@ -109,3 +109,25 @@ class RowSparseAdam(torch.optim.Optimizer):
             p.index_add_(0, rows, numer.div(denom).mul_(-step_size))
         self._ids = None  # consumed: the next gradients need their own ids
         return loss
+
+
+class LazyRMSprop(torch.optim.RMSprop):
+    """`--optimizer rmsprop`: torch.optim.RMSprop, and on the torch route exactly that.  The type is what the fused engine step looks for
+    (OptimSpec.from_optimizer: momentum 0, not centered): there a table row outside the batch owes `square_avg` only a factor
+    alpha^n, which the engine pays when the row is next touched, or when somebody reads the state ("Lazy RMSprop").  Bound
+    to an engine (SuperNet.engine_bind_optimizer) the optimizer carries a flush hook that brings every row current; `step()` and
+    `state_dict()` call it first, so whoever reads or advances the aliased `square_avg` sees torch.optim.RMSprop's state."""
+
+    _lazy_flush = None  # (set by SuperNet.engine_bind_optimizer; never part of a checkpoint)
+
+    def flush_lazy_rows(self):
+        if self._lazy_flush is not None:
+            self._lazy_flush()
+
+    def step(self, closure=None):
+        self.flush_lazy_rows()
+        return super().step(closure)
+
+    def state_dict(self):
+        self.flush_lazy_rows()
+        return super().state_dict()

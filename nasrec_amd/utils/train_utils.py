@@ -139,7 +139,8 @@ def _last_layer_step_applies(model, optimizer, l2_loss_fn, use_amp):
     from .dist import world_info
     if world_info()[1] > 1 or getattr(model, "_table_sharding", None) == "row" or getattr(model, "_place_embedding_on_cpu", False):
         return False
-    if _optim_spec(optimizer, l2_loss_fn) is None or not model._last_layer_only():
+    spec = _optim_spec(optimizer, l2_loss_fn)
+    if spec is None or spec.kind == "rmsprop" or not model._last_layer_only():  # (RMSprop: the fine-tune keeps the torch route)
         return False
     g = optimizer.param_groups[0]
     if not {id(p) for p in model._final.parameters()} <= {id(p) for p in g["params"]}:

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Cost of the optimizer choice (`--optimizer adagrad | adam | sgd | row-sparse-adam`, main_train.py:150-160) on the bench cfg-2 network:
+"""Cost of the optimizer choice (`--optimizer adagrad | adam | sgd | row-sparse-adam | rmsprop`, main_train.py:150-160) on the bench cfg-2 network:
 the Criteo best-1shot sub-network, full tables (33.76 M rows), batch 256, clip 5.0; Adagrad(eps 1e-2), Adam(eps 1e-8), SGD(momentum 0.9,
-Nesterov), row-sparse Adam (Adam's lr and eps; with --wd the L2 term leaves the tables out, as the optimizer requires).  Prints one JSON line per measured (route, optimizer, wd):
+Nesterov), row-sparse Adam (Adam's lr and eps; with --wd the L2 term leaves the tables out, as the optimizer requires), RMSprop (torch's
+defaults; fused: lazily decayed rows, with --wd the tables left out too; its line also carries `flush_ms`, the one launch that brings
+every row's square_avg current after the timed steps).  Prints one JSON line per measured (route, optimizer, wd):
 
     python tools/optim_step_bench.py --route fused --optimizer adam --wd 0     # the fused engine step
     python tools/optim_step_bench.py --route torch --optimizer adam --wd 0     # forward / autograd / clip_grad_norm_ / torch.optim
@@ -20,13 +22,13 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-LR = {"adagrad": 1e-3, "adam": 1e-3, "sgd": 1e-3, "row-sparse-adam": 1e-3}
+LR = {"adagrad": 1e-3, "adam": 1e-3, "sgd": 1e-3, "row-sparse-adam": 1e-3, "rmsprop": 1e-4}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--route", choices=["fused", "torch"], default="fused")
-    ap.add_argument("--optimizer", choices=["adagrad", "adam", "sgd", "row-sparse-adam"], default="adam")
+    ap.add_argument("--optimizer", choices=["adagrad", "adam", "sgd", "row-sparse-adam", "rmsprop"], default="adam")
     ap.add_argument("--wd", type=float, default=0.0)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
@@ -45,7 +47,7 @@ def main():
         return
     if a.all:
         for route in ("fused", "torch"):
-            for opt in ("adagrad", "adam", "sgd", "row-sparse-adam"):
+            for opt in ("adagrad", "adam", "sgd", "row-sparse-adam", "rmsprop"):
                 for wd in (0.0, 1e-8):
                     steps = a.steps if route == "fused" else min(a.steps, 20)
                     cmd = [sys.executable, os.path.abspath(__file__), "--route", route, "--optimizer", opt, "--wd", str(wd), "--steps", str(steps),
@@ -75,7 +77,8 @@ def main():
     lr = LR[a.optimizer]
     opt = MT.build_optimizer(a.optimizer, m, lr)
     spec = OptimSpec.from_optimizer(opt) if a.optimizer != "adagrad" else None
-    no_reg = "_embedding" if (a.optimizer == "row-sparse-adam" and a.wd) else None
+    lazy = a.optimizer in ("row-sparse-adam", "rmsprop") and a.route == "fused"  # (the fused step needs the tables left out of the L2 term)
+    no_reg = "_embedding" if ((a.optimizer == "row-sparse-adam" or lazy) and a.wd) else None
     loss_fn = torch.nn.BCEWithLogitsLoss()
     if a.route == "fused":
         m.engine_bind_optimizer(opt)
@@ -107,8 +110,20 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / a.steps
-    print(json.dumps({"route": a.route, "optimizer": a.optimizer, "wd": a.wd, "B": a.B, "steps": a.steps, "ms_per_step": round(ms, 4),
-                      "samples_per_s": round(a.B / ms * 1e3), "wall_ms_per_step": round((time.perf_counter() - t0) / a.steps * 1e3, 4),
+    wall_ms = (time.perf_counter() - t0) / a.steps * 1e3
+    extra = {}
+    if a.optimizer == "rmsprop" and a.route == "fused":
+        # the flush: every row outside the timed batches owes its square_avg a decay (one streaming launch, waited for)
+        wall = time.perf_counter()
+        m._engine.flush_lazy_rows()
+        torch.cuda.synchronize()
+        extra["flush_ms"] = round((time.perf_counter() - wall) * 1e3, 4)
+        wall = time.perf_counter()
+        m._engine.flush_lazy_rows()
+        torch.cuda.synchronize()
+        extra["flush_again_ms"] = round((time.perf_counter() - wall) * 1e3, 4)  # (nothing owed: the stamps are read, nothing else)
+    print(json.dumps({**extra, "route": a.route, "optimizer": a.optimizer, "wd": a.wd, "B": a.B, "steps": a.steps, "ms_per_step": round(ms, 4),
+                      "samples_per_s": round(a.B / ms * 1e3), "wall_ms_per_step": round(wall_ms, 4),
                       "table_rows": rows}))
 
 
