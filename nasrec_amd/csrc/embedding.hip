@@ -261,17 +261,7 @@ int launch_opt_reduce(hipStream_t st, const nasrec_opt_reduce_desc_t* d) {
 __global__ __launch_bounds__(256) void opt_apply_kernel(const nasrec_opt_apply_desc_t d) {
   __shared__ float sh_coef;
   const float lr = *d.dense.lr;  // (beside the partial sums' loads, not behind the barrier: one round trip less on every workgroup's path)
-  if (threadIdx.x < 64) {
-    float total;
-    const float c = clip_coef_wave(d.clip, threadIdx.x, &total);
-    if (threadIdx.x == 0) {
-      sh_coef = c;
-      if (blockIdx.x == 0) {
-        d.clip.out[0] = c;
-        d.clip.out[1] = total;
-      }
-    }
-  }
+  clip_head(d.clip, &sh_coef);
   __syncthreads();
   const float coef = sh_coef;
   if ((int)blockIdx.x < d.dense_blocks)

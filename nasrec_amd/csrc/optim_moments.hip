@@ -3,11 +3,13 @@
 // coefficient, dense chunks, the batch's touched rows, which it marks in a bitmap); phase 1 streams the untouched rows of every table
 // (a zero gradient still moves a row whose moments are non-zero: W and its one or two moment arrays, read and written once) and,
 // in the workgroup that finishes last, counts the step of every parameter it updated.
-// Row-sparse Adam (sparse_rows, include/nasrec_hip.h) is a phase 0 of its own, opt_moments_sparse_phase0_kernel: the same clip and dense
-// chunks, torch.optim.SparseAdam on the touched rows, no bitmap, and no phase 1 unless weight decay has gradients to restore.
-// RMSprop (NASREC_OPTIM_RMSPROP: momentum 0, not centered) has a phase 0 of its own too, opt_moments_rmsprop_phase0_kernel: a row whose
-// gradient is zero does not move and its square_avg only decays, so the touched rows pay the decay they owe (per-row stamps) and take
-// torch.optim.RMSprop's update; opt_moments_flush_kernel (phase 2) brings every row's square_avg current for whoever reads the state.
+// Phase 0 is one kernel, opt_moments_phase0_kernel<Rows>; what happens to one touched row, and whether the launch marks the bitmap or
+// counts the steps itself, is the row policy `Rows` (DenseRows, SparseAdamRows, LazyRmspropRows below).
+// Row-sparse Adam (sparse_rows, include/nasrec_hip.h): the same clip and dense chunks, torch.optim.SparseAdam on the touched rows, no
+// bitmap, and no phase 1 unless weight decay has gradients to restore.
+// RMSprop (NASREC_OPTIM_RMSPROP: momentum 0, not centered): a row whose gradient is zero does not move and its square_avg only decays,
+// so the touched rows pay the decay they owe (per-row stamps) and take torch.optim.RMSprop's update; opt_moments_flush_kernel (phase 2)
+// brings every row's square_avg current for whoever reads the state.
 #include "optimizer_bodies.h"
 
 namespace {
@@ -38,21 +40,21 @@ __device__ __forceinline__ void table_scalars(const nasrec_opt_moments_desc_t& d
   if (ALGO == NASREC_OPTIM_ADAM && f >= 0 && f < d.Fs) adam_scalars(d, d.step[d.table_step0 + f], lr, ss[f], bs[f]);
 }
 
-// phase 0's head: wavefront 0 of every workgroup computes the clip coefficient into *sh_coef (workgroup 0 writes clip.out); the caller
-// synchronises
-__device__ __forceinline__ void clip_head(const nasrec_opt_moments_desc_t& d, float* sh_coef) {
+// The workgroup that arrives last at d.counter (of the launch's `nblk`) adds 1 to step[inc[i]] and leaves the counter zero.  It may:
+// every workgroup has read its step counters (dense_chunks, the tables' scalars) when it arrives.
+__device__ __forceinline__ void count_steps_in_last_workgroup(const nasrec_opt_moments_desc_t& d, unsigned nblk) {
+  __shared__ int last;
   const int tid = threadIdx.x;
-  if (tid < 64) {
-    float total;
-    const float c = clip_coef_wave(d.clip, tid, &total);
-    if (tid == 0) {
-      *sh_coef = c;
-      if (blockIdx.x == 0) {
-        d.clip.out[0] = c;
-        d.clip.out[1] = total;
-      }
-    }
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence();
+    last = atomicAdd(d.counter, 1u) == nblk - 1u;
   }
+  __syncthreads();
+  if (!last) return;
+  __threadfence();
+  for (long i = tid; i < d.n_inc; i += 256) d.step[d.inc[i]] += 1.f;
+  if (tid == 0) *d.counter = 0u;
 }
 
 // phase 0's dense arena (workgroups [0, dense_blocks)): one parameter per chunk (its step counter), float4 pieces, then the chunk's tail
@@ -88,56 +90,94 @@ __device__ __forceinline__ void dense_chunks(const nasrec_opt_moments_desc_t& d,
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Row policies of phase 0: a small struct in LDS.  DENSE = the ALGO dense_chunks runs with; COUNTS = a launch without zero_chunks
+// counts the steps itself (there is no phase 1 behind it); scalars(d, lr) = the per-table scalars, by threads [64, 64 + Fs) of a row
+// workgroup (the kernel synchronises); row(d, f, row, q, g4, lr) = quarter q of touched row `row` of table f, g4 = the clipped quarter
+// of its summed gradient.
+// ---------------------------------------------------------------------------------------------------
+
+// Adam / momentum SGD on every row: the touched rows here, marked in the bitmap, the others in phase 1 (which counts the steps)
 template <int ALGO>
+struct DenseRows {
+  static constexpr int DENSE = ALGO;
+  static constexpr bool COUNTS = false;
+  float ss[NASREC_MAX_TABLES], bs[NASREC_MAX_TABLES];
+  __device__ __forceinline__ void scalars(const nasrec_opt_moments_desc_t& d, float lr) { table_scalars<ALGO>(d, 64, lr, ss, bs); }
+  __device__ __forceinline__ void row(const nasrec_opt_moments_desc_t& d, int f, long row, int q, const f32x4& g4, float lr) const {
+    const long o = row * 16 + q * 4;
+    f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o), m4 = *reinterpret_cast<const f32x4*>(d.tm[f] + o), v4 = {};
+    if (ALGO == NASREC_OPTIM_ADAM) v4 = *reinterpret_cast<const f32x4*>(d.tv[f] + o);
+    moments_vec<ALGO>(d, g4, p4, m4, v4, lr, ALGO == NASREC_OPTIM_ADAM ? ss[f] : 0.f, ALGO == NASREC_OPTIM_ADAM ? bs[f] : 1.f);
+    *reinterpret_cast<f32x4*>(d.table[f] + o) = p4;
+    *reinterpret_cast<f32x4*>(d.tm[f] + o) = m4;
+    if (ALGO == NASREC_OPTIM_ADAM) *reinterpret_cast<f32x4*>(d.tv[f] + o) = v4;
+    if (q == 0) atomicOr(d.bitmap + 2 * d.tile_off[f] + (row >> 5), 1u << (row & 31));  // (a set of bits: no value depends on the order)
+  }
+};
+
+// Row-sparse Adam (sparse_rows): a touched row takes torch.optim.SparseAdam's update with its summed gradient, zero or not; no bit is
+// marked, and no other row moves.
+struct SparseAdamRows {
+  static constexpr int DENSE = NASREC_OPTIM_ADAM;
+  static constexpr bool COUNTS = true;
+  float ss[NASREC_MAX_TABLES];
+  __device__ __forceinline__ void scalars(const nasrec_opt_moments_desc_t& d, float lr) {
+    const int f = (int)threadIdx.x - 64;
+    if (f >= 0 && f < d.Fs) ss[f] = sparse_adam_step_size(d, d.step[d.table_step0 + f], lr);
+  }
+  __device__ __forceinline__ void row(const nasrec_opt_moments_desc_t& d, int f, long row, int q, const f32x4& g4, float) const {
+    const long o = row * 16 + q * 4;
+    f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o), m4 = *reinterpret_cast<const f32x4*>(d.tm[f] + o);
+    f32x4 v4 = *reinterpret_cast<const f32x4*>(d.tv[f] + o);
+    const float step_size = ss[f];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float pe = p4[e], me = m4[e], ve = v4[e];
+      sparse_adam_elem(d, g4[e], pe, me, ve, step_size);
+      p4[e] = pe;
+      m4[e] = me;
+      v4[e] = ve;
+    }
+    *reinterpret_cast<f32x4*>(d.table[f] + o) = p4;
+    *reinterpret_cast<f32x4*>(d.tm[f] + o) = m4;
+    *reinterpret_cast<f32x4*>(d.tv[f] + o) = v4;
+  }
+};
+
+// RMSprop (p / g / v): a touched row first pays the decay its square_avg owes since its stamp (lazy_decay, optimizer_bodies.h), then
+// takes torch.optim.RMSprop's update with its summed gradient, and is stamped with this step; no bit is marked.  The four lanes of a
+// row read its stamp before lane 0 writes it: they sit in one wavefront, and the store follows the loads in program order.
+struct LazyRmspropRows {
+  static constexpr int DENSE = NASREC_OPTIM_RMSPROP;
+  static constexpr bool COUNTS = true;
+  __device__ __forceinline__ void scalars(const nasrec_opt_moments_desc_t&, float) {}
+  __device__ __forceinline__ void row(const nasrec_opt_moments_desc_t& d, int f, long row, int q, const f32x4& g4, float lr) const {
+    const long o = row * 16 + q * 4;
+    const long step = (long)d.step[d.table_step0 + f] + 1;
+    const long n = step - 1 - (long)d.stamp[f][row];
+    f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o), v4 = *reinterpret_cast<const f32x4*>(d.tv[f] + o), m4 = {};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v4[e] = lazy_decay(v4[e], d.beta2, n);
+    moments_vec<NASREC_OPTIM_RMSPROP>(d, g4, p4, m4, v4, lr, 0.f, 1.f);
+    *reinterpret_cast<f32x4*>(d.table[f] + o) = p4;
+    *reinterpret_cast<f32x4*>(d.tv[f] + o) = v4;
+    if (q == 0) d.stamp[f][row] = (uint32_t)step;
+  }
+};
+
+template <class Rows>
 __global__ __launch_bounds__(256) void opt_moments_phase0_kernel(const nasrec_opt_moments_desc_t d) {
   __shared__ float sh_coef;
-  __shared__ float t_ss[NASREC_MAX_TABLES], t_bs[NASREC_MAX_TABLES];
+  __shared__ Rows rows;
   const int tid = threadIdx.x, blk = blockIdx.x;
   const float lr = *d.lr;
-  clip_head(d, &sh_coef);
-  if (blk >= d.dense_blocks) table_scalars<ALGO>(d, 64, lr, t_ss, t_bs);
+  clip_head(d.clip, &sh_coef);
+  if (blk >= d.dense_blocks) rows.scalars(d, lr);
   __syncthreads();
   const float coef = sh_coef;
   if (blk < d.dense_blocks) {
-    dense_chunks<ALGO>(d, coef, lr);
-    return;
-  }
-  // touched rows: 4 lanes x float4 per (sample, field) pair; the leader of a row id carries the row's summed gradient
-  const long t = (long)(blk - d.dense_blocks) * 256 + tid;
-  const long pair = t >> 2;
-  const int q = (int)(t & 3);
-  if (pair >= (long)d.B * d.Fs) return;
-  const int f = (int)(pair % d.Fs);
-  if (!d.leader[pair]) return;
-  const long row = d.idx[pair];
-  if (row < 0 || row >= d.rows[f]) return;  // (flagged by the gather; never written outside a table)
-  const long o = row * 16 + q * 4;
-  f32x4 g4 = *reinterpret_cast<const f32x4*>(d.gsum + gsum_row_offset(pair, d.Fs, d.rank_B, d.rank_stride) + q * 4);
-  f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o), m4 = *reinterpret_cast<const f32x4*>(d.tm[f] + o), v4 = {};
-  if (ALGO == NASREC_OPTIM_ADAM) v4 = *reinterpret_cast<const f32x4*>(d.tv[f] + o);
-  g4 *= coef;
-  moments_vec<ALGO>(d, g4, p4, m4, v4, lr, ALGO == NASREC_OPTIM_ADAM ? t_ss[f] : 0.f, ALGO == NASREC_OPTIM_ADAM ? t_bs[f] : 1.f);
-  *reinterpret_cast<f32x4*>(d.table[f] + o) = p4;
-  *reinterpret_cast<f32x4*>(d.tm[f] + o) = m4;
-  if (ALGO == NASREC_OPTIM_ADAM) *reinterpret_cast<f32x4*>(d.tv[f] + o) = v4;
-  if (q == 0) atomicOr(d.bitmap + 2 * d.tile_off[f] + (row >> 5), 1u << (row & 31));  // (a set of bits: no value depends on the order)
-}
-
-// Row-sparse Adam's phase 0 (sparse_rows): clip and dense chunks as above; a touched row takes torch.optim.SparseAdam's update with its
-// summed gradient, zero or not; no bit is marked.  Without weight decay's zero_chunks there is no phase 1, and the workgroup that finishes
-// last counts the steps: every workgroup has read its counters (dense_chunks, the tables' step sizes) when it arrives at d.counter.
-__global__ __launch_bounds__(256) void opt_moments_sparse_phase0_kernel(const nasrec_opt_moments_desc_t d) {
-  __shared__ float sh_coef;
-  __shared__ float t_ss[NASREC_MAX_TABLES];
-  __shared__ int last;
-  const int tid = threadIdx.x, blk = blockIdx.x;
-  const float lr = *d.lr;
-  clip_head(d, &sh_coef);
-  if (blk >= d.dense_blocks && tid >= 64 && tid - 64 < d.Fs) t_ss[tid - 64] = sparse_adam_step_size(d, d.step[d.table_step0 + tid - 64], lr);
-  __syncthreads();
-  const float coef = sh_coef;
-  if (blk < d.dense_blocks) {
-    dense_chunks<NASREC_OPTIM_ADAM>(d, coef, lr);
+    dense_chunks<Rows::DENSE>(d, coef, lr);
   } else {
     // touched rows: 4 lanes x float4 per (sample, field) pair; the leader of a row id carries the row's summed gradient
     const long t = (long)(blk - d.dense_blocks) * 256 + tid;
@@ -147,88 +187,14 @@ __global__ __launch_bounds__(256) void opt_moments_sparse_phase0_kernel(const na
       const int f = (int)(pair % d.Fs);
       const long row = d.idx[pair];
       if (row >= 0 && row < d.rows[f]) {  // (flagged by the gather; never written outside a table)
-        const long o = row * 16 + q * 4;
         f32x4 g4 = *reinterpret_cast<const f32x4*>(d.gsum + gsum_row_offset(pair, d.Fs, d.rank_B, d.rank_stride) + q * 4);
-        f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o), m4 = *reinterpret_cast<const f32x4*>(d.tm[f] + o);
-        f32x4 v4 = *reinterpret_cast<const f32x4*>(d.tv[f] + o);
         g4 *= coef;
-        const float ss = t_ss[f];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float pe = p4[e], me = m4[e], ve = v4[e];
-          sparse_adam_elem(d, g4[e], pe, me, ve, ss);
-          p4[e] = pe;
-          m4[e] = me;
-          v4[e] = ve;
-        }
-        *reinterpret_cast<f32x4*>(d.table[f] + o) = p4;
-        *reinterpret_cast<f32x4*>(d.tm[f] + o) = m4;
-        *reinterpret_cast<f32x4*>(d.tv[f] + o) = v4;
+        rows.row(d, f, row, q, g4, lr);
       }
     }
   }
-  if (d.n_zero > 0) return;  // (phase 1 restores g over zero_chunks and counts)
-  __syncthreads();
-  if (tid == 0) {
-    __threadfence();
-    last = atomicAdd(d.counter, 1u) == gridDim.x - 1u;
-  }
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
-  for (long i = tid; i < d.n_inc; i += 256) d.step[d.inc[i]] += 1.f;
-  if (tid == 0) *d.counter = 0u;
-}
-
-// RMSprop's phase 0: clip and dense chunks as above (p / g / v); a touched row first pays the decay its square_avg owes since its stamp
-// (lazy_decay, optimizer_bodies.h), then takes torch.optim.RMSprop's update with its summed gradient, and is stamped with this step; no
-// bit is marked.  The four lanes of a row read its stamp before lane 0 writes it: they sit in one wavefront, and the store follows the
-// loads in program order.  Steps are counted as in opt_moments_sparse_phase0_kernel.
-__global__ __launch_bounds__(256) void opt_moments_rmsprop_phase0_kernel(const nasrec_opt_moments_desc_t d) {
-  __shared__ float sh_coef;
-  __shared__ int last;
-  const int tid = threadIdx.x, blk = blockIdx.x;
-  const float lr = *d.lr;
-  clip_head(d, &sh_coef);
-  __syncthreads();
-  const float coef = sh_coef;
-  if (blk < d.dense_blocks) {
-    dense_chunks<NASREC_OPTIM_RMSPROP>(d, coef, lr);
-  } else {
-    // touched rows: 4 lanes x float4 per (sample, field) pair; the leader of a row id carries the row's summed gradient
-    const long t = (long)(blk - d.dense_blocks) * 256 + tid;
-    const long pair = t >> 2;
-    const int q = (int)(t & 3);
-    if (pair < (long)d.B * d.Fs && d.leader[pair]) {
-      const int f = (int)(pair % d.Fs);
-      const long row = d.idx[pair];
-      if (row >= 0 && row < d.rows[f]) {  // (flagged by the gather; never written outside a table)
-        const long o = row * 16 + q * 4;
-        const long step = (long)d.step[d.table_step0 + f] + 1;
-        const long n = step - 1 - (long)d.stamp[f][row];
-        f32x4 g4 = *reinterpret_cast<const f32x4*>(d.gsum + gsum_row_offset(pair, d.Fs, d.rank_B, d.rank_stride) + q * 4);
-        f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o), v4 = *reinterpret_cast<const f32x4*>(d.tv[f] + o), m4 = {};
-        g4 *= coef;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v4[e] = lazy_decay(v4[e], d.beta2, n);
-        moments_vec<NASREC_OPTIM_RMSPROP>(d, g4, p4, m4, v4, lr, 0.f, 1.f);
-        *reinterpret_cast<f32x4*>(d.table[f] + o) = p4;
-        *reinterpret_cast<f32x4*>(d.tv[f] + o) = v4;
-        if (q == 0) d.stamp[f][row] = (uint32_t)step;
-      }
-    }
-  }
-  if (d.n_zero > 0) return;  // (phase 1 restores g over zero_chunks and counts)
-  __syncthreads();
-  if (tid == 0) {
-    __threadfence();
-    last = atomicAdd(d.counter, 1u) == gridDim.x - 1u;
-  }
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
-  for (long i = tid; i < d.n_inc; i += 256) d.step[d.inc[i]] += 1.f;
-  if (tid == 0) *d.counter = 0u;
+  if (!Rows::COUNTS || d.n_zero > 0) return;  // (phase 1 counts; with zero_chunks it also restores g over them)
+  count_steps_in_last_workgroup(d, gridDim.x);
 }
 
 // RMSprop's flush (phase 2): every row of every table whose stamp lies behind its table's step count pays the decay it owes and is
@@ -287,7 +253,6 @@ struct MomentRows {
 template <int ALGO>
 __global__ __launch_bounds__(256) void opt_moments_phase1_kernel(const nasrec_opt_moments_desc_t d) {
   __shared__ float t_ss[NASREC_MAX_TABLES], t_bs[NASREC_MAX_TABLES];
-  __shared__ int last;
   const int tid = threadIdx.x, blk = blockIdx.x, nblk = d.nblocks;
   const float lr = *d.lr, coef = *d.coef, two_r = 2.f * d.wd;
   table_scalars<ALGO>(d, 0, lr, t_ss, t_bs);
@@ -300,71 +265,59 @@ __global__ __launch_bounds__(256) void opt_moments_phase1_kernel(const nasrec_op
   MomentRows<ALGO> r{d, lr, coef, two_r, t_ss, t_bs};
   untouched_rows_pass(d.tile_off, d.rows, d.Fs, d.bitmap, blk, nblk, r);
   // the step counters move once every workgroup has read them (phase 0 read them in the launch before)
-  __syncthreads();
-  if (tid == 0) {
-    __threadfence();
-    last = atomicAdd(d.counter, 1u) == (unsigned)(nblk - 1);
-  }
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
-  for (long i = tid; i < d.n_inc; i += 256) d.step[d.inc[i]] += 1.f;
-  if (tid == 0) *d.counter = 0u;
+  count_steps_in_last_workgroup(d, (unsigned)nblk);
+}
+
+template <class Rows>
+void launch_phase0(hipStream_t st, const nasrec_opt_moments_desc_t* d, int nblk) {
+  hipLaunchKernelGGL(opt_moments_phase0_kernel<Rows>, dim3((unsigned)nblk), dim3(256), 0, st, *d);
 }
 
 template <int ALGO>
-int launch_phases(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
-  if (d->phase == 0) {
-    const long threads = (long)d->B * d->Fs * 4;
-    const int nrows = (int)((threads + 255) / 256);
-    if (d->dense_blocks < 0 || d->dense_blocks + nrows < 1) return nasrec_set_error(-2, "opt_moments: empty launch");
-    if (nrows > 0 && (!d->idx || !d->leader || !d->gsum || (!d->bitmap && !d->sparse_rows && ALGO != NASREC_OPTIM_RMSPROP))) return nasrec_set_error(-1, "opt_moments: row inputs missing");
-    if (d->rank_B < 0 || (d->rank_B > 0 && (d->rank_stride < (int64_t)d->rank_B * d->Fs * 16 || d->B % d->rank_B != 0)))
-      return nasrec_set_error(-2, "opt_moments: rank layout %d / %ld", d->rank_B, (long)d->rank_stride);
-    if constexpr (ALGO == NASREC_OPTIM_RMSPROP) {
-      if (d->n_zero <= 0 && (!d->counter || (d->n_inc > 0 && !d->inc))) return nasrec_set_error(-1, "opt_moments: RMSprop without zero_chunks counts the steps: counter / inc missing");
-      hipLaunchKernelGGL(opt_moments_rmsprop_phase0_kernel, dim3((unsigned)(d->dense_blocks + nrows)), dim3(256), 0, st, *d);
-    } else if (d->sparse_rows) {
-      if (d->n_zero <= 0 && (!d->counter || (d->n_inc > 0 && !d->inc))) return nasrec_set_error(-1, "opt_moments: sparse_rows without zero_chunks counts the steps: counter / inc missing");
-      hipLaunchKernelGGL(opt_moments_sparse_phase0_kernel, dim3((unsigned)(d->dense_blocks + nrows)), dim3(256), 0, st, *d);
-    } else {
-      hipLaunchKernelGGL(opt_moments_phase0_kernel<ALGO>, dim3((unsigned)(d->dense_blocks + nrows)), dim3(256), 0, st, *d);
-    }
-  } else if (d->phase == 1) {
-    if (d->nblocks <= 0) return nasrec_set_error(-1, "opt_moments: nblocks must be positive");
-    if (!d->bitmap || !d->counter || !d->coef) return nasrec_set_error(-1, "opt_moments: phase 1 inputs missing");
-    if (d->sparse_rows && (d->n_zero <= 0 || d->tile_off[d->Fs] != 0))
-      return nasrec_set_error(-1, "opt_moments: sparse_rows has a phase 1 only to restore zero_chunks, and no table owns a tile");
-    hipLaunchKernelGGL(opt_moments_phase1_kernel<ALGO>, dim3((unsigned)d->nblocks), dim3(256), 0, st, *d);
-  } else {
-    return nasrec_set_error(-1, "opt_moments: phase %d", d->phase);
-  }
-  return nasrec_check_launch("opt_moments");
-}
-
-// RMSprop: what the lazily decayed rows need, checked before anything is launched; phase 2 = the flush
-int launch_rmsprop(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
-  if (d->momentum != 0.f) return nasrec_set_error(-1, "opt_moments: RMSprop with momentum %g moves untouched rows", (double)d->momentum);
-  if (d->sparse_rows) return nasrec_set_error(-1, "opt_moments: sparse_rows is row-sparse Adam (algo %d)", d->algo);
-  for (int f = 0; f < d->Fs; ++f)
-    if (!d->stamp[f] || !d->tv[f]) return nasrec_set_error(-1, "opt_moments: RMSprop without the stamps / square_avg of table %d", f);
-  if (d->phase == 1 && (d->n_zero <= 0 || d->tile_off[d->Fs] != 0))
-    return nasrec_set_error(-1, "opt_moments: RMSprop has a phase 1 only to restore zero_chunks, and no table owns a tile");
-  if (d->phase != 2) return launch_phases<NASREC_OPTIM_RMSPROP>(st, d);
-  if (d->nblocks <= 0 || !d->bitmap) return nasrec_set_error(-1, "opt_moments: flush needs nblocks > 0 and the (all-zero) bitmap");
-  if (d->tile_off[d->Fs] <= 0) return 0;
-  hipLaunchKernelGGL(opt_moments_flush_kernel, dim3((unsigned)d->nblocks), dim3(256), 0, st, *d);
-  return nasrec_check_launch("opt_moments");
+void launch_phase1(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
+  hipLaunchKernelGGL(opt_moments_phase1_kernel<ALGO>, dim3((unsigned)d->nblocks), dim3(256), 0, st, *d);
 }
 
 }  // namespace
 
+// Every refusal comes before anything is launched.  The row form — dense (every row moves: bitmap + phase 1), row-sparse Adam, lazy
+// RMSprop — decides what a launch needs; the two lazy forms move the batch's rows only, so their phase 0 counts the steps unless
+// zero_chunks call for a phase 1, which then owns no tile.  Phase 2 is RMSprop's flush.
 int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
   if (d->Fs < 0 || d->Fs > NASREC_MAX_TABLES) return nasrec_set_error(-1, "opt_moments: Fs = %d", d->Fs);
   if (!d->lr || !d->step) return nasrec_set_error(-1, "opt_moments: lr / step missing");
-  if (d->algo == NASREC_OPTIM_RMSPROP) return launch_rmsprop(st, d);
-  if (d->sparse_rows && d->algo != NASREC_OPTIM_ADAM) return nasrec_set_error(-1, "opt_moments: sparse_rows is row-sparse Adam (algo %d)", d->algo);
-  if (d->algo == NASREC_OPTIM_ADAM) return launch_phases<NASREC_OPTIM_ADAM>(st, d);
-  if (d->algo == NASREC_OPTIM_SGD) return launch_phases<NASREC_OPTIM_SGD>(st, d);
-  return nasrec_set_error(-1, "opt_moments: algo %d", d->algo);
+  const bool adam = d->algo == NASREC_OPTIM_ADAM, rmsprop = d->algo == NASREC_OPTIM_RMSPROP, lazy = rmsprop || d->sparse_rows;
+  if (rmsprop && d->momentum != 0.f) return nasrec_set_error(-1, "opt_moments: RMSprop with momentum %g moves untouched rows", (double)d->momentum);
+  if (d->sparse_rows && !adam) return nasrec_set_error(-1, "opt_moments: sparse_rows is row-sparse Adam (algo %d)", d->algo);
+  if (!adam && !rmsprop && d->algo != NASREC_OPTIM_SGD) return nasrec_set_error(-1, "opt_moments: algo %d", d->algo);
+  if (d->phase < 0 || d->phase > (rmsprop ? 2 : 1)) return nasrec_set_error(-1, "opt_moments: phase %d", d->phase);
+  for (int f = 0; rmsprop && f < d->Fs; ++f)
+    if (!d->stamp[f] || !d->tv[f]) return nasrec_set_error(-1, "opt_moments: RMSprop without the stamps / square_avg of table %d", f);
+  if (d->phase == 0) {
+    const long threads = (long)d->B * d->Fs * 4;
+    const int nrows = (int)((threads + 255) / 256), nblk = d->dense_blocks + nrows;
+    if (d->dense_blocks < 0 || nblk < 1) return nasrec_set_error(-2, "opt_moments: empty launch");
+    if (nrows > 0 && (!d->idx || !d->leader || !d->gsum || (!d->bitmap && !lazy))) return nasrec_set_error(-1, "opt_moments: row inputs missing");
+    if (d->rank_B < 0 || (d->rank_B > 0 && (d->rank_stride < (int64_t)d->rank_B * d->Fs * 16 || d->B % d->rank_B != 0)))
+      return nasrec_set_error(-2, "opt_moments: rank layout %d / %ld", d->rank_B, (long)d->rank_stride);
+    if (lazy && d->n_zero <= 0 && (!d->counter || (d->n_inc > 0 && !d->inc)))
+      return nasrec_set_error(-1, "opt_moments: %s without zero_chunks counts the steps: counter / inc missing", rmsprop ? "RMSprop" : "sparse_rows");
+    if (rmsprop) launch_phase0<LazyRmspropRows>(st, d, nblk);
+    else if (d->sparse_rows) launch_phase0<SparseAdamRows>(st, d, nblk);
+    else if (adam) launch_phase0<DenseRows<NASREC_OPTIM_ADAM>>(st, d, nblk);
+    else launch_phase0<DenseRows<NASREC_OPTIM_SGD>>(st, d, nblk);
+  } else if (d->phase == 1) {
+    if (d->nblocks <= 0) return nasrec_set_error(-1, "opt_moments: nblocks must be positive");
+    if (!d->bitmap || !d->counter || !d->coef) return nasrec_set_error(-1, "opt_moments: phase 1 inputs missing");
+    if (lazy && (d->n_zero <= 0 || d->tile_off[d->Fs] != 0))
+      return nasrec_set_error(-1, "opt_moments: %s has a phase 1 only to restore zero_chunks, and no table owns a tile", rmsprop ? "RMSprop" : "sparse_rows");
+    if (rmsprop) launch_phase1<NASREC_OPTIM_RMSPROP>(st, d);
+    else if (adam) launch_phase1<NASREC_OPTIM_ADAM>(st, d);
+    else launch_phase1<NASREC_OPTIM_SGD>(st, d);
+  } else {
+    if (d->nblocks <= 0 || !d->bitmap) return nasrec_set_error(-1, "opt_moments: flush needs nblocks > 0 and the (all-zero) bitmap");
+    if (d->tile_off[d->Fs] <= 0) return 0;
+    hipLaunchKernelGGL(opt_moments_flush_kernel, dim3((unsigned)d->nblocks), dim3(256), 0, st, *d);
+  }
+  return nasrec_check_launch("opt_moments");
 }

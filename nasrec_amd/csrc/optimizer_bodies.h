@@ -111,6 +111,23 @@ __device__ __forceinline__ float clip_coef_wave(const nasrec_clip_coef_desc_t& d
   return coef;
 }
 
+// head of the apply launch and of Adam / SGD / RMSprop's phase 0: wavefront 0 of every workgroup computes the clip coefficient into
+// *sh_coef (workgroup 0 writes clip.out); the caller synchronises
+__device__ __forceinline__ void clip_head(const nasrec_clip_coef_desc_t& clip, float* sh_coef) {
+  const int tid = threadIdx.x;
+  if (tid < 64) {
+    float total;
+    const float c = clip_coef_wave(clip, tid, &total);
+    if (tid == 0) {
+      *sh_coef = c;
+      if (blockIdx.x == 0) {
+        clip.out[0] = c;
+        clip.out[1] = total;
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // One element of each optimizer, g = the clipped gradient: Adagrad (the apply launch, NASREC_OP_OPT_APPLY) and Adam / momentum SGD
 // (NASREC_OP_OPT_MOMENTS); NASREC_OP_LAST_LAYER_STEP calls the same functions.  D = a descriptor with beta1, beta2, eps, momentum,

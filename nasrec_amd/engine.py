@@ -854,19 +854,27 @@ class SupernetEngine:
         o, n = self.offsets[name], self.params[name].numel()
         return flat[o:o + n].view(self.params[name].shape)
 
+    def _tile_layout(self, d, owns):
+        """table[f], rows[f] and the untouched-row pass's layout of 64-row tiles on descriptor `d`: table f owns the tiles
+        [tile_off[f], tile_off[f + 1]) where owns(f), none otherwise (the pass leaves it alone) -> bit mask of the tables that own tiles"""
+        mask, tile = 0, 0
+        for f in range(self.Fs):
+            d.table[f], d.rows[f], d.tile_off[f] = self.tables[f].data_ptr(), self.num_embeddings[f], tile
+            if owns(f):
+                mask |= 1 << f
+                tile += (self.num_embeddings[f] + 63) // 64
+        d.tile_off[self.Fs] = tile
+        return mask
+
     def _flush_desc(self):
         """RMSprop's flush launch (phase 2): every row of every table, in 64-row tiles"""
         m = L.OptMomentsDesc()
         m.kind, m.phase, m.algo = L.OP_OPT_MOMENTS, 2, L.OPTIM_RMSPROP
         m.nblocks, m.Fs, m.table_step0 = self.WD_BLOCKS, self.Fs, len(self.dense_names)
         m.beta2 = self._lazy_alpha
-        tile = 0
+        self._tile_layout(m, lambda f: True)
         for f in range(self.Fs):
-            m.table[f], m.rows[f] = self.tables[f].data_ptr(), self.num_embeddings[f]
             m.tv[f], m.tm[f] = self.moments["square_avg"][1][f].data_ptr(), self.lazy_stamps[f].data_ptr()
-            m.tile_off[f] = tile
-            tile += (self.num_embeddings[f] + 63) // 64
-        m.tile_off[self.Fs] = tile
         m.bitmap = self._row_bitmap().data_ptr()
         m.step, m.lr = self.opt_steps.data_ptr(), self.lr_dev.data_ptr()
         return m
@@ -959,18 +967,12 @@ class SupernetEngine:
             m.idx, m.leader, m.gsum = cat_x.data_ptr(), t.bufs.leader.data_ptr(), gsum
             if rank_layout:
                 m.rank_B, m.rank_stride = rank_layout
-        mask, tile = 0, 0
+        self._tile_layout(m, lambda f: f in t.mom_tables and not lazy)  # (a table that does not move owns no tile)
         for f in range(self.Fs):
-            m.table[f], m.tm[f], m.rows[f] = self.tables[f].data_ptr(), first[1][f].data_ptr(), self.num_embeddings[f]
+            m.tm[f] = first[1][f].data_ptr()
             if second is not None:
                 m.tv[f] = second[1][f].data_ptr()
-            m.tile_off[f] = tile
-            if f in t.mom_tables and not lazy:  # (a table that does not move owns no tile: phase 1 leaves it alone)
-                tile += (self.num_embeddings[f] + 63) // 64
-            if spec.wd and f in t.wd_tables:
-                mask |= 1 << f
-        m.tile_off[self.Fs] = tile
-        m.reg_mask = mask
+        m.reg_mask = sum(1 << f for f in t.wd_tables) if spec.wd else 0
         m.bitmap = self._row_bitmap().data_ptr()
         m.step = self.opt_steps.data_ptr()
         m.inc, m.n_inc = t.mom_inc
@@ -995,17 +997,10 @@ class SupernetEngine:
             w.idx, w.leader, w.gsum = cat_x.data_ptr(), t.bufs.leader.data_ptr(), gsum
             if rank_layout:
                 w.rank_B, w.rank_stride = rank_layout
-        mask, tile = 0, 0
-        for f in range(self.Fs):
-            w.table[f], w.rows[f] = self.tables[f].data_ptr(), self.num_embeddings[f]
-            if self.table_state is not None:  # (read by phase 1 only, which Adam / SGD plans do not launch)
+        mask = w.reg_mask = self._tile_layout(w, lambda f: f in t.wd_tables)
+        if self.table_state is not None:  # (read by phase 1 only, which Adam / SGD plans do not launch)
+            for f in range(self.Fs):
                 w.state[f] = self.table_state[f].data_ptr()
-            w.tile_off[f] = tile
-            if f in t.wd_tables:
-                mask |= 1 << f
-                tile += (self.num_embeddings[f] + 63) // 64
-        w.tile_off[self.Fs] = tile
-        w.reg_mask = mask
         w.bitmap = self._row_bitmap().data_ptr()
         if t.spec.moments and mask != (1 << self.Fs) - 1:
             # Adam / SGD mark the touched rows of EVERY table, in a layout over all tables: phase 0's marks (over the regularised

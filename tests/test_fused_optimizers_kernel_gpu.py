@@ -2,7 +2,8 @@
 restatement of torch's formulas: small tables whose rows do not fill a tile, duplicate ids (leaders only), ids at and past the table
 end, dense chunks whose lengths are not multiples of 4, parameters with different step counts, a parameter outside the chunk table,
 the clip active and inactive, weight decay on and off.  The touched-row bitmap is all zero behind the step, the counters of exactly
-the listed parameters move, and two runs of the same step give the same bits."""
+the listed parameters move, and two runs of the same step give the same bits.  B = 8 leaves one row workgroup partly filled; B = 300
+fills ten, the last one partly."""
 import ctypes as C
 
 import numpy as np
@@ -24,7 +25,7 @@ INC = [0, 1, 3, 4]                    # the reached parameters and the tables
 ZERO = [(112, 6)]                     # a range whose gradient phase 1 sets back to zero
 
 
-def _case(seed):
+def _case(seed, B=B):
     g = torch.Generator().manual_seed(seed)
     c = {"tables": [torch.randn(n, 16, generator=g) for n in ROWS], "tm": [torch.randn(n, 16, generator=g) * 0.1 for n in ROWS],
          "tv": [torch.rand(n, 16, generator=g) * 0.01 for n in ROWS], "p": torch.randn(N_DENSE, generator=g),
@@ -47,6 +48,7 @@ def _case(seed):
 
 def _run(kind, c, max_norm, wd, lr=0.01, nesterov=True):
     dev = torch.device("cuda", 0)
+    B = int(c["idx"].shape[0])
     t = {k: ([x.clone().to(dev) for x in v] if isinstance(v, list) else v.clone().to(dev)) for k, v in c.items()}
     steps = torch.tensor(STEPS0, dtype=torch.float32, device=dev)
     tab = torch.tensor([v for ch in CHUNKS for v in ch] + INC + [v for z in ZERO for v in z], dtype=torch.int64, device=dev)
@@ -115,11 +117,8 @@ def _close(a, b, what):
     assert np.allclose(a, b, rtol=2e-6, atol=2e-7), (what, float(err))
 
 
-@pytest.mark.parametrize("kind", ["adam", "sgd"])
-@pytest.mark.parametrize("max_norm", [5.0, 0.0], ids=["clip-active", "clip-off"])
-@pytest.mark.parametrize("wd", [0.0, 0.05], ids=["wd0", "wd"])
-def test_opt_moments_kernel_against_fp64(kind, max_norm, wd):
-    c = _case(11)
+def _check_against_fp64(kind, max_norm, wd, B):
+    c = _case(11, B)
     out = _run(kind, c, max_norm, wd)
     lr = float(np.float32(0.01))
     coef = float(out["clip"][0])
@@ -163,6 +162,22 @@ def test_opt_moments_kernel_against_fp64(kind, max_norm, wd):
         assert torch.equal(out[key], again[key]), key
     for f in range(FS):
         assert torch.equal(out["tables"][f], again["tables"][f]) and torch.equal(out["tm"][f], again["tm"][f])
+
+
+@pytest.mark.parametrize("kind", ["adam", "sgd"])
+@pytest.mark.parametrize("max_norm", [5.0, 0.0], ids=["clip-active", "clip-off"])
+@pytest.mark.parametrize("wd", [0.0, 0.05], ids=["wd0", "wd"])
+def test_opt_moments_kernel_against_fp64(kind, max_norm, wd):
+    _check_against_fp64(kind, max_norm, wd, B)
+
+
+@pytest.mark.parametrize("kind", ["adam", "sgd"])
+@pytest.mark.parametrize("max_norm", [5.0, 0.0], ids=["clip-active", "clip-off"])
+@pytest.mark.parametrize("wd", [0.0, 0.05], ids=["wd0", "wd"])
+def test_opt_moments_kernel_against_fp64_ten_row_workgroups(kind, max_norm, wd):
+    """B = 300: 2400 row threads fill ten row workgroups, the last one partly; the same tables, fp64 reference and bars, ids at and
+    past the table end, duplicates, and the bitmap all zero behind phase 1"""
+    _check_against_fp64(kind, max_norm, wd, 300)
 
 
 def test_sgd_without_nesterov_and_first_step_buffer():

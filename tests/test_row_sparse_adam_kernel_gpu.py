@@ -3,7 +3,8 @@ of torch.optim.SparseAdam on the touched rows and torch.optim.Adam on the dense 
 (tables of 100 and 70 rows, B = 8 with duplicates and ids at and past the table end, dense chunks of 37 / 32 / 30 floats with their
 own step counts, a parameter outside the chunk table, clip active and off) and B = 300, whose rows span ten workgroups.  Every row
 outside the batch keeps its bits in W and both moments; the bitmap stays all zero; exactly the listed counters move, once — by the
-single phase-0 launch without zero_chunks, by phase 0 + phase 1 with them."""
+single phase-0 launch without zero_chunks, by phase 0 + phase 1 with them.  The summed rows in the receive buffer of an all-gather
+(two rank chunks with a NaN-filled gap between them) give the bits of the contiguous array."""
 import ctypes as C
 
 import numpy as np
@@ -51,10 +52,19 @@ def _case(seed, B):
     return c
 
 
-def _run(c, max_norm, zero, algo=None, sparse=1, phases=None, eps=1e-8):
+RANKS, GAP = 2, 36  # the rank layout: two chunks of B / 2 samples, 36 floats of something else behind each
+
+
+def _run(c, max_norm, zero, algo=None, sparse=1, phases=None, eps=1e-8, ranked=False):
     dev = torch.device("cuda", 0)
     B = int(c["idx"].shape[0])
     t = {k: ([x.clone().to(dev) for x in v] if isinstance(v, list) else v.clone().to(dev)) for k, v in c.items()}
+    rb, stride = B // RANKS, B // RANKS * FS * 16 + GAP
+    if ranked:  # (as test_dp_layout_kernel_gpu.py builds its buffer)
+        buf = torch.full((RANKS * stride,), float("nan"))
+        for r in range(RANKS):
+            buf[r * stride:r * stride + rb * FS * 16] = c["gsum"][r * rb:(r + 1) * rb].reshape(-1)
+        t["gsum"] = buf.to(dev)
     steps = torch.tensor(STEPS0, dtype=torch.float32, device=dev)
     tab = torch.tensor([v for ch in CHUNKS for v in ch] + INC + [v for z in ZERO for v in z], dtype=torch.int64, device=dev)
     bitmap = torch.zeros(sum(2 * ((n + 63) // 64) for n in ROWS), dtype=torch.int32, device=dev)
@@ -75,6 +85,8 @@ def _run(c, max_norm, zero, algo=None, sparse=1, phases=None, eps=1e-8):
     d.chunks, d.nchunks = tab.data_ptr(), len(CHUNKS)
     d.p, d.g, d.m, d.v = t["p"].data_ptr(), t["g"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr()
     d.idx, d.leader, d.gsum = t["idx"].data_ptr(), t["leader"].data_ptr(), t["gsum"].data_ptr()
+    if ranked:
+        d.rank_B, d.rank_stride = rb, stride
     for f in range(FS):  # (no table owns a tile: tile_off stays all zero)
         d.table[f], d.tm[f], d.tv[f], d.rows[f] = t["tables"][f].data_ptr(), t["tm"][f].data_ptr(), t["tv"][f].data_ptr(), ROWS[f]
     d.bitmap, d.step = bitmap.data_ptr(), steps.data_ptr()
@@ -91,6 +103,10 @@ def _run(c, max_norm, zero, algo=None, sparse=1, phases=None, eps=1e-8):
         rcs.append(lib.nasrec_opt_moments(s, C.addressof(x)))
     torch.cuda.synchronize()
     out = {k: ([x.cpu() for x in v] if isinstance(v, list) else v.cpu()) for k, v in t.items()}
+    if ranked:
+        buf = out["gsum"]
+        assert torch.isnan(torch.cat([buf[r * stride + rb * FS * 16:(r + 1) * stride] for r in range(RANKS)])).all(), "the gap was written"
+        out["gsum"] = torch.cat([buf[r * stride:r * stride + rb * FS * 16].view(rb, FS, 16) for r in range(RANKS)])
     out["steps"], out["bitmap"], out["counter"], out["clip"], out["rc"] = steps.cpu(), bitmap.cpu(), counter.cpu(), clip_out.cpu(), rcs
     return out
 
@@ -176,6 +192,24 @@ def test_sparse_rows_kernel_against_fp64(B, max_norm, zero, eps):
     for f in range(FS):
         for key in ("tables", "tm", "tv"):
             assert torch.equal(out[key][f], again[key][f]), (key, f)
+
+
+@pytest.mark.parametrize("max_norm", [5.0, 0.0], ids=["clip-active", "clip-off"])
+@pytest.mark.parametrize("zero", [False, True], ids=["one-launch", "zero-chunks"])
+def test_sparse_rows_kernel_reads_the_rank_layout(max_norm, zero):
+    """the B = 8 case with gsum in two rank chunks (rank_B = 4) and a NaN-filled gap between them: every output has the bits of the
+    contiguous run, and the gap is neither read nor written"""
+    c = _case(11, 8)
+    flat, ranked = _run(c, max_norm, zero), _run(c, max_norm, zero, ranked=True)
+    assert flat["rc"] == ranked["rc"] == [0] * (2 if zero else 1), (flat["rc"], ranked["rc"], L.load().nasrec_last_error())
+    assert set(flat) == set(ranked)
+    for key in flat:
+        if isinstance(flat[key], list) and key != "rc":
+            for f in range(FS):
+                assert torch.equal(flat[key][f], ranked[key][f]), (key, f)
+        elif key != "rc":
+            assert torch.equal(flat[key], ranked[key]), key
+    assert any(not torch.equal(a, b) for a, b in zip(flat["tables"], c["tables"]))  # (touched rows moved)
 
 
 def test_phase_0_leaves_the_counting_to_phase_1_when_there_are_zero_chunks():
