@@ -7,7 +7,7 @@
 #include "dedup_bodies.h"
 
 #define WL_LDS_BIG_FLOATS 9888  // 39.5 KB, 4 workgroups per CU: the Transformer backward (MHA_TOK_BWD_LDS_FLOATS)
-#define WL_LDS_FLOATS 7840  // 31 KB (5 workgroups per CU): the DotProduct cores up to k1 = 48; a 64x16x64 GEMM tile needs 5568, the Transformer forward 3744
+#define WL_LDS_FLOATS 7840  // 31 KB (5 workgroups per CU): the DotProduct cores up to k1 = 46 (4 * (k1 * TRI_LD + P4) floats: 47 needs 8096); a 64x16x64 GEMM tile needs 5568, the Transformer forward 3744
 static_assert(MHA_TOK_BWD_LDS_FLOATS <= WL_LDS_BIG_FLOATS && MHA_TOK_FWD_LDS_FLOATS <= WL_LDS_FLOATS, "Transformer bodies fit the worklist launches");
 
 #define WL_TK 64  // staged k depth of every GEMM item (a product with K <= 32 pads its one tile with zeros: same sums, bit for bit)

@@ -541,7 +541,7 @@ SOLO_TILES = int(os.environ.get("NASREC_WL_SOLO_TILES", "256"))
 
 def gemm_capable(d) -> bool:
     """mirror of csrc/worklist.hip wl_gemm_geometry: can this GEMM launch run as a worklist item?"""
-    if d.splitk == L.SPLITK_BALANCED or d.defer_second_pass:
+    if d.splitk == L.SPLITK_BALANCED or d.defer_second_pass or d.nseg < 1 or d.nseg > L.MAX_SEGS:
         return False
     kca, kcb = d.amode in (L.AM_KC, L.AM_TOKK), d.bmode in (L.AM_KC, L.AM_TOKK)
     if not kca and kcb:
@@ -580,6 +580,8 @@ def item_bytes(node):
     if isinstance(d, L.GemmDesc):
         if not gemm_capable(d):
             return None
+        if (node.part == "whole") != (d.splitk <= 1):  # (wl_gemm_geometry: a split product travels as main + second pass, an unsplit one whole)
+            return None
         return C.string_at(C.addressof(d), _GEMM_HEAD + d.nseg * _SEG_BYTES)
     if k in (L.OP_DOT_TRI_FWD, L.OP_DOT_TRI_BWD):
         P4 = (d.k1 * (d.k1 - 1) // 2 + 3) & ~3
@@ -587,7 +589,12 @@ def item_bytes(node):
             return None
     if k in (L.OP_MHA_FWD, L.OP_MHA_BWD) and (d.N < 1 or d.N > 64 or (k == L.OP_MHA_BWD and not d.saved)):
         return None
-    if k == L.OP_DEDUP_IDS and (d.B > 256 or d.cap != 256):
+    if k == L.OP_DEDUP_IDS and (d.B < 1 or d.B > 256 or d.cap != 256 or d.Fs < 1 or d.Fs > L.MAX_TABLES
+                                or not (d.idx and d.leader and d.order and d.lists and d.counts)):
+        return None
+    if k == L.OP_FINAL_FUSED and (not (d.y and d.logits and d.bias and d.w) or d.nsplit > 1 or any(d.dseg[q] and not d.seg[q] for q in range(d.nseg))):
+        return None  # (csrc/norm_loss_opt.hip final_fused_check)
+    if k == L.OP_FINAL_BWD and d.y and not d.logits:
         return None
     if k in _PLAIN_KINDS:
         return C.string_at(C.addressof(d), C.sizeof(d))
