@@ -88,7 +88,8 @@ enum {
   NASREC_OP_WEIGHT_DECAY = 39,
   NASREC_OP_OPT_MOMENTS = 40,
   NASREC_OP_LAST_LAYER_STEP = 41,
-  NASREC_OP_ROC_AUC = 42
+  NASREC_OP_ROC_AUC = 42,
+  NASREC_OP_WEIGHT_EMA = 43
 };
 
 /* algorithm of NASREC_OP_OPT_MOMENTS (ADAGRAD: NASREC_OP_LAST_LAYER_STEP only) */
@@ -667,6 +668,49 @@ typedef struct nasrec_roc_auc_desc {
 } nasrec_roc_auc_desc_t;
 
 /* ------------------------------------------------------------------------------------------------
+ * Exponential moving average of the weights (utils/optim.WeightEMA; DESIGN.md "Lazy weight EMA"): one shadow value s per parameter
+ * value p, after every optimizer step
+ *   s = fmaf(w, p - s, s),  w = (float)(1 - decay)                                   (the dense statement, fp32)
+ * on the dense arena and on EVERY table row.  A row whose weights rest for n steps obeys s <- p + decay^n (s - p), so the rows
+ * outside the batch are not walked: stamp[f][row] (one 32-bit word per row) = the update number at which s of that row is current,
+ * *count = the number of updates applied.  Invariant: stamp <= count, and the row's weights have not changed since its stamp.
+ * Appended WITHOUT a new nasrec_abi_version(), as NASREC_OP_ROC_AUC was (a binding's layout check covers it).
+ *   phase 0 (catch-up; before anything in the optimizer tail writes a table row): 4 lanes x float4 per (sample, field) pair; a leader
+ *     with its id in range: n = count - stamp; n > 0: s = (float)(p + pow(decay, n) (s - p)) in fp64, one rounding, and stamp = count;
+ *     n = 0 touches nothing.  Non-leaders, ids outside [0, rows[f]) and B = 0 write nothing.
+ *   phase 1 (update; behind the last launch that writes parameters): workgroups [0, dense_blocks) apply the dense statement to the
+ *     whole arena p / s [n]; the others apply it to the leader rows (which phase 0 left current) and set stamp = count + 1.  The
+ *     workgroup that arrives last at `counter` (zero before, left zero) adds 1 to *count: every workgroup has read it by then.
+ *   phase 2 (flush): every row of every table, in the 64-row tiles of tile_off (`bitmap`: all zero, only read): stamp < count takes
+ *     the catch-up and stamp = count.  Idempotent.  nblocks workgroups.
+ *   phase 3 (exchange): the flush, then p <-> s on every table row (nblocks workgroups) and every dense element (dense_blocks
+ *     workgroups), one pass.  Twice = the identity on both arrays, bit for bit.
+ * Refused (-1, nothing launched): a stamp, shadow or table pointer missing, decay outside (0, 1), a phase outside [0, 3], count or
+ * (phase 1) counter missing.  Same inputs -> same bits.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct nasrec_weight_ema_desc {
+  int32_t kind;  /* NASREC_OP_WEIGHT_EMA */
+  int32_t phase; /* 0 catch-up, 1 update, 2 flush, 3 exchange */
+  int32_t B, Fs; /* [B, Fs] id / leader arrays (B = 0: no touched rows) */
+  int32_t dense_blocks; /* phases 1 and 3: workgroups on the dense arena */
+  int32_t nblocks;      /* phases 2 and 3: workgroups on the tables */
+  double decay;
+  const int64_t* idx;    /* [B,Fs] */
+  const int32_t* leader; /* [B,Fs] */
+  float* table[NASREC_MAX_TABLES];
+  float* shadow[NASREC_MAX_TABLES];
+  uint32_t* stamp[NASREC_MAX_TABLES];
+  int64_t rows[NASREC_MAX_TABLES];
+  int64_t tile_off[NASREC_MAX_TABLES + 1]; /* phases 2 and 3: over ALL tables */
+  uint32_t* bitmap;      /* [2 tile_off[Fs]], all zero, read only */
+  float* p;              /* dense arena [n] */
+  float* s;              /* its shadow [n] */
+  int64_t n;
+  uint32_t* count;       /* device word: updates applied */
+  uint32_t* counter;     /* phase 1: the last arrival (zero before, left zero) */
+} nasrec_weight_ema_desc_t;
+
+/* ------------------------------------------------------------------------------------------------
  * The row-sparse embedding backward in two halves (round 5).  NASREC_OP_EMB_DEDUP above does everything behind the backward pass;
  * but which sample leads a row, and which samples repeat it, depends on the IDS only — known before the forward pass starts (one
  * GPU: when the batch is staged; N GPUs: when the ids all-gather lands, nasrec_amd/parallel.py).  So:
@@ -957,6 +1001,7 @@ int nasrec_weight_decay(void* stream, const nasrec_weight_decay_desc_t* d);
 int nasrec_opt_moments(void* stream, const nasrec_opt_moments_desc_t* d);
 int nasrec_last_layer_step(void* stream, const nasrec_last_layer_step_desc_t* d);
 int nasrec_roc_auc(void* stream, const nasrec_roc_auc_desc_t* d);
+int nasrec_weight_ema(void* stream, const nasrec_weight_ema_desc_t* d);
 int64_t nasrec_roc_auc_workspace_bytes(int64_t n); /* 0 for n < 2 or n > NASREC_ROC_AUC_MAX_N */
 int nasrec_worklist(void* stream, const nasrec_worklist_desc_t* d);
 

@@ -576,6 +576,8 @@ class SupernetEngine:
                     cp.level_tuning = None
                     if persist:
                         try:
+                            if spec.ema:
+                                raise S.PersistRefused("a weight-EMA plan keeps the default launches")
                             fb_descs, cp.fb_levels = S.pack_persistent(
                                 ids_in_program + jf + jb, lambda nb: torch.empty(max(int(nb), 16), dtype=torch.uint8, device=self.device),
                                 arena.ranges, alloc=ctx.alloc)
@@ -1142,7 +1144,98 @@ class SupernetEngine:
             apply = [m0]
         else:
             apply = [app] if rows else [cc, ad]
-        return reduce + ([wd0] if wd0 is not None else []) + apply + ([phase1] if phase1 is not None else [])
+        ema0, ema1 = [], []
+        if spec.ema:
+            # the weight average (csrc/weight_ema.hip): the batch's rows pay what they owe once the leaders are known and before
+            # anything moves them; every parameter is averaged behind the last launch that writes one
+            ema0, ema1 = self._ema_step_descs(spec, Bg if rows else 0, cat_x, b.leader)
+        return reduce + ema0 + ([wd0] if wd0 is not None else []) + apply + ([phase1] if phase1 is not None else []) + ema1
+
+    EMA_DENSE_BLOCKS = 1024  # workgroups on the dense arena (the apply launch's measured optimum for the same stream of 2.2 M floats)
+
+    def ensure_ema_state(self, decay: float):
+        """The weight average of utils/optim.WeightEMA in the engine: `ema_flat` (the layout of flat_p) and `ema_tables[f]`, both
+        initialised from the current parameters; `ema_stamps[f]`, one int32 per row = the update number at which that row's average
+        is current; `ema_count` = updates applied (csrc/weight_ema.hip).  One decay per engine."""
+        decay = float(decay)
+        if not 0.0 < decay < 1.0:
+            raise L.EngineError("weight EMA: decay %r is not inside (0, 1)" % (decay,))
+        if self.host_embedding:
+            raise L.EngineError("the fused weight EMA needs the embedding tables on the device")
+        have = getattr(self, "ema_decay", None)
+        if have is not None:
+            if have != decay:
+                raise L.EngineError("weight EMA: this engine averages with decay %r, not %r" % (have, decay))
+            return
+        with torch.cuda.stream(self.stream):
+            self.ema_flat = self.flat_p.detach().clone()
+            self.ema_tables = [t.detach().clone() for t in self.tables]
+            self.ema_stamps = [torch.zeros(n, dtype=torch.int32, device=self.device) for n in self.num_embeddings]
+            self.ema_count = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self._ema_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._row_bitmap()
+        self.stream.synchronize()
+        self.ema_decay, self.ema_swapped = decay, False
+
+    def ema_view(self, name: str):
+        """engine storage of the average of parameter `name` (shape of the parameter)"""
+        if name.startswith("_embedding."):
+            return self.ema_tables[int(name.split(".")[1])]
+        o, n = self.offsets[name], self.params[name].numel()
+        return self.ema_flat[o:o + n].view(self.params[name].shape)
+
+    def _ema_desc(self, phase: int):
+        d = L.WeightEmaDesc()
+        d.kind, d.phase, d.Fs, d.decay = L.OP_WEIGHT_EMA, phase, self.Fs, self.ema_decay
+        d.dense_blocks = max(1, min(self.EMA_DENSE_BLOCKS, (self.flat_numel // 4 + 255) // 256))
+        d.nblocks = self.WD_BLOCKS
+        self._tile_layout(d, lambda f: phase >= 2)
+        for f in range(self.Fs):
+            d.shadow[f], d.stamp[f] = self.ema_tables[f].data_ptr(), self.ema_stamps[f].data_ptr()
+        d.bitmap = self._row_bitmap().data_ptr()
+        d.p, d.s, d.n = self.flat_p.data_ptr(), self.ema_flat.data_ptr(), self.flat_numel
+        d.count, d.counter = self.ema_count.data_ptr(), self._ema_counter.data_ptr()
+        return d
+
+    def _ema_step_descs(self, spec, Bg, cat_x, leader):
+        """([catch-up], [update]) of a training plan with spec.ema: phases 0 and 1 over the batch's leaders (Bg = 0: no gradient
+        reaches the stem, no row moves — the update still averages the dense arena and counts, and the tables' rows owe)"""
+        self.ensure_ema_state(spec.ema)
+        out = []
+        for phase in (0, 1):
+            d = self._ema_desc(phase)
+            d.B = Bg
+            if Bg:
+                d.idx, d.leader = cat_x.data_ptr(), leader.data_ptr()
+            out.append([d])
+        return out
+
+    def _ema_launch(self, phase: int):
+        d = self._ema_desc(phase)
+        L.check(L.load().nasrec_weight_ema(self.stream.cuda_stream, C.addressof(d)))
+        self.stream.synchronize()  # (the reader may sit on another stream)
+
+    @_on_device
+    def flush_ema_rows(self):
+        """bring the average of every table row current (a row outside the batches owes decay^n since its stamp): what a reader of
+        the shadow needs.  One streaming launch, waited for; a no-op without EMA state."""
+        if getattr(self, "ema_decay", None) is not None:
+            torch.cuda.current_stream(self.device).synchronize()
+            self._ema_launch(2)
+
+    @_on_device
+    def swap_ema(self):
+        """exchange the parameters with their average, every row flushed first: one launch.  Called twice it restores both, bit for
+        bit; in between train_step and last_layer_step refuse (the engine would train the averaged weights)."""
+        if getattr(self, "ema_decay", None) is None:
+            raise L.EngineError("swap_ema: this engine keeps no weight average (ensure_ema_state)")
+        torch.cuda.current_stream(self.device).synchronize()
+        self._ema_launch(3)
+        self.ema_swapped = not self.ema_swapped
+
+    def _refuse_swapped(self, what):
+        if getattr(self, "ema_swapped", False):
+            raise L.EngineError("%s while the parameters hold their weight average (swap_ema / WeightEMA.averaged): leave it first" % what)
 
     @_on_device
     def reserve(self, B: int, train: bool = True, choice=None, freeze_gc: bool = False):
@@ -1284,7 +1377,7 @@ class SupernetEngine:
 
     @_on_device
     def train_step(self, int_x, cat_x, y, lr: float, choice=None, clip: Optional[float] = 5.0, eps: float = 1e-2, graph: Optional[bool] = False,
-                   staged: bool = False, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None):
+                   staged: bool = False, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None, ema: float = 0.0):
         """zero_grad -> forward -> BCE -> backward -> clip_grad_norm_ -> Adagrad (train_utils.py:262-286).
         Returns the (device) loss tensor of this step.  `staged`: inputs are already in the plan's static buffers.  graph: True = replay
         the captured step, False = launch its program, None = whichever is faster for this plan (prefers_graph).
@@ -1292,7 +1385,15 @@ class SupernetEngine:
         every regularised parameter and EVERY table row is decayed; wd_l2_sumsq then holds sum ||W||^2 of the pre-step weights.
         optim: an OptimSpec of kind adam / sgd replaces Adagrad (eps is then unused): torch.optim.Adam / SGD over the parameters the step
         reaches and EVERY table row, state in `moments` and `opt_steps` (ensure_moments_state); with sparse_rows the tables move in the
-        batch's rows only (utils/optim.RowSparseAdam), and weight decay must leave them out."""
+        batch's rows only (utils/optim.RowSparseAdam), and weight decay must leave them out.
+        ema: the decay of a weight average kept beside the step (ensure_ema_state; csrc/weight_ema.hip): two more launches in the
+        optimizer tail, exact only where the tables move in the batch's rows alone (Adagrad, row-sparse Adam, RMSprop; no regularised
+        table) — refused otherwise."""
+        self._refuse_swapped("train_step")
+        if ema and ((optim is not None and optim.kind in ("adam", "sgd") and not optim.sparse_rows)
+                    or (weight_decay and P.regularised(self.shapes, no_reg_param_name)[1])):
+            raise L.EngineError("the fused weight EMA averages the batch's table rows only: dense Adam, momentum SGD and a regularised "
+                                "table move every row (WeightEMA.update() on the torch route is the dense form)")
         choice = choice if choice is not None else self.warm_choice
         if graph is None:
             graph = self.cfg.fixed and self.prefers_graph(int(int_x.shape[0]) if int_x is not None else int(self._last_plan[2].cat_x.shape[0]))
@@ -1304,7 +1405,7 @@ class SupernetEngine:
         else:  # pre-staged inputs: the batch size is the one of the plan they were staged into
             assert staged and self._last_plan is not None, "train_step without inputs needs a previously compiled plan holding them"
             B = int(self._last_plan[2].cat_x.shape[0])
-        cp = self.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, spec=OptimSpec.of(eps, weight_decay, no_reg_param_name, optim))
+        cp = self.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, spec=OptimSpec.of(eps, weight_decay, no_reg_param_name, optim, ema))
         sp = self._sp()
         if not staged:
             whole = not graph and getattr(cp, "fb", None) is not None and not self.host_embedding
@@ -1397,6 +1498,7 @@ class SupernetEngine:
         (nothing else) -> [+ 2 wd W] -> clip_grad_norm_ over _final -> Adagrad (state: self.state) / Adam / SGD (optim, state:
         ensure_last_layer_state) on _final.{weight, bias} alone.  Returns the (device) loss.  graph: replay a captured program (fixed
         sub-networks).  The plan is the one the autograd route runs (compile(choice, B, train=True))."""
+        self._refuse_swapped("last_layer_step")
         choice = choice if choice is not None else self.warm_choice
         if self.host_embedding:
             raise L.EngineError("the last-layer step needs the embedding tables on the device")
@@ -1440,6 +1542,7 @@ class SupernetEngine:
         self.last_layer_plan = None
         self._uc_flat_arena = None
         self._sk_ws = None
+        self.ema_flat = self.ema_tables = self.ema_stamps = self.ema_count = self._ema_counter = self.ema_decay = None
 
     @_on_device
     def run_forward(self, cp, int_x, cat_x, rows=None):

@@ -97,6 +97,10 @@ def train_and_eval_one_model(model, args):
     from nasrec_amd.utils.dist import assert_replicas_identical, broadcast_replica_state
     broadcast_replica_state(model)  # data parallel: rank 0's weights, tables and accumulators are THE model
     assert_replicas_identical(model, optimizer)
+    ema = None
+    if args.ema > 0:  # (after the broadcast: every rank's average starts from THE model)
+        from nasrec_amd.utils.optim import WeightEMA
+        ema = WeightEMA(model, args.ema)
     print(model)
     create_dir(args.logging_dir)
     with open(os.path.join(args.logging_dir, "configs_args.json"), "w") as f:
@@ -108,16 +112,16 @@ def train_and_eval_one_model(model, args):
             model, epoch, optimizer, lr_scheduler, train_loader, test_loader, loss_fn, l2_loss_fn, args.train_batch_size, args.gpu,
             display_interval=args.display_interval, test_interval=args.test_interval if epoch != 1 else 100,
             max_train_steps=steps_per_epoch if epoch != 1 else 1000, test_only_at_last_step=(args.test_only_at_last_step) == 1,
-            tb_writer=writer, use_amp=False, grad_clip_value=5.0)
+            tb_writer=writer, use_amp=False, grad_clip_value=5.0, ema=ema)
         epoch_logs.append(logs)
     print("Dumping logs to {}!".format(args.logging_dir))
     from nasrec_amd.utils.dist import world_info
     ckpt = os.path.join(args.logging_dir, "{}_checkpoint.pt".format(args.net))
     if world_info()[0] == 0:  # replicas are identical (broadcast at start, same global-batch update on every rank): rank 0 writes the artefacts
-        save_model_checkpoint(model, ckpt, optimizer)
+        save_model_checkpoint(model, ckpt, optimizer, ema=ema)
         dump_pickle_data(os.path.join(args.logging_dir, "train_test_logs.pickle"), epoch_logs)
     elif getattr(model, "_table_sharding", None):  # row-sharded tables: the whole-table state_dict is a collective
-        save_model_checkpoint(model, None, optimizer)  # (tables and their accumulators are gathered: every rank takes part)
+        save_model_checkpoint(model, None, optimizer, ema=ema)  # (tables and their accumulators are gathered: every rank takes part)
     return epoch_logs
 
 
@@ -146,6 +150,13 @@ def main(args):
     print("Matmul precision: {}".format(args.matmul_precision))
     model = get_model(args).to(args.gpu)
     return train_and_eval_one_model(model, args)
+
+
+def _ema_strength(text):
+    v = float(text)
+    if not 0.0 <= v < 1.0:
+        raise argparse.ArgumentTypeError("--ema %r is not in [0, 1)" % (text,))
+    return v
 
 
 def build_parser():
@@ -177,7 +188,11 @@ def build_parser():
     p.add_argument("--no-reg-param-name", type=str, default=None, help="Name of the parameters that do not need to be regularized.")
     p.add_argument("--loss_function", type=str, default="bce", help="Loss function to perform the task.", choices=["bce"])
     p.add_argument("--test_only_at_last_step", type=int, default=0, help="Whether only test the last step.")
-    p.add_argument("--ema", type=float, default=0.0, help="EMA strength ranging from 0 to 1 (not implemented, as in the reference).")
+    p.add_argument("--ema", type=_ema_strength, default=0.0,
+                   help="EMA strength in [0, 1); 0.9 / 0.99 / ... is recommended, 0 = off.  Keeps an exponential moving average of every "
+                        "weight, s += (1 - ema) (w - s) after every optimizer step (utils/optim.WeightEMA); the tests run on the averaged "
+                        "weights and the checkpoint carries them as ema_state_dict.  Inside the fused step with --optimizer adagrad / "
+                        "row-sparse-adam / rmsprop and no weight decay on the tables, on the torch route otherwise")
     p.add_argument("--gpu", type=int, default=None, help="GPU ID to use.")
     # not a reference flag: placement of the embedding tables under torchrun (nasrec_amd/sharded_tables.py)
     p.add_argument("--table-sharding", dest="table_sharding", type=str, default="none", choices=["none", "row"],

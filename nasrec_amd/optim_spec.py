@@ -21,6 +21,7 @@ class OptimSpec(NamedTuple):
     no_reg: Optional[str] = None
     sparse_rows: bool = False  # Adam: row-sparse on the tables (utils/optim.RowSparseAdam: torch.optim.SparseAdam on the batch's rows)
     alpha: float = 0.99     # RMSprop's smoothing constant (utils/optim.LazyRMSprop: momentum 0, not centered)
+    ema: float = 0.0        # decay of a weight average kept beside the step (utils/optim.WeightEMA, csrc/weight_ema.hip); 0 = none
 
     @property
     def moments(self) -> bool:
@@ -33,14 +34,18 @@ class OptimSpec(NamedTuple):
         return {"adagrad": ("sum",), "adam": ("exp_avg", "exp_avg_sq"), "rmsprop": ("square_avg",)}.get(self.kind, ("momentum_buffer",))
 
     @staticmethod
-    def of(eps: float = 1e-2, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None) -> "OptimSpec":
+    def of(eps: float = 1e-2, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None, ema: float = 0.0) -> "OptimSpec":
         """the public entry points' optimizer arguments as one spec: optim None = Adagrad with `eps` (its only source: the default eps
-        of a spec is Adam's), else an Adam / SGD spec; no_reg_param_name only counts with weight decay"""
+        of a spec is Adam's), else an Adam / SGD spec; no_reg_param_name only counts with weight decay; ema: the decay of the weight
+        average the step keeps (0 = none, or what `optim` already carries)"""
         if optim is not None and not optim.moments:
             raise ValueError("optim is an Adam / SGD spec; Adagrad is optim=None with its eps")
         wd = float(weight_decay or 0.0)
         base = optim if optim is not None else OptimSpec("adagrad", eps=float(eps))
-        return base._replace(wd=wd, no_reg=no_reg_param_name if wd else None)
+        ema = float(ema or 0.0)
+        if ema and not 0.0 < ema < 1.0:
+            raise ValueError("ema decay %r is not inside (0, 1)" % (ema,))
+        return base._replace(wd=wd, no_reg=no_reg_param_name if wd else None, ema=ema if ema else base.ema)
 
     @staticmethod
     def from_optimizer(optimizer) -> Optional["OptimSpec"]:

@@ -622,7 +622,7 @@ class SuperNet(nn.Module):
         return self.forward(int_feats, cat_feats, choices)
 
     def engine_train_step(self, int_feats, cat_feats, y, lr: float, clip: Optional[float] = 5.0, eps: float = 1e-2, graph=None,
-                          weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None):
+                          weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None, ema_decay: float = 0.0):
         """Fused step on the engine (forward, BCE, backward, clip_grad_norm_, Adagrad with row-sparse table update):
         the counterpart of train_utils.py:262-286 for optimizer == Adagrad (torch's own weight_decay == 0).  weight_decay != 0: the loss
         is BCE + get_l2_loss(self, weight_decay, no_reg_param_name) — every regularised parameter and every table row is decayed
@@ -630,13 +630,21 @@ class SuperNet(nn.Module):
         replaces Adagrad (eps unused) — every table row moves every step, or with sparse_rows (utils/optim.RowSparseAdam) only the
         batch's rows, which weight decay must then leave out; engine_bind_optimizer / engine_sync_optimizer_steps share its
         state with the torch optimizer.  Both need whole tables; under data parallelism they run in the exchange step's optimizer over
-        the global batch (nasrec_amd/parallel.py)."""
+        the global batch (nasrec_amd/parallel.py).  ema_decay != 0: the step also averages every parameter (utils/optim.WeightEMA's
+        update, in the engine: engine_bind_ema / engine_sync_ema share the average with a WeightEMA) — one process, whole tables, and an
+        optimizer whose tables move in the batch's rows only (Adagrad, row-sparse Adam, RMSprop; no regularised table)."""
         if self._place_embedding_on_cpu:
             from .._lib import EngineError
             raise EngineError("engine_train_step needs the tables on the device; with place_embedding_on_cpu use forward / backward "
                               "and a torch optimizer")
+        if ema_decay:
+            import torch.distributed as dist
+            if self._table_sharding == "row" or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+                from .._lib import EngineError
+                raise EngineError("the fused weight EMA covers one process with whole tables: use WeightEMA.update() on the torch route")
         choice = self._resolve_choice(None)
         self._ensure_engine(int_feats)
+        self._engine._refuse_swapped("engine_train_step")
         # (graph=None: a fixed sub-network's step is replayed as a graph.  Launching the level-scheduled program instead is ~6 us faster per
         # step when the host does nothing else — bench.py, engine.prefers_graph — but this harness's host has a data pipe and a Python
         # loop to run: measured on TSV shards 832 k rows/s launched against 896 k replayed)
@@ -645,7 +653,7 @@ class SuperNet(nn.Module):
         d["_engine_steps"] = d.get("_engine_steps", 0) + 1
         d["_last_step_batch"] = int(int_feats.shape[0])
         from ..optim_spec import OptimSpec
-        spec = OptimSpec.of(eps, weight_decay, no_reg_param_name, optim)
+        spec = OptimSpec.of(eps, weight_decay, no_reg_param_name, optim, ema_decay)
         d["_last_step_key"] = (choice, clip, eps, graph, spec)
         d["_last_step_last_layer"] = False
         opt_kw = {}
@@ -655,6 +663,8 @@ class SuperNet(nn.Module):
                 raise EngineError("weight decay, Adam and SGD in the fused step need whole tables: row-sharded tables train them "
                                   "through the torch route")
             opt_kw = dict(weight_decay=spec.wd, no_reg_param_name=spec.no_reg, optim=optim)
+        if spec.ema:
+            return self._engine.train_step(int_feats, cat_feats, y, lr, choice, clip, eps, graph=graph, ema=spec.ema, **opt_kw)
         if self._table_sharding == "row":
             from ..sharded_tables import ShardedTableStep
             st = self.__dict__.get("_sharded_step")
@@ -785,6 +795,49 @@ class SuperNet(nn.Module):
         if spec.kind == "rmsprop":
             optimizer._lazy_flush = eng.flush_lazy_rows
         self._alias_state(optimizer, spec, slots, counts)
+
+    def engine_bind_ema(self, ema):
+        """Share a WeightEMA (utils/optim.py) with the engine: its shadows are copied into the engine's arrays (every row current as
+        of `num_updates`: the stamps and the count start there), `ema.shadow[name]` then aliases them, and the WeightEMA gets the
+        engine's hooks: `state_dict()` and `averaged()` flush first, `averaged()` exchanges in one launch, and a torch-route
+        `update()` in the middle of a fused run flushes, averages densely and advances the engine's count and stamps."""
+        eng = self._engine
+        assert eng is not None, "run one forward first (lazy shapes)"
+        from .._lib import EngineError
+        if self._table_sharding == "row" or self._place_embedding_on_cpu:
+            raise EngineError("the fused weight EMA needs whole tables on the device")
+        eng.ensure_ema_state(ema.decay)
+        eng.flush_ema_rows()  # (a second binding, e.g. the next epoch's: what the rows owe is paid before their stamps are set)
+        names = [n for n, _ in self.named_parameters()]
+        missing = [n for n in names if n not in eng.params]
+        if missing:
+            raise EngineError("engine_bind_ema: the engine holds no parameter %s" % missing[:3])
+        with torch.no_grad(), torch.cuda.stream(eng.stream):
+            for n in names:
+                tgt, src = eng.ema_view(n), ema.shadow[n]
+                if src.data_ptr() != tgt.data_ptr():
+                    tgt.copy_(src.to(tgt.device).view_as(tgt))
+                ema.shadow[n] = tgt
+            for stamp in eng.ema_stamps:
+                stamp.fill_(int(ema.num_updates))
+            eng.ema_count.fill_(int(ema.num_updates))
+        eng.stream.synchronize()
+
+        def advance():
+            with torch.cuda.stream(eng.stream):
+                eng.ema_count.add_(1)
+                for stamp in eng.ema_stamps:
+                    stamp.add_(1)  # (every row was flushed and averaged densely: all stamps equal the count)
+            eng.stream.synchronize()
+        ema._hooks = dict(flush=eng.flush_ema_rows, swap=eng.swap_ema, advance=advance)  # (the model keeps no reference to `ema`)
+
+    def engine_sync_ema(self, ema):
+        """read `num_updates` back from the engine's count (the fused steps since engine_bind_ema)"""
+        eng = self._engine
+        if eng is None or getattr(eng, "ema_count", None) is None:
+            return
+        torch.cuda.synchronize(eng.device)
+        ema.num_updates = int(eng.ema_count.cpu()[0])
 
     _FINAL = ("_final.weight", "_final.bias")
 

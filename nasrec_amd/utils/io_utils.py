@@ -96,13 +96,15 @@ def load_optimizer_state(model, optimizer, state_dict):
     optimizer.load_state_dict(state_dict)
 
 
-def save_model_checkpoint(model, save_path, optimizer=None):
+def save_model_checkpoint(model, save_path, optimizer=None, ema=None):
     """save_path None: build the checkpoint but write nothing — row-sharded tables make `model.state_dict()` and the optimizer's
     table accumulators collectives (every rank contributes its rows), so every rank calls this with the same arguments and only
     rank 0 passes a path"""
     blob = {"model_state_dict": model.state_dict()}
     if optimizer is not None:
         blob["optimizer_state_dict"] = optimizer_state_for_checkpoint(model, optimizer)
+    if ema is not None:  # (utils/optim.WeightEMA: decay, num_updates and the averaged weights, every row current)
+        blob["ema_state_dict"] = ema.state_dict()
     if save_path is None:
         return
     torch.save(blob, save_path)

@@ -7,9 +7,11 @@ whose summed gradient is exactly zero still decays its moments and moves, as a r
 
 `step()` is the torch route; the fused engine step reproduces it (OptimSpec.sparse_rows, csrc/optim_moments.hip) and shares its state
 through SuperNet.engine_bind_optimizer, as with torch.optim.Adam."""
+import contextlib
 import math
 from typing import Iterable
 
+import numpy as np
 import torch
 from torch.optim.adam import adam as _adam
 
@@ -131,3 +133,87 @@ class LazyRMSprop(torch.optim.RMSprop):
     def state_dict(self):
         self.flush_lazy_rows()
         return super().state_dict()
+
+
+class WeightEMA:
+    """`--ema DECAY`: an exponential moving average of every parameter of `model` (parameters only: no buffer of the model trains),
+    0 < decay < 1.  `shadow[name]` starts as a copy of the parameter; `update()`, called after every optimizer step that was taken,
+    averages every parameter whether or not it had a gradient, in fp32 with w = (float)(1 - decay):
+
+        s = s + w (p - s)        torch: `s.add_(p - s, alpha=w)`, one statement per tensor
+
+    No warm-up, no bias correction, no decay that depends on `num_updates`.  The fused engine step (SuperNet.engine_train_step(...,
+    ema_decay=)) computes `fmaf(w, p - s, s)` and pays the resting table rows in closed form (csrc/weight_ema.hip); it is checked
+    against this rule in fp64, not against torch's bits.  Bound to an engine (SuperNet.engine_bind_ema) the shadows alias the engine's
+    arrays and `state_dict()` / `averaged()` bring every row current first."""
+
+    def __init__(self, model, decay: float):
+        decay = float(decay)
+        if not 0.0 < decay < 1.0:
+            raise ValueError("WeightEMA: decay %r is not inside (0, 1)" % (decay,))
+        self.model, self.decay = model, decay
+        self.shadow = {n: p.detach().clone() for n, p in model.named_parameters()}
+        self.num_updates = 0
+        self._swapped = False
+        self._hooks = None  # (set by SuperNet.engine_bind_ema; never part of a checkpoint)
+
+    @property
+    def weight(self) -> float:
+        """w = (float)(1 - decay) as a Python float"""
+        return float(np.float32(1.0 - self.decay))
+
+    @torch.no_grad()
+    def update(self):
+        if self._swapped:
+            raise RuntimeError("WeightEMA.update() inside averaged(): the parameters hold the average")
+        if self._hooks is not None:
+            self._hooks["flush"]()
+        w = self.weight
+        for n, p in self.model.named_parameters():
+            s = self.shadow[n]
+            s.add_(p.detach().to(s.device) - s, alpha=w)
+        if self._hooks is not None:
+            self._hooks["advance"]()
+        self.num_updates += 1
+
+    @torch.no_grad()
+    def _exchange(self):
+        if self._hooks is not None:
+            self._hooks["swap"]()  # (flush + exchange, one launch)
+            return
+        for n, p in self.model.named_parameters():
+            s = self.shadow[n]
+            tmp = p.detach().clone()
+            p.copy_(s.to(p.device))
+            s.copy_(tmp.to(s.device))
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """inside, the model's parameters hold the averaged values and the shadow holds the parameters; on exit both are back, bit for
+        bit.  update() and a fused training step raise inside."""
+        if self._swapped:
+            raise RuntimeError("WeightEMA.averaged() is not re-entrant")
+        self._exchange()
+        self._swapped = True
+        try:
+            yield self.model
+        finally:
+            self._exchange()
+            self._swapped = False
+
+    def state_dict(self):
+        if self._swapped:
+            raise RuntimeError("WeightEMA.state_dict() inside averaged()")
+        if self._hooks is not None:
+            self._hooks["flush"]()
+        return {"decay": self.decay, "num_updates": int(self.num_updates), "shadow": {n: s.detach().clone() for n, s in self.shadow.items()}}
+
+    @torch.no_grad()
+    def load_state_dict(self, state):
+        if set(state["shadow"]) != set(self.shadow):
+            raise KeyError("WeightEMA.load_state_dict: parameter names differ")
+        if self._hooks is not None:
+            raise RuntimeError("WeightEMA.load_state_dict on a bound average: load first, then SuperNet.engine_bind_ema")
+        self.decay, self.num_updates = float(state["decay"]), int(state["num_updates"])
+        for n, s in self.shadow.items():
+            s.copy_(state["shadow"][n].to(s.device))

@@ -13,6 +13,7 @@ tables) and AMP is off — the whole step is ONE engine call
 Not available in this environment: fvcore and tensorboard.  FLOPs are counted analytically from the engine's launch plan
 (multiply-accumulates of every Linear / attention product, what fvcore's FlopCountAnalysis reports for the supported
 operators), the TensorBoard writer is optional (None disables it)."""
+import contextlib
 import copy
 import time
 from typing import Any, Optional, Union
@@ -159,8 +160,32 @@ def _whole_table_optimizers_apply(model) -> bool:
     return world_info()[1] <= 1 or bool(getattr(model, "engine_dp_optimizers", False))
 
 
-def _fused_step_spec(model, optimizer, l2_loss_fn, use_amp):
-    """the OptimSpec of the fused engine step that stands in for this model's torch step (OptimSpec.for_step), or None: the torch route"""
+def _ema_route(model, spec, l2_loss_fn):
+    """why a step with a weight average keeps the torch route (WeightEMA.update() is dense and exact there), or None: the fused step
+    averages the batch's table rows only, so it applies where the tables move in those rows alone — Adagrad, row-sparse Adam or
+    RMSprop, no regularised table — in one process with whole tables on the device"""
+    from ..optim_spec import regularises_tables
+    from .dist import world_info
+    if spec.kind in ("adam", "sgd") and not spec.sparse_rows:
+        return "%s moves every table row every step" % ("dense Adam" if spec.kind == "adam" else "momentum SGD")
+    if isinstance(l2_loss_fn, L2Loss) and regularises_tables(l2_loss_fn.wd, l2_loss_fn.no_reg_param_name):
+        return "weight decay reaches the embedding tables: every row moves every step"
+    if world_info()[1] > 1:
+        return "data-parallel run"  # (paths="per-rank" included: it exists only there)
+    if getattr(model, "_table_sharding", None) == "row":
+        return "row-sharded tables"
+    return None
+
+
+def _fused_step_spec(model, optimizer, l2_loss_fn, use_amp, ema=None):
+    """the OptimSpec of the fused engine step that stands in for this model's torch step (OptimSpec.for_step), or None: the torch route.
+    ema: a WeightEMA (utils/optim.py) kept beside the step — the spec then carries its decay, and the answer is None wherever the
+    fused average is not exact (_ema_route)"""
+    if ema is not None:
+        spec = _fused_step_spec(model, optimizer, l2_loss_fn, use_amp)
+        if spec is None or _ema_route(model, spec, l2_loss_fn) is not None:
+            return None
+        return spec._replace(ema=float(ema.decay))
     if use_amp or not hasattr(model, "engine_train_step"):
         return None
     spec = _optim_spec(optimizer, l2_loss_fn)
@@ -184,8 +209,21 @@ def _fused_step_spec(model, optimizer, l2_loss_fn, use_amp):
     return spec
 
 
-def _fused_step_applies(model, optimizer, l2_loss_fn, use_amp):
-    return _fused_step_spec(model, optimizer, l2_loss_fn, use_amp) is not None
+def _fused_step_applies(model, optimizer, l2_loss_fn, use_amp, ema=None):
+    return _fused_step_spec(model, optimizer, l2_loss_fn, use_amp, ema) is not None
+
+
+def _announce_ema_route(model, optimizer, l2_loss_fn, use_amp, ema, fused):
+    """one line per run: which route averages the weights, and why"""
+    if getattr(ema, "_route_announced", False):
+        return
+    ema._route_announced = True
+    if fused:
+        print("Weight EMA (decay {}): fused step, lazily averaged embedding rows.".format(ema.decay))
+        return
+    spec = _fused_step_spec(model, optimizer, l2_loss_fn, use_amp)
+    why = "the fused step does not apply" if spec is None else (_ema_route(model, spec, l2_loss_fn) or "the fused step was switched off")
+    print("Weight EMA (decay {}): torch route, dense WeightEMA.update() after every step ({}).".format(ema.decay, why))
 
 
 def _agreed_batches(train_loader, train_batch_size: int, world: int, gpu):
@@ -223,19 +261,25 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                              train_batch_size: int, gpu: Union[int, None], display_interval: int = 100, test_interval: int = 2000,
                              max_train_steps: int = -1, max_eval_steps: int = -1, test_only_at_last_step: bool = False,
                              grad_clip_value: float = None, tb_writer=None, use_amp: bool = False, use_engine_step: Optional[bool] = None,
-                             last_layer_step: bool = False):
+                             last_layer_step: bool = False, ema=None):
     """One epoch of training with tests in between; returns the reference's log dict (train_utils.py:181-390).
     `use_engine_step`: None = fused engine step whenever it applies, False = always the torch route.
     `last_layer_step`: a model in last-layer mode (set_mode_to_finelune_last_only) with a qualifying optimizer trains every full batch
-    through SuperNet.engine_last_layer_step (_last_layer_step_applies); False (default) = as before."""
+    through SuperNet.engine_last_layer_step (_last_layer_step_applies); False (default) = as before.
+    `ema`: a WeightEMA (utils/optim.py): every step that is taken updates it — inside the fused step where that is exact
+    (_fused_step_spec), by `ema.update()` otherwise — and the tests run on the averaged weights (`ema.averaged()`); None = no average."""
     _refuse_regularised_tables(optimizer, l2_loss_fn)
     _peek(test_loader)  # the reference peeks one test batch here (train_utils.py:224-225)
     model.train()
     logs = {k: [] for k in ("train_loss", "train_AUROC", "train_Accuracy", "test_loss", "test_AUROC", "test_Accuracy", "epoch", "iters")}
-    fused = _fused_step_applies(model, optimizer, l2_loss_fn, use_amp) if use_engine_step is None else bool(use_engine_step)
+    fused = _fused_step_applies(model, optimizer, l2_loss_fn, use_amp, ema) if use_engine_step is None else bool(use_engine_step)
+    if ema is not None:
+        if fused and use_engine_step is not None and not _fused_step_applies(model, optimizer, l2_loss_fn, use_amp, ema):
+            raise ValueError("use_engine_step=True with a weight EMA the fused step cannot keep exactly: leave use_engine_step=None")
+        _announce_ema_route(model, optimizer, l2_loss_fn, use_amp, ema, fused)
     last_only = bool(last_layer_step) and not fused and use_engine_step is not False and \
         _last_layer_step_applies(model, optimizer, l2_loss_fn, use_amp)
-    bound = False
+    bound = ema_bound = False
     scaler = torch.amp.GradScaler("cuda") if use_amp else None
     best_model, best_test_loss = None, 9999.99
     t_data0 = time.time()
@@ -257,6 +301,7 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
             opt_kw["optim"] = spec
         else:
             opt_kw["eps"] = spec.eps
+    step_kw = dict(opt_kw, ema_decay=float(ema.decay)) if (ema is not None and fused) else opt_kw
     wd = spec.wd if spec is not None else 0.0
     for batch_num, (int_x, cat_x, y) in enumerate(_agreed_batches(train_loader, train_batch_size, world, gpu)):
         t_data1 = time.time()
@@ -277,14 +322,19 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                 with torch.no_grad():
                     l2_loss = l2_loss_fn(model)
             loss = model.engine_last_layer_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value, **opt_kw)
+            if ema is not None:
+                ema.update()
             res = None
         elif fused and full:
             if not bound:  # lazy shapes + engine, then share the Adagrad accumulators (a resumed optimizer keeps its state)
                 model._ensure_engine(int_x)
                 model.engine_bind_optimizer(optimizer)
                 bound = True
+                if ema is not None:
+                    model.engine_bind_ema(ema)
+                    ema_bound = True
             group = optimizer.param_groups[0]
-            loss = model.engine_train_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value, **opt_kw)
+            loss = model.engine_train_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value, **step_kw)
             # the step's logits and the L2 term are only looked at on display steps: fetched there, not 3 900 times per epoch
             # (`torch.zeros` is a fill launch on the GPU, `engine_last_logits` a plan lookup)
             res = None
@@ -311,8 +361,11 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                         torch.nn.utils.clip_grad_norm_(model.parameters(), grad_clip_value)
                     if hasattr(optimizer, "touch"):
                         optimizer.touch(cat_x)
+                    scale0 = scaler.get_scale() if ema is not None else None
                     scaler.step(optimizer)
                     scaler.update()
+                    if ema is not None and scaler.get_scale() >= scale0:  # (a skipped step halves the scale: nothing to average)
+                        ema.update()
                 else:
                     total_loss.backward()
                     if world > 1:  # the torch route has no exchange of its own: average the gradients over the ranks
@@ -322,6 +375,8 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                     if hasattr(optimizer, "touch"):  # (RowSparseAdam: the rows this batch touches)
                         optimizer.touch(cat_x)
                     optimizer.step()
+                    if ema is not None:
+                        ema.update()
         t_gpu1 = time.time()
         last = batch_num == max_train_steps - 1
 
@@ -366,7 +421,10 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
             if (not test_only_at_last_step) or last:
                 model.eval()
                 t0 = time.time()
-                test_acc, test_auroc, test_loss = test_one_epoch(model, test_loader, loss_fn, gpu, max_steps=max_eval_steps, use_amp=use_amp)
+                if ema_bound:
+                    model.engine_sync_ema(ema)
+                with (ema.averaged() if ema is not None else contextlib.nullcontext()):  # (the averaged weights are what is tested)
+                    test_acc, test_auroc, test_loss = test_one_epoch(model, test_loader, loss_fn, gpu, max_steps=max_eval_steps, use_amp=use_amp)
                 print("{:.4f} seconds elasped for testing!".format(time.time() - t0))
                 print("Test Acc: {}, Test AUROC: {}, Test Loss: {}".format(test_acc, test_auroc, test_loss))
                 logs["test_loss"].append(test_loss)
@@ -389,6 +447,8 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
         print("Batch counter total: {}".format(batch_num))
     if bound:
         model.engine_sync_optimizer_steps(optimizer)
+    if ema_bound:
+        model.engine_sync_ema(ema)
     del best_model  # the reference rebinds a local name to a copy of it: no observable effect
     return logs
 

@@ -3,7 +3,10 @@
 the Criteo best-1shot sub-network, full tables (33.76 M rows), batch 256, clip 5.0; Adagrad(eps 1e-2), Adam(eps 1e-8), SGD(momentum 0.9,
 Nesterov), row-sparse Adam (Adam's lr and eps; with --wd the L2 term leaves the tables out, as the optimizer requires), RMSprop (torch's
 defaults; fused: lazily decayed rows, with --wd the tables left out too; its line also carries `flush_ms`, the one launch that brings
-every row's square_avg current after the timed steps).  Prints one JSON line per measured (route, optimizer, wd):
+every row's square_avg current after the timed steps).  `--ema DECAY` keeps utils/optim.WeightEMA beside the step: inside the fused
+step (Adagrad, row-sparse Adam, RMSprop), by WeightEMA.update() on the torch route; the line then carries `ema`, `flush_ms` (the launch
+that brings every row's average current) and `swap_ms` (flush + exchange with the parameters: what entering `averaged()` costs).
+Prints one JSON line per measured (route, optimizer, wd):
 
     python tools/optim_step_bench.py --route fused --optimizer adam --wd 0     # the fused engine step
     python tools/optim_step_bench.py --route torch --optimizer adam --wd 0     # forward / autograd / clip_grad_norm_ / torch.optim
@@ -33,6 +36,7 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--B", type=int, default=256)
+    ap.add_argument("--ema", type=float, default=0.0, help="decay of a weight average kept beside the step (0: none)")
     ap.add_argument("--bytes", action="store_true")
     ap.add_argument("--all", action="store_true", help="every route x optimizer x wd in {0, 1e-8}, one child process each")
     ap.add_argument("--timeout", type=int, default=600, help="--all: seconds per child")
@@ -82,14 +86,21 @@ def main():
     loss_fn = torch.nn.BCEWithLogitsLoss()
     if a.route == "fused":
         m.engine_bind_optimizer(opt)
+    ema, ema_kw = None, {}
+    if a.ema:
+        from nasrec_amd.utils.optim import WeightEMA
+        ema = WeightEMA(m, a.ema)
+        if a.route == "fused":
+            m.engine_bind_ema(ema)
+            ema_kw = dict(ema_decay=a.ema)
 
     def step(i):
         int_x, cat_x, y = batches[i % len(batches)]
         if a.route == "fused":
             if spec is not None:
-                m.engine_train_step(int_x, cat_x, y.view(-1), lr=lr, clip=5.0, weight_decay=a.wd, no_reg_param_name=no_reg, optim=spec)
+                m.engine_train_step(int_x, cat_x, y.view(-1), lr=lr, clip=5.0, weight_decay=a.wd, no_reg_param_name=no_reg, optim=spec, **ema_kw)
             else:
-                m.engine_train_step(int_x, cat_x, y.view(-1), lr=lr, clip=5.0, eps=1e-2, weight_decay=a.wd)
+                m.engine_train_step(int_x, cat_x, y.view(-1), lr=lr, clip=5.0, eps=1e-2, weight_decay=a.wd, **ema_kw)
             return
         opt.zero_grad()
         loss = loss_fn(m(int_x, cat_x), y.view(-1, 1)) + get_l2_loss(m, a.wd, no_reg, gpu=0)
@@ -98,6 +109,8 @@ def main():
         if hasattr(opt, "touch"):
             opt.touch(cat_x)
         opt.step()
+        if ema is not None:
+            ema.update()
 
     for i in range(a.warmup):
         step(i)
@@ -112,7 +125,17 @@ def main():
     ms = e0.elapsed_time(e1) / a.steps
     wall_ms = (time.perf_counter() - t0) / a.steps * 1e3
     extra = {}
-    if a.optimizer == "rmsprop" and a.route == "fused":
+    if ema is not None:
+        extra["ema"] = a.ema
+        if a.route == "fused":
+            # the flush (every row outside the timed batches owes its average a catch-up) and the exchange with the parameters, there and back
+            eng = m._engine
+            for key, fn in (("flush_ms", eng.flush_ema_rows), ("flush_again_ms", eng.flush_ema_rows), ("swap_ms", eng.swap_ema), ("swap_back_ms", eng.swap_ema)):
+                wall = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                extra[key] = round((time.perf_counter() - wall) * 1e3, 4)
+    elif a.optimizer == "rmsprop" and a.route == "fused":
         # the flush: every row outside the timed batches owes its square_avg a decay (one streaming launch, waited for)
         wall = time.perf_counter()
         m._engine.flush_lazy_rows()
