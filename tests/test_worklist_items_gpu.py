@@ -74,6 +74,36 @@ for the split-K cases the body named is the second pass, their main passes run o
   mha_fwd_n48_d0_b3_saved                -> mha_fwd
   mha_fwd_n48_d0_b3                      -> mha_fwd
   mha_bwd_n48_d0_b3                      -> mha_bwd
+  mha_fwd_n16_d-1_b5_slabs_saved         -> mha_fwd
+  mha_fwd_n16_d-1_b5_slabs               -> mha_fwd
+  mha_bwd_n16_d-1_b5_slabs_shared        -> mha_bwd
+  mha_fwd_n48_d-1_b3_slabs_saved         -> mha_fwd
+  mha_fwd_n48_d-1_b3_slabs               -> mha_fwd
+  mha_bwd_n48_d-1_b3_slabs_shared        -> mha_bwd
+  mha_fwd_n64_d40_b5_slabs_saved         -> mha_fwd
+  mha_fwd_n64_d40_b5_slabs               -> mha_fwd
+  mha_bwd_n64_d40_b5_slabs_shared        -> mha_bwd
+  mha_fwd_n7_d-1_b6_slabs_saved          -> mha_fwd
+  mha_fwd_n7_d-1_b6_slabs                -> mha_fwd
+  mha_bwd_n7_d-1_b6_slabs_shared         -> mha_bwd
+  mha_fwd_n16_d-1_b5_slab_saved          -> mha_fwd
+  mha_fwd_n16_d-1_b5_slab                -> mha_fwd
+  mha_bwd_n16_d-1_b5_slab_shared         -> mha_bwd
+  mha_fwd_n48_d-1_b3_own_saved           -> mha_fwd
+  mha_fwd_n48_d-1_b3_own                 -> mha_fwd
+  mha_bwd_n48_d-1_b3_own_shared          -> mha_bwd
+  mha_fwd_n48_d-1_b3_slab_saved          -> mha_fwd
+  mha_fwd_n48_d-1_b3_slab                -> mha_fwd
+  mha_bwd_n48_d-1_b3_slab_shared         -> mha_bwd
+  mha_fwd_n64_d64_b5_own_saved           -> mha_fwd
+  mha_fwd_n64_d64_b5_own                 -> mha_fwd
+  mha_bwd_n64_d64_b5_own_shared          -> mha_bwd
+  mha_fwd_n64_d40_b5_slab_saved          -> mha_fwd
+  mha_fwd_n64_d40_b5_slab                -> mha_fwd
+  mha_bwd_n64_d40_b5_slab_shared         -> mha_bwd
+  mha_fwd_n64_d-1_b3_slab_saved          -> mha_fwd
+  mha_fwd_n64_d-1_b3_slab                -> mha_fwd
+  mha_bwd_n64_d-1_b3_slab_shared         -> mha_bwd
   fm_fwd_b1_n1_acc0                      -> fm_fwd
   fm_bwd_b1_n1_acc0                      -> fm_bwd
   fm_fwd_b5_n26_acc1                     -> fm_fwd
@@ -86,6 +116,18 @@ for the split-K cases the body named is the second pass, their main passes run o
   fm_bwd_b5_n48_acc0                     -> fm_bwd
   fm_fwd_b1_n26_acc1                     -> fm_fwd
   fm_bwd_b1_n26_acc1                     -> fm_bwd
+  fm_fwd_b1_n16_add_tight                -> fm_fwd
+  fm_fwd_b1_n48_add_tight                -> fm_fwd
+  fm_fwd_b5_n16_add_tight                -> fm_fwd
+  fm_fwd_b5_n48_add_tight                -> fm_fwd
+  fm_fwd_b5_n16_tight                    -> fm_fwd
+  fm_bwd_b5_n16_tight_acc1               -> fm_bwd
+  fm_fwd_b5_n16_slab                     -> fm_fwd
+  fm_bwd_b5_n16_slab_acc1                -> fm_bwd
+  fm_fwd_b5_n48_tight                    -> fm_fwd
+  fm_bwd_b5_n48_tight_acc1               -> fm_bwd
+  fm_fwd_b5_n48_slab                     -> fm_fwd
+  fm_bwd_b5_n48_slab_acc1                -> fm_bwd
   dot_tri_fwd_k2_b3                      -> dot_tri_fwd
   dot_tri_bwd_k2_b3                      -> dot_tri_bwd
   dot_tri_fwd_k9_b11                     -> dot_tri_fwd
@@ -98,16 +140,59 @@ for the split-K cases the body named is the second pass, their main passes run o
   dot_tri_bwd_k33_b3                     -> dot_tri_bwd
   dot_tri_fwd_k46_b11                    -> dot_tri_fwd
   dot_tri_bwd_k46_b11                    -> dot_tri_bwd
+  dot_tri_fwd_k9_b3_tight                -> dot_tri_fwd
+  dot_tri_bwd_k9_b3_tight                -> dot_tri_bwd
+  dot_tri_fwd_k17_b5_tight               -> dot_tri_fwd
+  dot_tri_bwd_k17_b5_tight               -> dot_tri_bwd
+  dot_tri_fwd_k33_b3_tight               -> dot_tri_fwd
+  dot_tri_bwd_k33_b3_tight               -> dot_tri_bwd
+  dot_tri_fwd_k40_b5_tight               -> dot_tri_fwd
+  dot_tri_bwd_k40_b5_tight               -> dot_tri_bwd
+  dot_tri_fwd_k46_b3_tight               -> dot_tri_fwd
+  dot_tri_bwd_k46_b3_tight               -> dot_tri_bwd
   copy_forward_gap                       -> copy_segs
   copy_reverse_gap                       -> copy_segs
   copy_4097x4096_unpacked_table          -> copy_segs
+  copy_forward_accumulate_gap            -> copy_segs
+  copy_forward_null_segment_gap          -> copy_segs
+  copy_forward_accumulate_one_segment    -> copy_segs
+  copy_forward_zero_fill                 -> copy_segs
+  copy_reverse_one_segment               -> copy_segs
   gate_21x32_one_segment                 -> gate_bwd
   gate_21x32_two_segments                -> gate_bwd
+  gate_5x61_seven_segments               -> gate_bwd
+  gate_5x29_head_acc_tight               -> gate_bwd
+  gate_5x29_head_set_tight               -> gate_bwd
+  gate_5x29_head_no_dr_tight             -> gate_bwd
+  gate_5x29_all_set_tight                -> gate_bwd
+  gate_5x13_all_no_dr_tight              -> gate_bwd
+  gate_5x21_2_segments_tight             -> gate_bwd
+  gate_5x29_3_segments_tight             -> gate_bwd
+  gate_5x37_4_segments_tight             -> gate_bwd
+  gate_5x45_5_segments_tight             -> gate_bwd
+  gate_5x53_6_segments_tight             -> gate_bwd
+  gate_5x61_7_segments_tight             -> gate_bwd
+  gate_5x29_head_acc_wide                -> gate_bwd
+  gate_5x29_head_set_wide                -> gate_bwd
+  gate_5x29_head_no_dr_wide              -> gate_bwd
+  gate_5x29_all_set_wide                 -> gate_bwd
+  gate_5x13_all_no_dr_wide               -> gate_bwd
+  gate_5x21_2_segments_wide              -> gate_bwd
+  gate_5x29_3_segments_wide              -> gate_bwd
+  gate_5x37_4_segments_wide              -> gate_bwd
+  gate_5x45_5_segments_wide              -> gate_bwd
+  gate_5x53_6_segments_wide              -> gate_bwd
+  gate_5x61_7_segments_wide              -> gate_bwd
   reduce_r13_c1696_mha                   -> reduce_rows
   reduce_r256_c1696_mha                  -> reduce_rows
   reduce_r256_c37_16dst                  -> reduce_rows
   reduce_r1_c37_1dst                     -> reduce_rows
   reduce_r13_c37_16dst                   -> reduce_rows
+  reduce_r64_c37_16dst                   -> reduce_rows
+  reduce_r300_c37_16dst                  -> reduce_rows
+  reduce_r16_c34_2dst_tight              -> reduce_rows
+  reduce_r64_c34_2dst_tight              -> reduce_rows
+  reduce_r256_c1696_mha_tight            -> reduce_rows
   dedup_b1_fs5                           -> dedup_ids
   dedup_b37_fs5                          -> dedup_ids
   dedup_b255_fs5                         -> dedup_ids

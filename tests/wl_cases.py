@@ -343,19 +343,48 @@ def _mha_ref(x, p, dims):
     return out
 
 
-def _mha(ctx, N, dims, B, backward, saved=True):
+def _slab(ctx, B, N, lead, tail, fill):
+    """a token range [B, N, 16] that starts `lead` tokens into a slab of lead + N + tail tokens -> (host slab, host view, device slab,
+    device pointer of the view, batch stride, mask of the view inside the slab).  fill: "randn", NAN or SENTINEL for the view; the slab's
+    other tokens hold random values ("randn": an input) or the sentinel (an output)"""
+    Nt = lead + N + tail
+    inside = torch.zeros(B, Nt, 16, dtype=torch.bool)
+    inside[:, lead:lead + N] = True
+    if fill == "randn":
+        host = ctx.randn(B, Nt, 16)
+    else:
+        host = torch.full((B, Nt, 16), SENTINEL)
+        host[inside] = fill
+    dev = ctx.dev(host)
+    return host, host[:, lead:lead + N], dev, dev.data_ptr() + 4 * lead * 16, Nt * 16, inside
+
+
+def _view_check(got, host, inside, ref, tol, what):
+    """the view of an output slab against fp64, the slab's other tokens bit for bit what they were"""
+    got = got.cpu()
+    B = host.shape[0]
+    close(got[inside].view(B, -1, 16), ref, tol)
+    assert torch.equal(got[~inside], host[~inside]), "%s: slab tokens outside the view were written" % what
+
+
+def _mha(ctx, N, dims, B, backward, saved=True, xs=(0, 0), os=(0, 0), shared=None):
+    """xs / os: (tokens in front of, tokens behind) the view inside the slab of x / dx and of out / dout — the plan compiler hands the
+    Transformer a token range of a block's slab as its output (ldo > N * 16); shared: (partial_ld, first column) of this node's
+    parameter-gradient partials inside a buffer it shares with other nodes (plan.py _flush_mha_reduce), None: a buffer of its own"""
     p = [ctx.randn(*s, scale=(0.3 if len(s) == 2 else 0.1)) for s in MHA_SHAPES]
     p[4] = 0.17 + 0.02 * ctx.randn(16)
     p[10] = 0.17 + 0.02 * ctx.randn(16)
-    x = ctx.randn(B, N, 16)
+    xslab, x, gxs, xptr, ldx, _ = _slab(ctx, B, N, xs[0], xs[1], "randn")
     if dims >= 0:
         x[:, dims:] = 0  # supernet mode zeroes masked tokens before attention (modules.py:653-662)
-    gp, gx = [ctx.dev(t) for t in p], ctx.dev(x)
-    out = ctx.dev(torch.full((B, N, 16), NAN))
+        gxs.copy_(xslab)
+    x = x.clone()
+    gp = [ctx.dev(t) for t in p]
+    oslab, _, out, optr, ldo, oin = _slab(ctx, B, N, os[0], os[1], NAN)
     state = ctx.dev(torch.full((B * N * L.MHA_SAVED,), 0.5))
     f = L.MhaDesc()
-    f.kind, f.B, f.N, f.ldx, f.ldo, f.dims_in_use = L.OP_MHA_FWD, B, N, N * 16, N * 16, dims
-    f.x, f.out = gx.data_ptr(), out.data_ptr()
+    f.kind, f.B, f.N, f.ldx, f.ldo, f.dims_in_use = L.OP_MHA_FWD, B, N, ldx, ldo, dims
+    f.x, f.out = xptr, optr
     f.saved = state.data_ptr() if (saved or backward) else None
     for q in range(12):
         f.params[q] = gp[q].data_ptr()
@@ -367,25 +396,35 @@ def _mha(ctx, N, dims, B, backward, saved=True):
 
     if not backward:
         def check(got):
-            close(got["out"], reference()[2].detach(), 1e-5)
+            _view_check(got["out"], oslab, oin, reference()[2].detach(), 1e-5, "out")
         outs = {"out": out}
         if saved:
             outs["saved"] = state
         return Built(ctx, f, outs, check)
-    dout = ctx.randn(B, N, 16)
-    gdo = ctx.dev(dout)
-    dx, part = ctx.dev(torch.full((B, N, 16), NAN)), ctx.dev(torch.zeros(B, L.MHA_PARAMS))
+    _, dout, _, doptr, _, _ = _slab(ctx, B, N, os[0], os[1], "randn")
+    dout = dout.clone()
+    dxslab, _, dx, dxptr, _, dxin = _slab(ctx, B, N, xs[0], xs[1], NAN)
+    pld, pcol = shared if shared is not None else (L.MHA_PARAMS, 0)
+    phost = torch.full((B, pld), SENTINEL)
+    phost[:, pcol:pcol + L.MHA_PARAMS] = NAN
+    part = ctx.dev(phost)
     e = L.MhaDesc()
-    e.kind, e.B, e.N, e.ldx, e.ldo, e.dims_in_use = L.OP_MHA_BWD, B, N, N * 16, N * 16, dims
-    e.x, e.dout, e.dx, e.dparams_partial, e.saved = gx.data_ptr(), gdo.data_ptr(), dx.data_ptr(), part.data_ptr(), state.data_ptr()
+    e.kind, e.B, e.N, e.ldx, e.ldo, e.dims_in_use = L.OP_MHA_BWD, B, N, ldx, ldo, dims
+    e.x, e.dout, e.dx, e.dparams_partial, e.saved = xptr, doptr, dxptr, part.data_ptr() + 4 * pcol, state.data_ptr()
+    if shared is not None:
+        e.partial_ld = pld
     for q in range(12):
         e.params[q] = gp[q].data_ptr()
 
     def check_bwd(got):
         pd, xd, ref = reference()
         ref.backward(dout.double())
-        close(got["dx"], xd.grad, 2e-5)
-        sums, off = got["part"].double().sum(0).cpu(), 0
+        _view_check(got["dx"], dxslab, dxin, xd.grad, 2e-5, "dx")
+        g = got["part"].cpu()
+        keep = torch.ones(pld, dtype=torch.bool)
+        keep[pcol:pcol + L.MHA_PARAMS] = False
+        assert torch.equal(g[:, keep], phost[:, keep]), "columns of the shared partial buffer outside this node's were written"
+        sums, off = g[:, pcol:pcol + L.MHA_PARAMS].double().sum(0), 0
         for q, s in enumerate(MHA_SHAPES):
             n = pd[q].numel()
             close(sums[off:off + n], pd[q].grad.reshape(-1), 2e-5)
@@ -394,73 +433,100 @@ def _mha(ctx, N, dims, B, backward, saved=True):
     return Built(ctx, e, {"dx": dx, "part": part}, check_bwd, setup=(f,))
 
 
-def _fm(ctx, B, N, acc, backward):
-    Ntot = N + 8
+TAIL = 3  # floats of sentinel behind a buffer whose strides leave no room for guard columns
+
+
+def _tailed(B, ld, width, fill):
+    """a [B, ld] buffer with TAIL floats behind its last row, as one flat tensor -> (flat, mask of the [B, width] view): the view holds
+    `fill` (a tensor, NAN), every guard column and the tail the sentinel"""
+    flat = torch.full((B * ld + TAIL,), SENTINEL)
+    inside = torch.zeros(B * ld + TAIL, dtype=torch.bool)
+    inside[:B * ld].view(B, ld)[:, :width] = True
+    flat[inside] = fill if not torch.is_tensor(fill) else fill.reshape(-1)
+    return flat, inside
+
+
+def _fm(ctx, B, N, acc, backward, extra=8, ld_ix=20, add=False):
+    """extra: tokens of the slab behind the N the operator reads (0: ldx == N * 16); ld_ix = 16: the interaction lives in a buffer of
+    its own; add: out = add + FM term in one pass (plan.py op_fm: the node sum of a fixed sub-network without LayerNorm)"""
+    Ntot = N + extra
     slab = ctx.randn(B, Ntot, 16)
     gx = ctx.dev(slab)
     x = slab[:, :N]
     d = L.FmDesc()
-    d.B, d.N, d.ldx, d.ld_ix, d.accumulate, d.x = B, N, Ntot * 16, 20, acc, gx.data_ptr()
+    d.B, d.N, d.ldx, d.ld_ix, d.accumulate, d.x = B, N, Ntot * 16, ld_ix, acc, gx.data_ptr()
     xd = x.double().requires_grad_(True)
 
     def fm(xd):
         return xd.sum(1) ** 2 - (xd ** 2).sum(1)
 
     if not backward:
-        base = torch.full((B, 20), SENTINEL)
-        base[:, :16] = ctx.randn(B, 16) if acc else NAN
+        base, inside = _tailed(B, ld_ix, 16, ctx.randn(B, 16) if acc else NAN)
         ix = ctx.dev(base)
         d.kind, d.ix = L.OP_FM_FWD, ix.data_ptr()
+        addend = None
+        if add:  # (same row stride as ix; its guard columns are NaN: read, they would poison the result)
+            ah, ain = _tailed(B, ld_ix, 16, 1.0 + ctx.rand(B, 16))
+            ah[~ain] = NAN
+            addend = ah[ain].view(B, 16).double()
+            d.add = ctx.dev(ah).data_ptr()
 
         def check(got):
             g = got["ix"].cpu()
-            close(g[:, :16], fm(x.double()) + (base[:, :16].double() if acc else 0.0))
-            assert torch.equal(g[:, 16:], base[:, 16:])
+            ref = fm(x.double()) + (base[inside].view(B, 16).double() if acc else 0.0) + (addend if add else 0.0)
+            close(g[inside].view(B, 16), ref)
+            assert torch.equal(g[~inside], base[~inside]), "guard columns or the tail behind ix were written"
         return Built(ctx, d, {"ix": ix}, check)
-    dix = ctx.randn(B, 20)
-    init = torch.full((B, Ntot, 16), SENTINEL)
-    init[:, :N] = ctx.randn(B, N, 16) if acc else NAN
-    gdix, dx = ctx.dev(dix), ctx.dev(init)
+    dixh, dixin = _tailed(B, ld_ix, 16, ctx.randn(B, 16))
+    dixh[~dixin] = NAN
+    dix = dixh[dixin].view(B, 16)
+    init, inside = _tailed(B, Ntot * 16, N * 16, ctx.randn(B, N * 16) if acc else NAN)
+    gdix, dx = ctx.dev(dixh), ctx.dev(init)
     d.kind, d.dix, d.dx = L.OP_FM_BWD, gdix.data_ptr(), dx.data_ptr()
 
     def check_bwd(got):
         g = got["dx"].cpu()
-        fm(xd).backward(dix[:, :16].double())
-        close(g[:, :N], xd.grad + (init[:, :N].double() if acc else 0.0))
-        assert torch.equal(g[:, N:], init[:, N:])
+        fm(xd).backward(dix.double())
+        close(g[inside].view(B, N, 16), xd.grad + (init[inside].view(B, N, 16).double() if acc else 0.0))
+        assert torch.equal(g[~inside], init[~inside]), "tokens behind the view or the tail behind dx were written"
     return Built(ctx, d, {"dx": dx}, check_bwd)
 
 
-def _dot_tri(ctx, k1, B, backward):
+def _dot_tri(ctx, k1, B, backward, pad=3):
+    """pad = 0: ld_out == k1 (k1 - 1) / 2 exactly, as the plan compiler emits it (rows start off 16-byte boundaries)"""
     T = ctx.randn(B, k1, 16)
     P = k1 * (k1 - 1) // 2
     gT = ctx.dev(T)
     d = L.DotTriDesc()
-    d.B, d.k1, d.ld_out, d.T = B, k1, P + 3, gT.data_ptr()
+    d.B, d.k1, d.ld_out, d.T = B, k1, P + pad, gT.data_ptr()
     li, lj = torch.tril_indices(k1, k1, offset=-1)
 
     def tri(Td):
         return (Td @ Td.transpose(1, 2))[:, li, lj]
 
     if not backward:
-        init = torch.full((B, P + 3), SENTINEL)
-        init[:, :P] = NAN
+        init, inside = _tailed(B, P + pad, P, NAN)
         out = ctx.dev(init)
         d.kind, d.out = L.OP_DOT_TRI_FWD, out.data_ptr()
 
         def check(got):
             g = got["out"].cpu()
-            close(g[:, :P], tri(T.double()))
-            assert torch.equal(g[:, P:], init[:, P:]), "columns beyond the triangle were written"
+            close(g[inside].view(B, P), tri(T.double()))
+            assert torch.equal(g[~inside], init[~inside]), "columns beyond the triangle or the tail behind the last row were written"
         return Built(ctx, d, {"out": out}, check)
-    dout = ctx.randn(B, P + 3)
-    gdo, dT = ctx.dev(dout), ctx.dev(torch.full((B, k1, 16), NAN))
+    douth, doin = _tailed(B, P + pad, P, ctx.randn(B, P))
+    douth[~doin] = NAN  # (gradient columns beyond the triangle and behind the last row are nobody's: read, they poison dT)
+    dout = douth[doin].view(B, P)
+    dTh, dTin = _tailed(B, k1 * 16, k1 * 16, NAN)
+    gdo, dT = ctx.dev(douth), ctx.dev(dTh)
     d.kind, d.dout, d.dT = L.OP_DOT_TRI_BWD, gdo.data_ptr(), dT.data_ptr()
 
     def check_bwd(got):
         Td = T.double().requires_grad_(True)
-        tri(Td).backward(dout[:, :P].double())
-        close(got["dT"], Td.grad)
+        tri(Td).backward(dout.double())
+        g = got["dT"].cpu()
+        close(g[dTin].view(B, k1, 16), Td.grad)
+        assert torch.equal(g[~dTin], dTh[~dTin]), "the tail behind dT was written"
     return Built(ctx, d, {"dT": dT}, check_bwd)
 
 
@@ -499,54 +565,118 @@ def _copy(ctx, B, reverse, big=False):
     return Built(ctx, c, {"a": ga, "b": gb}, check_rev)
 
 
-def _gate(ctx, B, D, rsegs):
-    """rsegs: (offset, width, dr_accumulate) of the segments of R; columns outside every segment have R = 0"""
+def _copy_fwd(ctx, B, segs, accumulate, pad=3):
+    """forward copy of segments (offset, width, extra columns of the source's stride, NULL?) into dst [B, W + pad], W = the end of the
+    last segment.  A NULL segment counts as zeros (plan.py zero_fill); accumulate: dst += instead of dst ="""
+    W = max(o + w for o, w, _, _ in segs)
+    c = L.CopySegsDesc()
+    c.kind, c.B, c.nseg, c.ld_dst, c.accumulate, c.reverse = L.OP_COPY_SEGS, B, len(segs), W + pad, int(accumulate), 0
+    covered = torch.zeros(B * (W + pad) + TAIL, dtype=torch.bool)
+    for o, w, _, _ in segs:
+        covered[:B * (W + pad)].view(B, W + pad)[:, o:o + w] = True
+    dsth = torch.full((B * (W + pad) + TAIL,), SENTINEL)
+    dsth[covered] = ctx.randn(int(covered.sum())) if accumulate else NAN
+    dst = ctx.dev(dsth)
+    c.dst = dst.data_ptr()
+    ref = dsth.clone()
+    if not accumulate:
+        ref[covered] = 0.0
+    rv = ref[:B * (W + pad)].view(B, W + pad)
+    for q, (o, w, extra, null) in enumerate(segs):
+        src = ctx.randn(B, w + extra)
+        c.seg[q], c.width[q], c.ld[q], c.off[q] = (None if null else ctx.dev(src).data_ptr()), w, (1 if null else w + extra), o
+        if not null:
+            rv[:, o:o + w] += src[:, :w]
+
+    def check(got):
+        assert torch.equal(got["dst"].cpu(), ref)  # (one fp32 addition per element: exact)
+    return Built(ctx, c, {"dst": dst}, check)
+
+
+def _copy_rev(ctx, B, W, acc):
+    """the reverse of a one-segment copy without a gap: seg (+)= dst[:, :W]"""
+    c = L.CopySegsDesc()
+    c.kind, c.B, c.nseg, c.ld_dst, c.reverse = L.OP_COPY_SEGS, B, 1, W, 1
+    dsth = ctx.randn(B, W)
+    init, inside = _tailed(B, W + 2, W, ctx.randn(B, W) if acc else NAN)
+    seg = ctx.dev(init)
+    c.dst = ctx.dev(dsth).data_ptr()
+    c.seg[0], c.width[0], c.ld[0], c.off[0], c.seg_accumulate[0] = seg.data_ptr(), W, W + 2, 0, int(acc)
+
+    def check(got):
+        ref = init.clone()
+        ref[inside] = (init[inside] if acc else 0.0) + dsth.reshape(-1)
+        assert torch.equal(got["seg"].cpu(), ref)
+    return Built(ctx, c, {"seg": seg}, check)
+
+
+def _gate(ctx, B, D, rsegs, pads=(0, 0, 0)):
+    """rsegs: (offset, width, dr_accumulate[, dR wanted = True[, R given = True]]) of the segments of R; columns outside every segment,
+    and the columns of a segment whose R is NULL, have R = 0.  pads: extra columns of the row strides of dout, g and dz"""
     dout, gate = ctx.randn(B, D), ctx.rand(B, D)
-    gd, gg = ctx.dev(dout), ctx.dev(gate)
-    dz = ctx.dev(torch.full((B, D), NAN))
+
+    def padded(t, pad):  # (an input: the guard columns are NaN — read, they would poison the result)
+        h = torch.full((B, D + pad), NAN)
+        h[:, :D] = t
+        return ctx.dev(h)
+    gd, gg = padded(dout, pads[0]), padded(gate, pads[1])
+    dzh, dzin = _tailed(B, D + pads[2], D, NAN)
+    dz = ctx.dev(dzh)
     e = L.GateBwdDesc()
-    e.kind, e.B, e.D, e.ld_dout, e.ld_g, e.ld_dz = L.OP_GATE_BWD, B, D, D, D, D
+    e.kind, e.B, e.D, e.ld_dout, e.ld_g, e.ld_dz = L.OP_GATE_BWD, B, D, D + pads[0], D + pads[1], D + pads[2]
     e.dout, e.g, e.dz, e.nseg = gd.data_ptr(), gg.data_ptr(), dz.data_ptr(), len(rsegs)
     outs, rs = {"dz": dz}, []
     Rp = torch.zeros(B, D, dtype=torch.float64)
-    for q, (off, w, acc) in enumerate(rsegs):
+    for q, seg in enumerate(rsegs):
+        off, w, acc = seg[:3]
+        want_dr, have_r = (seg[3] if len(seg) > 3 else True), (seg[4] if len(seg) > 4 else True)
         R = ctx.randn(B, w + 2)
         init = torch.full((B, w + 2), SENTINEL)
         init[:, :w] = ctx.randn(B, w) if acc else NAN
         gR, dR = ctx.dev(R), ctx.dev(init)
-        e.r_ptr[q], e.dr_ptr[q], e.r_off[q], e.r_width[q], e.r_ld[q], e.dr_accumulate[q] = gR.data_ptr(), dR.data_ptr(), off, w, w + 2, acc
-        Rp[:, off:off + w] = R[:, :w].double()
-        outs["dR%d" % q] = dR
-        rs.append((off, w, acc, init))
+        e.r_ptr[q], e.dr_ptr[q] = (gR.data_ptr() if have_r else None), (dR.data_ptr() if want_dr else None)
+        e.r_off[q], e.r_width[q], e.r_ld[q], e.dr_accumulate[q] = off, w, w + 2, acc
+        if have_r:
+            Rp[:, off:off + w] = R[:, :w].double()
+        if want_dr:
+            outs["dR%d" % q] = dR
+            rs.append((q, off, w, acc, init))
 
     def check(got):
-        close(got["dz"], dout.double() * Rp * gate.double() * (1 - gate.double()))
-        for q, (off, w, acc, init) in enumerate(rs):
+        g = got["dz"].cpu()
+        close(g[dzin].view(B, D), dout.double() * Rp * gate.double() * (1 - gate.double()))
+        assert torch.equal(g[~dzin], dzh[~dzin]), "guard columns or the tail behind dz were written"
+        for q, off, w, acc, init in rs:
             g = got["dR%d" % q].cpu()
             close(g[:, :w], (dout.double() * gate.double())[:, off:off + w] + (init[:, :w].double() if acc else 0.0))
             assert torch.equal(g[:, w:], init[:, w:])
     return Built(ctx, e, outs, check)
 
 
-def _reduce(ctx, R, Cn, lens, first=0):
-    """column sums of [R, Cn] scattered to destinations of the given lengths, laid end to end from column `first`"""
-    x = ctx.randn(R, Cn + 3)
+def _reduce(ctx, R, Cn, lens, first=0, pad=3, null=(), skip=None):
+    """column sums of [R, Cn] scattered to destinations of the given lengths, laid end to end from column `first`.  pad: columns of
+    the row stride beyond Cn; null: destinations whose pointer is NULL (their sums are dropped); skip: (destination index, columns)
+    — a range of columns in front of that destination that belongs to nobody"""
+    x = ctx.randn(R, Cn + pad)
     gx = ctx.dev(x)
     r = L.ReduceRowsDesc()
-    r.kind, r.R, r.C, r.ld, r.ndst, r.in_ = L.OP_REDUCE_ROWS, R, Cn, Cn + 3, len(lens), gx.data_ptr()
+    r.kind, r.R, r.C, r.ld, r.ndst, r.in_ = L.OP_REDUCE_ROWS, R, Cn, Cn + pad, len(lens), gx.data_ptr()
     outs, dsts, off = {}, [], first
     for q, n in enumerate(lens):
+        if skip is not None and q == skip[0]:
+            off += skip[1]
         init = torch.cat([torch.full((n,), NAN), torch.full((2,), SENTINEL)])
         t = ctx.dev(init)
-        r.dst[q], r.dst_off[q], r.dst_len[q] = t.data_ptr(), off, n
-        outs["dst%d" % q] = t
-        dsts.append((off, n))
+        r.dst[q], r.dst_off[q], r.dst_len[q] = (None if q in null else t.data_ptr()), off, n
+        if q not in null:
+            outs["dst%d" % q] = t
+            dsts.append((q, off, n))
         off += n
     assert off <= Cn
 
     def check(got):
         sums = x[:, :Cn].double().sum(0)
-        for q, (o, n) in enumerate(dsts):
+        for q, o, n in dsts:
             g = got["dst%d" % q].cpu()
             close(g[:n], sums[o:o + n])
             assert bool((g[n:] == SENTINEL).all())
@@ -756,24 +886,86 @@ for _N, _dims, _B in [(1, -1, 3), (7, -1, 5), (17, 16, 6), (33, -1, 9), (64, 40,
     _add("mha_fwd", "mha_fwd_n%d_d%d_b%d_saved" % (_N, _dims, _B), "mha_fwd", (lambda a: lambda c: _mha(c, a[0], a[1], a[2], False, True))((_N, _dims, _B)))
     _add("mha_fwd", "mha_fwd_n%d_d%d_b%d" % (_N, _dims, _B), "mha_fwd", (lambda a: lambda c: _mha(c, a[0], a[1], a[2], False, False))((_N, _dims, _B)))
     _add("mha_bwd", "mha_bwd_n%d_d%d_b%d" % (_N, _dims, _B), "mha_bwd", (lambda a: lambda c: _mha(c, a[0], a[1], a[2], True))((_N, _dims, _B)))
+# ... and the forms the plan compiler emits (tests/op_forms.py harvests them; tests/test_op_forms_cpu.py holds this table against the harvest).
+# The Transformer's output is a token range of a block's slab: x 2 tokens into a slab of N + 3, out / dout 1 token into a slab of N + 5
+# (ldx != ldo, both != N * 16; the slab's other tokens must keep their bits), the backward's partials the second node of a shared
+# [B, 2 * 1696 + 3] buffer ...
+_SHARED2 = (2 * L.MHA_PARAMS + 3, L.MHA_PARAMS)
+for _N, _dims, _B in [(16, -1, 5), (48, -1, 3), (64, 40, 5), (7, -1, 6)]:
+    _kw = dict(xs=(2, 1), os=(1, 4))
+    _nm = "n%d_d%d_b%d_slabs" % (_N, _dims, _B)
+    _add("mha_fwd", "mha_fwd_%s_saved" % _nm, "mha_fwd", (lambda a, kw: lambda c: _mha(c, a[0], a[1], a[2], False, True, **kw))((_N, _dims, _B), _kw))
+    _add("mha_fwd", "mha_fwd_%s" % _nm, "mha_fwd", (lambda a, kw: lambda c: _mha(c, a[0], a[1], a[2], False, False, **kw))((_N, _dims, _B), _kw))
+    _add("mha_bwd", "mha_bwd_%s_shared" % _nm, "mha_bwd", (lambda a, kw: lambda c: _mha(c, a[0], a[1], a[2], True, shared=_SHARED2, **kw))((_N, _dims, _B), _kw))
+# ... and as the planner lays it out: x a buffer of the Transformer's own (ldx == N * 16), the output in its own buffer (`own`) or a
+# token range in front of the 8 dense-to-sparse rows of the block's slab (`slab`); dims = N is what a supernet path at full width carries
+_SHARED1 = (L.MHA_PARAMS + 3, 0)
+for _N, _dims, _B, _os in [(16, -1, 5, (0, 8)), (48, -1, 3, (0, 0)), (48, -1, 3, (0, 8)), (64, 64, 5, (0, 0)), (64, 40, 5, (0, 8)), (64, -1, 3, (0, 8))]:
+    _kw = dict(os=_os)
+    _nm = "n%d_d%d_b%d_%s" % (_N, _dims, _B, "slab" if _os[1] else "own")
+    _add("mha_fwd", "mha_fwd_%s_saved" % _nm, "mha_fwd", (lambda a, kw: lambda c: _mha(c, a[0], a[1], a[2], False, True, **kw))((_N, _dims, _B), _kw))
+    _add("mha_fwd", "mha_fwd_%s" % _nm, "mha_fwd", (lambda a, kw: lambda c: _mha(c, a[0], a[1], a[2], False, False, **kw))((_N, _dims, _B), _kw))
+    _add("mha_bwd", "mha_bwd_%s_shared" % _nm, "mha_bwd", (lambda a, kw: lambda c: _mha(c, a[0], a[1], a[2], True, shared=_SHARED1, **kw))((_N, _dims, _B), _kw))
 for _B, _N, _acc in [(1, 1, 0), (5, 26, 1), (37, 48, 1), (37, 1, 0), (5, 48, 0), (1, 26, 1)]:
     _add("fm_fwd", "fm_fwd_b%d_n%d_acc%d" % (_B, _N, _acc), "fm_fwd", (lambda a: lambda c: _fm(c, a[0], a[1], a[2], False))((_B, _N, _acc)))
     _add("fm_bwd", "fm_bwd_b%d_n%d_acc%d" % (_B, _N, _acc), "fm_bwd", (lambda a: lambda c: _fm(c, a[0], a[1], a[2], True))((_B, _N, _acc)))
+# the planner's strides: the interaction in a buffer of its own (ld_ix == 16), x a whole slab (ldx == N * 16: a sentinel tail stands
+# in for the guards) or the node tokens in front of the slab's 8 dense-to-sparse rows; `add`: out = node sum + FM term in one pass
+for _B in (1, 5):
+    for _N in (16, 48):
+        _add("fm_fwd", "fm_fwd_b%d_n%d_add_tight" % (_B, _N), "fm_fwd", (lambda a: lambda c: _fm(c, a[0], a[1], 0, False, extra=0, ld_ix=16, add=True))((_B, _N)))
+for _N in (16, 48):
+    for _extra in (0, 8):
+        _nm = "b5_n%d_%s" % (_N, "tight" if not _extra else "slab")
+        _add("fm_fwd", "fm_fwd_%s" % _nm, "fm_fwd", (lambda a: lambda c: _fm(c, 5, a[0], 0, False, extra=a[1], ld_ix=16))((_N, _extra)))
+        _add("fm_bwd", "fm_bwd_%s_acc1" % _nm, "fm_bwd", (lambda a: lambda c: _fm(c, 5, a[0], 1, True, extra=a[1], ld_ix=16))((_N, _extra)))
 for _k1, _B in [(2, 3), (9, 11), (16, 3), (17, 11), (33, 3), (46, 11)]:
     _add("dot_tri_fwd", "dot_tri_fwd_k%d_b%d" % (_k1, _B), "dot_tri_fwd", (lambda a: lambda c: _dot_tri(c, a[0], a[1], False))((_k1, _B)))
     _add("dot_tri_bwd", "dot_tri_bwd_k%d_b%d" % (_k1, _B), "dot_tri_bwd", (lambda a: lambda c: _dot_tri(c, a[0], a[1], True))((_k1, _B)))
+# ld_out == k1 (k1 - 1) / 2 exactly (the planner's: rows start off 16-byte boundaries); 3 floats of sentinel behind the last row
+for _k1, _B in [(9, 3), (17, 5), (33, 3), (40, 5), (46, 3)]:
+    _add("dot_tri_fwd", "dot_tri_fwd_k%d_b%d_tight" % (_k1, _B), "dot_tri_fwd", (lambda a: lambda c: _dot_tri(c, a[0], a[1], False, pad=0))((_k1, _B)))
+    _add("dot_tri_bwd", "dot_tri_bwd_k%d_b%d_tight" % (_k1, _B), "dot_tri_bwd", (lambda a: lambda c: _dot_tri(c, a[0], a[1], True, pad=0))((_k1, _B)))
 _add("copy_segs", "copy_forward_gap", "copy_segs", lambda c: _copy(c, 21, False))
 _add("copy_segs", "copy_reverse_gap", "copy_segs", lambda c: _copy(c, 21, True))
 BIG_COPY = "copy_4097x4096_unpacked_table"
 _add("copy_segs", BIG_COPY, "copy_segs", lambda c: _copy(c, 4097, False, big=True))
+_add("copy_segs", "copy_forward_accumulate_gap", "copy_segs", lambda c: _copy_fwd(c, 21, [(0, 5, 2, False), (12, 9 * 16, 0, False)], True))
+_add("copy_segs", "copy_forward_null_segment_gap", "copy_segs", lambda c: _copy_fwd(c, 21, [(0, 5, 2, False), (7, 40, 0, True), (50, 33, 1, False)], False))
+_add("copy_segs", "copy_forward_accumulate_one_segment", "copy_segs", lambda c: _copy_fwd(c, 21, [(0, 37, 3, False)], True))  # (_alias_add, masked_copy)
+_add("copy_segs", "copy_forward_zero_fill", "copy_segs", lambda c: _copy_fwd(c, 21, [(0, 37, 0, True)], False))  # (zero_fill)
+_add("copy_segs", "copy_reverse_one_segment", "copy_segs", lambda c: _copy_rev(c, 21, 37, 0))
 _add("gate_bwd", "gate_21x32_one_segment", "gate_bwd", lambda c: _gate(c, 21, 32, [(0, 13, 1)]))
 _add("gate_bwd", "gate_21x32_two_segments", "gate_bwd", lambda c: _gate(c, 21, 32, [(0, 13, 1), (16, 10, 0)]))
+# seven segments; the first wants no gradient (the raw dense features), one has no R, the accumulate flags mixed, three different wide
+# strides, columns 30 .. 32 in no segment
+_add("gate_bwd", "gate_5x61_seven_segments", "gate_bwd", lambda c: _gate(
+    c, 5, 61, [(0, 13, 0, False), (13, 8, 1), (21, 9, 0), (33, 5, 1, True, False), (38, 7, 0), (45, 10, 1), (55, 6, 0)], pads=(3, 19, 7)))
+# the planner's: one segment (a sampled path, a fixed sub-network) with and without a gradient, covering D or its head; the full path's
+# k + 1 segments of block k, the first without a gradient; strides == D (batch 256) or all three padded alike (batch 2048)
+for _pads in ((0, 0, 0), (19, 19, 19)):
+    _p = "tight" if not _pads[0] else "wide"
+    for _nm, _segs, _D in [("head_acc", [(0, 13, 1)], 29), ("head_set", [(0, 13, 0)], 29), ("head_no_dr", [(0, 13, 0, False)], 29),
+                           ("all_set", [(0, 29, 0)], 29), ("all_no_dr", [(0, 13, 0, False)], 13)]:
+        _add("gate_bwd", "gate_5x%d_%s_%s" % (_D, _nm, _p), "gate_bwd", (lambda a: lambda c: _gate(c, 5, a[0], a[1], pads=a[2]))((_D, _segs, _pads)))
+    for _n in range(2, 8):
+        _segs = [(0, 13, 0, False)] + [(13 + 8 * (q - 1), 8, 1) for q in range(1, _n)]
+        _add("gate_bwd", "gate_5x%d_%d_segments_%s" % (13 + 8 * (_n - 1), _n, _p), "gate_bwd",
+             (lambda a: lambda c: _gate(c, 5, a[0], a[1], pads=a[2]))((13 + 8 * (_n - 1), _segs, _pads)))
 _MHA_LENS = [48 * 16, 48, 256, 16, 16, 16, 256, 16, 256, 16, 16, 16]
+_16DST = [3, 1, 2, 5, 1, 1, 4, 2, 1, 3, 2, 1, 5, 2, 3, 1]
 _add("reduce_rows", "reduce_r13_c1696_mha", "reduce_rows", lambda c: _reduce(c, 13, 1696, _MHA_LENS))
 _add("reduce_rows", "reduce_r256_c1696_mha", "reduce_rows", lambda c: _reduce(c, 256, 1696, _MHA_LENS))
-_add("reduce_rows", "reduce_r256_c37_16dst", "reduce_rows", lambda c: _reduce(c, 256, 37, [3, 1, 2, 5, 1, 1, 4, 2, 1, 3, 2, 1, 5, 2, 3, 1]))
+_add("reduce_rows", "reduce_r256_c37_16dst", "reduce_rows", lambda c: _reduce(c, 256, 37, _16DST))
 _add("reduce_rows", "reduce_r1_c37_1dst", "reduce_rows", lambda c: _reduce(c, 1, 37, [26], first=5))
-_add("reduce_rows", "reduce_r13_c37_16dst", "reduce_rows", lambda c: _reduce(c, 13, 37, [3, 1, 2, 5, 1, 1, 4, 2, 1, 3, 2, 1, 5, 2, 3, 1]))
+_add("reduce_rows", "reduce_r13_c37_16dst", "reduce_rows", lambda c: _reduce(c, 13, 37, _16DST))
+# the three tiers of the row loop (256-row trips, 64-row trips, single rows): R = 64 runs the second alone, R = 300 the first and the third
+_add("reduce_rows", "reduce_r64_c37_16dst", "reduce_rows", lambda c: _reduce(c, 64, 37, _16DST))
+_add("reduce_rows", "reduce_r300_c37_16dst", "reduce_rows", lambda c: _reduce(c, 300, 37, _16DST))
+# the planner's: ld == C, every column somebody's — LayerNorm partials [16 or 64 workgroups, 2 D], one Transformer's partials [256, 1696]
+_add("reduce_rows", "reduce_r16_c34_2dst_tight", "reduce_rows", lambda c: _reduce(c, 16, 34, [17, 17], pad=0))
+_add("reduce_rows", "reduce_r64_c34_2dst_tight", "reduce_rows", lambda c: _reduce(c, 64, 34, [17, 17], pad=0))
+_add("reduce_rows", "reduce_r256_c1696_mha_tight", "reduce_rows", lambda c: _reduce(c, 256, 1696, _MHA_LENS, pad=0))
 for _B in (1, 37, 255, 256):
     _add("dedup_ids", "dedup_b%d_fs5" % _B, "dedup_ids", (lambda b: lambda c: _dedup(c, b))(_B))
 for _B in (5, 256, 1030):
