@@ -362,7 +362,29 @@ typedef struct nasrec_final_desc {
      gives such a segment: feature j of the (contiguous [B, N*16]) segment meets weight w[off[q] + (j / 16) * tok_stride[q] + j % 16];
      0 = the plain contiguous placement w[off[q] + j]. */
   int32_t tok_stride[NASREC_MAX_SEGS];
+  /* NASREC_OP_FINAL_FUSED, optional "head Linear" (head_x != NULL): the dense Linear whose output IS segment head_seg and has no other
+     forward reader, y = head_pre + x W^T + head_bias (no activation, mask or LayerNorm; head_K <= NASREC_FINAL_HEAD_K,
+     head_N <= NASREC_FINAL_HEAD_N), and the input gradient behind it, computed by the workgroup of sample b beside its logit:
+       forward   head_y[b, :] = seg[head_seg][b, :] is WRITTEN here (the Linear's weight-gradient product still reads it) and the logit
+                 is summed from it;
+       backward  dseg[head_seg][b, :] = d y[b, :] as without a head, and, with head_dx != NULL,
+                 head_dx[b, :] (+)= d y[b, :] W   (head_dx_accumulate: onto what is there).
+     Both products run on v_mfma_f32_16x16x4_f32 with the k order of the GEMM family (sample b's row in a 16-row tile) and the
+     epilogue order +pre, +bias, + accumulation target: bit-identical to the GEMM launches they replace.  seg[head_seg] must be
+     head_y with width[head_seg] = head_N, ld[head_seg] = head_ldy (head_pre has the same row stride) and tok_stride 0. */
+  const float* head_x;     /* [B, head_K], row stride head_ldx; NULL = no head Linear */
+  const float* head_w;     /* [head_N, head_K], row stride head_ldw */
+  const float* head_bias;  /* [head_N] or NULL */
+  const float* head_pre;   /* [B, head_N], row stride head_ldy, or NULL */
+  float* head_y;           /* [B, head_N], row stride head_ldy */
+  float* head_dx;          /* [B, head_K], row stride head_lddx, or NULL (forward half only) */
+  int32_t head_K, head_N;
+  int32_t head_ldx, head_ldw, head_ldy, head_lddx;
+  int32_t head_dx_accumulate;
+  int32_t head_seg;
 } nasrec_final_desc_t;
+#define NASREC_FINAL_HEAD_K 32
+#define NASREC_FINAL_HEAD_N 256
 
 /* BCEWithLogitsLoss(mean) forward + dlogits (main_train.py:122; train_utils.py:266):
  * loss = mean(max(z,0) - z*y + log1p(exp(-|z|))), dlogits[b] = (sigmoid(z_b) - y_b) * grad_scale. */

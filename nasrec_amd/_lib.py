@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("NASREC_HIP_LIB") or os.path.join(_HERE, "lib", "libna
 
 MAX_SEGS = 8
 MAX_TABLES = 32
+FINAL_HEAD_K, FINAL_HEAD_N = 32, 256  # NASREC_FINAL_HEAD_*: the widest head Linear OP_FINAL_FUSED takes with it
 EMB_DIM = 16
 MHA_PARAMS = 1696
 MHA_SAVED = 36
@@ -119,7 +120,11 @@ class FinalDesc(C.Structure):
     _fields_ = [("kind", i32), ("B", i32), ("nseg", i32), ("grad_scale", f32), ("w", vp), ("bias", vp), ("logits", vp), ("dlogits", vp),
                 ("dw", vp), ("dbias", vp), ("seg", vp * MAX_SEGS), ("dseg", vp * MAX_SEGS), ("width", i32 * MAX_SEGS),
                 ("ld", i32 * MAX_SEGS), ("off", i32 * MAX_SEGS), ("dseg_accumulate", i32 * MAX_SEGS), ("y", vp), ("loss", vp),
-                ("dlogits_out", vp), ("nsplit", i32), ("dseg_done", i32), ("tok_stride", i32 * MAX_SEGS)]
+                ("dlogits_out", vp), ("nsplit", i32), ("dseg_done", i32), ("tok_stride", i32 * MAX_SEGS),
+                # the optional head Linear of OP_FINAL_FUSED (include/nasrec_hip.h)
+                ("head_x", vp), ("head_w", vp), ("head_bias", vp), ("head_pre", vp), ("head_y", vp), ("head_dx", vp),
+                ("head_K", i32), ("head_N", i32), ("head_ldx", i32), ("head_ldw", i32), ("head_ldy", i32), ("head_lddx", i32),
+                ("head_dx_accumulate", i32), ("head_seg", i32)]
 
 
 class BceDesc(C.Structure):

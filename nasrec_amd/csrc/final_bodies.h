@@ -30,26 +30,33 @@ __host__ __device__ inline int final_seg_extent(const nasrec_final_desc_t& d, in
 // with the per-sample backward behind it — on the step's critical path, alone in its level.)
 // ---------------------------------------------------------------------------------------------------
 // -> the sample's logit in every thread; red: 4 floats of LDS
-__device__ __forceinline__ float final_logit(const nasrec_final_desc_t& d, int b, float* red) {
+// hs >= 0: segment hs of this sample is read from the workgroup's LDS row hy instead of memory (the head Linear's output, which the
+// workgroup has just computed: final_fused_block) — the same values in the same order of summation
+__device__ __forceinline__ float final_logit(const nasrec_final_desc_t& d, int b, float* red, int hs = -1, const float* hy = nullptr) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   float s = 0.f;
   for (int q = 0; q < d.nseg; ++q) {
     if (!d.seg[q]) continue;
-    const float* x = d.seg[q] + (long)b * d.ld[q];
     const float* w = d.w + d.off[q];
     const int W = d.width[q], ts = d.tok_stride[q];
-    for (int j0 = lane + 64 * wave; j0 < W; j0 += 256 * 4) {
-      float xv[4], wv[4];
+    auto trips = [&](const float* x) {
+      for (int j0 = lane + 64 * wave; j0 < W; j0 += 256 * 4) {
+        float xv[4], wv[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int j = min(j0 + 256 * u, W - 1);
-        xv[u] = x[j];
-        wv[u] = w[ts ? (j >> 4) * ts + (j & 15) : j];
+        for (int u = 0; u < 4; ++u) {
+          const int j = min(j0 + 256 * u, W - 1);
+          xv[u] = x[j];
+          wv[u] = w[ts ? (j >> 4) * ts + (j & 15) : j];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          if (j0 + 256 * u < W) s = fmaf(xv[u], wv[u], s);
       }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (j0 + 256 * u < W) s = fmaf(xv[u], wv[u], s);
-    }
+    };
+    if (q == hs)
+      trips(hy);
+    else
+      trips(d.seg[q] + (long)b * d.ld[q]);
   }
   s = wave_sum(s);
   __syncthreads();  // (red may still be read from an earlier use of the buffer)
@@ -70,14 +77,155 @@ __device__ __forceinline__ float bce_term(float z, float y) { return fmaxf(z, 0.
 
 // NASREC_OP_FINAL_FUSED: final_fwd_block, and behind it — in the workgroup that holds the sample's logit — the part of the backward that
 // needs nothing else: dseg[b, j] (+)= dlogits[b] * w[col(j)], the expression of final_bwd_block's part A.  workgroup vb of B.
+//
+// With a head Linear (nasrec_final_desc_t.head_x: y = pre + x W^T + bias, K <= 32 inputs, N <= 256 outputs, y = segment head_seg) the
+// workgroup computes its sample's row of y first and its row of dx = dy W last: two launches of the step's critical path (a 16-deep
+// Linear alone in its level in front of the logit, its input gradient alone in the level behind it) that are 2 K multiply-adds per
+// sample each.  Both run as the GEMM family runs them — v_mfma_f32_16x16x4_f32, MFMA j of 16-deep step s sums k = 16 s + 4 g + j
+// (wl_dense_small / wl_dense_small_dx in worklist_body.h), steps in order, then +pre, +bias, + accumulation target (epilogue_store) —
+// with the sample's row in all sixteen rows of the A tile (an output row depends on its own input row only): the same bits.
+// Wave v takes the column tiles v, v + 4, ... of y and tile v of dx.  Every load that does not depend on the logit is issued up front
+// (x, W for both products, pre, bias, the accumulation target of dx, the first lines of the other segments): one round trip.
+// red: FINAL_FUSED_LDS_FLOATS floats of LDS (4 without a head).
+#define FINAL_FUSED_LDS_FLOATS (16 + 2 * NASREC_FINAL_HEAD_N)  // the logit's four partial sums | y[b, :] | dy[b, :]
+#define FINAL_HEAD_DX_STEPS 8  // 16-deep k-steps of the dx product whose weights are in flight at once
+#define FINAL_HEAD_PRE_TRIPS 2  // trips of 1024 features of the other segment that are loaded beside the head's operands
 __device__ __forceinline__ void final_fused_block(const nasrec_final_desc_t& d, int vb, float* red) {
   const int b = vb;
   if (b >= d.B) return;
+  const int tid = threadIdx.x;
+  const bool head = d.head_x != nullptr;
+  const int hs = head ? d.head_seg : -1;
+  float* const ys = red + 16;
+  float* const dys = ys + NASREC_FINAL_HEAD_N;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int e = lane & 15, fg = lane >> 4;
+  const int hK = head ? d.head_K : 0, hN = head ? d.head_N : 0;
+  const bool head_dx = head && d.head_dx != nullptr && wave * 16 < hK;  // (this wave owns a tile of dx)
+  const int xcol = min(wave * 16 + e, max(hK - 1, 0));
+  float fbx[FINAL_HEAD_DX_STEPS][4];
+  float cvx = 0.f, whd = 0.f, yv[4] = {0.f, 0.f, 0.f, 0.f};
+  float px[FINAL_HEAD_PRE_TRIPS][4], pw[FINAL_HEAD_PRE_TRIPS][4];
+  int pq = -1;  // the segment whose first trips are preloaded
   const float yb = d.y[b];  // (in flight under the sum)
-  const float z = final_logit(d, b, red);
+  if (head) {
+    const int NT = (hN + 15) >> 4, ldw = d.head_ldw;
+    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.head_x + (long)b * d.head_ldx), 0, 4 * hK, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.head_w), 0, 4 * ((hN - 1) * ldw + hK), 0x00020000);
+    f32x4 fa[2], fb[4][2];
+    float pv[4], bv[4];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) fa[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ra, 4 * (16 * s + 4 * fg), 0, 0));  // (past K: zeros)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int col = min(min(wave + 4 * t, NT - 1) * 16 + e, hN - 1);
+#pragma unroll
+      for (int s = 0; s < 2; ++s) fb[t][s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, 4 * (col * ldw + 16 * s + 4 * fg), 0, 0));
+      pv[t] = d.head_pre ? d.head_pre[(long)b * d.head_ldy + col] : 0.f;
+      bv[t] = d.head_bias ? d.head_bias[col] : 0.f;
+    }
+    if (head_dx) {  // B(n, k) = W[k ldw + n] of the dx product: four rows of W per step, clamped (masked where they are used)
+#pragma unroll
+      for (int s = 0; s < FINAL_HEAD_DX_STEPS; ++s)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) fbx[s][j] = d.head_w[(long)min(16 * s + 4 * fg + j, hN - 1) * ldw + xcol];
+      if (d.head_dx_accumulate) cvx = d.head_dx[(long)b * d.head_lddx + xcol];
+    }
+    // ... and what the logit's sum needs beside y: the final weights of y's columns and the first FINAL_HEAD_PRE_TRIPS trips of the
+    // first other segment with its weights (the plan's activations live in uncached memory: a second read is a second trip to HBM)
+    whd = d.w[d.off[hs] + min(tid, hN - 1)];
+    for (int q = 0; q < d.nseg && pq < 0; ++q)
+      if (d.seg[q] && q != hs && d.width[q] > 0) pq = q;
+    if (pq >= 0) {
+      const float* x = d.seg[pq] + (long)b * d.ld[pq];
+      const float* w = d.w + d.off[pq];
+      const int W = d.width[pq], ts = d.tok_stride[pq];
+#pragma unroll
+      for (int t = 0; t < FINAL_HEAD_PRE_TRIPS; ++t)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int j = min(tid + 1024 * t + 256 * u, W - 1);
+          px[t][u] = x[j];
+          pw[t][u] = w[ts ? (j >> 4) * ts + (j & 15) : j];
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int nt = wave + 4 * t;
+      if (nt >= NT) break;  // (uniform)
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int l = hK - 16 * s;
+        if (l > 0) {  // (uniform)
+          f32x4 a = fa[s], w4 = fb[t][s];
+          if (l < 16) {  // last step: the 16-byte load of W may run into the next row
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const bool in = 4 * fg + j < l;
+              a[j] = in ? a[j] : 0.f;
+              w4[j] = in ? w4[j] : 0.f;
+            }
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], w4[j], acc, 0, 0, 0);
+        }
+      }
+      // C/D layout of v_mfma_f32_16x16x4_f32: col = lane & 15, row = 4 * (lane >> 4) + reg — row 0 is as good as any
+      const int col = nt * 16 + e;
+      if (fg == 0 && col < hN) {
+        float v = acc[0];
+        if (d.head_pre) v += pv[t];
+        if (d.head_bias) v += bv[t];
+        yv[t] = v;  // (stored behind the gradients: a store in front of the loads below would be waited for with them)
+        ys[col] = v;
+      }
+    }
+    __syncthreads();
+  }
+  float z;
+  if (!head) {
+    z = final_logit(d, b, red);
+  } else {  // final_logit with y from LDS and the preloaded operands: the same terms in the same order
+    float s = 0.f;
+    for (int q = 0; q < d.nseg; ++q) {
+      if (!d.seg[q]) continue;
+      const int W = d.width[q], ts = d.tok_stride[q];
+      if (q == hs) {
+        if (tid < W) s = fmaf(ys[tid], whd, s);
+        continue;
+      }
+      int j0 = tid;
+      if (q == pq) {
+#pragma unroll
+        for (int t = 0; t < FINAL_HEAD_PRE_TRIPS; ++t)
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (tid + 1024 * t + 256 * u < W) s = fmaf(px[t][u], pw[t][u], s);
+        j0 = tid + 1024 * FINAL_HEAD_PRE_TRIPS;
+      }
+      const float* x = d.seg[q] + (long)b * d.ld[q];
+      const float* w = d.w + d.off[q];
+      for (; j0 < W; j0 += 256 * 4) {
+        float xv[4], wv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int j = min(j0 + 256 * u, W - 1);
+          xv[u] = x[j];
+          wv[u] = w[ts ? (j >> 4) * ts + (j & 15) : j];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          if (j0 + 256 * u < W) s = fmaf(xv[u], wv[u], s);
+      }
+    }
+    s = wave_sum(s);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    z = ((red[0] + red[1]) + (red[2] + red[3])) + d.bias[0];
+  }
   if (threadIdx.x == 0) d.logits[b] = z;
   const float g = bce_grad(z, yb, d.grad_scale);
-  const int tid = threadIdx.x;
   for (int q = 0; q < d.nseg; ++q) {
     float* p = d.dseg[q];
     if (!p || !d.seg[q]) continue;
@@ -85,7 +233,33 @@ __device__ __forceinline__ void final_fused_block(const nasrec_final_desc_t& d, 
     const float* w = d.w + d.off[q];
     const int W = d.width[q], ts = d.tok_stride[q];
     const bool acc = d.dseg_accumulate[q] != 0;
-    for (int j0 = tid; j0 < W; j0 += 256 * 4) {  // reads first (weights; the accumulation targets), then the stores
+    int jf = tid;
+    if (q == hs) {  // dy[b, :]: the weights are in registers; the value goes to memory and, as the A operand of the dx product, to LDS
+      const float cv = (acc && tid < W) ? p[tid] : 0.f;
+      const float v = g * whd;
+      const float o = acc ? cv + v : v;
+      if (tid < W) {
+        p[tid] = o;
+        dys[tid] = o;
+      }
+      continue;
+    }
+    if (q == pq) {  // the preloaded trips: only the accumulation targets are read
+      float cv[FINAL_HEAD_PRE_TRIPS][4];
+#pragma unroll
+      for (int t = 0; t < FINAL_HEAD_PRE_TRIPS; ++t)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) cv[t][u] = acc ? p[min(tid + 1024 * t + 256 * u, W - 1)] : 0.f;
+#pragma unroll
+      for (int t = 0; t < FINAL_HEAD_PRE_TRIPS; ++t)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const float v = g * pw[t][u];
+          if (tid + 1024 * t + 256 * u < W) p[tid + 1024 * t + 256 * u] = acc ? cv[t][u] + v : v;
+        }
+      jf = tid + 1024 * FINAL_HEAD_PRE_TRIPS;
+    }
+    for (int j0 = jf; j0 < W; j0 += 256 * 4) {  // reads first (weights; the accumulation targets), then the stores
       float wv[4], cv[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -96,9 +270,44 @@ __device__ __forceinline__ void final_fused_block(const nasrec_final_desc_t& d, 
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const float v = g * wv[u];
-        if (j0 + 256 * u < W) p[j0 + 256 * u] = acc ? cv[u] + v : v;
+        const float o = acc ? cv[u] + v : v;
+        if (j0 + 256 * u < W) p[j0 + 256 * u] = o;
       }
     }
+  }
+  if (!head) return;  // (uniform)
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int col = (wave + 4 * t) * 16 + e;
+    if (fg == 0 && col < hN) d.head_y[(long)b * d.head_ldy + col] = yv[t];
+  }
+  if (!d.head_dx) return;  // (uniform)
+  __syncthreads();
+  if (!head_dx) return;
+  f32x4 accx = {0.f, 0.f, 0.f, 0.f};
+  for (int s0 = 0; 16 * s0 < hN; s0 += FINAL_HEAD_DX_STEPS) {
+    if (s0 > 0) {  // N > 128: the next eight steps' weights
+#pragma unroll
+      for (int s = 0; s < FINAL_HEAD_DX_STEPS; ++s)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) fbx[s][j] = d.head_w[(long)min(16 * (s0 + s) + 4 * fg + j, hN - 1) * d.head_ldw + xcol];
+    }
+#pragma unroll
+    for (int s = 0; s < FINAL_HEAD_DX_STEPS; ++s) {
+      if (16 * (s0 + s) < hN) {  // (uniform)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int k = 16 * (s0 + s) + 4 * fg + j;
+          const bool in = k < hN;
+          accx = __builtin_amdgcn_mfma_f32_16x16x4f32(in ? dys[k] : 0.f, in ? fbx[s][j] : 0.f, accx, 0, 0, 0);
+        }
+      }
+    }
+  }
+  if (fg == 0 && wave * 16 + e < hK) {
+    float v = accx[0];
+    if (d.head_dx_accumulate) v += cvx;
+    d.head_dx[(long)b * d.head_lddx + xcol] = v;
   }
 }
 

@@ -16,7 +16,7 @@ __global__ __launch_bounds__(256) void final_bwd_kernel(const nasrec_final_desc_
 }
 
 __global__ __launch_bounds__(256) void final_fused_kernel(const nasrec_final_desc_t d) {
-  __shared__ float red[4];
+  __shared__ float red[FINAL_FUSED_LDS_FLOATS];
   final_fused_block(d, blockIdx.x, red);
 }
 
@@ -25,6 +25,18 @@ int final_fused_check(const nasrec_final_desc_t* d) {
   if (d->nsplit > 1) return nasrec_set_error(-2, "final_fused: nsplit=%d (the batch-sliced backward keeps its own launch)", d->nsplit);
   for (int q = 0; q < d->nseg; ++q)
     if (d->dseg[q] && !d->seg[q]) return nasrec_set_error(-2, "final_fused: segment %d has a gradient destination and no input", q);
+  if (d->head_x) {  // the head Linear (include/nasrec_hip.h)
+    const int hs = d->head_seg;
+    if (!d->head_w || !d->head_y || d->head_K < 1 || d->head_K > NASREC_FINAL_HEAD_K || d->head_N < 1 || d->head_N > NASREC_FINAL_HEAD_N)
+      return nasrec_set_error(-2, "final_fused: head Linear needs W and y, 1 <= K <= %d, 1 <= N <= %d (K=%d N=%d)", NASREC_FINAL_HEAD_K,
+                              NASREC_FINAL_HEAD_N, d->head_K, d->head_N);
+    if (d->head_ldx < d->head_K || d->head_ldw < d->head_K || d->head_ldy < d->head_N || (d->head_dx && d->head_lddx < d->head_K))
+      return nasrec_set_error(-2, "final_fused: head Linear row strides shorter than the rows");
+    if (d->head_ldw > (1 << 20)) return nasrec_set_error(-2, "final_fused: head_ldw=%d (the body's offsets into W are 32-bit byte counts)", d->head_ldw);
+    if (hs < 0 || hs >= d->nseg || d->seg[hs] != d->head_y || d->width[hs] != d->head_N || d->ld[hs] != d->head_ldy || d->tok_stride[hs])
+      return nasrec_set_error(-2, "final_fused: segment head_seg=%d is not the head Linear's output", hs);
+    if (d->head_dx && !d->dseg[hs]) return nasrec_set_error(-2, "final_fused: head_dx needs the gradient destination of segment %d", hs);
+  }
   return 0;
 }
 

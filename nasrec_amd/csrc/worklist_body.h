@@ -505,6 +505,7 @@ __device__ __forceinline__ void wl_run(unsigned f01, unsigned f23, unsigned f45,
       final_fwd_block(wl_ref<nasrec_final_desc_t>(blob), __builtin_amdgcn_readfirstlane(vb), lds);
       break;
     case NASREC_OP_FINAL_FUSED:
+      wl_warm_blob(blob, (int)sizeof(nasrec_final_desc_t));  // (eight lines of descriptor, the head Linear's in the last two: one wait, not one per line)
       final_fused_block(wl_ref<nasrec_final_desc_t>(blob), __builtin_amdgcn_readfirstlane(vb), lds);
       break;
     case NASREC_OP_FINAL_BWD:

@@ -528,6 +528,7 @@ class SupernetEngine:
             if self.dead_code_elimination and cfg.fixed:
                 fwd_list, cp.dead_forward = S.eliminate_dead_forward(fwd_list, ctx.bwd if train else [])
             if scheduled:
+                fwd_list = S.order_two_term_accumulates(fwd_list)
                 fwd_descs, cp.fwd_levels = S.pack(fwd_list)
                 self._resident_worklists(cp, fwd_descs)
             else:
@@ -571,6 +572,7 @@ class SupernetEngine:
                     # (alloc: a forward product with several levels of slack may be re-cut into split-K items — only in the JOINT
                     # program, where the backward's latency-bound levels are there to hide it)
                     jf, jb = self._fuse_final(fwd_list, bwd_descs, fused) if _FUSE_FINAL else (fwd_list, bwd_descs)
+                    jf, jb = self._fuse_head(jf, jb)
                     fb_descs = None
                     cp.persistent = False
                     cp.level_tuning = None
@@ -1316,6 +1318,69 @@ class SupernetEngine:
         rest = L.FinalDesc.from_buffer_copy(fused)
         rest.dseg_done = 1
         return ([both if i == fi[0] else d for i, d in enumerate(fwd_list)], [rest if d is fused else d for d in bwd_descs])
+
+    @staticmethod
+    def _fuse_head(fwd_list, bwd_descs):
+        """joint program, behind _fuse_final: the last dense Linear y = pre_add + x W^T + b whose only forward reader is the final logit
+        (<= 32 inputs, <= 256 outputs: 2 K multiply-adds per sample in ea_criteo_kaggle_xlarge_best_1shot.json, alone in its level) and
+        its input gradient dx (+)= dy W (alone in the level behind the logit) become part of NASREC_OP_FINAL_FUSED: the workgroup that
+        sums a sample's logit computes the sample's row of both (csrc/final_bodies.h, same MFMA, same k order, same epilogue order:
+        the bit-identity tests against one launch per operator cover it).  Two levels less.  Everything else — an activation, mask,
+        LayerNorm or gating operand on the Linear, several K-segments, another forward reader of y, token-strided segments
+        (last_n_blocks_out > 1), an operator in between that the move would overtake — keeps today's descriptors; a Linear whose dx
+        product does not fit the pattern still gives its forward half."""
+        fi = [i for i, d in enumerate(fwd_list) if isinstance(d, L.FinalDesc) and d.kind == L.OP_FINAL_FUSED]
+        if len(fi) != 1:
+            return fwd_list, bwd_descs
+        fi = fi[0]
+        both = fwd_list[fi]
+        if both.head_x or any(both.tok_stride[q] for q in range(both.nseg)):
+            return fwd_list, bwd_descs
+        fn = [S.Node(d) for d in fwd_list]
+        if any(n.reads is None for n in fn):
+            return fwd_list, bwd_descs
+
+        def bare(d, zmode):
+            return (isinstance(d, L.GemmDesc) and d.nseg == 1 and d.zmode == zmode and d.splitk <= 1 and not d.defer_second_pass and d.act == L.ACT_NONE
+                    and d.dims_in_use < 0 and not d.save_z and not d.save_act and d.mul_nseg == 0 and d.precision == 0 and d.cmode == L.CM_PLAIN
+                    and d.amode == L.AM_KC and d.seg[0].A and not d.seg[0].Aaux and not d.seg[0].Baux and not d.seg[0].ones_col
+                    and not 0 < d.seg[0].Mvalid < d.seg[0].M)
+        for hi in range(fi - 1, -1, -1):
+            h = fwd_list[hi]
+            if not (bare(h, 0) and h.bmode == L.AM_KC and h.beta == 0):
+                continue
+            s = h.seg[0]
+            hq = [q for q in range(both.nseg) if both.seg[q] == s.C and both.width[q] == s.N and both.ld[q] == s.ldc]
+            if len(hq) != 1 or s.M != both.B or not (1 <= s.K <= L.FINAL_HEAD_K and 1 <= s.N <= L.FINAL_HEAD_N) or s.ldb > (1 << 20):
+                continue
+            hq = hq[0]
+            y = S.Acc(s.C, s.M, s.N, s.ldc)
+            others = [n for i, n in enumerate(fn) if i not in (hi, fi)]
+            if any(S.overlap(a, y) for n in others for a in n.reads + n.writes):
+                continue  # another forward reader (or writer) of y
+            if any(S._depends(fn[i], fn[hi]) for i in range(hi + 1, fi)):
+                continue  # the Linear cannot move behind an operator that overwrites one of its operands
+            new = L.FinalDesc.from_buffer_copy(both)
+            new.head_x, new.head_w, new.head_bias, new.head_pre, new.head_y = s.A, s.B, h.bias, h.pre_add, s.C
+            new.head_K, new.head_N, new.head_ldx, new.head_ldw, new.head_ldy, new.head_seg = s.K, s.N, s.lda, s.ldb, s.ldc, hq
+            jf = [new if i == fi else d for i, d in enumerate(fwd_list) if i != hi]
+            jb = list(bwd_descs)
+            # the input gradient: one problem dx = dy W on the same W, reading what this operator writes as dseg[hq]
+            for xi, x in enumerate(bwd_descs):
+                if not (bare(x, 1) and x.bmode == L.AM_RC and not x.bias and not x.pre_add and both.dseg[hq]):
+                    continue
+                t = x.seg[0]
+                if not (t.A == both.dseg[hq] and t.lda == both.ld[hq] and t.B == s.B and t.ldb == s.ldb and (t.M, t.N, t.K) == (s.M, s.K, s.N) and t.C):
+                    continue
+                xn = S.Node(x)
+                before = [S.Node(d) for d in fwd_list[fi + 1:] + bwd_descs[:xi]]  # what the product overtakes when it moves into the logit's operator
+                if any(n.reads is None or S._depends(xn, n) for n in before):
+                    break
+                new.head_dx, new.head_lddx, new.head_dx_accumulate = t.C, t.ldc, int(t.accumulate != 0)
+                jb = [d for i, d in enumerate(bwd_descs) if i != xi]
+                break
+            return jf, jb
+        return fwd_list, bwd_descs
 
     def _stage_inputs(self, sp, cp, int_x, cat_x, y=None, lr=None, rows=None, launch=True):
         """one launch: batch -> the plan's static buffers (+ this step's learning rate -> device scalar); host_embedding: the

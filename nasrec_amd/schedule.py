@@ -214,8 +214,9 @@ def desc_io(d, part="whole") -> Tuple[List[Acc], List[Acc]]:
             ts, Wq = d.tok_stride[q], d.width[q]
             return ((Wq - 1) // 16) * ts + (Wq - 1) % 16 + 1 if (ts and Wq > 0) else Wq
         K = max([d.off[q] + extent(q) for q in range(d.nseg)] + [0])
+        headed = k == L.OP_FINAL_FUSED and bool(d.head_x)
         for q in range(d.nseg):
-            if d.seg[q]:
+            if d.seg[q] and not (headed and q == d.head_seg):  # (a headed operator writes that segment itself: below)
                 R.append(Acc(d.seg[q], d.B, d.width[q], d.ld[q]))
         R.append(_flat(d.w, K))
         if k in (L.OP_FINAL_FWD, L.OP_FINAL_FUSED):
@@ -234,6 +235,18 @@ def desc_io(d, part="whole") -> Tuple[List[Acc], List[Acc]]:
                     W.append(a)
                     if d.dseg_accumulate[q]:
                         R.append(a)
+        if k == L.OP_FINAL_FUSED and d.head_x:  # the head Linear it takes with it: y = pre + x W^T + bias in, dx (+)= dy W out
+            R += [Acc(d.head_x, d.B, d.head_K, d.head_ldx), Acc(d.head_w, d.head_N, d.head_K, d.head_ldw)]
+            if d.head_bias:
+                R.append(_flat(d.head_bias, d.head_N))
+            if d.head_pre:
+                R.append(Acc(d.head_pre, d.B, d.head_N, d.head_ldy))
+            W.append(Acc(d.head_y, d.B, d.head_N, d.head_ldy))
+            if d.head_dx:
+                a = Acc(d.head_dx, d.B, d.head_K, d.head_lddx)
+                W.append(a)
+                if d.head_dx_accumulate:
+                    R.append(a)
         if k == L.OP_FINAL_BWD:
             W.append(_flat(d.dw, (K + 1) * max(d.nsplit, 1)))
             for ptr, n in ((d.dbias, 1), (d.loss, 1), (d.dlogits_out, d.B)):
@@ -343,7 +356,12 @@ def assign_levels(nodes: List[Node]) -> int:
 BALANCE = os.environ.get("NASREC_WL_BALANCE", "1") != "0"
 _PUSH = os.environ.get("NASREC_WL_PUSH", "1") != "0"  # (A/B knob: 0 = a node only moves inside the window its successors leave as they stand)
 _LATENCY_NS = int(os.environ.get("NASREC_WL_LAT_NS", "5000"))  # what a level costs however little it does (launch, descriptor + operand first touch on cold caches, drain)
-_GEMM_DIV = int(os.environ.get("NASREC_WL_GEMM_DIV", "20000"))  # M N K per ns of a product on the worklist tile (A/B knob of the balancing model)
+# M N K per ns of a product on the worklist tile (A/B knob of the balancing model).  20000 (40 TFLOP/s) until the joint cfg-2 program went
+# from 23 to 20 levels (order_two_term_accumulates, engine._fuse_head): with three short levels gone the slack products crowd into fewer
+# launches and what the model charges for them decides where — timed on the 20-level program (profiles/critical_path_cfg2.txt):
+# 6000 0.2221, 8000 0.2213, 10000 0.2176, 13000 0.2180, 16000 0.2217, 20000 0.2208 ms per step; 10000 - 13000 is also what the
+# worklist's 32 x 32 tile measures on a 0.6 GFLOP product (~30 TFLOP/s, RESPLIT below).
+_GEMM_DIV = int(os.environ.get("NASREC_WL_GEMM_DIV", "10000"))
 
 
 _BAL_R4 = os.environ.get("NASREC_WL_BAL_COST", "r4") == "r4"  # (A/B knob)
@@ -521,6 +539,70 @@ def levels_of(descs):
     for n in nodes:
         out[n.level].append(n)
     return out
+
+
+def _copy_desc(d):
+    c = type(d).from_buffer_copy(d)
+    c.__dict__.update(getattr(d, "__dict__", {}))  # (what keeps a workspace alive, the worklist-forcing mark)
+    return c
+
+
+def order_two_term_accumulates(fwd):
+    """A forward buffer C that is the sum of exactly two products, P (writes C, beta = 0) and Q (adds onto C, beta = 1), is written in
+    the order the plan emitted them — and Q sits a level behind P whenever its operands were ready first (the 16-wide Linear added
+    onto the one-pass 780-deep product of ea_criteo_kaggle_xlarge_best_1shot.json: a launch of the step's critical path that waits for
+    nothing but its turn).  Where Q's operands are ready at an earlier level than P's, Q goes first with beta = 0 and P accumulates.
+    The epilogue computes fl(fl(acc + bias) + old) and an IEEE addition of two terms commutes: the same bits.  Sums of three or more
+    terms keep their order (it is part of the result), and so does every pair with an activation, mask, saved pre-activation, gating
+    operand or residual, a split K, a reader of C between the two, or operators between the two that neither lets the other pass.
+    -> new forward list (the same objects where nothing changed); the backward program reads the buffers, not the order."""
+    nodes = [Node(d) for d in fwd]
+    if any(n.reads is None for n in nodes):
+        return fwd
+    assign_levels(nodes)
+
+    def plain(d):
+        return (isinstance(d, L.GemmDesc) and not d.zmode and d.splitk <= 1 and not d.defer_second_pass and d.act == L.ACT_NONE
+                and d.dims_in_use < 0 and not d.save_z and not d.save_act and d.mul_nseg == 0 and not d.pre_add
+                and not any(d.seg[q].ones_col for q in range(d.nseg)))
+
+    def cview(d):
+        s0 = d.seg[0]
+        return _cview(s0.C, d.cmode, s0.M, s0.N, s0.ldc)
+
+    for ip, P in enumerate(fwd):
+        if not (plain(P) and P.beta == 0 and P.seg[0].C):
+            continue
+        c = cview(P)
+        writers = [i for i, n in enumerate(nodes) if any(overlap(w, c) for w in n.writes)]
+        if len(writers) != 2 or writers[0] != ip:
+            continue
+        iq = writers[1]
+        Q = fwd[iq]
+        sp, sq = P.seg[0], Q.seg[0]
+        if not (plain(Q) and Q.beta == 1 and Q.cmode == P.cmode and (sq.C, sq.M, sq.N, sq.ldc) == (sp.C, sp.M, sp.N, sp.ldc)):
+            continue
+        between = range(ip + 1, iq)
+        if any(overlap(r, c) for i in between for r in nodes[i].reads):
+            continue
+        # the pair ends up side by side in the list: Q moves up to P if nothing in between feeds it, else P moves down to Q if nothing
+        # in between overwrites one of its operands
+        if not any(_depends(nodes[iq], nodes[i]) for i in between):
+            up = True
+        elif not any(_depends(nodes[i], nodes[ip]) for i in between):
+            up = False
+        else:
+            continue
+        ready_q = max([nodes[j].level + 1 for j in range(iq) if j != ip and _depends(nodes[iq], nodes[j])] + [0])
+        if ready_q >= nodes[ip].level:
+            continue
+        first, second = _copy_desc(Q), _copy_desc(P)
+        first.beta, second.beta = 0, 1
+        out = list(fwd)
+        rest = [fwd[i] for i in between]
+        out[ip:iq + 1] = [first, second] + rest if up else rest + [first, second]
+        return order_two_term_accumulates(out)  # (levels have moved: look again; a swapped pair does not qualify a second time)
+    return fwd
 
 
 # ----------------------------------------------------------------------------------------------------------------
