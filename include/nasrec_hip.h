@@ -933,6 +933,29 @@ typedef struct nasrec_worklist_dev_desc {
 } nasrec_worklist_dev_desc_t;
 int nasrec_worklist_prepare(const nasrec_worklist_desc_t* w, void* dev_buf, nasrec_worklist_dev_desc_t* out);
 
+/* What the launcher makes of ONE item (NASREC_OP_WORKLIST and NASREC_OP_PERSIST share the rule): the item's descriptor `desc` of `bytes`
+ * bytes in the worklist's format (a GEMM truncated behind its last segment, nasrec_wl_reduce_t for a reduction), `part` as item.part.
+ * A caller that decides what travels as an item asks here instead of restating the kernels' conditions.  Host only: it reads the
+ * descriptor's integers and whether its pointers are null, never what they point to, and needs no device.  -> 0 and *out, or non-zero
+ * with the message in nasrec_last_error when the kernels have no body for this item — an ordinary answer to this question, not a fault
+ * (an accepted item leaves nasrec_last_error as it was). */
+enum {
+  NASREC_WL_BODY_KIND = 0,          /* not a GEMM: the one body of the item's kind (also any item without workgroups) */
+  NASREC_WL_BODY_TILE = 1,          /* the run-time-binding tile body (csrc/gemm_rt.h), main passes of split-K products included */
+  NASREC_WL_BODY_SECOND_PASS = 2,   /* part 2: fixed-order slab sum + epilogue */
+  NASREC_WL_BODY_DENSE_SMALL = 3,   /* small dense Linear forward, a wavefront per 16 x 16 output tile */
+  NASREC_WL_BODY_DENSE_SMALL_DX = 4,/* its input gradients */
+  NASREC_WL_BODY_TOKEN_FWD = 5,     /* token-axis Linear forward, a wavefront per (sample, 16 rows of W) */
+  NASREC_WL_BODY_TOKEN_DX = 6       /* token-axis input gradients, a wavefront per (sample, segment, 16 token rows) */
+};
+typedef struct nasrec_wl_geometry {
+  int32_t nblk;    /* work units of the item (workgroups of a worklist launch) */
+  int32_t geom[3]; /* as nasrec_wl_item_t.geom */
+  int32_t big;     /* the item needs the large LDS buffer (a Transformer backward) */
+  int32_t body;    /* NASREC_WL_BODY_*: the code the item runs */
+} nasrec_wl_geometry_t;
+int nasrec_worklist_item_geometry(int kind, int part, const void* desc, int bytes, nasrec_wl_geometry_t* out);
+
 /* ------------------------------------------------------------------------------------------------
  * Persistent step (batch <= 256, round 6): the worklist items of MANY levels in ONE launch, ordered topologically, with the
  * dependencies between them resolved inside the kernel instead of by kernel boundaries.  A level launch lasts as long as its slowest

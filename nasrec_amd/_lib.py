@@ -242,6 +242,15 @@ class WorklistDesc(C.Structure):
                 ("blob", C.c_char * WL_BLOB_BYTES)]
 
 
+(WL_BODY_KIND, WL_BODY_TILE, WL_BODY_SECOND_PASS, WL_BODY_DENSE_SMALL, WL_BODY_DENSE_SMALL_DX, WL_BODY_TOKEN_FWD,
+ WL_BODY_TOKEN_DX) = range(7)        # NASREC_WL_BODY_* (nasrec_wl_geometry_t.body)
+
+
+class WlGeometry(C.Structure):
+    """what nasrec_worklist_item_geometry answers for one item: the launcher's own geometry, host only"""
+    _fields_ = [("nblk", i32), ("geom", i32 * 3), ("big", i32), ("body", i32)]
+
+
 class WorklistDevDesc(C.Structure):
     """NASREC_OP_WORKLIST with its descriptor resident in device memory (nasrec_worklist_prepare, ABI 17)"""
     _fields_ = [("kind", i32), ("total_blocks", i32), ("big", i32), ("_pad", i32), ("pf", C.c_uint32 * 6), ("pm", C.c_uint32 * 6), ("dev", vp)]
@@ -320,7 +329,7 @@ SYMBOLS = [
     "nasrec_event_record", "nasrec_event_elapsed_ms", "nasrec_event_destroy", "nasrec_last_error", "nasrec_abi_version",
     "nasrec_desc_sizes", "nasrec_tsv_parse", "nasrec_alloc_uncached", "nasrec_free_uncached", "nasrec_persist_prepare", "nasrec_worklist_prepare",
     "nasrec_weight_decay", "nasrec_opt_moments", "nasrec_last_layer_step", "nasrec_roc_auc", "nasrec_roc_auc_workspace_bytes", "nasrec_gemm_route",
-    "nasrec_weight_ema",
+    "nasrec_weight_ema", "nasrec_worklist_item_geometry",
 ]
 
 _lib = None
@@ -357,6 +366,7 @@ def load():
     lib.nasrec_free_uncached.argtypes = [vp]
     lib.nasrec_persist_prepare.argtypes = [vp]
     lib.nasrec_worklist_prepare.argtypes = [vp, vp, vp]
+    lib.nasrec_worklist_item_geometry.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(WlGeometry)]
     lib.nasrec_tsv_parse.argtypes = [vp, i64, i32, i32, vp, i64, vp, vp, vp, C.POINTER(i64), C.POINTER(i32)]
     lib.nasrec_tsv_parse.restype = i64
     for name in ("nasrec_gemm", "nasrec_embedding_gather", "nasrec_embedding_dedup", "nasrec_dot_tri", "nasrec_fm",

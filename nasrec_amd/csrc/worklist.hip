@@ -17,6 +17,7 @@
 
 // host side: geometry of every item, then ONE launch
 static int wl_gemm_geometry(const nasrec_gemm_desc_t* g, nasrec_wl_item_t& it, int blob_left) {
+  if (blob_left < (int)offsetof(nasrec_gemm_desc_t, seg)) return nasrec_set_error(-2, "worklist: gemm descriptor head runs past the blob");
   if (g->nseg < 1 || g->nseg > NASREC_MAX_SEGS) return nasrec_set_error(-2, "worklist: gemm nseg=%d", g->nseg);
   const int need = (int)offsetof(nasrec_gemm_desc_t, seg) + g->nseg * (int)sizeof(nasrec_gemm_seg_t);
   if (need > blob_left) return nasrec_set_error(-2, "worklist: truncated gemm descriptor (%d bytes) runs past the blob", need);
@@ -332,6 +333,21 @@ extern "C" int nasrec_worklist_prepare(const nasrec_worklist_desc_t* w, void* de
   out->big = big ? 1 : 0;
   out->_pad = 0;
   out->dev = reinterpret_cast<const nasrec_worklist_desc_t*>(dev_buf);
+  return 0;
+}
+
+// what the geometry above says of ONE item, for a caller that decides before it packs (nasrec_amd/schedule.py): host only, no device
+extern "C" int nasrec_worklist_item_geometry(int kind, int part, const void* desc, int bytes, nasrec_wl_geometry_t* out) {
+  if (!desc || !out) return nasrec_set_error(-1, "worklist_item_geometry: null descriptor / result");
+  nasrec_wl_item_t it = {};
+  it.kind = kind, it.part = part;
+  bool big = false;
+  const int rc = wl_item_geometry(it, static_cast<const char*>(desc), bytes, 0, big);
+  if (rc) return rc;
+  out->nblk = it.nblk;
+  out->geom[0] = it.geom[0], out->geom[1] = it.geom[1], out->geom[2] = it.geom[2];
+  out->big = big ? 1 : 0;
+  out->body = it.nblk > 0 ? wl_item_body(kind, part, it.geom) : NASREC_WL_BODY_KIND;  // (no workgroups: geom says nothing)
   return 0;
 }
 

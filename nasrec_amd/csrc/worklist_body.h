@@ -402,6 +402,16 @@ __device__ __forceinline__ void wl_mha_fwd(unsigned long long blob, int vb) {
 // stand-alone kernel).  WL_PACKED_NONE in f01: the table did not fit 16 bits per entry, use the copy in memory.
 #define WL_PACKED_NONE 0xffffffffu
 #define WL_HEAD_BYTES 48  // the twelve scalars in front of the descriptor in the argument segment
+// (host) the NASREC_WL_BODY_* that the dispatch of wl_run below and of ps_run_item (worklist.hip) picks for an item: the same tests in the
+// same order — a branch added to either goes in here too (tests/test_worklist_geometry_cpu.py decodes geom on its own and compares)
+static inline int wl_item_body(int kind, int part, const int32_t (&geom)[3]) {
+  if (kind != NASREC_OP_GEMM) return NASREC_WL_BODY_KIND;
+  if (part == 2) return NASREC_WL_BODY_SECOND_PASS;
+  const int cfg = geom[2];  // tile | binding pair << 2 | mask operand << 4
+  if ((cfg & 3) != WL_TOKS) return NASREC_WL_BODY_TILE;
+  if (((cfg >> 2) & 3) == 3) return geom[1] == 0 ? NASREC_WL_BODY_DENSE_SMALL_DX : NASREC_WL_BODY_DENSE_SMALL;
+  return ((cfg >> 2) & 3) == 1 ? NASREC_WL_BODY_TOKEN_FWD : NASREC_WL_BODY_TOKEN_DX;
+}
 // `base`: address of the launch's nasrec_worklist_desc_t — in the kernel-argument segment (passed by value) or in device memory (ABI 17:
 // uploaded once per plan; warm lines instead of a fresh copy per launch)
 template <bool BIG>

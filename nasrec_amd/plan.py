@@ -689,36 +689,13 @@ def _flush_mha_reduce(ctx):
 _LN_REDUCE_BATCH = _os.environ.get("NASREC_LN_REDUCE_BATCH", "1") != "0"
 
 
-class _ItemNode:
-    """what reports (bench.py, iter_ops) read of a worklist item — descriptor, part, footprints — with the footprints computed when
-    somebody asks (schedule.desc_io costs ~10 us per descriptor: not on the path of a per-step compile)"""
-    __slots__ = ("desc", "part", "_io", "level", "index")
-
-    def __init__(self, desc, part="whole"):
-        self.desc, self.part, self._io, self.level, self.index = desc, part, None, 0, 0
-
-    def _get(self):
-        if self._io is None:
-            from . import schedule as S
-            io = S.desc_io(self.desc, self.part)
-            self._io = io if io is not None else (None, None)
-        return self._io
-
-    @property
-    def reads(self):
-        return self._get()[0]
-
-    @property
-    def writes(self):
-        return self._get()[1]
-
-
 def _flush_ln_reduce(ctx):
     """the parked LayerNorm parameter-gradient reductions (fixed-order column sums of per-workgroup partials) as items of
     NASREC_OP_WORKLIST launches, twelve per launch: same body, same order of additions, one launch boundary instead of twelve"""
     jobs, ctx.ln_reduce = ctx.ln_reduce, []
     if not jobs:
         return
+    from . import schedule as S
     size = (C.sizeof(L.WlReduce) + 15) & ~15
     base = L.WorklistDesc.blob.offset
     for i0 in range(0, len(jobs), L.WL_MAX_ITEMS):
@@ -728,7 +705,7 @@ def _flush_ln_reduce(ctx):
             continue
         w = L.WorklistDesc()
         w.kind, w.n = L.OP_WORKLIST, len(grp)
-        w.nodes = [_ItemNode(r) for r in grp]  # (for reports: footprints are derived on demand, not on the per-step path)
+        w.nodes = [S.Node(r) for r in grp]  # (for reports: a Node derives its footprints when asked, not on the per-step path)
         assert len(grp) * size <= L.WL_BLOB_BYTES
         for k, r in enumerate(grp):
             it = w.item[k]

@@ -292,21 +292,32 @@ def desc_io(d, part="whole") -> Tuple[List[Acc], List[Acc]]:
 
 
 class Node:
-    __slots__ = ("desc", "part", "reads", "writes", "level", "index")
+    """a schedulable piece of the program.  reads / writes: desc_io of the piece (None, None: not modelled); item: what the piece is as a
+    worklist item, (bytes, launcher's geometry) or None (_item below).  All three are derived from the descriptor when somebody first
+    asks and kept: a plan that only carries its nodes for reports (plan._flush_ln_reduce) never pays for them."""
+    __slots__ = ("desc", "part", "reads", "writes", "item", "level", "index")
 
     def __init__(self, desc, part="whole"):
         self.desc, self.part = desc, part
-        io = desc_io(desc, part)
-        self.reads, self.writes = io if io is not None else (None, None)
         self.level = 0
         self.index = 0
 
+    def __getattr__(self, name):  # (only reached while the slot is still empty)
+        if name in ("reads", "writes"):
+            io = desc_io(self.desc, self.part)
+            self.reads, self.writes = io if io is not None else (None, None)
+        elif name == "item":
+            self.item = _item(self)
+        else:
+            raise AttributeError(name)
+        return getattr(self, name)
 
-def expand(descs) -> List[Node]:
-    """program -> schedulable nodes: split-K GEMMs become (main pass, second pass)"""
+
+def expand(descs, cut=lambda d: not d.defer_second_pass) -> List[Node]:
+    """program -> schedulable nodes: the split-K GEMMs that `cut` says yes to become (main pass, second pass)"""
     nodes = []
     for d in descs:
-        if isinstance(d, L.GemmDesc) and d.splitk > 1 and not d.defer_second_pass:
+        if isinstance(d, L.GemmDesc) and d.splitk > 1 and cut(d):
             nodes.append(Node(d, "main"))
             nodes.append(Node(d, "epi"))
         else:
@@ -314,6 +325,11 @@ def expand(descs) -> List[Node]:
     for i, n in enumerate(nodes):
         n.index = i
     return nodes
+
+
+def expand_for_worklists(descs) -> List[Node]:
+    """as expand(), but a split-K GEMM is cut in two only when both halves can ride in worklist launches"""
+    return expand(descs, gemm_capable)
 
 
 def _depends(later: Node, earlier: Node) -> bool:
@@ -610,9 +626,15 @@ def order_two_term_accumulates(fwd):
 # ----------------------------------------------------------------------------------------------------------------
 _GEMM_HEAD = L.GemmDesc.seg.offset
 _SEG_BYTES = C.sizeof(L.GemmSeg)
-_PLAIN_KINDS = (L.OP_MHA_FWD, L.OP_MHA_BWD, L.OP_FM_FWD, L.OP_FM_BWD, L.OP_DOT_TRI_FWD, L.OP_DOT_TRI_BWD, L.OP_COPY_SEGS, L.OP_GATE_BWD,
-                L.OP_FINAL_FWD, L.OP_FINAL_BWD, L.OP_DEDUP_IDS, L.OP_FINAL_FUSED)
-WL_LDS_FLOATS = 1696 + 5 * 1024 + 1024  # csrc/worklist_body.h WL_LDS_FLOATS
+_PART = {"whole": L.WL_WHOLE, "main": L.WL_MAIN, "epi": L.WL_EPI}
+
+
+def item_geometry(kind, part, b):
+    """the launcher's answer (nasrec_worklist_item_geometry: the rule the worklist and persistent launches run by, host only) for an
+    item of this kind and part that carries the bytes b -> L.WlGeometry (nblk, geom, big, body), or None: the kernels have no body
+    for it.  Which kinds, shapes and operand forms have one is stated in csrc/worklist.hip and nowhere else."""
+    g = L.WlGeometry()
+    return g if L.load().nasrec_worklist_item_geometry(kind, _PART[part], b, len(b), C.byref(g)) == 0 else None
 
 
 # measured on cfg 2 (ms per step): 128 -> 0.420, 160 -> 0.415, 260 -> 0.408, never solo -> 0.409: the two large backward products of
@@ -621,14 +643,14 @@ WL_LDS_FLOATS = 1696 + 5 * 1024 + 1024  # csrc/worklist_body.h WL_LDS_FLOATS
 SOLO_TILES = int(os.environ.get("NASREC_WL_SOLO_TILES", "256"))
 
 
-def gemm_capable(d) -> bool:
-    """mirror of csrc/worklist.hip wl_gemm_geometry: can this GEMM launch run as a worklist item?"""
-    if d.splitk == L.SPLITK_BALANCED or d.defer_second_pass or d.nseg < 1 or d.nseg > L.MAX_SEGS:
-        return False
-    kca, kcb = d.amode in (L.AM_KC, L.AM_TOKK), d.bmode in (L.AM_KC, L.AM_TOKK)
-    if not kca and kcb:
-        return False
-    if d.splitk > 1 and not d.workspace:
+def _gemm_bytes(d):
+    """a GEMM item's bytes: the descriptor cut behind its last segment (1 <= nseg <= MAX_SEGS is the caller's to check)"""
+    return C.string_at(C.addressof(d), _GEMM_HEAD + d.nseg * _SEG_BYTES)
+
+
+def _gemm_wanted(d) -> bool:
+    """scheduling policy: should this GEMM launch travel as a worklist item, supposing the kernels can run it?"""
+    if d.defer_second_pass or d.nseg < 1 or d.nseg > L.MAX_SEGS:
         return False
     # one large product (>= SOLO_TILES workgroups of 64x64) fills the chip on its own and is faster in its own kernel than on the
     # worklist kernel's small tiles
@@ -644,52 +666,37 @@ def gemm_capable(d) -> bool:
             one.splitk = 1
         if P.gemm_route(one)[1] & (1 << L.GEMM_ROUTE_KSLICE):
             return False  # csrc/gemm_kslice.hip: a kernel of its own (1024-thread workgroups, 133 KB of LDS)
-    s0 = d.seg[0]
-    if not d.zmode:
-        for q in range(d.nseg):
-            s = d.seg[q]
-            if s.ones_col != s0.ones_col or s.Mvalid != s0.Mvalid:
-                return False
-            if s.A and (bool(s.Aaux) != bool(s0.Aaux) or bool(s.Baux) != bool(s0.Baux)):
-                return False
     return True
 
 
-def item_bytes(node):
-    """the bytes a worklist item carries for this node, or None if the worklist kernel has no body for it"""
+def gemm_capable(d) -> bool:
+    """does this GEMM launch travel as a worklist item?  The policy above, and the launcher's word that the kernels have a body for it,
+    asked for the part the descriptor starts with (whole if it is unsplit, else its main pass)"""
+    return _gemm_wanted(d) and item_geometry(d.kind, "whole" if d.splitk <= 1 else "main", _gemm_bytes(d)) is not None
+
+
+def _item(node):
+    """Node.item: (the bytes a worklist item carries for this node, their geometry), or None if the node does not travel as an item"""
     d = node.desc
-    k = d.kind
     if isinstance(d, L.GemmDesc):
-        if not gemm_capable(d):
+        if not _gemm_wanted(d):
             return None
-        if (node.part == "whole") != (d.splitk <= 1):  # (wl_gemm_geometry: a split product travels as main + second pass, an unsplit one whole)
-            return None
-        return C.string_at(C.addressof(d), _GEMM_HEAD + d.nseg * _SEG_BYTES)
-    if k in (L.OP_DOT_TRI_FWD, L.OP_DOT_TRI_BWD):
-        P4 = (d.k1 * (d.k1 - 1) // 2 + 3) & ~3
-        if d.k1 < 2 or 4 * (d.k1 * 20 + P4) > WL_LDS_FLOATS:
-            return None
-    if k in (L.OP_MHA_FWD, L.OP_MHA_BWD) and (d.N < 1 or d.N > 64 or (k == L.OP_MHA_BWD and not d.saved)):
-        return None
-    if k == L.OP_DEDUP_IDS and (d.B < 1 or d.B > 256 or d.cap != 256 or d.Fs < 1 or d.Fs > L.MAX_TABLES
-                                or not (d.idx and d.leader and d.order and d.lists and d.counts)):
-        return None
-    if k == L.OP_FINAL_FUSED and (not (d.y and d.logits and d.bias and d.w) or d.nsplit > 1 or any(d.dseg[q] and not d.seg[q] for q in range(d.nseg))):
-        return None  # (csrc/norm_loss_opt.hip final_fused_check)
-    if k == L.OP_FINAL_BWD and d.y and not d.logits:
-        return None
-    if k in _PLAIN_KINDS:
-        return C.string_at(C.addressof(d), C.sizeof(d))
-    if k == L.OP_REDUCE_ROWS and 1 <= d.ndst <= L.WL_REDUCE_DST:
+        b = _gemm_bytes(d)
+    elif d.kind == L.OP_REDUCE_ROWS and d.ndst <= L.WL_REDUCE_DST:  # (the compact form has room for that many destinations)
         r = L.WlReduce()
         r.kind, r.R, r.C, r.ld, r.in_, r.ndst = d.kind, d.R, d.C, d.ld, d.in_, d.ndst
         for q in range(d.ndst):
             r.dst[q], r.dst_off[q], r.dst_len[q] = d.dst[q], d.dst_off[q], d.dst_len[q]
-        return C.string_at(C.addressof(r), C.sizeof(r))
-    return None
+        b = C.string_at(C.addressof(r), C.sizeof(r))
+    else:
+        b = C.string_at(C.addressof(d), C.sizeof(d))
+    g = item_geometry(d.kind, node.part, b)
+    return (b, g) if g is not None else None
 
 
-_PART = {"whole": L.WL_WHOLE, "main": L.WL_MAIN, "epi": L.WL_EPI}
+def item_bytes(node):
+    """the bytes a worklist item carries for this node, or None if the worklist kernel has no body for it (or policy keeps it out)"""
+    return node.item[0] if node.item is not None else None
 
 
 # stand-alone times of the non-GEMM items of the batch-256 step, ns (tools/step_table.py ITEMS=11)
@@ -756,37 +763,17 @@ def _cost_r4(node):
     return _ITEM_NS_R4.get(d.kind, 3000)
 
 
-def expand_for_worklists(descs) -> List[Node]:
-    """as expand(), but a split-K GEMM is cut in two only when both halves can ride in worklist launches"""
-    nodes = []
-    for d in descs:
-        if isinstance(d, L.GemmDesc) and d.splitk > 1 and gemm_capable(d):
-            nodes.append(Node(d, "main"))
-            nodes.append(Node(d, "epi"))
-        else:
-            nodes.append(Node(d))
-    for i, n in enumerate(nodes):
-        n.index = i
-    return nodes
-
-
 _SOLO_ITEMS = os.environ.get("NASREC_WL_SOLO_ITEMS", "1") != "0"  # (A/B knob)
 
 
 def _item_beats_kernel(d):
-    """a level's only operator normally runs as its stand-alone kernel; the token-axis input gradients (W^T dy per input segment, K <= 64
-    rows of the Linear, mask on dy allowed) are the exception: the worklist's wavefront-per-tile body (csrc/worklist_body.h wl_token_dx)
-    takes 3.6 - 5 us where the general template takes 5.5 - 8.9 (tools/step_table.py ITEMS=1; the conditions of csrc/worklist.hip)"""
-    if not (_SOLO_ITEMS and isinstance(d, L.GemmDesc) and d.zmode and d.splitk <= 1):
+    """a level's only operator normally runs as its stand-alone kernel; the token-axis input gradients (W^T dy per input segment) are the
+    exception where the launcher gives them the worklist's wavefront-per-tile body (csrc/worklist_body.h wl_token_dx): it takes
+    3.6 - 5 us where the general template takes 5.5 - 8.9 (tools/step_table.py ITEMS=1)"""
+    if not (_SOLO_ITEMS and isinstance(d, L.GemmDesc) and d.splitk <= 1 and 1 <= d.nseg <= L.MAX_SEGS):
         return False
-    if (d.amode, d.bmode, d.cmode) != (L.AM_RC, L.AM_TOKR, L.CM_TOKJ):
-        return False
-    n0 = d.seg[0].N
-    for q in range(d.nseg):
-        sg = d.seg[q]
-        if sg.Aaux or sg.ones_col or (0 < sg.Mvalid < sg.M) or sg.N != n0 or sg.K > 64 or sg.M <= 0:
-            return False
-    return n0 % 16 == 0
+    g = item_geometry(d.kind, "whole", _gemm_bytes(d))
+    return g is not None and g.body == L.WL_BODY_TOKEN_DX
 
 
 def pack(descs, alloc=None):
@@ -893,13 +880,11 @@ def pack_persistent(descs, dev_alloc, uc_ranges, alloc=None):
         blob = bytearray()
         for k, i in enumerate(seg):
             nd = nodes[i]
-            b = item_bytes(nd)
+            b, geo = nd.item
             it = items[k]
             it.kind, it.part, it.off = nd.desc.kind, _PART[nd.part], len(blob)
-            if hint[i] < 0:
-                # units of this operator: unknown here (the launcher's geometry); the window travels as "workgroups that finish in it at 5 us per unit":
-                # resolved below by a dry geometry pass
-                it._pad[1] = hint[i]
+            if hint[i] < 0:  # a window of -hint[i] ns: the workgroups that finish the operator's units (the launcher's geometry) in it at 5 us per unit
+                it._pad[1] = max(32, min(geo.nblk, -(-geo.nblk * 5000 // -hint[i])))
             blob += b
             blob += bytes((-len(blob)) % 16)
             ps = [j for j in pred[i] if j in inseg]
@@ -929,19 +914,6 @@ def pack_persistent(descs, dev_alloc, uc_ranges, alloc=None):
         d.kind, d.n, d.blob_bytes = L.OP_PERSIST, len(seg), len(blob)
         hb = C.create_string_buffer(bytes(blob), len(blob))
         d.host_items, d.host_blob = C.addressof(items), C.addressof(hb)
-        if any(items[k]._pad[1] < 0 for k in range(len(seg))):
-            win = [items[k]._pad[1] for k in range(len(seg))]
-            for k in range(len(seg)):
-                items[k]._pad[1] = 0
-            dry = L.PersistDesc.from_buffer_copy(d)
-            L.check(L.load().nasrec_persist_prepare(C.addressof(dry)))  # (geometry only: fills items[k].nblk)
-            for k in range(len(seg)):
-                if win[k] < 0:
-                    units = items[k].nblk
-                    items[k]._pad[1] = max(32, min(units, -(-units * 5000 // -win[k])))
-                else:
-                    items[k]._pad[1] = 0
-                items[k].nblk = items[k].first = 0
         d.nodes = [nodes[i] for i in seg]
         d._host = (items, hb)
         if dev_alloc is None:  # (descriptors and geometry only: CPU tests of the packing, tools)

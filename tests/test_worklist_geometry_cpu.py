@@ -1,8 +1,10 @@
-"""schedule.item_bytes / gemm_capable (the Python "mirror") against the launcher's own geometry (csrc/worklist.hip wl_item_geometry /
-wl_gemm_geometry) on every case of tests/wl_cases.py, without a device: nasrec_persist_prepare with items == NULL is a dry pass that
-writes each item's geometry back into host_items and never dereferences a descriptor's pointers.  Checked: Python accepts a descriptor
-exactly when the launcher does, the geometry names the body the case was written for (the table in the docstring of
-tests/test_worklist_items_gpu.py lists the same pairs), every body of the two kernels has a case, and both sides refuse what has no body."""
+"""The launcher's own geometry (csrc/worklist.hip wl_item_geometry / wl_gemm_geometry) on every case of tests/wl_cases.py, without a
+device, by its two host-only routes: nasrec_worklist_item_geometry, the query schedule.item_bytes / gemm_capable decide by (they state
+no condition of the kernels themselves), and nasrec_persist_prepare with items == NULL, a dry pass that writes each item's geometry
+back into host_items.  Neither dereferences a descriptor's pointers.  Checked: the scheduler accepts a descriptor exactly when the
+launcher does, the two routes give the same geometry, it names the body the case was written for (the table in the docstring of
+tests/test_worklist_items_gpu.py lists the same pairs) and the query's `body` says the same as the test's own decoding of geom, every
+body of the two kernels has a case, and every route refuses what has no body."""
 import ctypes as C
 
 import pytest
@@ -46,6 +48,13 @@ def dry(lib, kind, part, blob, blob_bytes=None):
     return rc, items[0], lib.nasrec_last_error().decode(errors="replace")
 
 
+def query(lib, kind, part, blob, nbytes=None):
+    """-> (return code, L.WlGeometry, message) of nasrec_worklist_item_geometry: the same rule asked directly"""
+    g = L.WlGeometry()
+    rc = lib.nasrec_worklist_item_geometry(kind, part, blob, len(blob) if nbytes is None else nbytes, C.byref(g))
+    return rc, g, lib.nasrec_last_error().decode(errors="replace")
+
+
 @pytest.fixture(scope="module")
 def built():
     return {c.name: c.build("cpu") for c in W.CASES}
@@ -62,6 +71,11 @@ def test_python_accepts_the_case_exactly_when_the_launcher_does_and_the_geometry
         assert rc == 0, msg
         assert got == raw_bytes(b.desc)
         assert it.nblk >= 1
+        rq, g, msg = query(lib, b.desc.kind, part, raw_bytes(b.desc))
+        assert rq == 0, msg
+        assert (g.nblk, list(g.geom)) == (it.nblk, list(it.geom)), (case.name, part)
+        assert W.BODY_ENUM_NAME[g.body] == W.body_enum_name(b.desc.kind, part, it.geom), (case.name, part, g.body)
+        assert g.big == (1 if b.desc.kind == L.OP_MHA_BWD else 0)
         bodies.append(W.body_of(b.desc.kind, part, it.geom))
     assert bodies[-1] == case.body, (case.name, bodies)
     if case.gemm:
@@ -160,10 +174,12 @@ _PART = {"whole": L.WL_WHOLE, "main": L.WL_MAIN, "epi": L.WL_EPI}
 
 @pytest.mark.parametrize("name,d,part", _refusals(), ids=[r[0] for r in _refusals()])
 def test_both_sides_refuse_what_has_no_body(lib, name, d, part):
-    """host-side refusals before any launch: the launcher returns non-zero with a message, Python returns None"""
+    """host-side refusals before any launch: the launcher returns non-zero with a message by either route, the scheduler returns None"""
     assert S.item_bytes(S.Node(d, part)) is None
     rc, _, msg = dry(lib, d.kind, _PART[part], raw_bytes(d))
     assert rc != 0 and msg, (name, rc, msg)
+    rq, _, msg_q = query(lib, d.kind, _PART[part], raw_bytes(d))
+    assert rq == rc and msg_q == msg, (name, rq, msg_q)
 
 
 def test_the_valid_forms_of_the_refused_descriptors_are_accepted(lib):
@@ -183,6 +199,8 @@ def test_the_valid_forms_of_the_refused_descriptors_are_accepted(lib):
         assert S.item_bytes(S.Node(d, part)) == raw_bytes(d)
         rc, it, msg = dry(lib, kind, _PART[part], raw_bytes(d))
         assert rc == 0 and it.nblk >= 1, msg
+        rq, g, msg = query(lib, kind, _PART[part], raw_bytes(d))
+        assert rq == 0 and (g.nblk, list(g.geom)) == (it.nblk, list(it.geom)), msg
 
 
 def test_a_descriptor_that_runs_past_the_blob_is_refused(lib):
@@ -199,6 +217,11 @@ def test_a_descriptor_that_runs_past_the_blob_is_refused(lib):
     assert dry(lib, f.kind, L.WL_WHOLE, raw_bytes(f))[0] == 0
     rc, _, msg = dry(lib, f.kind, L.WL_WHOLE, raw_bytes(f), blob_bytes=C.sizeof(L.FmDesc) - 16)
     assert rc != 0 and "blob" in msg
+    # ... the query is told the same lengths
+    assert query(lib, g.kind, L.WL_WHOLE, whole)[0] == 0 and query(lib, f.kind, L.WL_WHOLE, raw_bytes(f))[0] == 0
+    for kind, blob, n in [(g.kind, whole, len(whole) - C.sizeof(L.GemmSeg)), (g.kind, whole, 16), (f.kind, raw_bytes(f), C.sizeof(L.FmDesc) - 16)]:
+        rc, _, msg = query(lib, kind, L.WL_WHOLE, blob, nbytes=n)
+        assert rc != 0 and "blob" in msg
     # ... and the same refusal from the level launch's own finalize (nothing is launched: the geometry fails first)
     w = L.WorklistDesc()
     w.kind, w.n = L.OP_WORKLIST, 1
@@ -211,8 +234,68 @@ def test_a_descriptor_that_runs_past_the_blob_is_refused(lib):
     assert "blob" in lib.nasrec_last_error().decode()
 
 
-def test_the_dot_product_limit_is_what_the_shared_lds_buffer_holds():
-    """k1 = 46 is the largest DotProduct core whose four per-wavefront tiles and gradient rows fit WL_LDS_FLOATS"""
+def test_the_dot_product_limit_is_what_the_shared_lds_buffer_holds(lib):
+    """k1 = 46 is the largest DotProduct core whose four per-wavefront tiles and gradient rows fit WL_LDS_FLOATS, and it is where the
+    launcher draws the line"""
     def floats(k1):
         return 4 * (k1 * W.TRI_LD + ((k1 * (k1 - 1) // 2 + 3) & ~3))
-    assert floats(46) <= S.WL_LDS_FLOATS < floats(47) and S.WL_LDS_FLOATS == W.WL_LDS_FLOATS
+    assert floats(46) <= W.WL_LDS_FLOATS < floats(47)
+    for kind in (L.OP_DOT_TRI_FWD, L.OP_DOT_TRI_BWD):
+        d = L.DotTriDesc()
+        d.kind, d.B, d.T, d.out, d.dout, d.dT = kind, 4, 0x1000, 0x2000, 0x3000, 0x4000
+        for k1, accepted in ((46, True), (47, False)):
+            d.k1, d.ld_out = k1, k1 * (k1 - 1) // 2
+            rc, g, msg = query(lib, kind, L.WL_WHOLE, raw_bytes(d))
+            assert (rc == 0) == accepted and (accepted or "LDS" in msg), (kind, k1, rc, msg)
+            assert (S.item_bytes(S.Node(d)) is not None) == accepted
+
+
+def _layernorm_and_act_bwd():
+    ln = L.LayerNormDesc()
+    ln.kind, ln.mode, ln.R, ln.D, ln.ldx, ln.ldy, ln.dims_in_use, ln.eps = L.OP_LAYERNORM_FWD, L.AM_KC, 8, 32, 32, 32, -1, 1e-5
+    ln.x, ln.w, ln.b, ln.y, ln.stats = 0x1000, 0x2000, 0x3000, 0x4000, 0x5000
+    ab = L.ActBwdDesc()
+    ab.kind, ab.mode, ab.R, ab.D, ab.ld_dy, ab.ld_z, ab.ld_dz, ab.act, ab.dims_in_use = L.OP_ACT_BWD, L.AM_KC, 8, 32, 32, 32, 32, L.ACT_RELU, -1
+    ab.dy, ab.z, ab.dz = 0x1000, 0x2000, 0x3000
+    return [ln, ab]
+
+
+def test_the_query_refuses_a_kind_without_a_body_with_a_message_and_sets_no_error_on_acceptance(lib):
+    f = L.FmDesc()
+    f.kind, f.B, f.N, f.ldx, f.ld_ix, f.x, f.ix = L.OP_FM_FWD, 4, 8, 128, 16, 0x1000, 0x2000
+    for d in _layernorm_and_act_bwd():
+        rc, _, msg = query(lib, d.kind, L.WL_WHOLE, raw_bytes(d))
+        assert rc != 0 and "kind %d" % d.kind in msg and "no body" in msg, (rc, msg)
+        assert S.item_bytes(S.Node(d)) is None
+        # an accepted item leaves the message of the refusal before it in place: acceptance writes no error
+        rc, g, after = query(lib, f.kind, L.WL_WHOLE, raw_bytes(f))
+        assert rc == 0 and g.nblk == 1 and g.body == L.WL_BODY_KIND and after == msg
+
+
+def test_a_node_derives_its_footprints_when_asked_and_not_before(monkeypatch):
+    """plan._flush_ln_reduce hangs the reductions' Nodes on the worklist for reports: they answer reads / writes = desc_io of the
+    reduction, and nothing calls desc_io on the per-step path that only builds the launch"""
+    calls = []
+    real = S.desc_io
+    monkeypatch.setattr(S, "desc_io", lambda d, part="whole": (calls.append(d), real(d, part))[1])
+    jobs = []
+    for k in range(3):
+        r = L.ReduceRowsDesc()
+        r.kind, r.R, r.C, r.ld, r.in_, r.ndst = L.OP_REDUCE_ROWS, 8, 64, 64, 0x10000 * (k + 1), 2
+        for q in range(2):
+            r.dst[q], r.dst_off[q], r.dst_len[q] = 0x100000 * (k + 1) + 0x1000 * q, 32 * q, 32
+        jobs.append(r)
+
+    class Ctx:
+        ln_reduce, out = list(jobs), []
+        emit = out.append
+    P._flush_ln_reduce(Ctx)
+    (w,) = Ctx.out
+    assert isinstance(w, L.WorklistDesc) and w.n == 3 and [n.desc for n in w.nodes] == jobs and all(type(n) is S.Node for n in w.nodes)
+    assert calls == []
+    for n, r in zip(w.nodes, jobs):
+        want_r, want_w = real(r)
+        for got, want in ((n.reads, want_r), (n.writes, want_w)):
+            assert [(a.ptr, a.rows, a.width, a.stride) for a in got] == [(a.ptr, a.rows, a.width, a.stride) for a in want] and want
+    assert calls == jobs  # (once per node: asked again, the node answers from what it kept)
+    assert all(n.reads is n.reads for n in w.nodes) and calls == jobs

@@ -4,7 +4,8 @@ as the stand-alone launch and as an item), its inputs, its output buffers — gu
 sentinel, or with NaN where the operator must overwrite everything — and a check of those outputs against plain fp64 math.  Every case
 names the body it was written to reach (`body`; body_of() reads the same name off an item's geometry), so that a case that silently ran
 on another body is noticed.  tests/test_worklist_items_gpu.py runs the cases on the GPU; tests/test_worklist_geometry_cpu.py builds them
-on the host (the geometry pass never dereferences a pointer) and holds schedule.item_bytes against the launcher's own geometry.
+on the host (the geometry pass never dereferences a pointer) and holds the launcher's geometry query, which schedule.item_bytes decides
+by, against the dry pass of the persistent launch and against body_of().
 
 Plain Python: nothing here touches a GPU at import, and a case built with device="cpu" touches none at all."""
 import math
@@ -48,6 +49,20 @@ def body_of(kind, part, geom):
     return "%s.%s.%s" % (TILE_NAME[tile], BIND_NAME[bind], "mask" if aux else "plain")
 
 
+# what nasrec_worklist_item_geometry calls a body (NASREC_WL_BODY_*): the names above without tile shape, binding and batch count, which
+# stay private to csrc/; "kind" = the one body of a kind that is no GEMM
+BODY_ENUM_NAME = {L.WL_BODY_KIND: "kind", L.WL_BODY_TILE: "tile", L.WL_BODY_SECOND_PASS: "second_pass", L.WL_BODY_DENSE_SMALL: "dense_small",
+                  L.WL_BODY_DENSE_SMALL_DX: "dense_small_dx", L.WL_BODY_TOKEN_FWD: "token_fwd", L.WL_BODY_TOKEN_DX: "token_dx"}
+
+
+def body_enum_name(kind, part, geom):
+    """body_of at the granularity of the public enum"""
+    if kind != L.OP_GEMM:
+        return "kind"
+    head = body_of(kind, part, geom).split(".")[0]
+    return "tile" if head in TILE_NAME.values() else head
+
+
 class Ctx:
     """tensors of one case: generated on the host from the case's seed, moved to `device`, kept alive"""
 
@@ -88,7 +103,7 @@ class Case:
     def build(self, device, seed=0):
         b = self.fn(Ctx(device, seed * 1000003 + (hash_name(self.name) & 0xffff)))
         if self.force:
-            b.desc._wl_force = True  # (gemm_capable: refused for routing reasons only — the launcher's geometry accepts it)
+            b.desc._wl_force = True  # (schedule._gemm_wanted would keep it out by its routing policy; the launcher's geometry accepts it)
         return b
 
 
