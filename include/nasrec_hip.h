@@ -89,7 +89,8 @@ enum {
   NASREC_OP_OPT_MOMENTS = 40,
   NASREC_OP_LAST_LAYER_STEP = 41,
   NASREC_OP_ROC_AUC = 42,
-  NASREC_OP_WEIGHT_EMA = 43
+  NASREC_OP_WEIGHT_EMA = 43,
+  NASREC_OP_DECOUPLED_DECAY = 44
 };
 
 /* algorithm of NASREC_OP_OPT_MOMENTS (ADAGRAD: NASREC_OP_LAST_LAYER_STEP only) */
@@ -733,6 +734,55 @@ typedef struct nasrec_weight_ema_desc {
 } nasrec_weight_ema_desc_t;
 
 /* ------------------------------------------------------------------------------------------------
+ * Decoupled weight decay (utils/optim.DecoupledWeightDecay; DESIGN.md "Lazy decoupled weight decay"): in front of the optimizer's
+ * update, every selected parameter that has a gradient takes
+ *   p = p * (float)(1 - (double)lr * lambda)                                          (the dense statement, fp32)
+ * the statement of torch.optim.AdamW.  A table row outside the batch receives nothing else, so resting over several steps it owes
+ * the product of their factors and is not walked: level[f] (one double per table) = L_f = sum of log1p(-lr_i lambda) over the steps
+ * in which table f decayed, stamp[f][row] (one float per row) = the fp32 value of L_f at which that row's weights are current.  A row
+ * whose stamp is not (float)L_f owes exp(L_f - (double)stamp), computed in fp64; its weights are rounded once.
+ * Appended WITHOUT a new nasrec_abi_version(), as NASREC_OP_WEIGHT_EMA was (a binding's layout check covers it).
+ *   phase 0 (catch-up; in front of the launch that gathers the batch's rows): 4 lanes x float4 per (sample, field) pair of the RAW
+ *     ids (no leaders exist yet).  Lane 0 exchanges the row's stamp atomically with (float)L_f and hands the old value to the other
+ *     three: the one pair that reads an old stamp != (float)L_f pays what the row owes, every other pair of that row leaves it alone.
+ *     Ids outside [0, rows[f]), tables outside `mask` and B = 0 write nothing.
+ *   phase 1 (decay; behind the row dedup, in front of the optimizer's update): workgroups [0, dense_blocks) apply the dense statement
+ *     to the ranges `chunks` [offset, length] x n_chunks of the arena p; the others apply it to the leader rows of the tables in `mask`
+ *     (which phase 0 left current) and stamp them (float)(L_f + log1p(-lr lambda)).  The workgroup that arrives last at `counter`
+ *     (zero before, left zero) adds log1p(-lr lambda) to level[f] of every table in `mask`: every workgroup has read it by then.
+ *     B = 0 (no gradient reaches the tables): the dense part only, no level moves.  lr is read from the device scalar `lr`.
+ *   phase 2 (flush): every row of every table in `mask`, in the 64-row tiles of tile_off (over those tables; `bitmap`: all zero, only
+ *     read): a row pays what it owes and its stamp goes back to 0; the last workgroup sets level[f] = 0.  Idempotent.  nblocks
+ *     workgroups.
+ * Refused (-1, nothing launched): a table, stamp or level pointer missing, lambda < 0, lr_max * lambda >= 1 (lr_max: the caller's
+ * bound on what `lr` holds), a phase outside [0, 2], Fs > NASREC_MAX_TABLES, ids / leaders / lr / counter / chunks missing where the
+ * phase reads them.  Same inputs -> same bits.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct nasrec_decoupled_decay_desc {
+  int32_t kind;  /* NASREC_OP_DECOUPLED_DECAY */
+  int32_t phase; /* 0 catch-up, 1 decay, 2 flush */
+  int32_t B, Fs; /* [B, Fs] id / leader arrays (B = 0: no touched rows) */
+  int32_t dense_blocks; /* phase 1: workgroups on the dense ranges */
+  int32_t nblocks;      /* phase 2: workgroups on the tables */
+  uint32_t mask;        /* bit f: table f decays */
+  int32_t n_chunks;
+  double lambda;
+  double lr_max;         /* phase 1: an upper bound of *lr, for the refusal */
+  const int64_t* idx;    /* [B,Fs]: phase 0 the raw ids, phase 1 the staged ones */
+  const int32_t* leader; /* [B,Fs], phase 1 */
+  float* table[NASREC_MAX_TABLES];
+  float* stamp[NASREC_MAX_TABLES];
+  int64_t rows[NASREC_MAX_TABLES];
+  int64_t tile_off[NASREC_MAX_TABLES + 1]; /* phase 2: over the tables in `mask` */
+  uint32_t* bitmap;      /* [2 tile_off[Fs]], all zero, read only */
+  float* p;              /* dense arena */
+  const int64_t* chunks; /* [n_chunks][2]: offset, length (elements of p) */
+  double* level;         /* [Fs] */
+  const float* lr;       /* device scalar, phase 1 */
+  uint32_t* counter;     /* phases 1 and 2: the last arrival (zero before, left zero) */
+} nasrec_decoupled_decay_desc_t;
+
+/* ------------------------------------------------------------------------------------------------
  * The row-sparse embedding backward in two halves (round 5).  NASREC_OP_EMB_DEDUP above does everything behind the backward pass;
  * but which sample leads a row, and which samples repeat it, depends on the IDS only — known before the forward pass starts (one
  * GPU: when the batch is staged; N GPUs: when the ids all-gather lands, nasrec_amd/parallel.py).  So:
@@ -1047,6 +1097,7 @@ int nasrec_opt_moments(void* stream, const nasrec_opt_moments_desc_t* d);
 int nasrec_last_layer_step(void* stream, const nasrec_last_layer_step_desc_t* d);
 int nasrec_roc_auc(void* stream, const nasrec_roc_auc_desc_t* d);
 int nasrec_weight_ema(void* stream, const nasrec_weight_ema_desc_t* d);
+int nasrec_decoupled_decay(void* stream, const nasrec_decoupled_decay_desc_t* d);
 int64_t nasrec_roc_auc_workspace_bytes(int64_t n); /* 0 for n < 2 or n > NASREC_ROC_AUC_MAX_N */
 int nasrec_worklist(void* stream, const nasrec_worklist_desc_t* d);
 

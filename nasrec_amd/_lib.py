@@ -43,6 +43,7 @@ OPTIM_ADAGRAD, OPTIM_ADAM, OPTIM_SGD, OPTIM_RMSPROP = 0, 1, 2, 3  # NASREC_OPTIM
 LAST_LAYER_MAX = 8192  # NASREC_LAST_LAYER_MAX: K + 1 of NASREC_OP_LAST_LAYER_STEP
 OP_ROC_AUC = 42
 OP_WEIGHT_EMA = 43
+OP_DECOUPLED_DECAY = 44
 ROC_AUC_MAX_N = 1 << 30  # NASREC_ROC_AUC_MAX_N
 ROC_AUC_TOO_FEW, ROC_AUC_BAD_LABEL, ROC_AUC_NOT_FINITE, ROC_AUC_ONE_CLASS = 1, 2, 4, 8  # NASREC_ROC_AUC_* status bits
 
@@ -307,6 +308,13 @@ class WeightEmaDesc(C.Structure):
                 ("count", vp), ("counter", vp)]
 
 
+class DecoupledDecayDesc(C.Structure):
+    _fields_ = [("kind", i32), ("phase", i32), ("B", i32), ("Fs", i32), ("dense_blocks", i32), ("nblocks", i32), ("mask", C.c_uint32),
+                ("n_chunks", i32), ("lambda_", C.c_double), ("lr_max", C.c_double), ("idx", vp), ("leader", vp),
+                ("table", vp * MAX_TABLES), ("stamp", vp * MAX_TABLES), ("rows", i64 * MAX_TABLES), ("tile_off", i64 * (MAX_TABLES + 1)),
+                ("bitmap", vp), ("p", vp), ("chunks", vp), ("level", vp), ("lr", vp), ("counter", vp)]
+
+
 DESC_BY_KIND = {
     OP_GEMM: GemmDesc, OP_EMBED_GATHER: EmbedDesc, OP_DOT_TRI_FWD: DotTriDesc, OP_DOT_TRI_BWD: DotTriDesc, OP_FM_FWD: FmDesc,
     OP_FM_BWD: FmDesc, OP_MHA_FWD: MhaDesc, OP_MHA_BWD: MhaDesc, OP_REDUCE_ROWS: ReduceRowsDesc, OP_COPY_SEGS: CopySegsDesc,
@@ -317,7 +325,7 @@ DESC_BY_KIND = {
     OP_WORKLIST: WorklistDesc, OP_CONST_I64: ConstI64Desc, OP_SPLITK_EPILOGUES: SplitkEpiloguesDesc, OP_DEDUP_IDS: DedupIdsDesc,
     OP_OPT_REDUCE2: OptReduce2Desc, OP_FINAL_FUSED: FinalDesc, OP_PERSIST: PersistDesc, OP_WORKLIST_DEV: WorklistDevDesc,
     OP_WEIGHT_DECAY: WeightDecayDesc, OP_OPT_MOMENTS: OptMomentsDesc, OP_LAST_LAYER_STEP: LastLayerStepDesc,
-    OP_ROC_AUC: RocAucDesc, OP_WEIGHT_EMA: WeightEmaDesc,
+    OP_ROC_AUC: RocAucDesc, OP_WEIGHT_EMA: WeightEmaDesc, OP_DECOUPLED_DECAY: DecoupledDecayDesc,
 }
 
 # every symbol include/nasrec_hip.h declares
@@ -329,7 +337,7 @@ SYMBOLS = [
     "nasrec_event_record", "nasrec_event_elapsed_ms", "nasrec_event_destroy", "nasrec_last_error", "nasrec_abi_version",
     "nasrec_desc_sizes", "nasrec_tsv_parse", "nasrec_alloc_uncached", "nasrec_free_uncached", "nasrec_persist_prepare", "nasrec_worklist_prepare",
     "nasrec_weight_decay", "nasrec_opt_moments", "nasrec_last_layer_step", "nasrec_roc_auc", "nasrec_roc_auc_workspace_bytes", "nasrec_gemm_route",
-    "nasrec_weight_ema", "nasrec_worklist_item_geometry",
+    "nasrec_weight_ema", "nasrec_worklist_item_geometry", "nasrec_decoupled_decay",
 ]
 
 _lib = None
@@ -372,15 +380,15 @@ def load():
     for name in ("nasrec_gemm", "nasrec_embedding_gather", "nasrec_embedding_dedup", "nasrec_dot_tri", "nasrec_fm",
                  "nasrec_mha_ffn", "nasrec_layernorm", "nasrec_final_logit", "nasrec_bce_logits", "nasrec_adagrad_dense",
                  "nasrec_adagrad_rows", "nasrec_opt_reduce", "nasrec_opt_apply", "nasrec_worklist", "nasrec_dedup_ids", "nasrec_opt_reduce2", "nasrec_final_fused", "nasrec_weight_decay",
-                 "nasrec_opt_moments", "nasrec_last_layer_step", "nasrec_roc_auc", "nasrec_weight_ema"):
+                 "nasrec_opt_moments", "nasrec_last_layer_step", "nasrec_roc_auc", "nasrec_weight_ema", "nasrec_decoupled_decay"):
         getattr(lib, name).argtypes = [vp, vp]
     lib.nasrec_roc_auc_workspace_bytes.argtypes = [i64]
     lib.nasrec_roc_auc_workspace_bytes.restype = i64
     lib.nasrec_gemm_route.argtypes = [vp, C.POINTER(C.c_uint)]
     if lib.nasrec_abi_version() != 17:
         raise EngineError("ABI version mismatch: library %d, binding 17" % lib.nasrec_abi_version())
-    sizes = (i32 * 44)()
-    n = lib.nasrec_desc_sizes(sizes, 44)
+    sizes = (i32 * 45)()
+    n = lib.nasrec_desc_sizes(sizes, 45)
     for kind, cls in DESC_BY_KIND.items():
         if kind >= n or sizes[kind] != C.sizeof(cls):
             raise EngineError("struct layout mismatch for op kind %d: library %d bytes, binding %d bytes"

@@ -71,6 +71,7 @@ static int dispatch(hipStream_t st, const void* desc) {
     case NASREC_OP_LAST_LAYER_STEP: return launch_last_layer_step(st, (const nasrec_last_layer_step_desc_t*)desc);
     case NASREC_OP_ROC_AUC: return launch_roc_auc(st, (const nasrec_roc_auc_desc_t*)desc);
     case NASREC_OP_WEIGHT_EMA: return launch_weight_ema(st, (const nasrec_weight_ema_desc_t*)desc);
+    case NASREC_OP_DECOUPLED_DECAY: return launch_decoupled_decay(st, (const nasrec_decoupled_decay_desc_t*)desc);
     default: return nasrec_set_error(-1, "unknown op kind %d", kind);
   }
 }
@@ -168,6 +169,7 @@ TYPED(nasrec_opt_moments, nasrec_opt_moments_desc_t, kind == NASREC_OP_OPT_MOMEN
 TYPED(nasrec_last_layer_step, nasrec_last_layer_step_desc_t, kind == NASREC_OP_LAST_LAYER_STEP)
 TYPED(nasrec_roc_auc, nasrec_roc_auc_desc_t, kind == NASREC_OP_ROC_AUC)
 TYPED(nasrec_weight_ema, nasrec_weight_ema_desc_t, kind == NASREC_OP_WEIGHT_EMA)
+TYPED(nasrec_decoupled_decay, nasrec_decoupled_decay_desc_t, kind == NASREC_OP_DECOUPLED_DECAY)
 
 // Device memory that the XCDs' L2 caches do not hold (MTYPE uncached): plain stores go through to memory, and a plain load behind an
 // agent-scope acquire (buffer_inv sc1: the CU's L1) reads what another workgroup of the SAME launch stored — what the persistent step
@@ -263,6 +265,7 @@ int nasrec_desc_sizes(int32_t* out, int n) {
       (int32_t)sizeof(nasrec_last_layer_step_desc_t), // 41
       (int32_t)sizeof(nasrec_roc_auc_desc_t),       // 42
       (int32_t)sizeof(nasrec_weight_ema_desc_t),    // 43
+      (int32_t)sizeof(nasrec_decoupled_decay_desc_t), // 44
   };
   const int total = (int)(sizeof(sizes) / sizeof(sizes[0]));
   int w = 0;

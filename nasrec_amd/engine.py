@@ -11,6 +11,7 @@ There is no CPU path here: everything below needs the HIP library and a GPU.
 import copy
 import ctypes as C
 import json
+import math
 import os
 from typing import Dict, List, Optional
 
@@ -388,6 +389,8 @@ class SupernetEngine:
         self.stream.synchronize()
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
+        if self._decay_dirty:
+            self.flush_decay_rows()
         self.stream.synchronize()
         return {k: v.detach().cpu().clone() for k, v in self.params.items()}
 
@@ -414,6 +417,8 @@ class SupernetEngine:
             raise L.EngineError("weight decay is part of the fused training step's optimizer: it needs train=True")
         if spec.moments and not train:
             raise L.EngineError("Adam / SGD are the fused training step's optimizer: they need train=True")
+        if spec.dwd and not (train and local_optimizer):
+            raise L.EngineError("decoupled weight decay is part of the one-process fused training step's optimizer")
         fast = (id(choice), B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, spec)
         hit = self._last_plan
         if self.cfg.fixed and hit is not None and hit[0] == fast and hit[1] is choice:  # fixed sub-network, same choice object: skip the JSON key
@@ -426,7 +431,7 @@ class SupernetEngine:
         arena = None
         # (weight decay: the default launches — the persistent step is an opt-in that has not been built for it)
         persist = bool(self.persist and self.level_schedule and self.cfg.fixed and B <= 256 and train and local_optimizer and not spec.wd
-                       and not spec.moments)
+                       and not spec.moments and not spec.dwd)
         if self.cfg.fixed and B <= 256 and train and self.level_schedule and (_UC_ARENA or persist):
             arena = Arena(self.device, uncached=True)  # (see _UC_ARENA; the persistent step needs it whatever the knob says)
         if not self.cfg.fixed:
@@ -555,6 +560,8 @@ class SupernetEngine:
                 if local_optimizer:
                     odescs = self._optimizer_descs(cp.tail, B, cp.cat_x, sbuf.grad_tensor() if (sbuf.grad_written and not self.host_embedding)
                                                    else None, clip, eps)
+                # decoupled weight decay: the batch's rows pay what they owe in front of the launch that gathers them
+                cp.decay0 = cp.tail.decay0 if (local_optimizer and spec.dwd) else None
                 ids_in_program = []
                 ids = cp.tail.dedup_ids
                 if ids is not None:
@@ -763,6 +770,8 @@ class SupernetEngine:
             self._weight_decay_tables(t, ctx, arena, pre)
         if t.spec.moments:
             self._moments_tables(cp, ctx, arena, pre)
+        if t.spec.dwd:
+            self._decay_tables(t, ctx, arena, pre)
         cp.bce, cp._pre = bd, pre
 
     def _const_table(self, flat, arena, pre):
@@ -1151,7 +1160,99 @@ class SupernetEngine:
             # the weight average (csrc/weight_ema.hip): the batch's rows pay what they owe once the leaders are known and before
             # anything moves them; every parameter is averaged behind the last launch that writes one
             ema0, ema1 = self._ema_step_descs(spec, Bg if rows else 0, cat_x, b.leader)
-        return reduce + ema0 + ([wd0] if wd0 is not None else []) + apply + ([phase1] if phase1 is not None else []) + ema1
+        dec1 = []
+        if spec.dwd:
+            # decoupled weight decay (csrc/decoupled_decay.hip): torch's order — the L2 term's gradient of the weights as they were,
+            # then p (1 - lr lambda), then the update
+            dec1 = self._decay_step_descs(t, Bg, rows, cat_x, b.leader)
+        return reduce + ema0 + ([wd0] if wd0 is not None else []) + dec1 + apply + ([phase1] if phase1 is not None else []) + ema1
+
+    DECAY_DENSE_BLOCKS = 1024  # workgroups on the dense ranges (EMA_DENSE_BLOCKS: the same stream)
+    DECAY_REBASE = 1.0         # -level at which a step flushes first: a stamp's quantisation (|L| 2^-24) stays below one rounding of a weight
+    _decay_dirty = False       # a fused step with decoupled weight decay ran since the last flush: table rows may owe
+    _decay_mask = 0
+    _decay_owed = 0.0          # host mirror of -level (an upper bound: a step that skips the stem moves no level)
+
+    def ensure_decay_state(self):
+        """The lazily paid decoupled weight decay's state (csrc/decoupled_decay.hip): `decay_level`, one fp64 word per table = the sum
+        of log1p(-lr lambda) over the steps in which that table decayed; `decay_stamps[f]`, one float per row = the fp32 value of the
+        level at which that row's weights are current; and the last-arrival counter.  All zero: every row current."""
+        if self.host_embedding:
+            raise L.EngineError("the fused decoupled weight decay needs the embedding tables on the device")
+        if getattr(self, "decay_level", None) is not None:
+            return
+        with torch.cuda.stream(self.stream):
+            self.decay_stamps = [torch.zeros(n, dtype=torch.float32, device=self.device) for n in self.num_embeddings]
+            self.decay_level = torch.zeros(max(1, self.Fs), dtype=torch.float64, device=self.device)
+            self._decay_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._row_bitmap()
+        self.stream.synchronize()
+
+    def _decay_tables(self, t, ctx, arena, pre):
+        """Chunk table of a plan with decoupled weight decay: the selected dense ranges (P.regularised: get_l2_loss's rule) that the
+        backward reaches — torch's `p.grad is not None`; and the selected tables"""
+        self.ensure_decay_state()
+        reached = set(n for n in list(ctx.grad_params) + ["_final.weight", "_final.bias"] if not n.startswith("_embedding."))
+        reg, t.dwd_tables = P.regularised(self.shapes, t.spec.no_reg)
+        flat = P.path_chunks([(self.offsets[n], self.params[n].numel()) for n in reg if n in reached], chunk=1024)
+        t.dwd_tab = self._const_table(flat, arena, pre)
+        t.dwd_chunks = (t.dwd_tab.data_ptr(), len(flat) // 2)
+
+    def _decay_desc(self, phase: int, mask: int, lam: float = 0.0):
+        d = L.DecoupledDecayDesc()
+        d.kind, d.phase, d.Fs, d.mask, d.lambda_ = L.OP_DECOUPLED_DECAY, phase, self.Fs, mask, lam
+        d.nblocks = self.WD_BLOCKS
+        self._tile_layout(d, lambda f: phase == 2 and bool((mask >> f) & 1))
+        for f in range(self.Fs):
+            d.stamp[f] = self.decay_stamps[f].data_ptr()
+        d.bitmap = self._row_bitmap().data_ptr()
+        d.p = self.flat_p.data_ptr()
+        d.level, d.lr, d.counter = self.decay_level.data_ptr(), self.lr_dev.data_ptr(), self._decay_counter.data_ptr()
+        return d
+
+    def _decay_step_descs(self, t, Bg, rows, cat_x, leader):
+        """[decay] of a training plan with spec.dwd: phase 1 over the plan's dense ranges and the batch's leaders; leaves the
+        catch-up (phase 0, whose ids the step patches in: it runs in front of the staging launch) in t.decay0 and the decay in
+        t.decay1.  rows False: no gradient reaches the stem, no table decays (torch: `p.grad is None`) — the forward still gathers the
+        batch's rows, so the catch-up runs all the same."""
+        tables = sum(1 << f for f in t.dwd_tables)
+        mask = tables if rows else 0
+        d0, d1 = self._decay_desc(0, tables, t.spec.dwd), self._decay_desc(1, mask, t.spec.dwd)
+        d0.B, d0.idx = Bg, cat_x.data_ptr()
+        if mask:
+            d1.B, d1.idx, d1.leader = Bg, cat_x.data_ptr(), leader.data_ptr()
+        d1.chunks, d1.n_chunks = t.dwd_chunks
+        d1.dense_blocks = max(1, min(self.DECAY_DENSE_BLOCKS, d1.n_chunks))
+        t.decay0, t.decay1, t.decay_mask = (d0 if tables else None), d1, mask
+        return [d1]
+
+    @_on_device
+    def flush_decay_rows(self):
+        """bring every table row current (a row outside the batches owes the factors of the steps it rested through) and re-base the
+        stamps and levels to 0: what a reader of the table weights needs.  One streaming launch, waited for; a no-op when no fused
+        step with decoupled weight decay ran since the last flush."""
+        if not self._decay_dirty:
+            return
+        torch.cuda.current_stream(self.device).synchronize()
+        d = self._decay_desc(2, self._decay_mask)
+        L.check(L.load().nasrec_decoupled_decay(self.stream.cuda_stream, C.addressof(d)))
+        self.stream.synchronize()  # (the reader may sit on another stream)
+        self._decay_dirty, self._decay_mask, self._decay_owed = False, 0, 0.0
+
+    def _decay_begin(self, cp, lr: float):
+        """host bookkeeping of a fused step with decoupled weight decay, before anything is launched"""
+        t = cp.tail
+        lam = t.spec.dwd
+        if not float(lr) * lam < 1.0 or lr < 0:
+            raise L.EngineError("decoupled weight decay: lr %r x lambda %r is not inside [0, 1)" % (lr, lam))
+        t.decay1.lr_max = float(lr)
+        if not t.decay_mask:
+            return
+        owes = -math.log1p(-float(lr) * lam)
+        if self._decay_dirty and (t.decay_mask != self._decay_mask or self._decay_owed + owes > self.DECAY_REBASE):
+            self.flush_decay_rows()
+        self._decay_dirty, self._decay_mask = True, t.decay_mask
+        self._decay_owed += owes
 
     EMA_DENSE_BLOCKS = 1024  # workgroups on the dense arena (the apply launch's measured optimum for the same stream of 2.2 M floats)
 
@@ -1382,10 +1483,13 @@ class SupernetEngine:
             return jf, jb
         return fwd_list, bwd_descs
 
-    def _stage_inputs(self, sp, cp, int_x, cat_x, y=None, lr=None, rows=None, launch=True):
+    def _stage_inputs(self, sp, cp, int_x, cat_x, y=None, lr=None, rows=None, launch=True, catch_up=False):
         """one launch: batch -> the plan's static buffers (+ this step's learning rate -> device scalar); host_embedding: the
         looked-up rows [B, Fs, 16] come with the batch.  launch=False: only patch the prebuilt staging descriptor (the caller launches it
-        as the head of a program) — returns True when that is what happened, False when the inputs went another way and are staged"""
+        as the head of a program) — returns True when that is what happened, False when the inputs went another way and are staged.
+        catch_up (train_step): a plan with decoupled weight decay launches its phase 0 over this batch's ids in front of the gather
+        (launch=False: the caller's program carries it in front of the staging descriptor)"""
+        dec0 = getattr(cp, "decay0", None) if catch_up else None  # (decoupled weight decay: the batch's rows pay before the gather)
         if self.host_embedding:
             if rows is None:
                 raise L.EngineError("this engine holds no embedding table (place_embedding_on_cpu): pass the looked-up rows")
@@ -1400,6 +1504,9 @@ class SupernetEngine:
                 cp.y.copy_(y.reshape(cp.y.shape), non_blocking=True)
             if lr is not None:
                 self.lr_dev.fill_(float(lr))
+            if dec0 is not None:
+                dec0.idx = cp.cat_x.data_ptr()
+                L.check(L.load().nasrec_launch(sp, C.addressof(dec0)))
             if not self.host_embedding:
                 L.check(L.load().nasrec_launch(sp, C.addressof(cp.gather)))
             if getattr(cp, "ids_on_stage", False):  # (the staging launch would have carried it)
@@ -1408,12 +1515,16 @@ class SupernetEngine:
         d = cp.stage  # prebuilt per plan: only the sources change from step to step
         d.int_src, d.cat_src = int_x.data_ptr(), cat_x.data_ptr()
         d.y_src = y.data_ptr() if y is not None else None
+        if dec0 is not None:
+            dec0.idx = cat_x.data_ptr()  # (the raw ids: the staging launch has not copied them yet)
         if lr is not None:
             d.lr, d.lr_dst = float(lr), self.lr_dev.data_ptr()
         else:
             d.lr_dst = None
         if not launch:
             return True
+        if dec0 is not None:
+            L.check(L.load().nasrec_launch(sp, C.addressof(dec0)))
         L.check(L.load().nasrec_launch(sp, C.addressof(d)))
         return False
 
@@ -1421,6 +1532,8 @@ class SupernetEngine:
     def forward(self, int_x, cat_x, choice=None, graph=False, rows=None):
         """logits [B,1] for the given choice (fixed mode: the fixed choice)."""
         choice = choice if choice is not None else self.warm_choice
+        if self._decay_dirty:  # (fused steps with decoupled weight decay left table rows owing)
+            self.flush_decay_rows()
         B = int(int_x.shape[0])
         cp = self.compile(choice, B, train=False, graph=graph)
         sp = self._sp()
@@ -1442,7 +1555,8 @@ class SupernetEngine:
 
     @_on_device
     def train_step(self, int_x, cat_x, y, lr: float, choice=None, clip: Optional[float] = 5.0, eps: float = 1e-2, graph: Optional[bool] = False,
-                   staged: bool = False, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None, ema: float = 0.0):
+                   staged: bool = False, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None, ema: float = 0.0,
+                   decoupled_wd: float = 0.0):
         """zero_grad -> forward -> BCE -> backward -> clip_grad_norm_ -> Adagrad (train_utils.py:262-286).
         Returns the (device) loss tensor of this step.  `staged`: inputs are already in the plan's static buffers.  graph: True = replay
         the captured step, False = launch its program, None = whichever is faster for this plan (prefers_graph).
@@ -1453,8 +1567,20 @@ class SupernetEngine:
         batch's rows only (utils/optim.RowSparseAdam), and weight decay must leave them out.
         ema: the decay of a weight average kept beside the step (ensure_ema_state; csrc/weight_ema.hip): two more launches in the
         optimizer tail, exact only where the tables move in the batch's rows alone (Adagrad, row-sparse Adam, RMSprop; no regularised
-        table) — refused otherwise."""
+        table) — refused otherwise.
+        decoupled_wd: lambda of the decoupled weight decay p <- p (1 - lr lambda) in front of the update (utils/optim.
+        DecoupledWeightDecay; csrc/decoupled_decay.hip) over the parameters get_l2_loss's rule selects (no_reg_param_name) and the
+        step reaches: two more launches, the table rows outside the batch rest and owe — a raw read of a table needs
+        flush_decay_rows() first.  Refused where the tables move outside the batch's rows, and, when it reaches the tables, beside a
+        weight average or an L2 term on them."""
         self._refuse_swapped("train_step")
+        if decoupled_wd:
+            if optim is not None and optim.kind in ("adam", "sgd") and not optim.sparse_rows:
+                raise L.EngineError("the fused decoupled weight decay lets the table rows outside the batch rest: dense Adam and "
+                                    "momentum SGD move every row (DecoupledWeightDecay.apply() on the torch route is the dense form)")
+            if P.regularised(self.shapes, no_reg_param_name)[1] and (ema or weight_decay):
+                raise L.EngineError("a decoupled weight decay that reaches the embedding tables runs beside neither a fused weight "
+                                    "EMA nor an L2 term on the tables (DecoupledWeightDecay.apply() on the torch route is the dense form)")
         if ema and ((optim is not None and optim.kind in ("adam", "sgd") and not optim.sparse_rows)
                     or (weight_decay and P.regularised(self.shapes, no_reg_param_name)[1])):
             raise L.EngineError("the fused weight EMA averages the batch's table rows only: dense Adam, momentum SGD and a regularised "
@@ -1470,18 +1596,27 @@ class SupernetEngine:
         else:  # pre-staged inputs: the batch size is the one of the plan they were staged into
             assert staged and self._last_plan is not None, "train_step without inputs needs a previously compiled plan holding them"
             B = int(self._last_plan[2].cat_x.shape[0])
-        cp = self.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, spec=OptimSpec.of(eps, weight_decay, no_reg_param_name, optim, ema))
+        cp = self.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, spec=OptimSpec.of(eps, weight_decay, no_reg_param_name, optim, ema, decoupled_wd))
         sp = self._sp()
+        dec0 = None
+        if cp.tail.spec.dwd:
+            self._decay_begin(cp, lr)
+            dec0 = cp.decay0
+        elif self._decay_dirty:  # (a step without the decay behind steps with it: its gather reads current rows)
+            self.flush_decay_rows()
         if not staged:
             whole = not graph and getattr(cp, "fb", None) is not None and not self.host_embedding
-            if self._stage_inputs(sp, cp, int_x, cat_x, y, lr, launch=not whole):
+            if self._stage_inputs(sp, cp, int_x, cat_x, y, lr, launch=not whole, catch_up=True):
                 # a launched (not replayed) step: staging launch + joint program + optimizer as ONE host call
                 if getattr(cp, "whole", None) is None:
-                    cp.whole = Program([cp.stage] + list(cp.fb.descs) + list(cp.opt.descs))
+                    cp.whole = Program(([dec0] if dec0 is not None else []) + [cp.stage] + list(cp.fb.descs) + list(cp.opt.descs))
                 cp.whole.run(sp)
                 return cp.loss
         else:
             self.lr_dev.fill_(float(lr))
+            if dec0 is not None:
+                dec0.idx = cp.cat_x.data_ptr()
+                L.check(L.load().nasrec_launch(sp, C.addressof(dec0)))
             L.check(L.load().nasrec_launch(sp, C.addressof(cp.gather)))
             if getattr(cp, "ids_on_stage", False):
                 L.check(L.load().nasrec_launch(sp, C.addressof(cp.tail.dedup_ids)))
@@ -1564,6 +1699,8 @@ class SupernetEngine:
         ensure_last_layer_state) on _final.{weight, bias} alone.  Returns the (device) loss.  graph: replay a captured program (fixed
         sub-networks).  The plan is the one the autograd route runs (compile(choice, B, train=True))."""
         self._refuse_swapped("last_layer_step")
+        if self._decay_dirty:
+            self.flush_decay_rows()
         choice = choice if choice is not None else self.warm_choice
         if self.host_embedding:
             raise L.EngineError("the last-layer step needs the embedding tables on the device")
@@ -1586,6 +1723,8 @@ class SupernetEngine:
     def close(self):
         """Release what this engine holds outside torch's allocator now, not at the next garbage collection: captured graphs and the
         uncached arenas of its plans (hipExtMallocWithFlags memory, freed when the last view of it goes).  The engine is unusable after."""
+        if self._decay_dirty:  # (the tables outlive the engine: their rows are left current)
+            self.flush_decay_rows()
         self.stream.synchronize()
         for cp in list(self._plans.values()):
             for prog in [getattr(cp, n, None) for n in ("step", "fwd", "whole")] + [p for pr in getattr(cp, "last_layer", {}).values() for p in pr]:
@@ -1608,10 +1747,13 @@ class SupernetEngine:
         self._uc_flat_arena = None
         self._sk_ws = None
         self.ema_flat = self.ema_tables = self.ema_stamps = self.ema_count = self._ema_counter = self.ema_decay = None
+        self.decay_stamps = self.decay_level = self._decay_counter = None
 
     @_on_device
     def run_forward(self, cp, int_x, cat_x, rows=None):
         """forward program of an already compiled (training) plan; logits land in cp.logits"""
+        if self._decay_dirty:
+            self.flush_decay_rows()
         sp = self._sp()
         self._stage_inputs(sp, cp, int_x, cat_x, rows=rows)
         cp.fwd.run(sp)
@@ -1627,6 +1769,8 @@ class SupernetEngine:
         """forward + BCE + backward only (gradients left in self.grads / plan.sparse0 gradient); used by the data-parallel
         wrapper and by the parity tests."""
         choice = choice if choice is not None else self.warm_choice
+        if self._decay_dirty:
+            self.flush_decay_rows()
         B = int(int_x.shape[0])
         cp = self.compile(choice, B, train=True, grad_scale=grad_scale)
         sp = self._sp()

@@ -101,6 +101,10 @@ def train_and_eval_one_model(model, args):
     if args.ema > 0:  # (after the broadcast: every rank's average starts from THE model)
         from nasrec_amd.utils.optim import WeightEMA
         ema = WeightEMA(model, args.ema)
+    decay = None
+    if args.decoupled_wd > 0:
+        from nasrec_amd.utils.optim import DecoupledWeightDecay
+        decay = DecoupledWeightDecay(model, args.decoupled_wd, args.no_reg_param_name)
     print(model)
     create_dir(args.logging_dir)
     with open(os.path.join(args.logging_dir, "configs_args.json"), "w") as f:
@@ -112,7 +116,7 @@ def train_and_eval_one_model(model, args):
             model, epoch, optimizer, lr_scheduler, train_loader, test_loader, loss_fn, l2_loss_fn, args.train_batch_size, args.gpu,
             display_interval=args.display_interval, test_interval=args.test_interval if epoch != 1 else 100,
             max_train_steps=steps_per_epoch if epoch != 1 else 1000, test_only_at_last_step=(args.test_only_at_last_step) == 1,
-            tb_writer=writer, use_amp=False, grad_clip_value=5.0, ema=ema)
+            tb_writer=writer, use_amp=False, grad_clip_value=5.0, ema=ema, decay=decay)
         epoch_logs.append(logs)
     print("Dumping logs to {}!".format(args.logging_dir))
     from nasrec_amd.utils.dist import world_info
@@ -150,6 +154,13 @@ def main(args):
     print("Matmul precision: {}".format(args.matmul_precision))
     model = get_model(args).to(args.gpu)
     return train_and_eval_one_model(model, args)
+
+
+def _decoupled_wd(text):
+    v = float(text)
+    if not v >= 0.0:
+        raise argparse.ArgumentTypeError("--decoupled-wd %r is negative" % (text,))
+    return v
 
 
 def _ema_strength(text):
@@ -193,6 +204,11 @@ def build_parser():
                         "weight, s += (1 - ema) (w - s) after every optimizer step (utils/optim.WeightEMA); the tests run on the averaged "
                         "weights and the checkpoint carries them as ema_state_dict.  Inside the fused step with --optimizer adagrad / "
                         "row-sparse-adam / rmsprop and no weight decay on the tables, on the torch route otherwise")
+    p.add_argument("--decoupled-wd", dest="decoupled_wd", type=_decoupled_wd, default=0.0,
+                   help="decoupled weight decay (the W of AdamW), 0 = off: before every optimizer step w *= 1 - lr * LAMBDA on the "
+                        "parameters --wd would regularise (>= 2 dimensions, --no-reg-param-name left out) that have a gradient "
+                        "(utils/optim.DecoupledWeightDecay).  Independent of --wd.  Inside the fused step with --optimizer adagrad / "
+                        "row-sparse-adam / rmsprop (embedding rows outside the batch pay lazily), on the torch route otherwise")
     p.add_argument("--gpu", type=int, default=None, help="GPU ID to use.")
     # not a reference flag: placement of the embedding tables under torchrun (nasrec_amd/sharded_tables.py)
     p.add_argument("--table-sharding", dest="table_sharding", type=str, default="none", choices=["none", "row"],

@@ -21,6 +21,9 @@ class OptimSpec(NamedTuple):
     no_reg: Optional[str] = None
     sparse_rows: bool = False  # Adam: row-sparse on the tables (utils/optim.RowSparseAdam: torch.optim.SparseAdam on the batch's rows)
     alpha: float = 0.99     # RMSprop's smoothing constant (utils/optim.LazyRMSprop: momentum 0, not centered)
+    dwd: float = 0.0        # decoupled weight decay p <- p (1 - lr dwd) before the update (utils/optim.DecoupledWeightDecay,
+                            # csrc/decoupled_decay.hip) over the parameters no_reg leaves in; 0 = none.  (In front of `ema`, which tests pin as the last field:
+                            # every positional use stops at `alpha`.)
     ema: float = 0.0        # decay of a weight average kept beside the step (utils/optim.WeightEMA, csrc/weight_ema.hip); 0 = none
 
     @property
@@ -34,10 +37,12 @@ class OptimSpec(NamedTuple):
         return {"adagrad": ("sum",), "adam": ("exp_avg", "exp_avg_sq"), "rmsprop": ("square_avg",)}.get(self.kind, ("momentum_buffer",))
 
     @staticmethod
-    def of(eps: float = 1e-2, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None, ema: float = 0.0) -> "OptimSpec":
+    def of(eps: float = 1e-2, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None, ema: float = 0.0,
+           decoupled_wd: float = 0.0) -> "OptimSpec":
         """the public entry points' optimizer arguments as one spec: optim None = Adagrad with `eps` (its only source: the default eps
-        of a spec is Adam's), else an Adam / SGD spec; no_reg_param_name only counts with weight decay; ema: the decay of the weight
-        average the step keeps (0 = none, or what `optim` already carries)"""
+        of a spec is Adam's), else an Adam / SGD spec; no_reg_param_name only counts with weight decay (the L2 term's or the decoupled one);
+        ema: the decay of the weight average the step keeps (0 = none, or what `optim` already carries); decoupled_wd: the lambda of
+        the decoupled weight decay in front of the update (0 = none, or what `optim` already carries)"""
         if optim is not None and not optim.moments:
             raise ValueError("optim is an Adam / SGD spec; Adagrad is optim=None with its eps")
         wd = float(weight_decay or 0.0)
@@ -45,7 +50,11 @@ class OptimSpec(NamedTuple):
         ema = float(ema or 0.0)
         if ema and not 0.0 < ema < 1.0:
             raise ValueError("ema decay %r is not inside (0, 1)" % (ema,))
-        return base._replace(wd=wd, no_reg=no_reg_param_name if wd else None, ema=ema if ema else base.ema)
+        dwd = float(decoupled_wd or 0.0)
+        if dwd < 0.0:
+            raise ValueError("decoupled weight decay %r is negative" % (dwd,))
+        dwd = dwd if dwd else base.dwd
+        return base._replace(wd=wd, no_reg=no_reg_param_name if (wd or dwd) else None, ema=ema if ema else base.ema, dwd=dwd)
 
     @staticmethod
     def from_optimizer(optimizer) -> Optional["OptimSpec"]:

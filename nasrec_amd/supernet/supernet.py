@@ -289,7 +289,9 @@ class SuperNet(nn.Module):
 
     def state_dict(self, *args, **kwargs):
         """row-sharded tables: `_embedding.f.weight` is returned WHOLE (all-gather of the shards — a collective when world > 1: every
-        rank must call it), so checkpoints keep the reference's keys and shapes whatever the placement"""
+        rank must call it), so checkpoints keep the reference's keys and shapes whatever the placement.  Fused steps with decoupled
+        weight decay leave table rows owing their decay: they are paid first (engine_flush_decay)"""
+        self.engine_flush_decay()
         sd = super().state_dict(*args, **kwargs)
         if self._table_sharding == "row" and self._sharded is not None and self._sharded.world > 1:
             prefix = kwargs.get("prefix", args[1] if len(args) > 1 else "")
@@ -298,6 +300,7 @@ class SuperNet(nn.Module):
         return sd
 
     def load_state_dict(self, state_dict, *args, **kwargs):
+        self.engine_flush_decay()  # (what fused steps with decoupled weight decay left owing is paid on the OLD weights, not the loaded ones)
         if self._table_sharding == "row":  # whole tables in, this rank's rows kept
             state_dict = dict(state_dict)
             for f in range(self._sparse_input_size):
@@ -513,6 +516,7 @@ class SuperNet(nn.Module):
             self._bind_engine(dev)
 
     def __deepcopy__(self, memo):
+        self.engine_flush_decay()  # (the copy holds every table row current)
         eng, names, sh = self._engine, self._param_names, (self._sharded, self._sharded_ops, self.__dict__.pop("_sharded_step", None))
         # (the data-parallel step cached by engine_train_step drives THIS model's engine: the copy builds its own when it trains)
         dp = self.__dict__.pop("_dp_step", None)
@@ -541,6 +545,7 @@ class SuperNet(nn.Module):
             self._device_args = args
             return self
         eng = self._engine
+        self.engine_flush_decay()  # (the copy that moves must hold every table row current)
         before = [p.data_ptr() for p in self.parameters() if not isinstance(p, nn.parameter.UninitializedParameter)] if eng is not None else None
         out = super().to(*args, **kwargs)
         if eng is not None:
@@ -622,7 +627,8 @@ class SuperNet(nn.Module):
         return self.forward(int_feats, cat_feats, choices)
 
     def engine_train_step(self, int_feats, cat_feats, y, lr: float, clip: Optional[float] = 5.0, eps: float = 1e-2, graph=None,
-                          weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None, ema_decay: float = 0.0):
+                          weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None, ema_decay: float = 0.0,
+                          decoupled_wd: float = 0.0):
         """Fused step on the engine (forward, BCE, backward, clip_grad_norm_, Adagrad with row-sparse table update):
         the counterpart of train_utils.py:262-286 for optimizer == Adagrad (torch's own weight_decay == 0).  weight_decay != 0: the loss
         is BCE + get_l2_loss(self, weight_decay, no_reg_param_name) — every regularised parameter and every table row is decayed
@@ -632,15 +638,24 @@ class SuperNet(nn.Module):
         state with the torch optimizer.  Both need whole tables; under data parallelism they run in the exchange step's optimizer over
         the global batch (nasrec_amd/parallel.py).  ema_decay != 0: the step also averages every parameter (utils/optim.WeightEMA's
         update, in the engine: engine_bind_ema / engine_sync_ema share the average with a WeightEMA) — one process, whole tables, and an
-        optimizer whose tables move in the batch's rows only (Adagrad, row-sparse Adam, RMSprop; no regularised table)."""
+        optimizer whose tables move in the batch's rows only (Adagrad, row-sparse Adam, RMSprop; no regularised table).
+        decoupled_wd != 0: utils/optim.DecoupledWeightDecay's apply(lr) in front of the update, in the engine — the parameters
+        get_l2_loss's rule selects (no_reg_param_name) and the step reaches take p (1 - lr decoupled_wd); a table row outside the batch
+        rests and pays the factors it missed when it is next in a batch or read.  Same conditions as ema_decay, and, when the decay
+        reaches the tables, neither ema_decay nor an L2 term on the tables.  Between fused steps `_embedding.<f>.weight` holds rows that
+        still owe: a RAW read of it needs engine_flush_decay() first.  forward (outside this step), state_dict,
+        engine_sync_optimizer_steps and a bound DecoupledWeightDecay's apply (engine_bind_decay) flush by themselves."""
         if self._place_embedding_on_cpu:
             from .._lib import EngineError
             raise EngineError("engine_train_step needs the tables on the device; with place_embedding_on_cpu use forward / backward "
                               "and a torch optimizer")
-        if ema_decay:
+        if ema_decay or decoupled_wd:
             import torch.distributed as dist
             if self._table_sharding == "row" or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
                 from .._lib import EngineError
+                if decoupled_wd:
+                    raise EngineError("the fused decoupled weight decay covers one process with whole tables: use "
+                                      "DecoupledWeightDecay.apply() on the torch route")
                 raise EngineError("the fused weight EMA covers one process with whole tables: use WeightEMA.update() on the torch route")
         choice = self._resolve_choice(None)
         self._ensure_engine(int_feats)
@@ -653,7 +668,7 @@ class SuperNet(nn.Module):
         d["_engine_steps"] = d.get("_engine_steps", 0) + 1
         d["_last_step_batch"] = int(int_feats.shape[0])
         from ..optim_spec import OptimSpec
-        spec = OptimSpec.of(eps, weight_decay, no_reg_param_name, optim, ema_decay)
+        spec = OptimSpec.of(eps, weight_decay, no_reg_param_name, optim, ema_decay, decoupled_wd)
         d["_last_step_key"] = (choice, clip, eps, graph, spec)
         d["_last_step_last_layer"] = False
         opt_kw = {}
@@ -663,6 +678,9 @@ class SuperNet(nn.Module):
                 raise EngineError("weight decay, Adam and SGD in the fused step need whole tables: row-sharded tables train them "
                                   "through the torch route")
             opt_kw = dict(weight_decay=spec.wd, no_reg_param_name=spec.no_reg, optim=optim)
+        if spec.dwd:
+            return self._engine.train_step(int_feats, cat_feats, y, lr, choice, clip, eps, graph=graph, ema=spec.ema, weight_decay=spec.wd,
+                                           no_reg_param_name=spec.no_reg, optim=optim, decoupled_wd=spec.dwd)
         if spec.ema:
             return self._engine.train_step(int_feats, cat_feats, y, lr, choice, clip, eps, graph=graph, ema=spec.ema, **opt_kw)
         if self._table_sharding == "row":
@@ -831,6 +849,18 @@ class SuperNet(nn.Module):
             eng.stream.synchronize()
         ema._hooks = dict(flush=eng.flush_ema_rows, swap=eng.swap_ema, advance=advance)  # (the model keeps no reference to `ema`)
 
+    def engine_flush_decay(self):
+        """Pay what fused steps with decoupled weight decay (engine_train_step(..., decoupled_wd=)) left owing: afterwards every row of
+        `_embedding.<f>.weight` holds its current value.  One streaming launch over the tables when something is owed, else nothing."""
+        eng = self.__dict__.get("_engine")
+        if eng is not None and eng._decay_dirty:
+            eng.flush_decay_rows()
+
+    def engine_bind_decay(self, decay):
+        """Give a DecoupledWeightDecay (utils/optim.py) the engine's flush as its hook: a torch-route `apply()` in the middle of a fused
+        run then multiplies tables whose rows are all current (the model keeps no reference to `decay`)"""
+        decay._flush = self.engine_flush_decay
+
     def engine_sync_ema(self, ema):
         """read `num_updates` back from the engine's count (the fused steps since engine_bind_ema)"""
         eng = self._engine
@@ -884,6 +914,7 @@ class SuperNet(nn.Module):
         """add the fused steps taken since engine_bind_optimizer to the optimizer's per-parameter step counters
         (Adam / SGD: the counters of the engine, and state entries for the parameters stepped for the first time)"""
         spec, last_layer = self.__dict__.get("_bound", (None, False))
+        self.engine_flush_decay()
         if spec is not None and spec.moments:
             self._engine.flush_lazy_rows()  # (RMSprop: the state about to be aliased is read with every row current; else a no-op)
             self._engine.stream.synchronize()

@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from nasrec_amd.main_train import _num_embedding_dict, _num_sparse_inputs_dict, build_lr_scheduler, build_optimizer, summary_writer  # noqa: E402
+from nasrec_amd.main_train import _num_embedding_dict, _num_sparse_inputs_dict, _decoupled_wd, build_lr_scheduler, build_optimizer, summary_writer  # noqa: E402
 from nasrec_amd.supernet.supernet import SuperNet, ops_config_lib  # noqa: E402
 from nasrec_amd.utils.data_pipes import make_loaders  # noqa: E402
 from nasrec_amd.utils.io_utils import create_dir, dump_pickle_data, load_model_checkpoint, load_optimizer_state, save_model_checkpoint  # noqa: E402
@@ -49,6 +49,10 @@ def train_and_eval_one_model(model, args):
     from nasrec_amd.utils.dist import assert_replicas_identical, broadcast_replica_state
     broadcast_replica_state(model)  # data parallel: rank 0's weights, tables and accumulators are THE model
     assert_replicas_identical(model, optimizer)
+    decay = None
+    if args.decoupled_wd > 0:
+        from nasrec_amd.utils.optim import DecoupledWeightDecay
+        decay = DecoupledWeightDecay(model, args.decoupled_wd, args.no_reg_param_name)
     print(model)
     strategy_name = args.strategy if args.strategy == "single-path" else args.strategy + "-" + args.anypath_choice
     logging_dir = os.path.join(args.logging_dir, "supernet_{}blocks_layernorm{:d}_{}_lr{:.2f}_supernetwarmup_{}".format(
@@ -61,7 +65,7 @@ def train_and_eval_one_model(model, args):
         logs = train_and_test_one_epoch(
             model, epoch, optimizer, lr_scheduler, train_loader, test_loader, loss_fn, l2_loss_fn, args.train_batch_size, args.gpu,
             display_interval=args.display_interval, test_interval=args.test_interval, max_train_steps=steps_per_epoch,
-            test_only_at_last_step=True, grad_clip_value=5.0, tb_writer=writer)
+            test_only_at_last_step=True, grad_clip_value=5.0, tb_writer=writer, decay=decay)
         epoch_logs.append(logs)
     print("Dumping logs to {}!".format(logging_dir))
     from nasrec_amd.utils.dist import world_info
@@ -114,6 +118,9 @@ def build_parser():
     p.add_argument("--train_split", type=str, default="train", choices=["train", "trainval"])
     p.add_argument("--validate_split", type=str, default="test", choices=["val", "test"])
     p.add_argument("--no-reg-param-name", type=str, default=None, help="Name of the parameters that do not need to be regularized.")
+    p.add_argument("--decoupled-wd", dest="decoupled_wd", type=_decoupled_wd, default=0.0,
+                   help="decoupled weight decay (the W of AdamW), 0 = off: before every optimizer step w *= 1 - lr * LAMBDA on the parameters "
+                        "--wd would regularise that have a gradient (utils/optim.DecoupledWeightDecay; main_train.py --decoupled-wd)")
     p.add_argument("--loss_function", type=str, default="bce", choices=["bce"])
     p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rmsprop", "ds-optimizer"])
     p.add_argument("--pretrained_dlrm_emb_path", type=str, default=None, help="Pretrained embedding path from DLRM model.")

@@ -217,3 +217,46 @@ class WeightEMA:
         self.decay, self.num_updates = float(state["decay"]), int(state["num_updates"])
         for n, s in self.shadow.items():
             s.copy_(state["shadow"][n].to(s.device))
+
+
+class DecoupledWeightDecay:
+    """`--decoupled-wd LAMBDA`: decoupled weight decay beside any optimizer, the "W" of torch.optim.AdamW.  `apply(lr)`, called
+    immediately before `optimizer.step()` (after clipping and `optimizer.touch`), runs torch.optim.AdamW's statement
+
+        p.mul_(1 - lr * weight_decay)
+
+    on every SELECTED parameter that has a gradient this step; a parameter whose grad is None is skipped exactly as AdamW skips it (a
+    supernet parameter off the sampled path; a table in a step whose backward stops short of the stem).  Selected is get_l2_loss's
+    rule: at least 2 dimensions and a name that does not start with `no_reg_param_name`.  No state: nothing goes into a checkpoint.
+
+    The fused engine step (SuperNet.engine_train_step(..., decoupled_wd=)) multiplies the dense parameters and the batch's table rows
+    and lets every other row rest; a resting row owes the product of the factors it missed, paid when it is next touched or read
+    (csrc/decoupled_decay.hip).  Between fused steps the table tensors therefore hold rows that still owe their decay: a RAW read of
+    `_embedding.<f>.weight` needs `SuperNet.engine_flush_decay()` first.  `SuperNet.forward`, `SuperNet.state_dict`,
+    `engine_sync_optimizer_steps`, the end of train_and_test_one_epoch and `apply` of a bound helper (SuperNet.engine_bind_decay) flush
+    by themselves."""
+
+    def __init__(self, model, weight_decay: float, no_reg_param_name=None):
+        weight_decay = float(weight_decay)
+        if not weight_decay >= 0.0:
+            raise ValueError("DecoupledWeightDecay: weight_decay %r is negative" % (weight_decay,))
+        self.model, self.weight_decay, self.no_reg_param_name = model, weight_decay, no_reg_param_name
+        self._flush = None  # (set by SuperNet.engine_bind_decay: pays what the fused steps left owing; never part of a checkpoint)
+
+    def selected(self):
+        """[(name, parameter)] the decay covers: get_l2_loss's rule"""
+        skip = self.no_reg_param_name
+        return [(n, p) for n, p in self.model.named_parameters() if p.dim() >= 2 and not (skip is not None and n.startswith(skip))]
+
+    @torch.no_grad()
+    def apply(self, lr: float):
+        if not self.weight_decay:
+            return
+        lr = float(lr)
+        if not lr * self.weight_decay < 1.0:
+            raise ValueError("DecoupledWeightDecay: lr %r x weight_decay %r is not below 1" % (lr, self.weight_decay))
+        if self._flush is not None:
+            self._flush()
+        for _, p in self.selected():
+            if p.grad is not None:
+                p.mul_(1 - lr * self.weight_decay)

@@ -177,10 +177,31 @@ def _ema_route(model, spec, l2_loss_fn):
     return None
 
 
-def _fused_step_spec(model, optimizer, l2_loss_fn, use_amp, ema=None):
+def _decay_route(model, spec, l2_loss_fn, decay, ema=None):
+    """why a step with decoupled weight decay keeps the torch route (DecoupledWeightDecay.apply() is dense and exact there), or None:
+    the fused step decays the batch's table rows and lets the others rest, so it applies where _ema_route's conditions hold — and,
+    when the decay reaches the tables, with neither a fused weight EMA (its rows' weights would change while they rest) nor an L2 term
+    on the tables"""
+    from ..optim_spec import regularises_tables
+    why = _ema_route(model, spec, l2_loss_fn)
+    if why is None and ema is not None and regularises_tables(decay.weight_decay, decay.no_reg_param_name):
+        why = "a weight EMA is kept beside the step and the decay reaches the embedding tables"
+    return why
+
+
+def _fused_step_spec(model, optimizer, l2_loss_fn, use_amp, ema=None, decay=None):
     """the OptimSpec of the fused engine step that stands in for this model's torch step (OptimSpec.for_step), or None: the torch route.
     ema: a WeightEMA (utils/optim.py) kept beside the step — the spec then carries its decay, and the answer is None wherever the
-    fused average is not exact (_ema_route)"""
+    fused average is not exact (_ema_route).  decay: a DecoupledWeightDecay (utils/optim.py) applied in front of the update — the
+    spec then carries its lambda as `dwd` and its no_reg_param_name, and the answer is None wherever the lazily paid decay is not
+    exact (_decay_route)"""
+    if decay is not None:
+        spec = _fused_step_spec(model, optimizer, l2_loss_fn, use_amp, ema)
+        if spec is None or _decay_route(model, spec, l2_loss_fn, decay, ema) is not None:
+            return None
+        if spec.wd and spec.no_reg != decay.no_reg_param_name:
+            return None  # (one notion of "regularised" per step: the L2 term and the decay share no_reg_param_name)
+        return spec._replace(dwd=float(decay.weight_decay), no_reg=decay.no_reg_param_name)
     if ema is not None:
         spec = _fused_step_spec(model, optimizer, l2_loss_fn, use_amp)
         if spec is None or _ema_route(model, spec, l2_loss_fn) is not None:
@@ -209,8 +230,25 @@ def _fused_step_spec(model, optimizer, l2_loss_fn, use_amp, ema=None):
     return spec
 
 
-def _fused_step_applies(model, optimizer, l2_loss_fn, use_amp, ema=None):
-    return _fused_step_spec(model, optimizer, l2_loss_fn, use_amp, ema) is not None
+def _fused_step_applies(model, optimizer, l2_loss_fn, use_amp, ema=None, decay=None):
+    return _fused_step_spec(model, optimizer, l2_loss_fn, use_amp, ema, decay) is not None
+
+
+def _announce_decay_route(model, optimizer, l2_loss_fn, use_amp, ema, decay, fused):
+    """one line per run: which route applies the decoupled weight decay, and why"""
+    if getattr(decay, "_route_announced", False):
+        return
+    decay._route_announced = True
+    if fused:
+        print("Decoupled weight decay (lambda {}): fused step, lazily decayed embedding rows.".format(decay.weight_decay))
+        return
+    spec = _fused_step_spec(model, optimizer, l2_loss_fn, use_amp, ema)
+    if spec is None:
+        why = "the fused step does not apply"
+    else:
+        why = _decay_route(model, spec, l2_loss_fn, decay, ema) or "the fused step was switched off"
+    print("Decoupled weight decay (lambda {}): torch route, dense DecoupledWeightDecay.apply() before every step ({}).".format(
+        decay.weight_decay, why))
 
 
 def _announce_ema_route(model, optimizer, l2_loss_fn, use_amp, ema, fused):
@@ -261,23 +299,34 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                              train_batch_size: int, gpu: Union[int, None], display_interval: int = 100, test_interval: int = 2000,
                              max_train_steps: int = -1, max_eval_steps: int = -1, test_only_at_last_step: bool = False,
                              grad_clip_value: float = None, tb_writer=None, use_amp: bool = False, use_engine_step: Optional[bool] = None,
-                             last_layer_step: bool = False, ema=None):
+                             last_layer_step: bool = False, ema=None, decay=None):
     """One epoch of training with tests in between; returns the reference's log dict (train_utils.py:181-390).
     `use_engine_step`: None = fused engine step whenever it applies, False = always the torch route.
     `last_layer_step`: a model in last-layer mode (set_mode_to_finelune_last_only) with a qualifying optimizer trains every full batch
     through SuperNet.engine_last_layer_step (_last_layer_step_applies); False (default) = as before.
     `ema`: a WeightEMA (utils/optim.py): every step that is taken updates it — inside the fused step where that is exact
-    (_fused_step_spec), by `ema.update()` otherwise — and the tests run on the averaged weights (`ema.averaged()`); None = no average."""
+    (_fused_step_spec), by `ema.update()` otherwise — and the tests run on the averaged weights (`ema.averaged()`); None = no average.
+    `decay`: a DecoupledWeightDecay (utils/optim.py): every step that is taken multiplies the selected parameters that have a gradient
+    by 1 - lr lambda in front of the optimizer's update — inside the fused step where the lazily paid decay is exact
+    (_fused_step_spec), by `decay.apply(lr)` otherwise; None = no decay."""
     _refuse_regularised_tables(optimizer, l2_loss_fn)
     _peek(test_loader)  # the reference peeks one test batch here (train_utils.py:224-225)
     model.train()
     logs = {k: [] for k in ("train_loss", "train_AUROC", "train_Accuracy", "test_loss", "test_AUROC", "test_Accuracy", "epoch", "iters")}
-    fused = _fused_step_applies(model, optimizer, l2_loss_fn, use_amp, ema) if use_engine_step is None else bool(use_engine_step)
+    if decay is not None and not decay.weight_decay:
+        decay = None  # (lambda = 0 is "no helper")
+    fused = _fused_step_applies(model, optimizer, l2_loss_fn, use_amp, ema, decay) if use_engine_step is None else bool(use_engine_step)
     if ema is not None:
         if fused and use_engine_step is not None and not _fused_step_applies(model, optimizer, l2_loss_fn, use_amp, ema):
             raise ValueError("use_engine_step=True with a weight EMA the fused step cannot keep exactly: leave use_engine_step=None")
         _announce_ema_route(model, optimizer, l2_loss_fn, use_amp, ema, fused)
-    last_only = bool(last_layer_step) and not fused and use_engine_step is not False and \
+    if decay is not None:
+        if fused and use_engine_step is not None and not _fused_step_applies(model, optimizer, l2_loss_fn, use_amp, ema, decay):
+            raise ValueError("use_engine_step=True with a decoupled weight decay the fused step cannot keep exactly: leave "
+                             "use_engine_step=None")
+        _announce_decay_route(model, optimizer, l2_loss_fn, use_amp, ema, decay, fused)
+    # (a decoupled decay keeps the last-layer fine-tune on the torch route: the fused last-layer step has none)
+    last_only = bool(last_layer_step) and not fused and use_engine_step is not False and decay is None and \
         _last_layer_step_applies(model, optimizer, l2_loss_fn, use_amp)
     bound = ema_bound = False
     scaler = torch.amp.GradScaler("cuda") if use_amp else None
@@ -302,6 +351,8 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
         else:
             opt_kw["eps"] = spec.eps
     step_kw = dict(opt_kw, ema_decay=float(ema.decay)) if (ema is not None and fused) else opt_kw
+    if decay is not None and fused:
+        step_kw = dict(step_kw, decoupled_wd=float(decay.weight_decay), no_reg_param_name=decay.no_reg_param_name)
     wd = spec.wd if spec is not None else 0.0
     for batch_num, (int_x, cat_x, y) in enumerate(_agreed_batches(train_loader, train_batch_size, world, gpu)):
         t_data1 = time.time()
@@ -333,6 +384,8 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                 if ema is not None:
                     model.engine_bind_ema(ema)
                     ema_bound = True
+            if decay is not None and decay._flush is None:  # (a torch-route apply() in the middle of the fused run flushes first)
+                model.engine_bind_decay(decay)
             group = optimizer.param_groups[0]
             loss = model.engine_train_step(int_x, cat_x, y.view(-1), lr=float(group["lr"]), clip=grad_clip_value, **step_kw)
             # the step's logits and the L2 term are only looked at on display steps: fetched there, not 3 900 times per epoch
@@ -361,6 +414,8 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                         torch.nn.utils.clip_grad_norm_(model.parameters(), grad_clip_value)
                     if hasattr(optimizer, "touch"):
                         optimizer.touch(cat_x)
+                    if decay is not None:
+                        decay.apply(float(optimizer.param_groups[0]["lr"]))
                     scale0 = scaler.get_scale() if ema is not None else None
                     scaler.step(optimizer)
                     scaler.update()
@@ -374,6 +429,8 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                         torch.nn.utils.clip_grad_norm_(model.parameters(), grad_clip_value)
                     if hasattr(optimizer, "touch"):  # (RowSparseAdam: the rows this batch touches)
                         optimizer.touch(cat_x)
+                    if decay is not None:
+                        decay.apply(float(optimizer.param_groups[0]["lr"]))
                     optimizer.step()
                     if ema is not None:
                         ema.update()
@@ -447,6 +504,8 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
         print("Batch counter total: {}".format(batch_num))
     if bound:
         model.engine_sync_optimizer_steps(optimizer)
+    if decay is not None and hasattr(model, "engine_flush_decay"):
+        model.engine_flush_decay()  # (every table row current: whoever reads the tables next needs no flush of their own)
     if ema_bound:
         model.engine_sync_ema(ema)
     del best_model  # the reference rebinds a local name to a copy of it: no observable effect

@@ -6,6 +6,9 @@ defaults; fused: lazily decayed rows, with --wd the tables left out too; its lin
 every row's square_avg current after the timed steps).  `--ema DECAY` keeps utils/optim.WeightEMA beside the step: inside the fused
 step (Adagrad, row-sparse Adam, RMSprop), by WeightEMA.update() on the torch route; the line then carries `ema`, `flush_ms` (the launch
 that brings every row's average current) and `swap_ms` (flush + exchange with the parameters: what entering `averaged()` costs).
+`--decoupled-wd LAMBDA` applies utils/optim.DecoupledWeightDecay in front of the update: inside the fused step (Adagrad, row-sparse Adam,
+RMSprop: the rows outside the batch pay lazily), by `apply(lr)` on the torch route; the line then carries `decoupled_wd` and
+`decay_flush_ms` (the launch that brings every table row current and re-bases the stamps).
 Prints one JSON line per measured (route, optimizer, wd):
 
     python tools/optim_step_bench.py --route fused --optimizer adam --wd 0     # the fused engine step
@@ -37,8 +40,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--B", type=int, default=256)
     ap.add_argument("--ema", type=float, default=0.0, help="decay of a weight average kept beside the step (0: none)")
+    ap.add_argument("--decoupled-wd", dest="decoupled_wd", type=float, default=0.0, help="lambda of a decoupled weight decay in front of the update (0: none)")
     ap.add_argument("--bytes", action="store_true")
-    ap.add_argument("--all", action="store_true", help="every route x optimizer x wd in {0, 1e-8}, one child process each")
+    ap.add_argument("--all", action="store_true", help="every route x optimizer x wd in {0, 1e-8}, then the fused lazy optimizers x "
+                                                       "decoupled lambda in {0, 1e-5}, one child process each")
     ap.add_argument("--timeout", type=int, default=600, help="--all: seconds per child")
     a = ap.parse_args()
     from nasrec_amd.utils.config import NUM_EMBEDDINGS_CRITEO
@@ -61,6 +66,15 @@ def main():
                         sys.stderr.write(r.stdout + r.stderr)
                         raise SystemExit("%s exited with %d" % (" ".join(cmd[2:]), r.returncode))
                     print(r.stdout.strip().splitlines()[-1], flush=True)
+        for opt in ("adagrad", "row-sparse-adam", "rmsprop"):
+            for lam in (0.0, 1e-5):
+                cmd = [sys.executable, os.path.abspath(__file__), "--route", "fused", "--optimizer", opt, "--decoupled-wd", str(lam),
+                       "--steps", str(a.steps), "--warmup", str(a.warmup), "--B", str(a.B)]
+                r = subprocess.run(cmd, timeout=a.timeout, capture_output=True, text=True)
+                if r.returncode != 0:
+                    sys.stderr.write(r.stdout + r.stderr)
+                    raise SystemExit("%s exited with %d" % (" ".join(cmd[2:]), r.returncode))
+                print(r.stdout.strip().splitlines()[-1], flush=True)
         return
 
     import torch
@@ -93,6 +107,13 @@ def main():
         if a.route == "fused":
             m.engine_bind_ema(ema)
             ema_kw = dict(ema_decay=a.ema)
+    decay = None
+    if a.decoupled_wd:
+        from nasrec_amd.utils.optim import DecoupledWeightDecay
+        decay = DecoupledWeightDecay(m, a.decoupled_wd, no_reg)
+        if a.route == "fused":
+            m.engine_bind_decay(decay)
+            ema_kw = dict(ema_kw, decoupled_wd=a.decoupled_wd)
 
     def step(i):
         int_x, cat_x, y = batches[i % len(batches)]
@@ -108,6 +129,8 @@ def main():
         torch.nn.utils.clip_grad_norm_(m.parameters(), 5.0)
         if hasattr(opt, "touch"):
             opt.touch(cat_x)
+        if decay is not None:
+            decay.apply(lr)
         opt.step()
         if ema is not None:
             ema.update()
@@ -125,6 +148,13 @@ def main():
     ms = e0.elapsed_time(e1) / a.steps
     wall_ms = (time.perf_counter() - t0) / a.steps * 1e3
     extra = {}
+    if decay is not None:
+        extra["decoupled_wd"] = a.decoupled_wd
+        if a.route == "fused":  # the flush: every row outside the timed batches pays the factors it rested through
+            wall = time.perf_counter()
+            m.engine_flush_decay()
+            torch.cuda.synchronize()
+            extra["decay_flush_ms"] = round((time.perf_counter() - wall) * 1e3, 4)
     if ema is not None:
         extra["ema"] = a.ema
         if a.route == "fused":
