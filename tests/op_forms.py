@@ -7,7 +7,9 @@ harvest() compiles launch plans on the host (made-up addresses stand in for the 
 nothing is launched) — the fixed sub-networks of nasrec_amd/configs, the full-path supernets of both search spaces, a SiLU supernet and sampled
 sub-paths — and returns one example descriptor per form.  tests/test_op_forms_cpu.py asks that every harvested form is the form of
 a kernel case (tests/wl_cases.py, tests/test_op_forms_gpu.py), so that a planner change that starts emitting a form no kernel test
-sets is noticed.
+sets is noticed.  NASREC_OP_GEMM has a form too (_gemm: kernel family, tile configuration or launcher branch, binding, segments,
+split-K class, the epilogue's predicates; 324 forms in the harvest); tests/test_gemm_forms_cpu.py holds the table of
+tests/gemm_cases.py against those.
 
 Plain Python: nothing here touches a GPU."""
 import glob
@@ -149,7 +151,134 @@ def _final(d):
             "batch_slices" if (bwd and d.nsplit > 0) else "no_slices", "rows16" if (bwd and d.B >= 1024) else "rows1")
 
 
-FORM_FN = {L.OP_MHA_FWD: _mha, L.OP_MHA_BWD: _mha, L.OP_FM_FWD: _fm, L.OP_FM_BWD: _fm, L.OP_DOT_TRI_FWD: _dot_tri, L.OP_DOT_TRI_BWD: _dot_tri,
+# ---- NASREC_OP_GEMM ----------------------------------------------------------------------------------------------------------------------
+GEMM_FAMILY = {L.GEMM_ROUTE_GENERAL: "general", L.GEMM_ROUTE_KSLICE: "kslice", L.GEMM_ROUTE_SKINNY_N: "skinny_n", L.GEMM_ROUTE_TINYK: "tinyk",
+               L.GEMM_ROUTE_TOKEN_LINEAR: "token_linear", L.GEMM_ROUTE_TOKEN_DW: "token_dw", L.GEMM_ROUTE_FAST: "fast"}
+_AM = {L.AM_KC: "KC", L.AM_RC: "RC", L.AM_TOKR: "TOKR", L.AM_TOKK: "TOKK"}
+_CM = {L.CM_PLAIN: "PLAIN", L.CM_TOKJ: "TOKJ"}
+_ACT = {L.ACT_NONE: "act_none", L.ACT_RELU: "relu", L.ACT_SILU: "silu", L.ACT_SIGMOID: "sigmoid"}
+_PRECISION = {L.PRECISION_HIGHEST: "highest", L.PRECISION_HIGH: "high", L.PRECISION_MEDIUM: "medium"}
+# the configurations of the general template (csrc/gemm.hip launch_general_t) x the bodies launch_ring picks between
+GENERAL_CONFIGS = ("big64x64", "mid64x64.deep", "mid64x64.shallow", "z32x32.deep", "64x16.deep", "64x16.shallow", "16x64.deep", "16x64.shallow")
+GENERAL_BODIES = ("ring", "ring_aux", "plain_template")
+
+
+def gemm_problems(d):
+    """the segments that are problems of their own: every segment of a zmode launch, seg[0] otherwise"""
+    return [d.seg[q] for q in range(d.nseg if d.zmode else 1)]
+
+
+def gemm_uniform(d):
+    """launch_ring's `uniform` (csrc/gemm.hip): the k-segments of one product agree on ones_col, Mvalid and on having mask operands"""
+    if d.zmode:
+        return True
+    s0 = d.seg[0]
+    for q in range(d.nseg):
+        s = d.seg[q]
+        if s.ones_col != s0.ones_col or s.Mvalid != s0.Mvalid:
+            return False
+        if s.A and (bool(s.Aaux) != bool(s0.Aaux) or bool(s.Baux) != bool(s0.Baux)):
+            return False
+    return True
+
+
+def general_config(d):
+    """-> (tile configuration, body) of the general template, as launch_general_t and launch_ring of csrc/gemm.hip decide: by the live
+    workgroups of a 64 x 64 tiling x split-K (>= 1024: the 256-thread 64 x 64 template; >= GEMM_SKINNY_BELOW = 128: 64 x 64 on 1024
+    threads, or 32 x 32 for a zmode batch of deep products; below: 64 x 16 strips when Nmax >= Mmax, else 16 x 64), by the deepest live
+    k-segment (> 32: "deep"), and — except for the first — ring / ring with mask operands / the plain template when the k-segments
+    disagree"""
+    probs = gemm_problems(d)
+    S = d.splitk if d.splitk > 1 else 1
+    wgs = sum(((s.M + 63) // 64) * ((s.N + 63) // 64) * S for s in probs)
+    deep = max([d.seg[q].K for q in range(d.nseg) if d.seg[q].A] + [0]) > 32
+    Mmax, Nmax = max(s.M for s in probs), max(s.N for s in probs)
+    if wgs >= 1024:
+        return "big64x64", "plain_template"
+    if wgs >= 128:
+        cfg = "z32x32.deep" if (d.zmode and len(probs) > 1 and deep) else ("mid64x64.deep" if deep else "mid64x64.shallow")
+    else:
+        cfg = ("64x16" if Nmax >= Mmax else "16x64") + (".deep" if deep else ".shallow")
+    if not gemm_uniform(d):
+        return cfg, "plain_template"
+    aux = any(d.seg[q].Aaux or d.seg[q].Baux for q in range(d.nseg))
+    return cfg, "ring_aux" if aux else "ring"
+
+
+def _fast_paths(d, probs, split):
+    """the ways through ft_epilogue (csrc/gemm_fast_common.h) the problems of a launch take: a split launch leaves the epilogue to the
+    common second pass; else acc_in_tile (ft_acc_init), the `plain` stores, the one-array path by what it reads, or the full path"""
+    if split.startswith("split"):
+        return ("second_pass",)
+    out = set()
+    for s in probs:
+        acc = bool(s.accumulate if d.zmode else d.beta)
+        mv = 0 < s.Mvalid < s.M
+        bare = not (d.bias or d.pre_add or d.save_z or d.save_act or d.act != L.ACT_NONE or d.mul_nseg > 0 or d.dims_in_use >= 0 or s.ones_col)
+        if bare and acc and not mv and split == "s1":
+            out.add("acc_in_tile")
+        elif bare and not acc:
+            out.add("plain")
+        elif s.ones_col:
+            out.add("full_ones")
+        else:
+            nread = (1 if d.mul_nseg > 0 else 0) + (1 if d.pre_add else 0) + (1 if acc else 0)
+            out.add("nread0" if nread == 0 else ("nread1" if nread == 1 else "full_nread2+"))
+    return tuple(sorted(out))
+
+
+def _gemm(d):
+    """One property per branch of the seven GEMM families' launchers and epilogues (csrc/gemm.hip, gemm_tile.h, gemm_ring.h,
+    gemm_fast_common.h, gemm_fast.hip, gemm_kslice.hip, gemm_skinny.hip, token_linear.hip, token_linear_common.h).  The family and the
+    kernel's name are the library's own answers (plan.gemm_route = nasrec_gemm_route, plan.gemm_kernel_name); the general template's
+    configuration restates launch_general_t / launch_ring (general_config above).  What no kernel branches on is left out: the value of
+    dims_in_use (a comparison per element), the shapes beyond what picks a configuration, the strides.  The precision is part of the
+    form; the harvest compiles at HIGHEST only — the bf16 bodies are held to their own error bound by tests/test_gemm_bf16_gpu.py and
+    tests/test_token_linear_bf16_gpu.py and have no case in tests/gemm_cases.py."""
+    route = P.gemm_route(d)[0]
+    family = GEMM_FAMILY.get(route, "rejected%d" % route)
+    kernel = P.gemm_kernel_name(d) if route >= 0 else "none"
+    probs = gemm_problems(d)
+    segs = [d.seg[q] for q in range(d.nseg)]
+    split = "balanced" if d.splitk == L.SPLITK_BALANCED else ("s1" if d.splitk <= 1 else ("split_deferred" if d.defer_second_pass else "split"))
+    Mmax, Nmax = max(s.M for s in probs), max(s.N for s in probs)
+    if route == L.GEMM_ROUTE_GENERAL:
+        cfg = ".".join(general_config(d))
+    elif route == L.GEMM_ROUTE_FAST:
+        cfg = ("ones_template" if any(s.ones_col for s in segs) else "no_ones_template") + "." + "+".join(_fast_paths(d, probs, split))
+    elif route == L.GEMM_ROUTE_SKINNY_N:
+        cfg = "4waves" if (probs[0].M + 15) // 16 >= 512 else "8waves"  # launch_gemm_skinny_n
+    elif route == L.GEMM_ROUTE_TINYK:  # gemm_tinyk_kernel's `simple`
+        simple = not (d.pre_add or d.mul_nseg > 0 or d.dims_in_use >= 0 or (d.bias and d.bias_on_rows) or any((s.accumulate if d.zmode else d.beta) for s in probs))
+        cfg = "simple" if simple else "col4"
+    elif route == L.GEMM_ROUTE_TOKEN_LINEAR:  # launch_token_linear: RB row blocks; the grid is shared out over the problems of a batch (z = blockIdx.x / wgs)
+        cfg = "rb%d.%s" % ((probs[0].M + 15) // 16, "batch" if len(probs) > 1 else "one_problem")
+    elif route == L.GEMM_ROUTE_TOKEN_DW:  # launch_token_dw: RB x CB blocks of 16
+        cfg = "rb%d.cb%d" % ((Mmax + 15) // 16, (Nmax + 15) // 16)
+    else:
+        cfg = "-"
+    accs = set(bool(s.accumulate if d.zmode else d.beta) for s in probs)
+    acc = "acc_mixed" if len(accs) > 1 else ("accumulate" if accs.pop() else "overwrite")
+    gate = "no_gate"
+    if d.mul_nseg > 0:
+        gap = not _covered(Nmax, [(d.mul_off[q], d.mul_width[q]) for q in range(d.mul_nseg)])
+        null = any(not d.mul_ptr[q] for q in range(d.mul_nseg))
+        gate = "gate_" + ("gap" if gap else "covering") + ("_null" if null else "")
+    ones = "no_ones"
+    if any(s.ones_col for s in segs):
+        own = set(bool(s.rowsum) for s in probs if s.ones_col)
+        ones = "ones_own_rowsum" if own == {True} else ("ones_rowsum_out" if own == {False} else "ones_both")
+    aux = "aux_" + (("A" if any(s.Aaux for s in segs) else "") + ("B" if any(s.Baux for s in segs) else "") or "none")
+    return (KIND_NAME[d.kind], family, kernel, cfg, "%s.%s.%s" % (_AM[d.amode], _AM[d.bmode], _CM[d.cmode]),
+            ("z" if d.zmode else "k") + ("1" if d.nseg == 1 else "N"), "uniform" if gemm_uniform(d) else "disagree", split, _ACT[d.act],
+            "no_bias" if not d.bias else ("bias_rows" if d.bias_on_rows else "bias_cols"),
+            "no_mask" if d.dims_in_use < 0 else ("mask_rows" if d.mask_on_rows else "mask_cols"), acc, "pre_add" if d.pre_add else "no_pre",
+            "save_z" if d.save_z else "no_z", "save_act" if d.save_act else "no_sact", gate, ones, aux,
+            "mvalid<M" if any(0 <= s.Mvalid < s.M for s in segs) else "mvalid=M", "null_A" if any(not s.A for s in segs) else "live_A",
+            _PRECISION.get(d.precision, "precision%d" % d.precision))
+
+
+FORM_FN = {L.OP_GEMM: _gemm, L.OP_MHA_FWD: _mha, L.OP_MHA_BWD: _mha, L.OP_FM_FWD: _fm, L.OP_FM_BWD: _fm, L.OP_DOT_TRI_FWD: _dot_tri, L.OP_DOT_TRI_BWD: _dot_tri,
            L.OP_GATE_BWD: _gate, L.OP_COPY_SEGS: _copy, L.OP_REDUCE_ROWS: _reduce, L.OP_ACT_BWD: _act_bwd, L.OP_ROWSUM: _rowsum,
            L.OP_MEMSET: _memset, L.OP_CONST_I64: _const_i64, L.OP_SCALE: _scale, L.OP_FINAL_FWD: _final, L.OP_FINAL_FUSED: _final,
            L.OP_FINAL_BWD: _final}

@@ -3,7 +3,8 @@
 tests/op_forms.py compiles launch plans on the host — the six fixed sub-networks of nasrec_amd/configs, the 7-block full-path supernets
 of both search spaces with LayerNorm, the same with SiLU and without LayerNorm, 24 sampled sub-paths, each at batch 256 and 2048, for
 training and for inference — and reduces every operator descriptor of the forward and backward programs to its form: the properties that
-select code or addressing in its kernel.  A kind is either EXEMPT below (another test file owns it, named there) or known to
+select code or addressing in its kernel (NASREC_OP_GEMM included: its cases are the table of tests/gemm_cases.py, and
+tests/test_gemm_forms_cpu.py carries the table of its forms).  A kind is either EXEMPT below (another test file owns it, named there) or known to
 op_forms.form_of; every harvested form of a known kind must be the form of a case of tests/wl_cases.py (which runs stand-alone, as a
 worklist item by value and resident, in mixed and in persistent launches: tests/test_worklist_items_gpu.py) or of the STANDALONE table
 of tests/test_op_forms_gpu.py.  Nothing is skipped and no list of tolerated gaps exists: a planner change that emits a new form fails
@@ -84,6 +85,7 @@ import os
 
 import pytest
 
+import gemm_cases
 import op_forms as F
 import test_op_forms_gpu as G
 import wl_cases as W
@@ -94,7 +96,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 # kinds whose kernels other test files hold to their own references: kind -> the file that owns it
 EXEMPT = {
-    L.OP_GEMM: "test_ops_gpu.py",  # (and test_gemm_*_gpu.py, test_token_linear_bf16_gpu.py, test_worklist_items_gpu.py by family)
     L.OP_LAYERNORM_FWD: "test_layernorm_kernel_gpu.py",
     L.OP_LAYERNORM_BWD: "test_layernorm_kernel_gpu.py",
     L.OP_WORKLIST: "test_worklist_items_gpu.py",
@@ -144,6 +145,8 @@ def case_forms():
         for d in fn("cpu").descs:
             if d.kind in F.FORM_FN:
                 out.setdefault(F.form_of(d), name)
+    for c in gemm_cases.CASES:  # (NASREC_OP_GEMM: tests/test_gemm_forms_cpu.py carries their table)
+        out.setdefault(c.form(), c.name)
     return out
 
 
@@ -226,7 +229,8 @@ def test_a_reduction_of_more_than_16_destinations_is_refused_as_an_item_by_the_d
 
 
 def coverage_table(forms, covered):
-    return ["  %-58s <- %s" % (show(f), covered[f]) for f in sorted(forms, key=show)]
+    """(without the NASREC_OP_GEMM forms: tests/test_gemm_forms_cpu.py holds their table against the same harvest)"""
+    return ["  %-58s <- %s" % (show(f), covered[f]) for f in sorted(forms, key=show) if f[0] != "gemm"]
 
 
 def test_the_table_in_this_modules_docstring_is_the_harvest(harvested, covered):
