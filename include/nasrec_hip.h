@@ -578,7 +578,21 @@ typedef struct nasrec_weight_decay_desc {
  *   phase 2 (flush; RMSprop only): every row of every table, in the tiles of tile_off (here over ALL tables; `bitmap` all zero, read
  *     only): n = step[table_step0 + f] - stamp; n > 0: v_row *= alpha^n as above and stamp = step.  Idempotent.  nblocks workgroups.
  * Refused (-1, nothing launched): stamps missing, momentum != 0, sparse_rows != 0, a table owning a tile in phase 1.
+ *
+ * table_algo = NASREC_TABLE_ALGO_ADAGRAD (algo = NASREC_OPTIM_ADAM only; table_algo, table_eps and table_lr_scale each took the slot of
+ * a padding word, which every caller of the earlier structure left zero = NASREC_TABLE_ALGO_SAME: the structure keeps its size and
+ * nasrec_abi_version() stays): the split optimizer — Adam on the dense chunks as above, torch.optim.Adagrad(lr * table_lr_scale, eps = table_eps) on
+ * the tables.  tv[f] holds table f's Adagrad accumulator `sum`; tm is never read or written.  A leader row with its id in range, g =
+ * its summed gradient * coef, tlr = lr * table_lr_scale (one fp32 product):
+ *   sum = sum + g^2;  p = p - tlr * (g / (sqrt(sum) + table_eps))
+ * A zero gradient changes neither (table_eps > 0), so the update is exactly row-sparse: no bit is marked and every other row keeps its
+ * bits in table and tv.  Steps are counted as with sparse_rows: by the workgroup of phase 0 that finishes last when n_zero == 0, else
+ * by phase 1, which runs with tile_off all zero.
+ * Refused (-1, nothing launched): table_algo != 0 with algo != NASREC_OPTIM_ADAM, with sparse_rows != 0, with table_eps <= 0, with
+ * reg_mask != 0 or a table owning a tile in phase 1; an unknown table_algo.
  * ---------------------------------------------------------------------------------------------- */
+#define NASREC_TABLE_ALGO_SAME 0    /* the tables take `algo` */
+#define NASREC_TABLE_ALGO_ADAGRAD 1 /* Adagrad on the tables (above) */
 typedef struct nasrec_opt_moments_desc {
   int32_t kind;  /* NASREC_OP_OPT_MOMENTS */
   int32_t phase; /* 0 / 1 (above); 2 = RMSprop's flush */
@@ -589,7 +603,8 @@ typedef struct nasrec_opt_moments_desc {
   int32_t B, Fs;        /* [B, Fs] id / leader arrays (B = 0: no touched rows) */
   int32_t table_step0;
   uint32_t reg_mask;    /* bit f: table f is regularised (phase 1's g = 2 wd W) */
-  float eps, momentum, wd, _pad;
+  float eps, momentum, wd;
+  float table_eps;      /* NASREC_TABLE_ALGO_ADAGRAD: Adagrad's eps on the tables, > 0 (the slot of a padding word) */
   double beta1, beta2;
   nasrec_clip_coef_desc_t clip;
   const int64_t* chunks; /* [nchunks, 3] */
@@ -619,10 +634,11 @@ typedef struct nasrec_opt_moments_desc {
   const float* lr;       /* device scalars */
   const float* coef;     /* phase 1: clip.out of phase 0 */
   int32_t rank_B;        /* layout of `gsum` (phase 0) as in nasrec_adagrad_rows_desc_t: 0 = contiguous [B,Fs,16]; > 0 = rank_B */
-  int32_t _pad2;         /*   samples per rank chunk of an all-gather's receive buffer, chunks rank_stride floats apart */
+  float table_lr_scale;  /*   samples per rank chunk of an all-gather's receive buffer, chunks rank_stride floats apart.  table_lr_scale
+                          *   (the slot of a padding word): NASREC_TABLE_ALGO_ADAGRAD: the tables' learning rate as a multiple of *lr */
   int64_t rank_stride;
   int32_t sparse_rows;   /* 0 = every table row moves every step; != 0 = row-sparse Adam (above) */
-  int32_t _pad3;
+  int32_t table_algo;    /* NASREC_TABLE_ALGO_SAME / NASREC_TABLE_ALGO_ADAGRAD (above; the slot of a padding word) */
 } nasrec_opt_moments_desc_t;
 
 /* ------------------------------------------------------------------------------------------------

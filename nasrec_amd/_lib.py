@@ -40,6 +40,7 @@ OP_WEIGHT_DECAY = 39
 OP_OPT_MOMENTS = 40
 OP_LAST_LAYER_STEP = 41
 OPTIM_ADAGRAD, OPTIM_ADAM, OPTIM_SGD, OPTIM_RMSPROP = 0, 1, 2, 3  # NASREC_OPTIM_* (algorithm of NASREC_OP_OPT_MOMENTS / _LAST_LAYER_STEP)
+TABLE_ALGO_SAME, TABLE_ALGO_ADAGRAD = 0, 1  # NASREC_TABLE_ALGO_* (nasrec_opt_moments_desc_t.table_algo: the split optimizer)
 LAST_LAYER_MAX = 8192  # NASREC_LAST_LAYER_MAX: K + 1 of NASREC_OP_LAST_LAYER_STEP
 OP_ROC_AUC = 42
 OP_WEIGHT_EMA = 43
@@ -279,14 +280,16 @@ class WeightDecayDesc(C.Structure):
 
 
 class OptMomentsDesc(C.Structure):
+    # (the split optimizer's table_eps / table_lr_scale / table_algo sit in what were the padding words _pad / _pad2 / _pad3)
     # (OPTIM_RMSPROP keeps no first moment: the slots of `tm` carry its per-row stamps, `stamp` in the header's union, and beta2 its alpha)
     _fields_ = [("kind", i32), ("phase", i32), ("algo", i32), ("nesterov", i32), ("dense_blocks", i32), ("nblocks", i32), ("B", i32),
-                ("Fs", i32), ("table_step0", i32), ("reg_mask", C.c_uint32), ("eps", f32), ("momentum", f32), ("wd", f32), ("_pad", f32),
+                ("Fs", i32), ("table_step0", i32), ("reg_mask", C.c_uint32), ("eps", f32), ("momentum", f32), ("wd", f32), ("table_eps", f32),
                 ("beta1", C.c_double), ("beta2", C.c_double), ("clip", ClipCoefDesc), ("chunks", vp), ("nchunks", i64), ("p", vp),
                 ("g", vp), ("m", vp), ("v", vp), ("idx", vp), ("leader", vp), ("gsum", vp), ("table", vp * MAX_TABLES),
                 ("tm", vp * MAX_TABLES), ("tv", vp * MAX_TABLES), ("rows", i64 * MAX_TABLES), ("tile_off", i64 * (MAX_TABLES + 1)),
                 ("bitmap", vp), ("step", vp), ("inc", vp), ("n_inc", i64), ("zero_chunks", vp), ("n_zero", i64), ("counter", vp),
-                ("lr", vp), ("coef", vp), ("rank_B", i32), ("_pad2", i32), ("rank_stride", i64), ("sparse_rows", i32), ("_pad3", i32)]
+                ("lr", vp), ("coef", vp), ("rank_B", i32), ("table_lr_scale", f32), ("rank_stride", i64), ("sparse_rows", i32),
+                ("table_algo", i32)]
 
 
 class LastLayerStepDesc(C.Structure):

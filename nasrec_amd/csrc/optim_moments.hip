@@ -4,7 +4,7 @@
 // (a zero gradient still moves a row whose moments are non-zero: W and its one or two moment arrays, read and written once) and,
 // in the workgroup that finishes last, counts the step of every parameter it updated.
 // Phase 0 is one kernel, opt_moments_phase0_kernel<Rows>; what happens to one touched row, and whether the launch marks the bitmap or
-// counts the steps itself, is the row policy `Rows` (DenseRows, SparseAdamRows, LazyRmspropRows below).
+// counts the steps itself, is the row policy `Rows` (DenseRows, SparseAdamRows, LazyRmspropRows, AdagradTableRows below).
 // Row-sparse Adam (sparse_rows, include/nasrec_hip.h): the same clip and dense chunks, torch.optim.SparseAdam on the touched rows, no
 // bitmap, and no phase 1 unless weight decay has gradients to restore.
 // RMSprop (NASREC_OPTIM_RMSPROP: momentum 0, not centered): a row whose gradient is zero does not move and its square_avg only decays,
@@ -166,6 +166,30 @@ struct LazyRmspropRows {
   }
 };
 
+// The split optimizer (table_algo = NASREC_TABLE_ALGO_ADAGRAD; Adam on the dense chunks): a touched row takes torch.optim.Adagrad's
+// update with its summed gradient, at the tables' own learning rate lr * table_lr_scale and eps; tv holds the accumulator `sum`, tm is
+// never read or written, no bit is marked.  A zero gradient leaves sum and W as they are (table_eps > 0: the quotient is an exact zero),
+// so every row outside the batch AND a touched row whose gradient sums to zero keep their bits: exact, nothing is owed.
+struct AdagradTableRows {
+  static constexpr int DENSE = NASREC_OPTIM_ADAM;
+  static constexpr bool COUNTS = true;
+  __device__ __forceinline__ void scalars(const nasrec_opt_moments_desc_t&, float) {}
+  __device__ __forceinline__ void row(const nasrec_opt_moments_desc_t& d, int f, long row, int q, const f32x4& g4, float lr) const {
+    const long o = row * 16 + q * 4;
+    const float tlr = lr * d.table_lr_scale;
+    f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o), s4 = *reinterpret_cast<const f32x4*>(d.tv[f] + o);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float pe = p4[e], se = s4[e];
+      adagrad_elem(g4[e], se, pe, tlr, d.table_eps);
+      p4[e] = pe;
+      s4[e] = se;
+    }
+    *reinterpret_cast<f32x4*>(d.table[f] + o) = p4;
+    *reinterpret_cast<f32x4*>(d.tv[f] + o) = s4;
+  }
+};
+
 template <class Rows>
 __global__ __launch_bounds__(256) void opt_moments_phase0_kernel(const nasrec_opt_moments_desc_t d) {
   __shared__ float sh_coef;
@@ -281,12 +305,21 @@ void launch_phase1(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
 }  // namespace
 
 // Every refusal comes before anything is launched.  The row form — dense (every row moves: bitmap + phase 1), row-sparse Adam, lazy
-// RMSprop — decides what a launch needs; the two lazy forms move the batch's rows only, so their phase 0 counts the steps unless
-// zero_chunks call for a phase 1, which then owns no tile.  Phase 2 is RMSprop's flush.
+// RMSprop, Adagrad on the tables — decides what a launch needs; the last three move the batch's rows only, so their phase 0 counts the
+// steps unless zero_chunks call for a phase 1, which then owns no tile.  Phase 2 is RMSprop's flush.
 int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
   if (d->Fs < 0 || d->Fs > NASREC_MAX_TABLES) return nasrec_set_error(-1, "opt_moments: Fs = %d", d->Fs);
   if (!d->lr || !d->step) return nasrec_set_error(-1, "opt_moments: lr / step missing");
-  const bool adam = d->algo == NASREC_OPTIM_ADAM, rmsprop = d->algo == NASREC_OPTIM_RMSPROP, lazy = rmsprop || d->sparse_rows;
+  const bool adam = d->algo == NASREC_OPTIM_ADAM, rmsprop = d->algo == NASREC_OPTIM_RMSPROP;
+  const bool split = d->table_algo == NASREC_TABLE_ALGO_ADAGRAD, lazy = rmsprop || d->sparse_rows || split;
+  if (d->table_algo != NASREC_TABLE_ALGO_SAME && !split) return nasrec_set_error(-1, "opt_moments: table_algo %d", d->table_algo);
+  if (split && !adam) return nasrec_set_error(-1, "opt_moments: table_algo (Adagrad on the tables) goes with Adam on the rest (algo %d)", d->algo);
+  if (split && d->sparse_rows) return nasrec_set_error(-1, "opt_moments: table_algo with sparse_rows: the tables take one rule");
+  if (split && !(d->table_eps > 0.f))
+    return nasrec_set_error(-1, "opt_moments: table_eps %g must be positive (a zero gradient must leave its row alone)", (double)d->table_eps);
+  if (split && d->reg_mask != 0u)
+    return nasrec_set_error(-1, "opt_moments: table_algo with reg_mask %u: a regularised table moves in every row", d->reg_mask);
+  const char* lazy_name = rmsprop ? "RMSprop" : split ? "table_algo" : "sparse_rows";
   if (rmsprop && d->momentum != 0.f) return nasrec_set_error(-1, "opt_moments: RMSprop with momentum %g moves untouched rows", (double)d->momentum);
   if (d->sparse_rows && !adam) return nasrec_set_error(-1, "opt_moments: sparse_rows is row-sparse Adam (algo %d)", d->algo);
   if (!adam && !rmsprop && d->algo != NASREC_OPTIM_SGD) return nasrec_set_error(-1, "opt_moments: algo %d", d->algo);
@@ -298,11 +331,14 @@ int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
     const int nrows = (int)((threads + 255) / 256), nblk = d->dense_blocks + nrows;
     if (d->dense_blocks < 0 || nblk < 1) return nasrec_set_error(-2, "opt_moments: empty launch");
     if (nrows > 0 && (!d->idx || !d->leader || !d->gsum || (!d->bitmap && !lazy))) return nasrec_set_error(-1, "opt_moments: row inputs missing");
+    for (int f = 0; split && nrows > 0 && f < d->Fs; ++f)
+      if (!d->table[f] || !d->tv[f]) return nasrec_set_error(-1, "opt_moments: table_algo without the weights / accumulator (tv) of table %d", f);
     if (d->rank_B < 0 || (d->rank_B > 0 && (d->rank_stride < (int64_t)d->rank_B * d->Fs * 16 || d->B % d->rank_B != 0)))
       return nasrec_set_error(-2, "opt_moments: rank layout %d / %ld", d->rank_B, (long)d->rank_stride);
     if (lazy && d->n_zero <= 0 && (!d->counter || (d->n_inc > 0 && !d->inc)))
-      return nasrec_set_error(-1, "opt_moments: %s without zero_chunks counts the steps: counter / inc missing", rmsprop ? "RMSprop" : "sparse_rows");
+      return nasrec_set_error(-1, "opt_moments: %s without zero_chunks counts the steps: counter / inc missing", lazy_name);
     if (rmsprop) launch_phase0<LazyRmspropRows>(st, d, nblk);
+    else if (split) launch_phase0<AdagradTableRows>(st, d, nblk);
     else if (d->sparse_rows) launch_phase0<SparseAdamRows>(st, d, nblk);
     else if (adam) launch_phase0<DenseRows<NASREC_OPTIM_ADAM>>(st, d, nblk);
     else launch_phase0<DenseRows<NASREC_OPTIM_SGD>>(st, d, nblk);
@@ -310,7 +346,7 @@ int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
     if (d->nblocks <= 0) return nasrec_set_error(-1, "opt_moments: nblocks must be positive");
     if (!d->bitmap || !d->counter || !d->coef) return nasrec_set_error(-1, "opt_moments: phase 1 inputs missing");
     if (lazy && (d->n_zero <= 0 || d->tile_off[d->Fs] != 0))
-      return nasrec_set_error(-1, "opt_moments: %s has a phase 1 only to restore zero_chunks, and no table owns a tile", rmsprop ? "RMSprop" : "sparse_rows");
+      return nasrec_set_error(-1, "opt_moments: %s has a phase 1 only to restore zero_chunks, and no table owns a tile", lazy_name);
     if (rmsprop) launch_phase1<NASREC_OPTIM_RMSPROP>(st, d);
     else if (adam) launch_phase1<NASREC_OPTIM_ADAM>(st, d);
     else launch_phase1<NASREC_OPTIM_SGD>(st, d);

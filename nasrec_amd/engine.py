@@ -526,7 +526,7 @@ class SupernetEngine:
             cp.fwd_levels = cp.bwd_levels = None
             cp.dead_forward = []
             if train:  # (the backward program decides which forward results are read: built further down, before the packing)
-                if not spec.moments:  # (Adagrad's table state: Adam / SGD keep theirs in `moments` instead)
+                if not spec.moments or spec.table_kind:  # (Adagrad's table state: Adam / SGD keep theirs in `moments` instead)
                     self._ensure_table_state()
                 self._build_training_tail(cp, ctx, w, bptr, fsegs, B, K, grad_scale)
             fwd_list = list(ctx.fwd)
@@ -836,9 +836,11 @@ class SupernetEngine:
             setattr(self, name, t)
         return t
 
-    def ensure_moments_state(self, kind: str):
+    def ensure_moments_state(self, kind: str, tables: bool = True):
         """Adam's exp_avg / exp_avg_sq or SGD's momentum_buffer for the dense arena (flat, the layout of flat_p) and for every table,
         allocated on first use, zero; and the per-parameter step counters (dense parameters in dense_names order, then the tables).
+        tables = False (the split optimizer, OptimSpec.table_kind): the dense arena's arrays only — the tables' state is Adagrad's
+        `table_state`, and no moment array the size of a table is allocated ([] until a plan that needs them asks).
         "rmsprop": square_avg, and `lazy_stamps` — per table one int32 per row, the table's step count at which that row's square_avg
         is current (csrc/optim_moments.hip); engine-private, never part of optimizer.state.
         -> {state key: (flat arena, [table arrays])}"""
@@ -847,7 +849,9 @@ class SupernetEngine:
         with torch.cuda.stream(self.stream):
             for k in keys:
                 if k not in st:
-                    st[k] = (torch.zeros(self.flat_numel, dtype=torch.float32, device=self.device), [torch.zeros_like(t) for t in self.tables])
+                    st[k] = (torch.zeros(self.flat_numel, dtype=torch.float32, device=self.device), [])
+                if tables and not st[k][1]:
+                    st[k][1].extend(torch.zeros_like(t) for t in self.tables)
             if kind == "rmsprop" and getattr(self, "lazy_stamps", None) is None:
                 self.lazy_stamps = [torch.zeros(n, dtype=torch.int32, device=self.device) for n in self.num_embeddings]
             if getattr(self, "opt_steps", None) is None:
@@ -863,6 +867,9 @@ class SupernetEngine:
         """engine storage of moment `key` of parameter `name` (shape of the parameter)"""
         flat, tabs = self.moments[key]
         if name.startswith("_embedding."):
+            if not tabs:
+                raise L.EngineError("no %s of %s: with Adagrad on the tables (OptimSpec.table_kind) their state is table_state, "
+                                    "Adagrad's sum" % (key, name))
             return tabs[int(name.split(".")[1])]
         o, n = self.offsets[name], self.params[name].numel()
         return flat[o:o + n].view(self.params[name].shape)
@@ -920,7 +927,10 @@ class SupernetEngine:
         if spec.sparse_rows and spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
             raise L.EngineError("row-sparse Adam with a regularised table: the L2 term puts a gradient on every row; leave the tables out "
                                 "(no_reg_param_name='_embedding') or use weight_decay=0")
-        self.ensure_moments_state(spec.kind)
+        if spec.table_kind and spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
+            raise L.EngineError("Adagrad on the tables with a regularised table: the L2 term puts a gradient on every row; leave the "
+                                "tables out (no_reg_param_name='_embedding') or use weight_decay=0")
+        self.ensure_moments_state(spec.kind, tables=not spec.table_kind)
         names = [n for n in list(ctx.grad_params) + ["_final.weight", "_final.bias"] if not n.startswith("_embedding.")]
         if spec.wd:
             names += P.regularised(self.shapes, spec.no_reg)[0]
@@ -943,6 +953,8 @@ class SupernetEngine:
     @staticmethod
     def _optim_scalars(d, spec):
         """algo and hyperparameters of an Adam / SGD spec on an OptMomentsDesc or a LastLayerStepDesc"""
+        if spec.table_kind not in ("", "adagrad") or (spec.table_kind and spec.kind != "adam"):
+            raise L.EngineError("table_kind %r with %s: the split optimizer is Adam with Adagrad on the tables" % (spec.table_kind, spec.kind))
         d.algo = {"adam": L.OPTIM_ADAM, "rmsprop": L.OPTIM_RMSPROP}.get(spec.kind, L.OPTIM_SGD)
         d.eps, d.momentum, d.nesterov = spec.eps, spec.momentum, int(bool(spec.nesterov))
         d.beta1, d.beta2 = spec.beta1, (spec.alpha if spec.kind == "rmsprop" else spec.beta2)  # (RMSprop's alpha travels in beta2)
@@ -953,15 +965,19 @@ class SupernetEngine:
         Row-sparse Adam: no table owns a tile, and phase 1 is None unless weight decay left unreached ranges of g to restore — phase 0
         then counts the steps itself; with them phase 1 runs in its no-table-moves form on all its workgroups (the ranges of a supernet
         are millions of floats).  RMSprop: the same shape of launches (its rows rest too, owing only a decay); m is unused and the
-        slots of `tm` carry the stamps."""
+        slots of `tm` carry the stamps.  Adagrad on the tables (spec.table_kind): the same shape again; tv carries `table_state`, tm
+        nothing, and the tables' learning rate is lr * table_lr_scale in the kernel."""
         spec = t.spec
         st = self.moments
-        lazy = spec.sparse_rows or spec.kind == "rmsprop"  # (the tables move in the batch's rows only)
+        lazy = spec.rows_only  # (the tables move in the batch's rows only)
+        split = spec.table_kind == "adagrad"
         m = L.OptMomentsDesc()
         m.kind, m.phase = L.OP_OPT_MOMENTS, 0
         self._optim_scalars(m, spec)
         m.dense_blocks = min(2048, t.mom_chunks[1])
         m.sparse_rows = int(bool(spec.sparse_rows))
+        if split:
+            m.table_algo, m.table_eps, m.table_lr_scale = L.TABLE_ALGO_ADAGRAD, spec.table_eps, spec.table_lr_scale
         m.nblocks = self.WD_BLOCKS if (t.mom_tables or lazy) else 1  # (no table moves: phase 1 only counts the step and restores g)
         m.B, m.Fs = (Bg, self.Fs) if gsum is not None else (0, self.Fs)
         m.table_step0 = len(self.dense_names)
@@ -982,6 +998,9 @@ class SupernetEngine:
                 m.rank_B, m.rank_stride = rank_layout
         self._tile_layout(m, lambda f: f in t.mom_tables and not lazy)  # (a table that does not move owns no tile)
         for f in range(self.Fs):
+            if split:  # (Adagrad's accumulators; the kernel never looks at tm)
+                m.tv[f] = self.table_state[f].data_ptr()
+                continue
             m.tm[f] = first[1][f].data_ptr()
             if second is not None:
                 m.tv[f] = second[1][f].data_ptr()
@@ -1566,8 +1585,8 @@ class SupernetEngine:
         reaches and EVERY table row, state in `moments` and `opt_steps` (ensure_moments_state); with sparse_rows the tables move in the
         batch's rows only (utils/optim.RowSparseAdam), and weight decay must leave them out.
         ema: the decay of a weight average kept beside the step (ensure_ema_state; csrc/weight_ema.hip): two more launches in the
-        optimizer tail, exact only where the tables move in the batch's rows alone (Adagrad, row-sparse Adam, RMSprop; no regularised
-        table) — refused otherwise.
+        optimizer tail, exact only where the tables move in the batch's rows alone (OptimSpec.rows_only: Adagrad, row-sparse Adam,
+        RMSprop, Adam with Adagrad on the tables; no regularised table) — refused otherwise.
         decoupled_wd: lambda of the decoupled weight decay p <- p (1 - lr lambda) in front of the update (utils/optim.
         DecoupledWeightDecay; csrc/decoupled_decay.hip) over the parameters get_l2_loss's rule selects (no_reg_param_name) and the
         step reaches: two more launches, the table rows outside the batch rest and owe — a raw read of a table needs
@@ -1575,13 +1594,13 @@ class SupernetEngine:
         weight average or an L2 term on them."""
         self._refuse_swapped("train_step")
         if decoupled_wd:
-            if optim is not None and optim.kind in ("adam", "sgd") and not optim.sparse_rows:
+            if optim is not None and not optim.rows_only:
                 raise L.EngineError("the fused decoupled weight decay lets the table rows outside the batch rest: dense Adam and "
                                     "momentum SGD move every row (DecoupledWeightDecay.apply() on the torch route is the dense form)")
             if P.regularised(self.shapes, no_reg_param_name)[1] and (ema or weight_decay):
                 raise L.EngineError("a decoupled weight decay that reaches the embedding tables runs beside neither a fused weight "
                                     "EMA nor an L2 term on the tables (DecoupledWeightDecay.apply() on the torch route is the dense form)")
-        if ema and ((optim is not None and optim.kind in ("adam", "sgd") and not optim.sparse_rows)
+        if ema and ((optim is not None and not optim.rows_only)
                     or (weight_decay and P.regularised(self.shapes, no_reg_param_name)[1])):
             raise L.EngineError("the fused weight EMA averages the batch's table rows only: dense Adam, momentum SGD and a regularised "
                                 "table move every row (WeightEMA.update() on the torch route is the dense form)")
@@ -1706,6 +1725,8 @@ class SupernetEngine:
             raise L.EngineError("the last-layer step needs the embedding tables on the device")
         if optim is not None and optim.kind == "rmsprop":
             raise L.EngineError("the last-layer step has no RMSprop: the fine-tune keeps the torch route with it")
+        if optim is not None and optim.table_kind:
+            raise L.EngineError("the last-layer step has no split optimizer: the fine-tune keeps the torch route with it")
         B = int(int_x.shape[0])
         cp = self.compile(choice, B, train=True)
         self.last_layer_plan = cp  # (its logits: SuperNet.engine_last_logits)

@@ -43,7 +43,7 @@ def train_and_eval_one_model(model, args):
         raise NotImplementedError("Loss function {} is not implemented!".format(args.loss_function))
     loss_fn = torch.nn.BCEWithLogitsLoss()
     model.apply(init_weights)
-    optimizer = build_optimizer(args.optimizer, model, args.learning_rate)
+    optimizer = build_optimizer(args.optimizer, model, args.learning_rate, args.table_lr_scale, args.table_eps)
     steps_per_epoch = args.train_limit // args.train_batch_size
     # (the warm-up shrinks with the number of epochs here — :134 — unlike main_train.py)
     lr_scheduler = build_lr_scheduler(args.lr_schedule, optimizer, steps_per_epoch * args.num_epochs, steps_per_epoch // 10 // args.num_epochs,
@@ -122,7 +122,12 @@ def build_parser():
     p.add_argument("--choice_from_pickle_file", type=str, default=None,
                    help="Pre-sampled cached choices from a pickle file; the number of records overrides 'num_subnets'.")
     p.add_argument("--no-reg-param-name", type=str, default=None, help="Name of the parameters that do not need to be regularized.")
-    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rmsprop"])
+    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rmsprop", "adam-adagrad-tables"])
+    p.add_argument("--table-lr-scale", dest="table_lr_scale", type=float, default=1.0,
+                   help="--optimizer adam-adagrad-tables: the embedding tables' learning rate as a multiple of --learning_rate "
+                        "(Adam's 1e-3 with 160 gives the tables 0.16)")
+    p.add_argument("--table-eps", dest="table_eps", type=float, default=1e-2,
+                   help="--optimizer adam-adagrad-tables: eps of the tables' Adagrad (> 0)")
     p.add_argument("--loss_function", type=str, default="bce", choices=["bce"])
     p.add_argument("--gpu", type=int, default=0, help="GPU ID to use.")
     p.add_argument("--matmul-precision", dest="matmul_precision", type=str, default="highest", choices=["highest", "high", "medium"],

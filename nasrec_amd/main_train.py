@@ -43,10 +43,11 @@ def summary_writer(logging_dir):
         return None
 
 
-def build_optimizer(name, model, lr):
+def build_optimizer(name, model, lr, table_lr_scale=1.0, table_eps=1e-2):
     """main_train.py:150-160 (Adagrad eps 1e-2; Adam eps 1e-8; SGD nesterov momentum 0.9); row-sparse-adam: Adam's lr and eps, the
     tables moving in the batch's rows only (utils/optim.RowSparseAdam); rmsprop: torch's defaults (alpha 0.99, eps 1e-8) as
-    utils/optim.LazyRMSprop, which is torch.optim.RMSprop and the type the fused step takes"""
+    utils/optim.LazyRMSprop, which is torch.optim.RMSprop and the type the fused step takes; adam-adagrad-tables: Adam's lr and eps
+    on the dense parameters, Adagrad with lr * table_lr_scale and table_eps on the tables (utils/optim.AdamAdagradTables)"""
     if name == "adagrad":
         return torch.optim.Adagrad(model.parameters(), lr=lr, eps=1e-2)
     if name == "adam":
@@ -59,6 +60,10 @@ def build_optimizer(name, model, lr):
             raise ValueError("--optimizer row-sparse-adam needs whole tables: a row-sharded table holds one rank's rows under local ids; "
                              "use --optimizer adam with --table-sharding row")
         return RowSparseAdam(model.parameters(), list(model._embedding.parameters()), lr=lr, eps=1e-8)
+    if name == "adam-adagrad-tables":
+        from nasrec_amd.utils.optim import AdamAdagradTables
+        return AdamAdagradTables(model.parameters(), list(model._embedding.parameters()), lr=lr, eps=1e-8, table_lr_scale=table_lr_scale,
+                                 table_eps=table_eps)
     if name == "rmsprop":
         from nasrec_amd.utils.optim import LazyRMSprop
         return LazyRMSprop(model.parameters(), lr=lr)
@@ -88,7 +93,7 @@ def train_and_eval_one_model(model, args):
 
     l2_loss_fn = L2Loss(args.wd, args.no_reg_param_name, gpu=args.gpu)  # (a spec the fused engine step folds in: any --wd)
 
-    optimizer = build_optimizer(args.optimizer, model, args.learning_rate)
+    optimizer = build_optimizer(args.optimizer, model, args.learning_rate, args.table_lr_scale, args.table_eps)
     steps_per_epoch = args.train_limit // args.train_batch_size
     num_train_steps = steps_per_epoch * args.num_epochs
     num_warmup_steps = steps_per_epoch // 10 // args.num_epochs
@@ -187,7 +192,12 @@ def build_parser():
                    help="Data split for validation (evaluation). Can be one of ['val', 'test']")
     p.add_argument("--train_batch_size", type=int, default=200, help="Training batch size.")
     p.add_argument("--test_batch_size", type=int, default=16368, help="Testing batch size.")
-    p.add_argument("--optimizer", type=str, default="adagrad", help="Optimizer", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rmsprop", "ds-optimizer"])
+    p.add_argument("--optimizer", type=str, default="adagrad", help="Optimizer", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rmsprop", "adam-adagrad-tables", "ds-optimizer"])
+    p.add_argument("--table-lr-scale", dest="table_lr_scale", type=float, default=1.0,
+                   help="--optimizer adam-adagrad-tables: the embedding tables' learning rate as a multiple of --learning_rate "
+                        "(Adam's 1e-3 with 160 gives the tables 0.16)")
+    p.add_argument("--table-eps", dest="table_eps", type=float, default=1e-2,
+                   help="--optimizer adam-adagrad-tables: eps of the tables' Adagrad (> 0)")
     # Criteo: train 36672495 / val 4584061 / test 4584061 / trainval 41256556; Avazu: 32343175 / 4042896 / 4042896 / 36386071;
     # KDD: 119711284 / 14963910 / 14963910 / 134675194
     p.add_argument("--train_limit", type=int, default=41256556, help="Maximum number of training examples.")
@@ -203,12 +213,12 @@ def build_parser():
                    help="EMA strength in [0, 1); 0.9 / 0.99 / ... is recommended, 0 = off.  Keeps an exponential moving average of every "
                         "weight, s += (1 - ema) (w - s) after every optimizer step (utils/optim.WeightEMA); the tests run on the averaged "
                         "weights and the checkpoint carries them as ema_state_dict.  Inside the fused step with --optimizer adagrad / "
-                        "row-sparse-adam / rmsprop and no weight decay on the tables, on the torch route otherwise")
+                        "row-sparse-adam / rmsprop / adam-adagrad-tables and no weight decay on the tables, on the torch route otherwise")
     p.add_argument("--decoupled-wd", dest="decoupled_wd", type=_decoupled_wd, default=0.0,
                    help="decoupled weight decay (the W of AdamW), 0 = off: before every optimizer step w *= 1 - lr * LAMBDA on the "
                         "parameters --wd would regularise (>= 2 dimensions, --no-reg-param-name left out) that have a gradient "
                         "(utils/optim.DecoupledWeightDecay).  Independent of --wd.  Inside the fused step with --optimizer adagrad / "
-                        "row-sparse-adam / rmsprop (embedding rows outside the batch pay lazily), on the torch route otherwise")
+                        "row-sparse-adam / rmsprop / adam-adagrad-tables (embedding rows outside the batch pay lazily), on the torch route otherwise")
     p.add_argument("--gpu", type=int, default=None, help="GPU ID to use.")
     # not a reference flag: placement of the embedding tables under torchrun (nasrec_amd/sharded_tables.py)
     p.add_argument("--table-sharding", dest="table_sharding", type=str, default="none", choices=["none", "row"],

@@ -166,9 +166,12 @@ class RowShardedTables:
             tot += (g * g).sum()
         return tot
 
-    def whole_table(self, f: int, which: str = "tables") -> torch.Tensor:
-        """all-gather of table f (which = "tables"), or of its Adagrad accumulator ("state") — tests / checkpoints; a collective"""
+    def whole_table(self, f: int, which: str = "tables", shard: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """all-gather of table f (which = "tables"), or of its Adagrad accumulator ("state") — tests / checkpoints; a collective.
+        shard: this rank's rows of some other per-row array of table f (an optimizer's own state) to gather instead"""
         src = self.tables if which == "tables" else self.state
+        if shard is not None:
+            src = {f: shard}
         n, rp = self.num_embeddings[f], self.rp[f]
         mine = torch.zeros(rp, E, dtype=src[f].dtype, device=self.device)
         k = self.hi[f] - self.lo[f]

@@ -633,7 +633,8 @@ class SuperNet(nn.Module):
         the counterpart of train_utils.py:262-286 for optimizer == Adagrad (torch's own weight_decay == 0).  weight_decay != 0: the loss
         is BCE + get_l2_loss(self, weight_decay, no_reg_param_name) — every regularised parameter and every table row is decayed
         (engine_last_l2 = that term on the pre-step weights).  optim: an OptimSpec (nasrec_amd/optim_spec.py) of torch.optim.Adam / SGD
-        replaces Adagrad (eps unused) — every table row moves every step, or with sparse_rows (utils/optim.RowSparseAdam) only the
+        replaces Adagrad (eps unused) — every table row moves every step, or with sparse_rows (utils/optim.RowSparseAdam) or
+        table_kind "adagrad" (utils/optim.AdamAdagradTables: Adagrad on the tables at lr * table_lr_scale) only the
         batch's rows, which weight decay must then leave out; engine_bind_optimizer / engine_sync_optimizer_steps share its
         state with the torch optimizer.  Both need whole tables; under data parallelism they run in the exchange step's optimizer over
         the global batch (nasrec_amd/parallel.py).  ema_decay != 0: the step also averages every parameter (utils/optim.WeightEMA's
@@ -768,12 +769,14 @@ class SuperNet(nn.Module):
         state of every parameter that has some aliases them.  last_layer: the same for engine_last_layer_step, over _final.{weight,
         bias} only: the frozen parameters' state is left as it is.  LazyRMSprop: every row of an existing square_avg is current (torch
         keeps it so), so a table's row stamps start at that table's step count; the optimizer gets the engine's flush as its hook
-        (utils/optim.LazyRMSprop), and last_layer keeps the Adagrad accumulators: that step has no RMSprop."""
+        (utils/optim.LazyRMSprop), and last_layer keeps the Adagrad accumulators: that step has no RMSprop.  AdamAdagradTables: the
+        dense parameters as with Adam; a table shares `sum` with the engine's Adagrad accumulators (table_state) and its step counter
+        with the state's `step`, and the engine holds no moment array of a table."""
         eng = self._engine
         assert eng is not None, "run one forward first (lazy shapes)"
         from ..optim_spec import OptimSpec
         spec = OptimSpec.for_step(optimizer)
-        if spec is None or not spec.moments or (last_layer and spec.kind == "rmsprop"):
+        if spec is None or not spec.moments or (last_layer and (spec.kind == "rmsprop" or spec.table_kind)):
             spec = OptimSpec.of()  # (the Adagrad accumulators: also what an optimizer the fused step does not reproduce gets)
         if spec.moments and not last_layer and self._table_sharding == "row":
             from .._lib import EngineError
@@ -894,9 +897,15 @@ class SuperNet(nn.Module):
         if last_layer:
             arrays = eng.ensure_last_layer_state(spec.kind)
             return [(params[n], {k: arrays[k][i] for k in spec.state_keys}, i) for i, n in enumerate(self._FINAL)], eng.ll_steps
-        eng.ensure_moments_state(spec.kind)
-        return [(p, {k: eng.moments_view(k, n) for k in spec.state_keys}, eng.param_index[n]) for n, p in params.items()
-                if n in eng.param_index], eng.opt_steps
+        eng.ensure_moments_state(spec.kind, tables=not spec.table_kind)
+        if spec.table_kind:  # (AdamAdagradTables: a table's state is Adagrad's sum, the engine's table_state; its counter is the state's step)
+            eng._ensure_table_state()
+
+        def views(n):
+            if spec.table_kind and n.startswith("_embedding."):
+                return {"sum": eng.table_state[int(n.split(".")[1])]}
+            return {k: eng.moments_view(k, n) for k in spec.state_keys}
+        return [(p, views(n), eng.param_index[n]) for n, p in params.items() if n in eng.param_index], eng.opt_steps
 
     @staticmethod
     def _alias_state(optimizer, spec, slots, counts):

@@ -35,7 +35,7 @@ def train_and_eval_one_model(model, args):
 
     l2_loss_fn = L2Loss(args.wd, args.no_reg_param_name, gpu=args.gpu)
 
-    optimizer = build_optimizer(args.optimizer, model, args.learning_rate)
+    optimizer = build_optimizer(args.optimizer, model, args.learning_rate, args.table_lr_scale, args.table_eps)
     steps_per_epoch = args.train_limit // args.train_batch_size
     num_train_steps = steps_per_epoch * args.num_epochs
     lr_scheduler = build_lr_scheduler(args.lr_schedule, optimizer, num_train_steps, num_train_steps // 10, args.learning_rate)
@@ -122,7 +122,12 @@ def build_parser():
                    help="decoupled weight decay (the W of AdamW), 0 = off: before every optimizer step w *= 1 - lr * LAMBDA on the parameters "
                         "--wd would regularise that have a gradient (utils/optim.DecoupledWeightDecay; main_train.py --decoupled-wd)")
     p.add_argument("--loss_function", type=str, default="bce", choices=["bce"])
-    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rmsprop", "ds-optimizer"])
+    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rmsprop", "adam-adagrad-tables", "ds-optimizer"])
+    p.add_argument("--table-lr-scale", dest="table_lr_scale", type=float, default=1.0,
+                   help="--optimizer adam-adagrad-tables: the embedding tables' learning rate as a multiple of --learning_rate "
+                        "(Adam's 1e-3 with 160 gives the tables 0.16)")
+    p.add_argument("--table-eps", dest="table_eps", type=float, default=1e-2,
+                   help="--optimizer adam-adagrad-tables: eps of the tables' Adagrad (> 0)")
     p.add_argument("--pretrained_dlrm_emb_path", type=str, default=None, help="Pretrained embedding path from DLRM model.")
     p.add_argument("--gpu", type=int, default=0, help="GPU ID to use.")
     # not a reference flag: placement of the embedding tables under torchrun (nasrec_amd/sharded_tables.py)

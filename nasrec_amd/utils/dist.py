@@ -54,7 +54,8 @@ def world_info():
 
 def _replica_tensors(model):
     """every tensor that defines a replica: parameters, buffers, and the engine's optimizer state once it exists — Adagrad's
-    accumulators, Adam's / SGD's / RMSprop's moments (flat arena and table arrays), their step counters and RMSprop's row stamps"""
+    accumulators (under a moments spec too: AdamAdagradTables keeps the tables' `sum` there and no table moments), Adam's / SGD's /
+    RMSprop's moments (flat arena and table arrays), their step counters and RMSprop's row stamps"""
     sharded = getattr(model, "_table_sharding", None) == "row"  # row-sharded tables: every rank owns DIFFERENT rows — not replica state
     out = [p.data for n, p in model.named_parameters() if not (sharded and n.startswith("_embedding."))] + [b.data for b in model.buffers()]
     eng = getattr(model, "_engine", None)
@@ -93,7 +94,8 @@ def replica_checksum(model) -> torch.Tensor:
 
 def assert_replicas_identical(model, optimizer=None):
     """raise unless every rank holds the same weights (checked before the first step of a data-parallel run); optimizer: also unless
-    every rank runs the same table semantic (OptimSpec.sparse_rows: row-sparse Adam on some ranks and Adam on others would drift)"""
+    every rank runs the same table semantic (OptimSpec.sparse_rows / table_kind: row-sparse Adam or Adagrad on the tables on some ranks
+    and Adam on others would drift)"""
     rank, world = world_info()
     if world <= 1:
         return
@@ -111,14 +113,15 @@ def assert_replicas_identical(model, optimizer=None):
     if optimizer is not None:
         from ..optim_spec import OptimSpec
         spec = OptimSpec.from_optimizer(optimizer)
-        sparse = bool(spec is not None and spec.sparse_rows)
+        sparse = (2 if spec.table_kind else int(bool(spec.sparse_rows))) if spec is not None else 0  # (the tables' rule)
         lo = torch.tensor([float(sparse)], dtype=mine.dtype, device=mine.device)
         hi = lo.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         if not torch.equal(lo, hi):
-            raise RuntimeError("data-parallel ranks disagree on the optimizer's table rows (rank %d: sparse_rows=%r): pass the same "
-                               "--optimizer to every rank" % (rank, sparse))
+            raise RuntimeError("data-parallel ranks disagree on the optimizer's table rows (rank %d: sparse_rows=%r, table_kind=%r): pass the "
+                               "same --optimizer to every rank" % (rank, bool(spec is not None and spec.sparse_rows),
+                                                                    spec.table_kind if spec is not None else ""))
     lo, hi = mine.clone(), mine.clone()
     dist.all_reduce(lo, op=dist.ReduceOp.MIN)
     dist.all_reduce(hi, op=dist.ReduceOp.MAX)

@@ -65,7 +65,10 @@ def optimizer_state_for_checkpoint(model, optimizer):
         for i, f in _embedding_state_slots(model, optimizer):
             if i in state and "sum" in state[i]:
                 st = dict(state[i])
-                st["sum"] = sh.whole_table(f, "state")
+                # (utils/optim.AdamAdagradTables trains row-sharded tables on the torch route: its `sum` is its own tensor, not the
+                # engine's accumulator)
+                own = st["sum"] if type(optimizer).__name__ == "AdamAdagradTables" else None
+                st["sum"] = sh.whole_table(f, "state", shard=own)
                 state[i] = st
         sd = {"state": state, "param_groups": sd["param_groups"]}
     return sd

@@ -113,6 +113,78 @@ class RowSparseAdam(torch.optim.Optimizer):
         return loss
 
 
+class AdamAdagradTables(torch.optim.Optimizer):
+    """`--optimizer adam-adagrad-tables`: torch.optim.Adam on the dense parameters, torch.optim.Adagrad on the embedding tables with
+    their own learning rate `lr * table_lr_scale` and `table_eps` — how recommendation models are usually trained.  Adagrad with a
+    zero gradient changes neither the accumulator nor the weight (`0 / (sqrt(sum) + table_eps)` is an exact zero: table_eps > 0), so
+    the dense statements are already exactly row-sparse: no ids, no `touch`, no catch-up.
+
+    params: every parameter of the model, the tables included; table_params: the tables.  ONE param group — Adam's keys plus
+    table_lr_scale and table_eps — so a scheduler that publishes one lr moves both halves together.  State: step, exp_avg, exp_avg_sq
+    on a dense parameter (Adam's), step, sum on a table (Adagrad's).
+
+    `step()` is the torch route, on any device; the fused engine step reproduces it (OptimSpec.table_kind, csrc/optim_moments.hip)
+    and shares its state through SuperNet.engine_bind_optimizer."""
+
+    def __init__(self, params, table_params: Iterable[torch.Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 table_lr_scale: float = 1.0, table_eps: float = 1e-2):
+        if lr < 0.0 or eps < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+            raise ValueError("AdamAdagradTables: lr %r, betas %r, eps %r" % (lr, betas, eps))
+        if not table_eps > 0.0:
+            raise ValueError("AdamAdagradTables: table_eps %r is not positive (a row with a zero gradient must stay where it is)" % (table_eps,))
+        if not table_lr_scale > 0.0:
+            raise ValueError("AdamAdagradTables: table_lr_scale %r is not positive" % (table_lr_scale,))
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0, amsgrad=False, maximize=False, capturable=False,
+                        differentiable=False, fused=None, table_lr_scale=table_lr_scale, table_eps=table_eps)
+        super().__init__(params, defaults)
+        if len(self.param_groups) != 1:
+            raise ValueError("AdamAdagradTables keeps one param group")
+        tables = list(table_params)
+        own = {id(p) for p in self.param_groups[0]["params"]}
+        if not all(id(t) in own for t in tables):
+            raise ValueError("AdamAdagradTables: every table must be one of params")
+        self._table_ids = {id(t) for t in tables}
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        group = self.param_groups[0]
+        beta1, beta2 = group["betas"]
+        lr, eps = group["lr"], group["eps"]
+        table_lr, table_eps = lr * group["table_lr_scale"], group["table_eps"]
+        dense = ([], [], [], [], [])
+        for p in group["params"]:
+            if p.grad is None:
+                continue  # (a parameter the sampled path does not reach; a table when the backward stops short of the stem)
+            if p.grad.is_sparse:
+                raise RuntimeError("AdamAdagradTables reads dense gradients (nn.Embedding(sparse=False))")
+            st = self.state[p]
+            if id(p) in self._table_ids:
+                # torch.optim.Adagrad's dense single-tensor statements (torch/optim/adagrad.py), lr_decay 0 and weight_decay 0
+                if len(st) == 0:
+                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    st["sum"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["step"] += 1
+                st["sum"].addcmul_(p.grad, p.grad, value=1)
+                std = st["sum"].sqrt().add_(table_eps)
+                p.addcdiv_(p.grad, std, value=-table_lr)
+                continue
+            if len(st) == 0:
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            for lst, v in zip(dense, (p, p.grad, st["exp_avg"], st["exp_avg_sq"], st["step"])):
+                lst.append(v)
+        if dense[0]:
+            # torch.optim.Adam itself, per-parameter step counters included
+            _adam(dense[0], dense[1], dense[2], dense[3], [], dense[4], amsgrad=False, beta1=beta1, beta2=beta2, lr=lr, weight_decay=0,
+                  eps=eps, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None, has_complex=False)
+        return loss
+
+
 class LazyRMSprop(torch.optim.RMSprop):
     """`--optimizer rmsprop`: torch.optim.RMSprop, and on the torch route exactly that.  The type is what the fused engine step looks for
     (OptimSpec.from_optimizer: momentum 0, not centered): there a table row outside the batch owes `square_avg` only a factor

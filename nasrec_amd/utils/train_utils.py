@@ -141,7 +141,7 @@ def _last_layer_step_applies(model, optimizer, l2_loss_fn, use_amp):
     if world_info()[1] > 1 or getattr(model, "_table_sharding", None) == "row" or getattr(model, "_place_embedding_on_cpu", False):
         return False
     spec = _optim_spec(optimizer, l2_loss_fn)
-    if spec is None or spec.kind == "rmsprop" or not model._last_layer_only():  # (RMSprop: the fine-tune keeps the torch route)
+    if spec is None or spec.kind == "rmsprop" or spec.table_kind or not model._last_layer_only():  # (RMSprop, AdamAdagradTables: the fine-tune keeps the torch route)
         return False
     g = optimizer.param_groups[0]
     if not {id(p) for p in model._final.parameters()} <= {id(p) for p in g["params"]}:
@@ -162,11 +162,11 @@ def _whole_table_optimizers_apply(model) -> bool:
 
 def _ema_route(model, spec, l2_loss_fn):
     """why a step with a weight average keeps the torch route (WeightEMA.update() is dense and exact there), or None: the fused step
-    averages the batch's table rows only, so it applies where the tables move in those rows alone — Adagrad, row-sparse Adam or
-    RMSprop, no regularised table — in one process with whole tables on the device"""
+    averages the batch's table rows only, so it applies where the tables move in those rows alone (OptimSpec.rows_only) — Adagrad,
+    row-sparse Adam, RMSprop or Adam with Adagrad on the tables, no regularised table — in one process with whole tables on the device"""
     from ..optim_spec import regularises_tables
     from .dist import world_info
-    if spec.kind in ("adam", "sgd") and not spec.sparse_rows:
+    if not spec.rows_only:
         return "%s moves every table row every step" % ("dense Adam" if spec.kind == "adam" else "momentum SGD")
     if isinstance(l2_loss_fn, L2Loss) and regularises_tables(l2_loss_fn.wd, l2_loss_fn.no_reg_param_name):
         return "weight decay reaches the embedding tables: every row moves every step"
@@ -264,6 +264,24 @@ def _announce_ema_route(model, optimizer, l2_loss_fn, use_amp, ema, fused):
     print("Weight EMA (decay {}): torch route, dense WeightEMA.update() after every step ({}).".format(ema.decay, why))
 
 
+def _announce_split_route(optimizer, l2_loss_fn, fused, switched_off=False):
+    """one line per run with AdamAdagradTables (utils/optim.py): which route takes the step, and why"""
+    from .optim import AdamAdagradTables
+    if type(optimizer) is not AdamAdagradTables or getattr(optimizer, "_route_announced", False):
+        return
+    optimizer._route_announced = True
+    g = optimizer.param_groups[0]
+    head = "Adam + Adagrad on the tables (table lr = lr x {}, table eps {})".format(g["table_lr_scale"], g["table_eps"])
+    if fused:
+        print(head + ": fused step, exactly row-sparse table update.")
+        return
+    from ..optim_spec import regularises_tables
+    why = "the fused step was switched off" if switched_off else "the fused step does not apply"
+    if isinstance(l2_loss_fn, L2Loss) and regularises_tables(l2_loss_fn.wd, l2_loss_fn.no_reg_param_name):
+        why = "weight decay reaches the embedding tables: every row has a gradient (--no-reg-param-name _embedding leaves them out)"
+    print(head + ": torch route, AdamAdagradTables.step() ({}).".format(why))
+
+
 def _agreed_batches(train_loader, train_batch_size: int, world: int, gpu):
     """The batches of one epoch.  Single process: the loader as it is (incl. its short last batch, which the reference evaluates
     without training on it).  Data parallel: every rank reads its own shards, which differ in length — the ranks agree one step
@@ -316,6 +334,7 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
     if decay is not None and not decay.weight_decay:
         decay = None  # (lambda = 0 is "no helper")
     fused = _fused_step_applies(model, optimizer, l2_loss_fn, use_amp, ema, decay) if use_engine_step is None else bool(use_engine_step)
+    _announce_split_route(optimizer, l2_loss_fn, fused, switched_off=use_engine_step is False)
     if ema is not None:
         if fused and use_engine_step is not None and not _fused_step_applies(model, optimizer, l2_loss_fn, use_amp, ema):
             raise ValueError("use_engine_step=True with a weight EMA the fused step cannot keep exactly: leave use_engine_step=None")

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Cost of the optimizer choice (`--optimizer adagrad | adam | sgd | row-sparse-adam | rmsprop`, main_train.py:150-160) on the bench cfg-2 network:
+"""Cost of the optimizer choice (`--optimizer adagrad | adam | sgd | row-sparse-adam | rmsprop | adam-adagrad-tables`, main_train.py:150-160) on the bench cfg-2 network:
 the Criteo best-1shot sub-network, full tables (33.76 M rows), batch 256, clip 5.0; Adagrad(eps 1e-2), Adam(eps 1e-8), SGD(momentum 0.9,
 Nesterov), row-sparse Adam (Adam's lr and eps; with --wd the L2 term leaves the tables out, as the optimizer requires), RMSprop (torch's
 defaults; fused: lazily decayed rows, with --wd the tables left out too; its line also carries `flush_ms`, the one launch that brings
-every row's square_avg current after the timed steps).  `--ema DECAY` keeps utils/optim.WeightEMA beside the step: inside the fused
+every row's square_avg current after the timed steps), adam-adagrad-tables (Adam's lr and eps on the network, Adagrad at lr x
+`--table-lr-scale` on the tables: one phase-0 launch, W and `sum` of the batch's rows; with --wd the tables left out).  `--ema DECAY` keeps utils/optim.WeightEMA beside the step: inside the fused
 step (Adagrad, row-sparse Adam, RMSprop), by WeightEMA.update() on the torch route; the line then carries `ema`, `flush_ms` (the launch
 that brings every row's average current) and `swap_ms` (flush + exchange with the parameters: what entering `averaged()` costs).
 `--decoupled-wd LAMBDA` applies utils/optim.DecoupledWeightDecay in front of the update: inside the fused step (Adagrad, row-sparse Adam,
@@ -28,13 +29,15 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-LR = {"adagrad": 1e-3, "adam": 1e-3, "sgd": 1e-3, "row-sparse-adam": 1e-3, "rmsprop": 1e-4}
+LR = {"adagrad": 1e-3, "adam": 1e-3, "sgd": 1e-3, "row-sparse-adam": 1e-3, "rmsprop": 1e-4, "adam-adagrad-tables": 1e-3}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--route", choices=["fused", "torch"], default="fused")
-    ap.add_argument("--optimizer", choices=["adagrad", "adam", "sgd", "row-sparse-adam", "rmsprop"], default="adam")
+    ap.add_argument("--optimizer", choices=["adagrad", "adam", "sgd", "row-sparse-adam", "rmsprop", "adam-adagrad-tables"], default="adam")
+    ap.add_argument("--table-lr-scale", dest="table_lr_scale", type=float, default=1.0,
+                    help="adam-adagrad-tables: the tables' learning rate as a multiple of the network's")
     ap.add_argument("--wd", type=float, default=0.0)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
@@ -56,11 +59,11 @@ def main():
         return
     if a.all:
         for route in ("fused", "torch"):
-            for opt in ("adagrad", "adam", "sgd", "row-sparse-adam", "rmsprop"):
+            for opt in ("adagrad", "adam", "sgd", "row-sparse-adam", "rmsprop", "adam-adagrad-tables"):
                 for wd in (0.0, 1e-8):
                     steps = a.steps if route == "fused" else min(a.steps, 20)
                     cmd = [sys.executable, os.path.abspath(__file__), "--route", route, "--optimizer", opt, "--wd", str(wd), "--steps", str(steps),
-                           "--warmup", str(a.warmup), "--B", str(a.B)]
+                           "--warmup", str(a.warmup), "--B", str(a.B), "--table-lr-scale", str(a.table_lr_scale)]
                     r = subprocess.run(cmd, timeout=a.timeout, capture_output=True, text=True)
                     if r.returncode != 0:  # (stop at the first failure: nothing more is started on the GPU)
                         sys.stderr.write(r.stdout + r.stderr)
@@ -93,9 +96,9 @@ def main():
     with torch.no_grad():
         m(batches[0][0], batches[0][1])
     lr = LR[a.optimizer]
-    opt = MT.build_optimizer(a.optimizer, m, lr)
+    opt = MT.build_optimizer(a.optimizer, m, lr, a.table_lr_scale)
     spec = OptimSpec.from_optimizer(opt) if a.optimizer != "adagrad" else None
-    lazy = a.optimizer in ("row-sparse-adam", "rmsprop") and a.route == "fused"  # (the fused step needs the tables left out of the L2 term)
+    lazy = a.optimizer in ("row-sparse-adam", "rmsprop", "adam-adagrad-tables") and a.route == "fused"  # (the fused step needs the tables left out of the L2 term)
     no_reg = "_embedding" if ((a.optimizer == "row-sparse-adam" or lazy) and a.wd) else None
     loss_fn = torch.nn.BCEWithLogitsLoss()
     if a.route == "fused":
@@ -175,6 +178,8 @@ def main():
         m._engine.flush_lazy_rows()
         torch.cuda.synchronize()
         extra["flush_again_ms"] = round((time.perf_counter() - wall) * 1e3, 4)  # (nothing owed: the stamps are read, nothing else)
+    if a.optimizer == "adam-adagrad-tables":
+        extra["table_lr_scale"] = a.table_lr_scale
     print(json.dumps({**extra, "route": a.route, "optimizer": a.optimizer, "wd": a.wd, "B": a.B, "steps": a.steps, "ms_per_step": round(ms, 4),
                       "samples_per_s": round(a.B / ms * 1e3), "wall_ms_per_step": round(wall_ms, 4),
                       "table_rows": rows}))
