@@ -1021,6 +1021,12 @@ typedef struct nasrec_wl_geometry {
   int32_t body;    /* NASREC_WL_BODY_*: the code the item runs */
 } nasrec_wl_geometry_t;
 int nasrec_worklist_item_geometry(int kind, int part, const void* desc, int bytes, nasrec_wl_geometry_t* out);
+/* The wide form of the 32 x 32 tile (bit 5 of geom[2]; geom[0] / geom[1] then hold a 64 x 64 grid; the body stays NASREC_WL_BODY_TILE and
+ * the bits stay the 32 x 32 tile's): a GEMM item without a mask operand whose every problem has M >= 64 and N >= 64 takes it when its
+ * 32 x 32 launch would hold at least `wide_min` workgroups (<= 0: never).  The initial value comes from the environment variable
+ * NASREC_WL_WIDE_MIN, read once; this call replaces it — for tests and tools — and returns the previous value.  Host only; launches
+ * that were finalized or prepared before keep their geometry.  (Added WITHOUT a new nasrec_abi_version(), as the query above was.) */
+int nasrec_worklist_set_wide_min(int wide_min);
 
 /* ------------------------------------------------------------------------------------------------
  * Persistent step (batch <= 256, round 6): the worklist items of MANY levels in ONE launch, ordered topologically, with the

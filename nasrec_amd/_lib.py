@@ -340,7 +340,7 @@ SYMBOLS = [
     "nasrec_event_record", "nasrec_event_elapsed_ms", "nasrec_event_destroy", "nasrec_last_error", "nasrec_abi_version",
     "nasrec_desc_sizes", "nasrec_tsv_parse", "nasrec_alloc_uncached", "nasrec_free_uncached", "nasrec_persist_prepare", "nasrec_worklist_prepare",
     "nasrec_weight_decay", "nasrec_opt_moments", "nasrec_last_layer_step", "nasrec_roc_auc", "nasrec_roc_auc_workspace_bytes", "nasrec_gemm_route",
-    "nasrec_weight_ema", "nasrec_worklist_item_geometry", "nasrec_decoupled_decay",
+    "nasrec_weight_ema", "nasrec_worklist_item_geometry", "nasrec_decoupled_decay", "nasrec_worklist_set_wide_min",
 ]
 
 _lib = None
@@ -378,6 +378,7 @@ def load():
     lib.nasrec_persist_prepare.argtypes = [vp]
     lib.nasrec_worklist_prepare.argtypes = [vp, vp, vp]
     lib.nasrec_worklist_item_geometry.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(WlGeometry)]
+    lib.nasrec_worklist_set_wide_min.argtypes = [C.c_int]
     lib.nasrec_tsv_parse.argtypes = [vp, i64, i32, i32, vp, i64, vp, vp, vp, C.POINTER(i64), C.POINTER(i32)]
     lib.nasrec_tsv_parse.restype = i64
     for name in ("nasrec_gemm", "nasrec_embedding_gather", "nasrec_embedding_dedup", "nasrec_dot_tri", "nasrec_fm",

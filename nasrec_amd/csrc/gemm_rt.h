@@ -63,10 +63,15 @@ __device__ __forceinline__ void rt_epilogue_store_col4(int cm, const nasrec_gemm
 
 #define GEMM_RT_LDS_FLOATS(TBM, TBN, TK) (((TBM) + (TBN)) * ((TK) + 4) + 128)
 
-template <bool KCA, bool KCB, int NT, int TK, int TBM, int TBN, bool AUX, int RING>
+// KU: the k UNIT in which tiles are counted and split-K partitions them (default: the staged depth TK).  With KU = n TK a unit is walked
+// as n TK-deep tiles (a tile that lies wholly beyond the segment's K is staged as zeros, like the tail of a partial tile), so every output
+// element accumulates the k sequence — and meets the split boundaries — of the body with TK = KU: same bits from a shallower staging buffer.
+template <bool KCA, bool KCB, int NT, int TK, int TBM, int TBN, bool AUX, int RING, int KU = TK>
 __device__ __forceinline__ void gemm_tile_rt(const nasrec_gemm_desc_t& d, int Mmax, int Nmax, const int bx, const int by, const int bz, float* lds) {
   const int AM = d.amode, BMODE = d.bmode, CM = d.cmode;
   constexpr int LDS_LD = TK + 4;
+  constexpr int SUB = KU / TK;  // staged tiles per k unit
+  static_assert(KU % TK == 0 && SUB >= 1, "a k unit is whole staged tiles");
   constexpr int VA = 4, VB = 4;                                        // floats per staging load
   constexpr int NITA = TBM * TK / NT / VA, NITB = TBN * TK / NT / VB;  // staging loads per thread and k-tile
   static_assert((TBM * TK / NT) % VA == 0 && (TBN * TK / NT) % VB == 0 && TK % 16 == 0 && TBM % 4 == 0 && TBN % 4 == 0, "whole 16-byte pieces");
@@ -108,12 +113,12 @@ __device__ __forceinline__ void gemm_tile_rt(const nasrec_gemm_desc_t& d, int Mm
   }
   int T = 0;
   if (!use_table) {
-    T = (s0.A != nullptr && s0.K > 0) ? (s0.K + TK - 1) / TK : 0;
+    T = (s0.A != nullptr && s0.K > 0) ? (s0.K + KU - 1) / KU : 0;
   } else {
     for (int q = 0; q < d.nseg; ++q)
-      if (sinfo[q].live) T += (sinfo[q].K + TK - 1) / TK;
+      if (sinfo[q].live) T += (sinfo[q].K + KU - 1) / KU;
   }
-  const int t0 = (int)((long)T * ks / S), t1 = (int)((long)T * (ks + 1) / S);
+  const int t0 = SUB * (int)((long)T * ks / S), t1 = SUB * (int)((long)T * (ks + 1) / S);  // (the split is drawn in units, walked in tiles)
 
   f32x4 acc[FA][FB];
 #pragma unroll
@@ -147,7 +152,7 @@ __device__ __forceinline__ void gemm_tile_rt(const nasrec_gemm_desc_t& d, int Mm
     fs = 0;
     int skip = t0;
     while (fs < d.nseg) {
-      const int nt = sinfo[fs].live ? (sinfo[fs].K + TK - 1) / TK : 0;
+      const int nt = sinfo[fs].live ? SUB * ((sinfo[fs].K + KU - 1) / KU) : 0;
       if (skip < nt) break;
       skip -= nt;
       ++fs;
@@ -197,7 +202,7 @@ __device__ __forceinline__ void gemm_tile_rt(const nasrec_gemm_desc_t& d, int Mm
     rsAx = hasAaux ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sg.Aaux), 0, extA, 0x00020000) : rs_null;
     rsBx = hasBaux ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sg.Baux), 0, extB, 0x00020000) : rs_null;
     cK = sg.K;
-    seg_tiles = (cK + TK - 1) / TK;
+    seg_tiles = SUB * ((cK + KU - 1) / KU);
     stepA = (int)(4 * rt_offset(sa_, 0, TK));
     stepB = (int)(4 * rt_offset(sb_, 0, TK));
 #pragma unroll

@@ -15,6 +15,22 @@
 
 #include "worklist_body.h"
 
+// smallest 32 x 32 workgroup count at which an eligible product takes the wide tile (<= 0: never); NASREC_WL_WIDE_MIN is read once (A/B knob),
+// nasrec_worklist_set_wide_min replaces it for tests and tools.  Geometry is decided when a launch is finalized / prepared: a plan that was
+// prepared keeps the tiles it was prepared with.
+// 700, measured on the batch-256 step (profiles/wide_tile_cfg2.txt): the input gradient of the 780 -> 768 Linear (800 workgroups of 32 x 32, split-K 4)
+// gains from the wide tile, its weight gradient (600, unsplit, K = 256: twice the staging round trips on a quarter of the workgroups) loses
+#define WL_WIDE_MIN_DEFAULT 700
+static int& wl_wide_min() {
+  static int v = getenv("NASREC_WL_WIDE_MIN") ? atoi(getenv("NASREC_WL_WIDE_MIN")) : WL_WIDE_MIN_DEFAULT;
+  return v;
+}
+extern "C" int nasrec_worklist_set_wide_min(int wide_min) {
+  const int prev = wl_wide_min();
+  wl_wide_min() = wide_min;
+  return prev;
+}
+
 // host side: geometry of every item, then ONE launch
 static int wl_gemm_geometry(const nasrec_gemm_desc_t* g, nasrec_wl_item_t& it, int blob_left) {
   if (blob_left < (int)offsetof(nasrec_gemm_desc_t, seg)) return nasrec_set_error(-2, "worklist: gemm descriptor head runs past the blob");
@@ -54,6 +70,11 @@ static int wl_gemm_geometry(const nasrec_gemm_desc_t* g, nasrec_wl_item_t& it, i
     const int per = (int)(((long)Mmax * Nmax + 255) / 256);
     it.geom[0] = per;
     it.nblk = per * nprob;
+    if (WL_COMPACT_Z && g->zmode) {  // a workgroup per 256 elements of EACH problem (wl_gemm_second_pass walks the same counts)
+      long units = 0;
+      for (int q = 0; q < nprob; ++q) units += wl_z_units(g->seg[q].M, g->seg[q].N);
+      it.nblk = (int)units;
+    }
     return 0;
   }
   // small dense Linear forward (x W^T, binding KC / KC / plain), unsplit, no mask operands / row predicates / ones column, at most
@@ -156,11 +177,22 @@ static int wl_gemm_geometry(const nasrec_gemm_desc_t* g, nasrec_wl_item_t& it, i
       tile = WL_T16x64, tbm = 16, tbn = 64;
     }
   }
+  // the wide form of the 32 x 32 tile (worklist_body.h WL_WIDE): products without a mask operand whose every problem spans a whole 64 x 64
+  // tile and whose 32 x 32 launch would hold at least wl_wide_min() workgroups (<= 0: never) — the ones that crowd a level's workgroup slots
+  bool wide64 = tile == WL_T32x32 && !aux && wl_wide_min() > 0;
+  for (int q = 0; q < nprob && wide64; ++q) wide64 = g->seg[q].M >= 64 && g->seg[q].N >= 64;
+  if (wide64 && (long)((Nmax + 31) / 32) * ((Mmax + 31) / 32) * nprob * S >= wl_wide_min()) tbm = 64, tbn = 64;
+  else wide64 = false;
   it.geom[0] = (Nmax + tbn - 1) / tbn;
   it.geom[1] = (Mmax + tbm - 1) / tbm;
   const bool kca_ = g->amode == NASREC_AM_KC || g->amode == NASREC_AM_TOKK, kcb_ = g->bmode == NASREC_AM_KC || g->bmode == NASREC_AM_TOKK;
-  it.geom[2] = tile | ((kca_ && kcb_ ? 0 : (kca_ ? 1 : 2)) << 2) | ((aux ? 1 : 0) << 4);
+  it.geom[2] = tile | ((kca_ && kcb_ ? 0 : (kca_ ? 1 : 2)) << 2) | ((aux ? 1 : 0) << 4) | (wide64 ? WL_WIDE : 0);
   it.nblk = it.geom[0] * it.geom[1] * nprob * S;
+  if (WL_COMPACT_Z && g->zmode) {  // only the tiles each problem has (wl_gemm_cfg walks the same counts)
+    long units = 0;
+    for (int q = 0; q < nprob; ++q) units += (long)wl_z_tiles(g->seg[q].M, g->seg[q].N, tbm, tbn) * S;
+    it.nblk = (int)units;
+  }
   return 0;
 }
 
@@ -381,7 +413,7 @@ __device__ __forceinline__ void ps_run_item(int it_kind, int it_part, int g0, in
         for (int u = vb; u < nblk; u += nwg) wl_gemm_second_pass(blob, u, g0);
         break;
       }
-      const int cfg = g2;  // tile | binding pair << 2 | mask operand << 4
+      const int cfg = g2;  // tile | binding pair << 2 | mask operand << 4 | WL_WIDE
       if ((cfg & 3) == WL_TOKS && ((cfg >> 2) & 3) == 3 && g1 == 0) wl_dense_small_dx(blob, vb, g0);
       else if ((cfg & 3) == WL_TOKS && ((cfg >> 2) & 3) == 3) wl_dense_small(blob, vb, g0, g1);
       else if ((cfg & 3) == WL_TOKS && ((cfg >> 2) & 3) == 1) wl_token_fwd(blob, vb, g0);
@@ -393,7 +425,7 @@ __device__ __forceinline__ void ps_run_item(int it_kind, int it_part, int g0, in
         }
       } else {
         for (int u = vb; u < nblk; u += nwg) {  // (tiles of a product: the bulk items walk several per workgroup)
-          wl_gemm_bind<false>((cfg >> 2) & 3, cfg & 3, blob, u, g0, g1);
+          wl_gemm_bind<false>((cfg >> 2) & 3, cfg & (3 | WL_WIDE), blob, u, g0, g1);
           if (u + nwg < nblk) __syncthreads();
         }
       }

@@ -10,12 +10,19 @@
 #define WL_LDS_FLOATS 7840  // 31 KB (5 workgroups per CU): the DotProduct cores up to k1 = 46 (4 * (k1 * TRI_LD + P4) floats: 47 needs 8096); a 64x16x64 GEMM tile needs 5568, the Transformer forward 3744
 static_assert(MHA_TOK_BWD_LDS_FLOATS <= WL_LDS_BIG_FLOATS && MHA_TOK_FWD_LDS_FLOATS <= WL_LDS_FLOATS, "Transformer bodies fit the worklist launches");
 
-#define WL_TK 64  // staged k depth of every GEMM item (a product with K <= 32 pads its one tile with zeros: same sums, bit for bit)
+#define WL_TK 64  // k unit of every GEMM item, and the staged depth of all but the wide form below (a product with K <= 32 pads its one tile with zeros: same sums, bit for bit)
 // tile configurations of GEMM items: geom[2] = tile | binding pair << 2 | mask operand << 4
 #ifndef WL_AUX_RING2
 #define WL_AUX_RING2 0  // (A/B knob: ring depth 2 for the mask-operand instantiations too)
 #endif
 enum { WL_TOKS = 0, WL_T32x32 = 1, WL_T64x16 = 2, WL_T16x64 = 3 };  // WL_TOKS: wl_token_fwd (a wavefront per sample)
+// The WIDE form of WL_T32x32 (bit 5 of geom[2], on top of the tile value; never with a mask operand): a 64 x 64 output tile — each wave
+// 32 x 32 — over WL_WIDE_TK-deep staged tiles, two per WL_TK unit.  It stages what the 32 x 32 x 64 tile stages per k-tile ((64 + 64) x 32 =
+// (32 + 32) x 64 floats: 16 per thread, ring depth 2, the same 128 registers) for four times the output, so a large product asks for a
+// quarter of the workgroups and fetches every operand element half as often; split-K partitions and the k order inside a unit are the
+// 32 x 32 tile's (gemm_rt.h KU), so the bits are too.  geom[0] / geom[1] hold the 64 x 64 grid.
+#define WL_WIDE 32
+#define WL_WIDE_TK 32
 
 // All bodies share the launch's DYNAMIC LDS buffer (sized by the launcher: 31 KB, or 39.5 KB when a Transformer backward is in the level).
 extern __shared__ __attribute__((aligned(16))) float wl_lds[];
@@ -30,7 +37,21 @@ __device__ __forceinline__ const T& wl_ref(unsigned long long addr) {
   return *(const T*)(const __attribute__((address_space(4))) T*)(((unsigned long long)hi << 32) | lo);
 }
 
-template <bool KCA, bool KCB, int TBM, int TBN, bool AUX>
+// Items of SEVERAL problems (zmode) own only the work units their problems have: the launcher sums the per-problem counts below into nblk
+// and a body finds (problem, unit) by a scalar walk over the same counts.  Sized by the largest problem instead (gx gy nprob S), the input
+// gradients [(128,14,256), (128,32,256), (128,768,256)] S = 4 launched 1152 workgroups for 416 tiles and held a level's workgroup slots
+// with workgroups that return at once.  (A/B knob: 0 restores the grid of the largest problem.)
+#ifndef WL_COMPACT_Z
+#define WL_COMPACT_Z 1
+#endif
+__host__ __device__ __forceinline__ int wl_z_tiles(int M, int N, int tbm, int tbn) {
+  return (M > 0 && N > 0) ? ((M + tbm - 1) / tbm) * ((N + tbn - 1) / tbn) : 0;
+}
+__host__ __device__ __forceinline__ int wl_z_units(int M, int N) {  // second pass: 256 elements per workgroup
+  return (M > 0 && N > 0) ? (int)(((long)M * N + 255) / 256) : 0;
+}
+
+template <bool KCA, bool KCB, int TBM, int TBN, bool AUX, int TK = WL_TK>
 __device__ __forceinline__ void wl_gemm_cfg(unsigned long long blob, int vb_, int gx_, int gy_) {
   // ring depth 2: the kernel must fit 128 registers so that FOUR workgroups of different items share a CU (a level's items only run
   // side by side if they are resident together); a staged k-tile is <= 20 floats per thread on these tiles.  With mask operands a
@@ -45,15 +66,30 @@ __device__ __forceinline__ void wl_gemm_cfg(unsigned long long blob, int vb_, in
     Mmax = max(Mmax, g.seg[q].M);
     Nmax = max(Nmax, g.seg[q].N);
   }
-  const int bx = vb % gx, by = (vb / gx) % gy, bz = vb / (gx * gy);
-  gemm_tile_rt<KCA, KCB, 256, WL_TK, TBM, TBN, AUX, RING>(g, Mmax, Nmax, bx, by, bz, wl_lds);
+  int bx = vb % gx, by = (vb / gx) % gy, bz = vb / (gx * gy);
+  if (WL_COMPACT_Z && g.zmode) {  // (problem, tile, split) of unit vb: problems in order, each with its own grid, splits outermost
+    const int S = g.splitk > 1 ? g.splitk : 1;
+    int z = 0, v = vb;
+    for (; z < nprob - 1; ++z) {
+      const int cnt = wl_z_tiles(g.seg[z].M, g.seg[z].N, TBM, TBN) * S;
+      if (v < cnt) break;
+      v -= cnt;
+    }
+    const int gxz = max((g.seg[z].N + TBN - 1) / TBN, 1), gyz = max((g.seg[z].M + TBM - 1) / TBM, 1);
+    bx = v % gxz, by = (v / gxz) % gyz, bz = z * S + min(v / (gxz * gyz), S - 1);
+  }
+  gemm_tile_rt<KCA, KCB, 256, TK, TBM, TBN, AUX, RING, WL_TK>(g, Mmax, Nmax, bx, by, bz, wl_lds);
 }
 
+// tile: cfg & (3 | WL_WIDE) of the item's geom[2]
 template <bool KCA, bool KCB, bool AUX>
 __device__ __forceinline__ void wl_gemm_tile(int tile, unsigned long long off, int vb, int gx, int gy) {
   switch (tile) {
     case WL_T32x32: wl_gemm_cfg<KCA, KCB, 32, 32, AUX>(off, vb, gx, gy); break;
     case WL_T64x16: wl_gemm_cfg<KCA, KCB, 64, 16, AUX>(off, vb, gx, gy); break;
+    case WL_T32x32 | WL_WIDE:
+      if constexpr (!AUX) wl_gemm_cfg<KCA, KCB, 64, 64, false, WL_WIDE_TK>(off, vb, gx, gy);  // (the launcher never sets the bit on a mask item)
+      break;
     default: wl_gemm_cfg<KCA, KCB, 16, 64, AUX>(off, vb, gx, gy); break;
   }
 }
@@ -380,8 +416,16 @@ __device__ __forceinline__ void wl_gemm_second_pass(unsigned long long blob, int
     Mmax = max(Mmax, g.seg[q].M);
     Nmax = max(Nmax, g.seg[q].N);
   }
-  const int z = vb / per;
-  const long e = (long)(vb - z * per) * 256 + threadIdx.x;
+  int z = vb / per, v = vb - z * per;
+  if (WL_COMPACT_Z && g.zmode) {  // (problem, 256 elements) of unit vb: the launcher sized the item by the per-problem counts
+    z = 0, v = vb;
+    for (; z < nprob - 1; ++z) {
+      const int cnt = wl_z_units(g.seg[z].M, g.seg[z].N);
+      if (v < cnt) break;
+      v -= cnt;
+    }
+  }
+  const long e = (long)v * 256 + threadIdx.x;
   if (g.cmode == NASREC_CM_PLAIN)
     splitk_second_pass<NASREC_CM_PLAIN>(g, Mmax, Nmax, z, e);
   else
@@ -453,13 +497,13 @@ __device__ __forceinline__ void wl_run(unsigned f01, unsigned f23, unsigned f45,
         wl_gemm_second_pass(blob, vb, it.geom[0]);
         break;
       }
-      const int cfg = it.geom[2];  // tile | binding pair << 2 | mask operand << 4
+      const int cfg = it.geom[2];  // tile | binding pair << 2 | mask operand << 4 | WL_WIDE
       if ((cfg & 3) == WL_TOKS && ((cfg >> 2) & 3) == 3 && it.geom[1] == 0) wl_dense_small_dx(blob, vb, it.geom[0]);
       else if ((cfg & 3) == WL_TOKS && ((cfg >> 2) & 3) == 3) wl_dense_small(blob, vb, it.geom[0], it.geom[1]);
       else if ((cfg & 3) == WL_TOKS && ((cfg >> 2) & 3) == 1) wl_token_fwd(blob, vb, it.geom[0]);
       else if ((cfg & 3) == WL_TOKS) wl_token_dx(blob, vb, it.geom[0]);
       else if ((cfg >> 4) & 1) wl_gemm_bind<true>((cfg >> 2) & 3, cfg & 3, blob, vb, it.geom[0], it.geom[1]);
-      else wl_gemm_bind<false>((cfg >> 2) & 3, cfg & 3, blob, vb, it.geom[0], it.geom[1]);
+      else wl_gemm_bind<false>((cfg >> 2) & 3, cfg & (3 | WL_WIDE), blob, vb, it.geom[0], it.geom[1]);
       break;
     }
     case NASREC_OP_MHA_FWD:
