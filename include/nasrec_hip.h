@@ -949,13 +949,24 @@ typedef struct nasrec_stage_desc {
  * stand-alone kernel on them (bit-identical results; at batch 256 every launch costs ~5 us whatever it does, so a step is as long
  * as its number of dependent launches).
  *   item.kind   NASREC_OP_GEMM (part 0 = the whole launch of an unsplit product, 1 = main pass of a split-K product: slabs only,
- *               2 = its second pass: fixed-order slab sum + epilogue), _DOT_TRI_FWD/_BWD, _FM_FWD/_BWD, _MHA_FWD/_BWD,
+ *               2 = its second pass: fixed-order slab sum + epilogue, NASREC_WL_CHAIN = chained input gradients: below),
+ *               _DOT_TRI_FWD/_BWD, _FM_FWD/_BWD, _MHA_FWD/_BWD,
  *               _COPY_SEGS, _GATE_BWD, _REDUCE_ROWS (compact form nasrec_wl_reduce_t, <= NASREC_WL_REDUCE_DST destinations);
  *   item.off    byte offset (multiple of 16) of the item's descriptor inside `blob`; a GEMM descriptor may be truncated behind its
  *               last used segment (offsetof(seg) + nseg * sizeof(seg) bytes);
  *   first / nblk / geom are filled in by the launcher (callers leave them 0).
  * All workgroups have 256 threads; GEMM items run the run-time-binding body (csrc/gemm_rt.h) on 64x64 / 32x32 / 64x16 / 16x64 tiles.
  * ---------------------------------------------------------------------------------------------- */
+/* item.part NASREC_WL_CHAIN: several token-axis input gradients (binding RC / TOKR / TOKJ, unsplit) that add into the SAME outputs, as one
+ * item.  The descriptor is an ordinary zmode nasrec_gemm_desc_t of c h problems, c >= 2: problems q, q + h, ..., q + (c - 1) h are the
+ * members of chain q, in the order their launches would run — all with the C, M, N and ldc of problem q, accumulate = 1 from the second
+ * member on; h is the first q > 0 with seg[q].C == seg[0].C.  A wavefront computes the 16 x 16 tile of every member of a chain and adds
+ * them in chain order (v = acc_0, or acc_0 + C if member 0 accumulates; v = acc_m + v), which are the additions the members' own launches
+ * perform through memory: bit-identical, with one store.  A member with A == NULL or K <= 0 contributes nothing.  Required: N a multiple
+ * of 16 and equal everywhere, every K <= 64, no Aaux (Baux per member is honoured), no ones_col / Mvalid, no bias, activation,
+ * dims_in_use, pre_add, gate, save_z or save_act; anything else is refused with an error.  Such a descriptor must never run as an
+ * ordinary zmode launch (its problems would race on C), and NASREC_OP_PERSIST refuses it. */
+#define NASREC_WL_CHAIN 3
 #define NASREC_WL_MAX_ITEMS 12
 #define NASREC_WL_BLOB_BYTES 3680
 #define NASREC_WL_REDUCE_DST 16
@@ -1012,7 +1023,8 @@ enum {
   NASREC_WL_BODY_DENSE_SMALL = 3,   /* small dense Linear forward, a wavefront per 16 x 16 output tile */
   NASREC_WL_BODY_DENSE_SMALL_DX = 4,/* its input gradients */
   NASREC_WL_BODY_TOKEN_FWD = 5,     /* token-axis Linear forward, a wavefront per (sample, 16 rows of W) */
-  NASREC_WL_BODY_TOKEN_DX = 6       /* token-axis input gradients, a wavefront per (sample, segment, 16 token rows) */
+  NASREC_WL_BODY_TOKEN_DX = 6,      /* token-axis input gradients, a wavefront per (sample, segment, 16 token rows) */
+  NASREC_WL_BODY_TOKEN_DX_CHAIN = 7 /* part NASREC_WL_CHAIN: the same, every member of a chain in one unit (geom[0] as _TOKEN_DX, geom[1] = h) */
 };
 typedef struct nasrec_wl_geometry {
   int32_t nblk;    /* work units of the item (workgroups of a worklist launch) */

@@ -227,7 +227,7 @@ class OptApplyDesc(C.Structure):
 
 
 WL_MAX_ITEMS, WL_BLOB_BYTES, WL_REDUCE_DST = 12, 3680, 16  # NASREC_WL_*
-WL_WHOLE, WL_MAIN, WL_EPI = 0, 1, 2                      # nasrec_wl_item_t.part of a GEMM item
+WL_WHOLE, WL_MAIN, WL_EPI, WL_CHAIN = 0, 1, 2, 3           # nasrec_wl_item_t.part of a GEMM item (WL_CHAIN: NASREC_WL_CHAIN)
 
 
 class WlItem(C.Structure):
@@ -245,7 +245,7 @@ class WorklistDesc(C.Structure):
 
 
 (WL_BODY_KIND, WL_BODY_TILE, WL_BODY_SECOND_PASS, WL_BODY_DENSE_SMALL, WL_BODY_DENSE_SMALL_DX, WL_BODY_TOKEN_FWD,
- WL_BODY_TOKEN_DX) = range(7)        # NASREC_WL_BODY_* (nasrec_wl_geometry_t.body)
+ WL_BODY_TOKEN_DX, WL_BODY_TOKEN_DX_CHAIN) = range(8)        # NASREC_WL_BODY_* (nasrec_wl_geometry_t.body)
 
 
 class WlGeometry(C.Structure):
@@ -399,8 +399,22 @@ def load():
                               % (kind, sizes[kind] if kind < n else -1, C.sizeof(cls)))
     if n <= 37 or sizes[37] != C.sizeof(PersistItem):
         raise EngineError("struct layout mismatch for nasrec_persist_item_t: library %d bytes, binding %d bytes" % (sizes[37] if n > 37 else -1, C.sizeof(PersistItem)))
+    # (item part WL_CHAIN came without a new nasrec_abi_version(): a library from before it has no such part — ask it)
+    g, probe = WlGeometry(), _chain_probe()
+    if lib.nasrec_worklist_item_geometry(OP_GEMM, WL_CHAIN, probe, len(probe), C.byref(g)) != 0 or (g.nblk, g.geom[0], g.geom[1], g.body) != (1, 1, 1, WL_BODY_TOKEN_DX_CHAIN):
+        raise EngineError("the library does not know the chained worklist item (part %d): rebuild it" % WL_CHAIN)
     _lib = lib
     return lib
+
+
+def _chain_probe():
+    """the smallest legal chained item: two 16 x 16 x 16 members of one chain (pointers are never followed by the geometry query)"""
+    d = GemmDesc()
+    d.kind, d.amode, d.bmode, d.cmode, d.nseg, d.zmode, d.dims_in_use = OP_GEMM, AM_RC, AM_TOKR, CM_TOKJ, 2, 1, -1
+    for q in range(2):
+        s = d.seg[q]
+        s.A, s.B, s.C, s.M, s.N, s.K, s.lda, s.ldb, s.ldc, s.accumulate = 64, 64, 64, 16, 16, 16, 16, 256, 256, q
+    return C.string_at(C.addressof(d), GemmDesc.seg.offset + 2 * C.sizeof(GemmSeg))
 
 
 def check(rc):

@@ -32,6 +32,39 @@ extern "C" int nasrec_worklist_set_wide_min(int wide_min) {
 }
 
 // host side: geometry of every item, then ONE launch
+// A chained token-axis input gradient (part NASREC_WL_CHAIN, worklist_body.h wl_token_dx_chain): c h problems, problems q, q + h, ... add into
+// the C of problem q in that order.  h is read off the descriptor — the first problem that writes seg[0].C again — and everything the body
+// takes for granted is checked here; a descriptor that misses any of it is refused, never run as something else.
+static int wl_chain_geometry(const nasrec_gemm_desc_t* g, nasrec_wl_item_t& it) {
+  if (!g->zmode || g->amode != NASREC_AM_RC || g->bmode != NASREC_AM_TOKR || g->cmode != NASREC_CM_TOKJ)
+    return nasrec_set_error(-2, "worklist: a chained item is a zmode token-axis input gradient (a=%d b=%d c=%d zmode=%d)", g->amode, g->bmode, g->cmode, g->zmode);
+  if (g->splitk > 1) return nasrec_set_error(-2, "worklist: a chained item is unsplit (splitk=%d)", g->splitk);
+  if (g->bias || g->act != NASREC_ACT_NONE || g->dims_in_use >= 0 || g->pre_add || g->mul_nseg != 0 || g->save_z || g->save_act)
+    return nasrec_set_error(-2, "worklist: a chained item has a plain epilogue (no bias, activation, mask, residual, gate or saved copy)");
+  if (!g->seg[0].C) return nasrec_set_error(-2, "worklist: chained item without an output");
+  int h = 0;
+  for (int q = 1; q < g->nseg && !h; ++q)
+    if (g->seg[q].C == g->seg[0].C) h = q;
+  if (h < 1 || g->nseg % h != 0) return nasrec_set_error(-2, "worklist: chained item of %d problems: no second writer of the first output, or chains of unequal length", g->nseg);
+  const int N = g->seg[0].N;
+  if (N <= 0 || (N & 15)) return nasrec_set_error(-2, "worklist: chained item with N=%d (whole samples of 16 columns)", N);
+  int TU = 0;
+  for (int q = 0; q < g->nseg; ++q) {
+    const nasrec_gemm_seg_t &s = g->seg[q], &s0 = g->seg[q % h];
+    if (s.Aaux || s.ones_col || (s.Mvalid > 0 && s.Mvalid < s.M)) return nasrec_set_error(-2, "worklist: chained problem %d has a weight mask, a ones column or a row predicate", q);
+    if (s.K > 16 * WL_TOKDX_STEPS) return nasrec_set_error(-2, "worklist: chained problem %d has K=%d > %d", q, s.K, 16 * WL_TOKDX_STEPS);
+    if (s.M <= 0 || s.N != N) return nasrec_set_error(-2, "worklist: chained problem %d is %d x %d (N=%d everywhere)", q, s.M, s.N, N);
+    if (s.C != s0.C || s.M != s0.M || s.ldc != s0.ldc) return nasrec_set_error(-2, "worklist: chained problem %d does not write what problem %d writes", q, q % h);
+    if (q >= h && !s.accumulate) return nasrec_set_error(-2, "worklist: chained problem %d overwrites the sum of its predecessors", q);
+    if (q < h) TU += (s.M + 15) / 16;
+  }
+  it.geom[0] = TU;
+  it.geom[1] = h;
+  it.geom[2] = WL_TOKS | (2 << 2);
+  it.nblk = std::min(((N >> 4) * TU + 3) / 4, WL_TOK_MAX_WG);
+  return 0;
+}
+
 static int wl_gemm_geometry(const nasrec_gemm_desc_t* g, nasrec_wl_item_t& it, int blob_left) {
   if (blob_left < (int)offsetof(nasrec_gemm_desc_t, seg)) return nasrec_set_error(-2, "worklist: gemm descriptor head runs past the blob");
   if (g->nseg < 1 || g->nseg > NASREC_MAX_SEGS) return nasrec_set_error(-2, "worklist: gemm nseg=%d", g->nseg);
@@ -40,6 +73,7 @@ static int wl_gemm_geometry(const nasrec_gemm_desc_t* g, nasrec_wl_item_t& it, i
   const int nprob = g->zmode ? g->nseg : 1;
   const int S = g->splitk > 1 ? g->splitk : 1;
   if (g->splitk == NASREC_SPLITK_BALANCED) return nasrec_set_error(-2, "worklist: the balanced schedule is a throughput-regime launch");
+  if (it.part == NASREC_WL_CHAIN) return wl_chain_geometry(g, it);
   if ((it.part == 0) != (S == 1)) return nasrec_set_error(-2, "worklist: gemm part %d with splitk %d", it.part, g->splitk);
   if (S > 1 && !g->workspace) return nasrec_set_error(-3, "worklist: splitk=%d needs a workspace", S);
   int Mmax = 0, Nmax = 0, Kmax = 0;
@@ -598,6 +632,7 @@ int nasrec_persist_prepare(nasrec_persist_desc_t* d) {
   for (int k = 0; k < d->n; ++k) {
     nasrec_persist_item_t& p = tab[k];
     if (p.off < 0 || (p.off & 15) || p.off >= d->blob_bytes) return nasrec_set_error(-2, "persist: item %d offset %d", k, p.off);
+    if (p.kind == NASREC_OP_GEMM && p.part == NASREC_WL_CHAIN) return nasrec_set_error(-2, "persist: item %d is a chained product; the persistent form takes the unchained program", k);
     if (p.ndeps < 0 || p.ndeps > NASREC_PS_MAX_DEPS) return nasrec_set_error(-2, "persist: item %d has %d dependencies", k, p.ndeps);
     for (int q = 0; q < p.ndeps; ++q)
       if (p.deps[q] < 0 || p.deps[q] >= k) return nasrec_set_error(-2, "persist: item %d depends on item %d (not an earlier one)", k, p.deps[q]);

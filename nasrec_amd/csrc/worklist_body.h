@@ -407,6 +407,103 @@ __device__ __forceinline__ void wl_token_dx_unit(const nasrec_gemm_desc_t& g, in
   }
 }
 
+// CHAINED token-axis input gradients (item part NASREC_WL_CHAIN): the blob is a zmode descriptor of c h problems in which problems q, q + h,
+// ..., q + (c - 1) h — the MEMBERS of chain q — all add into the same C.  As c launches they run one after the other for no reason but that
+// buffer (the raw-embedding gradient of the batch-256 step has five such writers, each a level behind the last); here a wavefront owns the
+// 16 x 16 tile of chain q and computes every member's product with wl_token_dx_unit's loads, masks and MFMA order, then adds them in chain
+// order — v = acc_0 (+ old), v = acc_m + v — which are the very additions the members' epilogues perform through memory: the same bits,
+// one store instead of store + (load + store) per further member.  Members are taken two at a time: both members' operands are in flight
+// behind one wait (2 x 32 registers of operands, a mask operand's 16 applied member by member).  The launcher (wl_gemm_geometry) admits plain
+// epilogues only, so no epilogue code is needed here.
+__device__ __forceinline__ void wl_token_dx_chain_unit(const nasrec_gemm_desc_t& g, int unit, int TU, int h, int c, int e, int fg) {
+  const int b = unit / TU;
+  int t = unit - b * TU, q = 0;
+  while (q < h - 1 && t >= ((g.seg[q].M + 15) >> 4)) t -= (g.seg[q].M + 15) >> 4, ++q;  // (chain, row block) of this unit
+  const nasrec_gemm_seg_t& s0 = g.seg[q];
+  const int M = s0.M, ldc = s0.ldc, i0 = t * 16 + 4 * fg;
+  const int row = min(t * 16 + e, M - 1);
+  float* const Cp = s0.C;
+  long o[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) o[r] = c_offset<NASREC_CM_TOKJ>(min(i0 + r, M - 1), b * 16 + e, ldc);  // (clamped: rows >= M are read, never stored)
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  if (s0.accumulate) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = Cp[o[r]];
+  }
+  for (int m = 0; m < c; m += 2) {
+    float fa[2][WL_TOKDX_STEPS][4], fb[2][WL_TOKDX_STEPS][4];
+    int K2[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const nasrec_gemm_seg_t& sg = g.seg[q + min(m + u, c - 1) * h];
+      const bool live = m + u < c && sg.A != nullptr && sg.K > 0;  // (uniform)
+      const int K = live ? sg.K : 0;
+      K2[u] = K;
+      if (live) {
+        const float* wp = sg.A + row;                      // A(r, k) = A[k lda + r]
+        const float* yb = sg.B + (long)b * sg.ldb + e;     // B(j, k) = B[b ldb + e + 16 k]
+#pragma unroll
+        for (int s = 0; s < WL_TOKDX_STEPS; ++s)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int k = min(16 * s + 4 * fg + j, K - 1);  // (clamped, masked below)
+            fa[u][s][j] = wp[(long)k * sg.lda];
+            fb[u][s][j] = yb[k * 16];
+          }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const nasrec_gemm_seg_t& sg = g.seg[q + min(m + u, c - 1) * h];
+      const int K = K2[u];
+      if (K > 0 && sg.Baux) {  // fused ReLU backward of this member: B(j, k) counts as 0 where Baux(j, k) <= 0
+        const float* xb = sg.Baux + (long)b * sg.ldb + e;
+        float fx[WL_TOKDX_STEPS][4];
+#pragma unroll
+        for (int s = 0; s < WL_TOKDX_STEPS; ++s)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) fx[s][j] = xb[min(16 * s + 4 * fg + j, K - 1) * 16];
+#pragma unroll
+        for (int s = 0; s < WL_TOKDX_STEPS; ++s)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) fb[u][s][j] = fx[s][j] > 0.f ? fb[u][s][j] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int K = K2[u];
+      if (K <= 0) continue;  // a dead member contributes nothing
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < WL_TOKDX_STEPS; ++s) {
+        if (16 * s < K) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const bool in = 16 * s + 4 * fg + j < K;
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(in ? fa[u][s][j] : 0.f, in ? fb[u][s][j] : 0.f, acc, 0, 0, 0);
+          }
+        }
+      }
+      // the member's epilogue: C = acc, or C = acc + C (plain adds; only member 0 may overwrite — dead, it leaves the zeros v starts with)
+      const bool over = m + u == 0 && !s0.accumulate;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[r] = over ? acc[r] : acc[r] + v[r];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if (i0 + r < M) Cp[o[r]] = v[r];
+}
+__device__ __forceinline__ void wl_token_dx_chain(unsigned long long blob, int vb_, int TU_, int h_) {
+  const nasrec_gemm_desc_t& g = wl_ref<nasrec_gemm_desc_t>(blob);
+  const int vb = __builtin_amdgcn_readfirstlane(vb_), TU = __builtin_amdgcn_readfirstlane(TU_), h = __builtin_amdgcn_readfirstlane(h_);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  wl_warm_blob(blob, (int)offsetof(nasrec_gemm_desc_t, seg) + g.nseg * (int)sizeof(nasrec_gemm_seg_t));  // (the walks below read every segment's fields)
+  const int total = (g.seg[0].N >> 4) * TU, stride = 4 * min((total + 3) >> 2, WL_TOK_MAX_WG);
+  for (int unit = vb * 4 + wave; unit < total; unit += stride) wl_token_dx_chain_unit(g, unit, TU, h, g.nseg / h, lane & 15, lane >> 4);
+}
+
 __device__ __forceinline__ void wl_gemm_second_pass(unsigned long long blob, int vb_, int per_) {
   const nasrec_gemm_desc_t& g = wl_ref<nasrec_gemm_desc_t>(blob);
   const int vb = __builtin_amdgcn_readfirstlane(vb_), per = __builtin_amdgcn_readfirstlane(per_);
@@ -451,6 +548,7 @@ __device__ __forceinline__ void wl_mha_fwd(unsigned long long blob, int vb) {
 static inline int wl_item_body(int kind, int part, const int32_t (&geom)[3]) {
   if (kind != NASREC_OP_GEMM) return NASREC_WL_BODY_KIND;
   if (part == 2) return NASREC_WL_BODY_SECOND_PASS;
+  if (part == NASREC_WL_CHAIN) return NASREC_WL_BODY_TOKEN_DX_CHAIN;
   const int cfg = geom[2];  // tile | binding pair << 2 | mask operand << 4
   if ((cfg & 3) != WL_TOKS) return NASREC_WL_BODY_TILE;
   if (((cfg >> 2) & 3) == 3) return geom[1] == 0 ? NASREC_WL_BODY_DENSE_SMALL_DX : NASREC_WL_BODY_DENSE_SMALL;
@@ -495,6 +593,10 @@ __device__ __forceinline__ void wl_run(unsigned f01, unsigned f23, unsigned f45,
     case NASREC_OP_GEMM: {
       if (it_part == 2) {
         wl_gemm_second_pass(blob, vb, it.geom[0]);
+        break;
+      }
+      if (it_part == NASREC_WL_CHAIN) {  // (geom: units per sample, chains)
+        wl_token_dx_chain(blob, vb, it.geom[0], it.geom[1]);
         break;
       }
       const int cfg = it.geom[2];  // tile | binding pair << 2 | mask operand << 4 | WL_WIDE

@@ -534,7 +534,7 @@ class SupernetEngine:
                 fwd_list, cp.dead_forward = S.eliminate_dead_forward(fwd_list, ctx.bwd if train else [])
             if scheduled:
                 fwd_list = S.order_two_term_accumulates(fwd_list)
-                fwd_descs, cp.fwd_levels = S.pack(fwd_list)
+                fwd_descs, cp.fwd_levels = S.pack(S.chain_accumulates(fwd_list))
                 self._resident_worklists(cp, fwd_descs)
             else:
                 fwd_descs = fwd_list
@@ -596,12 +596,14 @@ class SupernetEngine:
                             import warnings
                             warnings.warn("persistent step refused (%s): one launch per level instead" % (e,))
                     if fb_descs is None:
-                        fb_descs, cp.fb_levels = S.pack(ids_in_program + jf + jb, alloc=ctx.alloc)
+                        # (level launches only: same-target input gradients become chained items — the persistent form takes the program as it is)
+                        joint = S.chain_accumulates(ids_in_program + jf + jb)
+                        fb_descs, cp.fb_levels = S.pack(joint, alloc=ctx.alloc)
                         if _WL_TUNE and S.BALANCE:
-                            fb_descs, cp.level_tuning = self._tune_levels(ids_in_program + jf + jb, ctx.alloc, fb_descs)
+                            fb_descs, cp.level_tuning = self._tune_levels(joint, ctx.alloc, fb_descs)
                     self._resident_worklists(cp, fb_descs)
                     cp.fb = Program(fb_descs)
-                    bwd_descs, cp.bwd_levels = S.pack(bwd_descs)
+                    bwd_descs, cp.bwd_levels = S.pack(S.chain_accumulates(bwd_descs))
                     self._resident_worklists(cp, bwd_descs)
                 cp.bwd = Program(bwd_descs)
                 cp.bwd_tail_start = len(pre) - 1 + ctx.bwd_tail_start  # cp.bwd.descs[this:] = the parked weight-gradient products

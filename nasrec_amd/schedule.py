@@ -75,7 +75,10 @@ def _cview(ptr, cmode, M, N, ldc):
 
 
 def _gemm_io(d, part):
-    """part: 'whole' | 'main' (operands -> split-K slabs) | 'epi' (slabs -> epilogue -> C)"""
+    """part: 'whole' | 'main' (operands -> split-K slabs) | 'epi' (slabs -> epilogue -> C) | 'chain' (chain_accumulates below: the merged
+    descriptor lists every member as a problem, so its footprints as a whole launch are already the union of the members')"""
+    if part == "chain":
+        part = "whole"
     R, W = [], []
     nprob = d.nseg if d.zmode else 1
     S = d.splitk if d.splitk > 1 else 1
@@ -320,6 +323,8 @@ def expand(descs, cut=lambda d: not d.defer_second_pass) -> List[Node]:
         if isinstance(d, L.GemmDesc) and d.splitk > 1 and cut(d):
             nodes.append(Node(d, "main"))
             nodes.append(Node(d, "epi"))
+        elif getattr(d, "_chain", 0):  # (a product of chain_accumulates)
+            nodes.append(Node(d, "chain"))
         else:
             nodes.append(Node(d))
     for i, n in enumerate(nodes):
@@ -621,12 +626,94 @@ def order_two_term_accumulates(fwd):
     return fwd
 
 
+CHAIN = os.environ.get("NASREC_WL_CHAIN", "1") != "0"  # (A/B knob)
+_CHAIN_HEAD = ("amode", "bmode", "cmode", "zmode", "act", "dims_in_use", "splitk", "defer_second_pass", "bias", "save_z", "save_act", "mul_nseg",
+               "pre_add", "bias_on_rows", "mask_on_rows")
+
+
+def _merged_chain(P, Q):
+    """P (an input-gradient launch or an earlier chain of h problems per member) with Q's problems appended as the next member, marked
+    `_chain = h` — or None when the two do not write the same outputs problem for problem, Q overwrites, or the launcher has no chained
+    body for the result (csrc/worklist.hip wl_chain_geometry: bindings, depths, epilogue, masks — asked, not restated here)"""
+    h = getattr(P, "_chain", 0) or P.nseg
+    if Q.nseg != h or P.nseg + h > L.MAX_SEGS or any(getattr(P, f) != getattr(Q, f) for f in _CHAIN_HEAD):
+        return None
+    for q in range(h):
+        p, s = P.seg[q], Q.seg[q]
+        if not s.C or (s.C, s.M, s.N, s.ldc) != (p.C, p.M, p.N, p.ldc) or not s.accumulate:
+            return None
+    m = _copy_desc(P)
+    for q in range(h):
+        m.seg[P.nseg + q] = Q.seg[q]
+    m.nseg = P.nseg + h
+    m._chain = h
+    m._chain_of = getattr(P, "_chain_of", (P,)) + (Q,)  # (the members, in chain order: reports, and whatever they keep alive)
+    return m if item_geometry(m.kind, "chain", _gemm_bytes(m)) is not None else None
+
+
+def chain_accumulates(descs):
+    """Several token-axis input gradients (W^T dy per input segment) may add into the same buffers — the raw-embedding gradient of the
+    batch-256 step has five such writers — and assign_levels puts each a level behind the last for no reason but that buffer: Q, whose
+    operands were ready long ago, waits for its turn behind P, and whatever reads the sum waits for Q.  Where the pair is P before Q,
+    both unsplit products the launcher has the wavefront-per-tile body for, Q adds everywhere onto exactly what P writes, nothing between
+    them touches those buffers, one of them can move next to the other, and Q's operands are ready by P's level, the two become ONE node:
+    a copy of P with Q's problems appended (`_chain`: problems per member), which the worklist kernel runs as a chained item
+    (csrc/worklist_body.h wl_token_dx_chain: every member's product in one unit, added in chain order — the bits of the separate
+    launches, one store).  Repeats until nothing changes: a third writer joins the chain of the first two when the condition holds again.
+    -> new descriptor list (the same objects where nothing changed).  Scheduling only: the plan's descriptors are what they were."""
+    if not CHAIN:
+        return descs
+    nodes = expand_for_worklists(descs)
+    assign_levels(nodes)
+
+    def candidate(n):
+        d = n.desc
+        return (n.part in ("whole", "chain") and isinstance(d, L.GemmDesc) and d.zmode and d.splitk <= 1 and n.reads is not None
+                and 1 <= d.nseg <= L.MAX_SEGS)
+
+    for ip, p in enumerate(nodes):
+        if not candidate(p):
+            continue
+        P = p.desc
+        h = getattr(P, "_chain", 0) or P.nseg
+        cs = [c for c in (_cview(P.seg[q].C, P.cmode, P.seg[q].M, P.seg[q].N, P.seg[q].ldc) for q in range(h)) if c is not None]
+        if len(cs) != h:
+            continue
+        # Q: the first node behind P that reads or writes one of P's outputs (so nothing between the two does)
+        iq = next((i for i in range(ip + 1, len(nodes))
+                   if nodes[i].reads is None or any(overlap(a, c) for c in cs for a in nodes[i].reads + nodes[i].writes)), None)
+        if iq is None or nodes[iq].part != "whole" or not candidate(nodes[iq]):
+            continue
+        q = nodes[iq]
+        between = range(ip + 1, iq)
+        if not any(_depends(q, nodes[i]) for i in between):
+            up = True   # Q moves up to P: nothing in between feeds it
+        elif not any(_depends(nodes[i], p) for i in between):
+            up = False  # P moves down to Q: nothing in between waits for it or overwrites one of its operands
+        else:
+            continue
+        ready_q = max([nodes[j].level + 1 for j in range(iq) if j != ip and _depends(q, nodes[j])] + [0])
+        if ready_q > p.level:
+            continue  # Q would hold the pair back: no level is gained
+        if p.part == "whole" and (p.item is None or p.item[1].body != L.WL_BODY_TOKEN_DX):
+            continue
+        if q.item is None or q.item[1].body != L.WL_BODY_TOKEN_DX:
+            continue
+        m = _merged_chain(P, q.desc)
+        if m is None:
+            continue
+        out = [d for d in descs if d is not (q.desc if up else P)]
+        out[next(k for k, d in enumerate(out) if d is (P if up else q.desc))] = m
+        return chain_accumulates(out)  # (levels have moved: look again)
+    return descs
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # packing levels into NASREC_OP_WORKLIST launches
 # ----------------------------------------------------------------------------------------------------------------
 _GEMM_HEAD = L.GemmDesc.seg.offset
 _SEG_BYTES = C.sizeof(L.GemmSeg)
-_PART = {"whole": L.WL_WHOLE, "main": L.WL_MAIN, "epi": L.WL_EPI}
+_PART = {"whole": L.WL_WHOLE, "main": L.WL_MAIN, "epi": L.WL_EPI, "chain": L.WL_CHAIN}
 
 
 def item_geometry(kind, part, b):
@@ -679,7 +766,7 @@ def _item(node):
     """Node.item: (the bytes a worklist item carries for this node, their geometry), or None if the node does not travel as an item"""
     d = node.desc
     if isinstance(d, L.GemmDesc):
-        if not _gemm_wanted(d):
+        if node.part != "chain" and not _gemm_wanted(d):  # (a chained product ALWAYS travels as an item: launched as a plain zmode kernel its members would race on C)
             return None
         b = _gemm_bytes(d)
     elif d.kind == L.OP_REDUCE_ROWS and d.ndst <= L.WL_REDUCE_DST:  # (the compact form has room for that many destinations)
@@ -794,7 +881,7 @@ def pack(descs, alloc=None):
             b = item_bytes(n)
             (items if b is not None else solo).append((n, b))
         for n, _ in solo:
-            assert n.part == "whole"
+            assert n.part == "whole", n.part
             out.append(n.desc)
         if len(items) == 1 and items[0][0].part == "whole" and not _item_beats_kernel(items[0][0].desc):
             out.append(items[0][0].desc)  # nothing to share a launch with: the stand-alone kernel

@@ -54,7 +54,7 @@ if __name__ == "__main__":
     cfgp = os.path.join(ROOT, "nasrec_amd", "configs", "criteo", "ea_criteo_kaggle_xlarge_best_1shot.json")
     ctx = build_cpu_plan(cfgp, 256, 13, 26, defer_dw=("--defer" in sys.argv))
     for name, prog in (("forward", ctx.fwd), ("backward", ctx.bwd)):
-        lv = S.levels_of(prog)
+        lv = S.levels_of(S.chain_accumulates(list(prog)))  # (NASREC_WL_CHAIN=0: the program as planned; GEMM[chain] = a chained item)
         print("%s: %d descriptors -> %d nodes in %d levels" % (name, len(prog), sum(len(x) for x in lv), len(lv)))
         for i, nodes in enumerate(lv):
             print("  L%-2d %s" % (i, " || ".join(describe(n) for n in nodes)))
