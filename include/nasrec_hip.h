@@ -590,9 +590,17 @@ typedef struct nasrec_weight_decay_desc {
  * by phase 1, which runs with tile_off all zero.
  * Refused (-1, nothing launched): table_algo != 0 with algo != NASREC_OPTIM_ADAM, with sparse_rows != 0, with table_eps <= 0, with
  * reg_mask != 0 or a table owning a tile in phase 1; an unknown table_algo.
+ *
+ * table_algo = NASREC_TABLE_ALGO_ROWWISE_ADAGRAD (3; the value 2 is unknown and refused): the same split with row-wise Adagrad on the
+ * tables — one accumulator per ROW, fed the mean of the row's squared gradient.  tv[f] points at rows[f] floats, ONE per row; tm is never
+ * read or written.  A leader row with its id in range, g = its summed gradient * coef (16 floats), tlr = lr * table_lr_scale:
+ *   sum[row] = sum[row] + (g[0]^2 + ... + g[15]^2) / 16;  p[e] = p[e] - tlr * (g[e] / (sqrt(sum[row]) + table_eps)),  e = 0 .. 15
+ * A zero gradient changes neither, so it is exactly row-sparse in the same way: no bit is marked, every other row keeps its bits in
+ * table and tv, steps are counted as above.  The same refusals as NASREC_TABLE_ALGO_ADAGRAD.
  * ---------------------------------------------------------------------------------------------- */
 #define NASREC_TABLE_ALGO_SAME 0    /* the tables take `algo` */
 #define NASREC_TABLE_ALGO_ADAGRAD 1 /* Adagrad on the tables (above) */
+#define NASREC_TABLE_ALGO_ROWWISE_ADAGRAD 3 /* row-wise Adagrad on the tables: tv[f] = one float per row (above) */
 typedef struct nasrec_opt_moments_desc {
   int32_t kind;  /* NASREC_OP_OPT_MOMENTS */
   int32_t phase; /* 0 / 1 (above); 2 = RMSprop's flush */
@@ -638,7 +646,7 @@ typedef struct nasrec_opt_moments_desc {
                           *   (the slot of a padding word): NASREC_TABLE_ALGO_ADAGRAD: the tables' learning rate as a multiple of *lr */
   int64_t rank_stride;
   int32_t sparse_rows;   /* 0 = every table row moves every step; != 0 = row-sparse Adam (above) */
-  int32_t table_algo;    /* NASREC_TABLE_ALGO_SAME / NASREC_TABLE_ALGO_ADAGRAD (above; the slot of a padding word) */
+  int32_t table_algo;    /* NASREC_TABLE_ALGO_SAME / _ADAGRAD / _ROWWISE_ADAGRAD (above; the slot of a padding word) */
 } nasrec_opt_moments_desc_t;
 
 /* ------------------------------------------------------------------------------------------------

@@ -40,7 +40,7 @@ OP_WEIGHT_DECAY = 39
 OP_OPT_MOMENTS = 40
 OP_LAST_LAYER_STEP = 41
 OPTIM_ADAGRAD, OPTIM_ADAM, OPTIM_SGD, OPTIM_RMSPROP = 0, 1, 2, 3  # NASREC_OPTIM_* (algorithm of NASREC_OP_OPT_MOMENTS / _LAST_LAYER_STEP)
-TABLE_ALGO_SAME, TABLE_ALGO_ADAGRAD = 0, 1  # NASREC_TABLE_ALGO_* (nasrec_opt_moments_desc_t.table_algo: the split optimizer)
+TABLE_ALGO_SAME, TABLE_ALGO_ADAGRAD, TABLE_ALGO_ROWWISE_ADAGRAD = 0, 1, 3  # NASREC_TABLE_ALGO_* (nasrec_opt_moments_desc_t.table_algo: the split optimizer)
 LAST_LAYER_MAX = 8192  # NASREC_LAST_LAYER_MAX: K + 1 of NASREC_OP_LAST_LAYER_STEP
 OP_ROC_AUC = 42
 OP_WEIGHT_EMA = 43

@@ -4,7 +4,7 @@
 // (a zero gradient still moves a row whose moments are non-zero: W and its one or two moment arrays, read and written once) and,
 // in the workgroup that finishes last, counts the step of every parameter it updated.
 // Phase 0 is one kernel, opt_moments_phase0_kernel<Rows>; what happens to one touched row, and whether the launch marks the bitmap or
-// counts the steps itself, is the row policy `Rows` (DenseRows, SparseAdamRows, LazyRmspropRows, AdagradTableRows below).
+// counts the steps itself, is the row policy `Rows` (DenseRows, SparseAdamRows, LazyRmspropRows, AdagradTableRows, RowwiseAdagradTableRows below).
 // Row-sparse Adam (sparse_rows, include/nasrec_hip.h): the same clip and dense chunks, torch.optim.SparseAdam on the touched rows, no
 // bitmap, and no phase 1 unless weight decay has gradients to restore.
 // RMSprop (NASREC_OPTIM_RMSPROP: momentum 0, not centered): a row whose gradient is zero does not move and its square_avg only decays,
@@ -190,6 +190,41 @@ struct AdagradTableRows {
   }
 };
 
+// Row-wise Adagrad on the tables (table_algo = NASREC_TABLE_ALGO_ROWWISE_ADAGRAD; Adam on the dense chunks): tv[f] holds ONE float per
+// row, the accumulator of the mean of the row's squared gradient; sum += mean(g^2), then Adagrad's weight statement with that one sum
+// for all 16 elements, at lr * table_lr_scale and table_eps.  tm is never read or written, no bit is marked, and a zero gradient leaves
+// sum and W as they are, as with AdagradTableRows.
+struct RowwiseAdagradTableRows {
+  static constexpr int DENSE = NASREC_OPTIM_ADAM;
+  static constexpr bool COUNTS = true;
+  __device__ __forceinline__ void scalars(const nasrec_opt_moments_desc_t&, float) {}
+  __device__ __forceinline__ void row(const nasrec_opt_moments_desc_t& d, int f, long row, int q, const f32x4& g4, float lr) const {
+    const long o = row * 16 + q * 4;
+    const float tlr = lr * d.table_lr_scale;
+    f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o);
+    float s = d.tv[f][row];  // (all four lanes load it; lane q == 0 stores it below, after the loads in program order)
+    float sq = g4[0] * g4[0];
+    sq = fmaf(g4[1], g4[1], sq);
+    sq = fmaf(g4[2], g4[2], sq);
+    sq = fmaf(g4[3], g4[3], sq);
+    // Sum over the row's four lanes, into each of them (a + b is commutative: the four totals have the same bits).  The quad is the
+    // aligned lanes 4k .. 4k + 3 of one wavefront, and its lanes arrive here together or not at all: every branch in front of this
+    // (pair < B * Fs, leader[pair], the row-range test) is a function of `pair` = t >> 2 alone.  quad_perm reads inside the quad only,
+    // so the other quads of the wavefront may be inactive.  A branch on q in front of this line would break it.
+    sq += dpp_mov<0xb1>(sq);  // quad_perm:[1,0,3,2]
+    sq += dpp_mov<0x4e>(sq);  // quad_perm:[2,3,0,1]
+    s += sq * 0.0625f;        // (the mean of 16: an exact scaling)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float pe = p4[e];
+      adagrad_weight(g4[e], s, pe, tlr, d.table_eps);
+      p4[e] = pe;
+    }
+    *reinterpret_cast<f32x4*>(d.table[f] + o) = p4;
+    if (q == 0) d.tv[f][row] = s;
+  }
+};
+
 template <class Rows>
 __global__ __launch_bounds__(256) void opt_moments_phase0_kernel(const nasrec_opt_moments_desc_t d) {
   __shared__ float sh_coef;
@@ -305,13 +340,14 @@ void launch_phase1(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
 }  // namespace
 
 // Every refusal comes before anything is launched.  The row form — dense (every row moves: bitmap + phase 1), row-sparse Adam, lazy
-// RMSprop, Adagrad on the tables — decides what a launch needs; the last three move the batch's rows only, so their phase 0 counts the
+// RMSprop, Adagrad or row-wise Adagrad on the tables — decides what a launch needs; all but the first move the batch's rows only, so their phase 0 counts the
 // steps unless zero_chunks call for a phase 1, which then owns no tile.  Phase 2 is RMSprop's flush.
 int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
   if (d->Fs < 0 || d->Fs > NASREC_MAX_TABLES) return nasrec_set_error(-1, "opt_moments: Fs = %d", d->Fs);
   if (!d->lr || !d->step) return nasrec_set_error(-1, "opt_moments: lr / step missing");
   const bool adam = d->algo == NASREC_OPTIM_ADAM, rmsprop = d->algo == NASREC_OPTIM_RMSPROP;
-  const bool split = d->table_algo == NASREC_TABLE_ALGO_ADAGRAD, lazy = rmsprop || d->sparse_rows || split;
+  const bool rowwise = d->table_algo == NASREC_TABLE_ALGO_ROWWISE_ADAGRAD;  // (tv: one float per row)
+  const bool split = d->table_algo == NASREC_TABLE_ALGO_ADAGRAD || rowwise, lazy = rmsprop || d->sparse_rows || split;
   if (d->table_algo != NASREC_TABLE_ALGO_SAME && !split) return nasrec_set_error(-1, "opt_moments: table_algo %d", d->table_algo);
   if (split && !adam) return nasrec_set_error(-1, "opt_moments: table_algo (Adagrad on the tables) goes with Adam on the rest (algo %d)", d->algo);
   if (split && d->sparse_rows) return nasrec_set_error(-1, "opt_moments: table_algo with sparse_rows: the tables take one rule");
@@ -338,6 +374,7 @@ int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
     if (lazy && d->n_zero <= 0 && (!d->counter || (d->n_inc > 0 && !d->inc)))
       return nasrec_set_error(-1, "opt_moments: %s without zero_chunks counts the steps: counter / inc missing", lazy_name);
     if (rmsprop) launch_phase0<LazyRmspropRows>(st, d, nblk);
+    else if (rowwise) launch_phase0<RowwiseAdagradTableRows>(st, d, nblk);
     else if (split) launch_phase0<AdagradTableRows>(st, d, nblk);
     else if (d->sparse_rows) launch_phase0<SparseAdamRows>(st, d, nblk);
     else if (adam) launch_phase0<DenseRows<NASREC_OPTIM_ADAM>>(st, d, nblk);

@@ -133,9 +133,11 @@ __device__ __forceinline__ void clip_head(const nasrec_clip_coef_desc_t& clip, f
 // (NASREC_OP_OPT_MOMENTS); NASREC_OP_LAST_LAYER_STEP calls the same functions.  D = a descriptor with beta1, beta2, eps, momentum,
 // nesterov.
 // ---------------------------------------------------------------------------------------------------
+// Adagrad's weight statement with the accumulator `s` already current (shared with row-wise Adagrad, whose s is one number per row)
+__device__ __forceinline__ void adagrad_weight(float g, float s, float& p, float lr, float eps) { p = p - lr * (g / (sqrtf(s) + eps)); }
 __device__ __forceinline__ void adagrad_elem(float g, float& s, float& p, float lr, float eps) {
   s = fmaf(g, g, s);
-  p = p - lr * (g / (sqrtf(s) + eps));
+  adagrad_weight(g, s, p, lr, eps);
 }
 
 // Adam's per-parameter scalars of this step, from the step counter as torch computes them in Python doubles (torch/optim/adam.py,

@@ -324,6 +324,7 @@ class SupernetEngine:
             else:
                 self.tables = [torch.zeros(n, E, dtype=torch.float32, device=self.device) for n in self.num_embeddings]
             self.table_state: Optional[List[torch.Tensor]] = None
+            self.table_row_state: Optional[List[torch.Tensor]] = None  # (row-wise Adagrad on the tables: one float per row)
             self.lr_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
             self.clip_out = torch.ones(2, dtype=torch.float32, device=self.device)  # [coef, total_norm]
             self.oob = torch.zeros(2, dtype=torch.int32, device=self.device)  # [index out of range, dedup hash partition overflow]
@@ -386,6 +387,9 @@ class SupernetEngine:
             if self.table_state is not None:
                 for t in self.table_state:
                     t.zero_()
+            if self.table_row_state is not None:
+                for t in self.table_row_state:
+                    t.zero_()
         self.stream.synchronize()
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
@@ -398,6 +402,20 @@ class SupernetEngine:
         if self.table_state is None:
             with torch.cuda.stream(self.stream):
                 self.table_state = [torch.zeros_like(t) for t in self.tables]
+
+    def _ensure_table_row_state(self):
+        """row-wise Adagrad's accumulators (OptimSpec.table_kind "rowwise_adagrad"): per table one fp32 per row, zero, on first use.
+        Never `table_state`: the Adagrad apply launch and weight decay's phase 1 index that as [rows, 16]."""
+        if getattr(self, "table_row_state", None) is None:
+            with torch.cuda.stream(self.stream):
+                self.table_row_state = [torch.zeros(t.shape[0], dtype=torch.float32, device=self.device) for t in self.tables]
+
+    def _ensure_split_table_state(self, spec):
+        """the tables' state of a split-optimizer spec: `table_row_state` for the row-wise rule, `table_state` for the element-wise one"""
+        if spec.table_kind == "rowwise_adagrad":
+            self._ensure_table_row_state()
+        else:
+            self._ensure_table_state()
 
     # -------------------------------------------------------------------------------------------------------
     @_on_device
@@ -527,7 +545,7 @@ class SupernetEngine:
             cp.dead_forward = []
             if train:  # (the backward program decides which forward results are read: built further down, before the packing)
                 if not spec.moments or spec.table_kind:  # (Adagrad's table state: Adam / SGD keep theirs in `moments` instead)
-                    self._ensure_table_state()
+                    self._ensure_split_table_state(spec)
                 self._build_training_tail(cp, ctx, w, bptr, fsegs, B, K, grad_scale)
             fwd_list = list(ctx.fwd)
             if self.dead_code_elimination and cfg.fixed:
@@ -842,7 +860,7 @@ class SupernetEngine:
         """Adam's exp_avg / exp_avg_sq or SGD's momentum_buffer for the dense arena (flat, the layout of flat_p) and for every table,
         allocated on first use, zero; and the per-parameter step counters (dense parameters in dense_names order, then the tables).
         tables = False (the split optimizer, OptimSpec.table_kind): the dense arena's arrays only — the tables' state is Adagrad's
-        `table_state`, and no moment array the size of a table is allocated ([] until a plan that needs them asks).
+        `table_state` (row-wise: `table_row_state`), and no moment array the size of a table is allocated ([] until a plan that needs them asks).
         "rmsprop": square_avg, and `lazy_stamps` — per table one int32 per row, the table's step count at which that row's square_avg
         is current (csrc/optim_moments.hip); engine-private, never part of optimizer.state.
         -> {state key: (flat arena, [table arrays])}"""
@@ -871,7 +889,7 @@ class SupernetEngine:
         if name.startswith("_embedding."):
             if not tabs:
                 raise L.EngineError("no %s of %s: with Adagrad on the tables (OptimSpec.table_kind) their state is table_state, "
-                                    "Adagrad's sum" % (key, name))
+                                    "Adagrad's sum (row-wise: table_row_state)" % (key, name))
             return tabs[int(name.split(".")[1])]
         o, n = self.offsets[name], self.params[name].numel()
         return flat[o:o + n].view(self.params[name].shape)
@@ -955,8 +973,8 @@ class SupernetEngine:
     @staticmethod
     def _optim_scalars(d, spec):
         """algo and hyperparameters of an Adam / SGD spec on an OptMomentsDesc or a LastLayerStepDesc"""
-        if spec.table_kind not in ("", "adagrad") or (spec.table_kind and spec.kind != "adam"):
-            raise L.EngineError("table_kind %r with %s: the split optimizer is Adam with Adagrad on the tables" % (spec.table_kind, spec.kind))
+        if spec.table_kind not in ("", "adagrad", "rowwise_adagrad") or (spec.table_kind and spec.kind != "adam"):
+            raise L.EngineError("table_kind %r with %s: the split optimizer is Adam with (row-wise) Adagrad on the tables" % (spec.table_kind, spec.kind))
         d.algo = {"adam": L.OPTIM_ADAM, "rmsprop": L.OPTIM_RMSPROP}.get(spec.kind, L.OPTIM_SGD)
         d.eps, d.momentum, d.nesterov = spec.eps, spec.momentum, int(bool(spec.nesterov))
         d.beta1, d.beta2 = spec.beta1, (spec.alpha if spec.kind == "rmsprop" else spec.beta2)  # (RMSprop's alpha travels in beta2)
@@ -968,18 +986,20 @@ class SupernetEngine:
         then counts the steps itself; with them phase 1 runs in its no-table-moves form on all its workgroups (the ranges of a supernet
         are millions of floats).  RMSprop: the same shape of launches (its rows rest too, owing only a decay); m is unused and the
         slots of `tm` carry the stamps.  Adagrad on the tables (spec.table_kind): the same shape again; tv carries `table_state`, tm
-        nothing, and the tables' learning rate is lr * table_lr_scale in the kernel."""
+        nothing, and the tables' learning rate is lr * table_lr_scale in the kernel; row-wise Adagrad: tv carries `table_row_state`,
+        one float per row."""
         spec = t.spec
         st = self.moments
         lazy = spec.rows_only  # (the tables move in the batch's rows only)
-        split = spec.table_kind == "adagrad"
+        split, rowwise = bool(spec.table_kind), spec.table_kind == "rowwise_adagrad"
         m = L.OptMomentsDesc()
         m.kind, m.phase = L.OP_OPT_MOMENTS, 0
         self._optim_scalars(m, spec)
         m.dense_blocks = min(2048, t.mom_chunks[1])
         m.sparse_rows = int(bool(spec.sparse_rows))
         if split:
-            m.table_algo, m.table_eps, m.table_lr_scale = L.TABLE_ALGO_ADAGRAD, spec.table_eps, spec.table_lr_scale
+            m.table_algo = L.TABLE_ALGO_ROWWISE_ADAGRAD if rowwise else L.TABLE_ALGO_ADAGRAD
+            m.table_eps, m.table_lr_scale = spec.table_eps, spec.table_lr_scale
         m.nblocks = self.WD_BLOCKS if (t.mom_tables or lazy) else 1  # (no table moves: phase 1 only counts the step and restores g)
         m.B, m.Fs = (Bg, self.Fs) if gsum is not None else (0, self.Fs)
         m.table_step0 = len(self.dense_names)
@@ -1001,7 +1021,7 @@ class SupernetEngine:
         self._tile_layout(m, lambda f: f in t.mom_tables and not lazy)  # (a table that does not move owns no tile)
         for f in range(self.Fs):
             if split:  # (Adagrad's accumulators; the kernel never looks at tm)
-                m.tv[f] = self.table_state[f].data_ptr()
+                m.tv[f] = (self.table_row_state if rowwise else self.table_state)[f].data_ptr()
                 continue
             m.tm[f] = first[1][f].data_ptr()
             if second is not None:

@@ -43,7 +43,8 @@ def train_and_eval_one_model(model, args):
         raise NotImplementedError("Loss function {} is not implemented!".format(args.loss_function))
     loss_fn = torch.nn.BCEWithLogitsLoss()
     model.apply(init_weights)
-    optimizer = build_optimizer(args.optimizer, model, args.learning_rate, args.table_lr_scale, args.table_eps)
+    optimizer = build_optimizer(args.optimizer, model, args.learning_rate, args.table_lr_scale, args.table_eps,
+                                table_rowwise=args.table_rowwise)
     steps_per_epoch = args.train_limit // args.train_batch_size
     # (the warm-up shrinks with the number of epochs here — :134 — unlike main_train.py)
     lr_scheduler = build_lr_scheduler(args.lr_schedule, optimizer, steps_per_epoch * args.num_epochs, steps_per_epoch // 10 // args.num_epochs,
@@ -128,6 +129,9 @@ def build_parser():
                         "(Adam's 1e-3 with 160 gives the tables 0.16)")
     p.add_argument("--table-eps", dest="table_eps", type=float, default=1e-2,
                    help="--optimizer adam-adagrad-tables: eps of the tables' Adagrad (> 0)")
+    p.add_argument("--table-rowwise", dest="table_rowwise", action="store_true",
+                   help="--optimizer adam-adagrad-tables: row-wise Adagrad on the tables — one accumulator per embedding row, fed the "
+                        "mean of the row's squared gradient (1/16 of the element-wise state); refused with any other --optimizer")
     p.add_argument("--loss_function", type=str, default="bce", choices=["bce"])
     p.add_argument("--gpu", type=int, default=0, help="GPU ID to use.")
     p.add_argument("--matmul-precision", dest="matmul_precision", type=str, default="highest", choices=["highest", "high", "medium"],

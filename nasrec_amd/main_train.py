@@ -43,11 +43,14 @@ def summary_writer(logging_dir):
         return None
 
 
-def build_optimizer(name, model, lr, table_lr_scale=1.0, table_eps=1e-2):
+def build_optimizer(name, model, lr, table_lr_scale=1.0, table_eps=1e-2, table_rowwise=False):
     """main_train.py:150-160 (Adagrad eps 1e-2; Adam eps 1e-8; SGD nesterov momentum 0.9); row-sparse-adam: Adam's lr and eps, the
     tables moving in the batch's rows only (utils/optim.RowSparseAdam); rmsprop: torch's defaults (alpha 0.99, eps 1e-8) as
     utils/optim.LazyRMSprop, which is torch.optim.RMSprop and the type the fused step takes; adam-adagrad-tables: Adam's lr and eps
-    on the dense parameters, Adagrad with lr * table_lr_scale and table_eps on the tables (utils/optim.AdamAdagradTables)"""
+    on the dense parameters, Adagrad with lr * table_lr_scale and table_eps on the tables (utils/optim.AdamAdagradTables), row-wise
+    Adagrad with table_rowwise — which goes with that optimizer only"""
+    if table_rowwise and name != "adam-adagrad-tables":
+        raise ValueError("--table-rowwise is the tables' rule of --optimizer adam-adagrad-tables; it does nothing with --optimizer %s" % name)
     if name == "adagrad":
         return torch.optim.Adagrad(model.parameters(), lr=lr, eps=1e-2)
     if name == "adam":
@@ -63,7 +66,7 @@ def build_optimizer(name, model, lr, table_lr_scale=1.0, table_eps=1e-2):
     if name == "adam-adagrad-tables":
         from nasrec_amd.utils.optim import AdamAdagradTables
         return AdamAdagradTables(model.parameters(), list(model._embedding.parameters()), lr=lr, eps=1e-8, table_lr_scale=table_lr_scale,
-                                 table_eps=table_eps)
+                                 table_eps=table_eps, table_rowwise=table_rowwise)
     if name == "rmsprop":
         from nasrec_amd.utils.optim import LazyRMSprop
         return LazyRMSprop(model.parameters(), lr=lr)
@@ -93,7 +96,8 @@ def train_and_eval_one_model(model, args):
 
     l2_loss_fn = L2Loss(args.wd, args.no_reg_param_name, gpu=args.gpu)  # (a spec the fused engine step folds in: any --wd)
 
-    optimizer = build_optimizer(args.optimizer, model, args.learning_rate, args.table_lr_scale, args.table_eps)
+    optimizer = build_optimizer(args.optimizer, model, args.learning_rate, args.table_lr_scale, args.table_eps,
+                                table_rowwise=args.table_rowwise)
     steps_per_epoch = args.train_limit // args.train_batch_size
     num_train_steps = steps_per_epoch * args.num_epochs
     num_warmup_steps = steps_per_epoch // 10 // args.num_epochs
@@ -198,6 +202,9 @@ def build_parser():
                         "(Adam's 1e-3 with 160 gives the tables 0.16)")
     p.add_argument("--table-eps", dest="table_eps", type=float, default=1e-2,
                    help="--optimizer adam-adagrad-tables: eps of the tables' Adagrad (> 0)")
+    p.add_argument("--table-rowwise", dest="table_rowwise", action="store_true",
+                   help="--optimizer adam-adagrad-tables: row-wise Adagrad on the tables — one accumulator per embedding row, fed the "
+                        "mean of the row's squared gradient (1/16 of the element-wise state); refused with any other --optimizer")
     # Criteo: train 36672495 / val 4584061 / test 4584061 / trainval 41256556; Avazu: 32343175 / 4042896 / 4042896 / 36386071;
     # KDD: 119711284 / 14963910 / 14963910 / 134675194
     p.add_argument("--train_limit", type=int, default=41256556, help="Maximum number of training examples.")

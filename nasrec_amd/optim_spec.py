@@ -22,7 +22,9 @@ class OptimSpec(NamedTuple):
     sparse_rows: bool = False  # Adam: row-sparse on the tables (utils/optim.RowSparseAdam: torch.optim.SparseAdam on the batch's rows)
     alpha: float = 0.99     # RMSprop's smoothing constant (utils/optim.LazyRMSprop: momentum 0, not centered)
     table_kind: str = ""    # "" = the tables take `kind`; "adagrad" (kind "adam": utils/optim.AdamAdagradTables) = torch.optim.Adagrad on
-                            # the tables, exactly row-sparse, with table_eps and the learning rate lr * table_lr_scale
+                            # the tables, exactly row-sparse, with table_eps and the learning rate lr * table_lr_scale;
+                            # "rowwise_adagrad" (AdamAdagradTables(table_rowwise=True)) = the same with ONE accumulator per row, fed
+                            # the mean of the row's squared gradient
     table_eps: float = 1e-2
     table_lr_scale: float = 1.0
     dwd: float = 0.0        # decoupled weight decay p <- p (1 - lr dwd) before the update (utils/optim.DecoupledWeightDecay,
@@ -38,8 +40,8 @@ class OptimSpec(NamedTuple):
     @property
     def rows_only(self) -> bool:
         """the tables move in the batch's rows only (a row outside it keeps its bits, or owes only a closed-form factor): Adagrad,
-        row-sparse Adam, RMSprop and Adam with Adagrad on the tables"""
-        return self.kind in ("adagrad", "rmsprop") or bool(self.sparse_rows) or self.table_kind == "adagrad"
+        row-sparse Adam, RMSprop and Adam with Adagrad (element- or row-wise) on the tables"""
+        return self.kind in ("adagrad", "rmsprop") or bool(self.sparse_rows) or self.table_kind in ("adagrad", "rowwise_adagrad")
 
     @property
     def state_keys(self):
@@ -72,7 +74,8 @@ class OptimSpec(NamedTuple):
         Adam: one group, amsgrad, weight_decay, maximize, capturable, differentiable and fused all off.
         SGD: one group, momentum != 0 (plain SGD keeps the torch route), dampening 0, weight_decay 0, not maximize / differentiable / fused.
         RowSparseAdam: Adam's conditions (its one group carries Adam's keys) -> sparse_rows.
-        AdamAdagradTables: Adam's conditions -> table_kind "adagrad" with the group's table_eps / table_lr_scale (plain numbers).
+        AdamAdagradTables: Adam's conditions -> table_kind "adagrad", or "rowwise_adagrad" where the group's table_rowwise is set, with
+        the group's table_eps / table_lr_scale (plain numbers).
         LazyRMSprop (that type exactly: a hand-built torch.optim.RMSprop keeps the torch route): one group, momentum 0, not centered,
         weight_decay 0, not maximize / capturable / differentiable."""
         from .utils.optim import AdamAdagradTables, LazyRMSprop, RowSparseAdam
@@ -90,7 +93,8 @@ class OptimSpec(NamedTuple):
             if type(optimizer) is AdamAdagradTables:
                 if torch.is_tensor(g["table_eps"]) or torch.is_tensor(g["table_lr_scale"]) or torch.is_tensor(g["eps"]):
                     return None
-                return OptimSpec("adam", beta1=float(b1), beta2=float(b2), eps=float(g["eps"]), table_kind="adagrad",
+                return OptimSpec("adam", beta1=float(b1), beta2=float(b2), eps=float(g["eps"]),
+                                 table_kind="rowwise_adagrad" if g.get("table_rowwise", False) else "adagrad",
                                  table_eps=float(g["table_eps"]), table_lr_scale=float(g["table_lr_scale"]))
             return OptimSpec("adam", beta1=float(b1), beta2=float(b2), eps=float(g["eps"]), sparse_rows=type(optimizer) is RowSparseAdam)
         if type(optimizer) is LazyRMSprop:

@@ -168,12 +168,13 @@ class RowShardedTables:
 
     def whole_table(self, f: int, which: str = "tables", shard: Optional[torch.Tensor] = None) -> torch.Tensor:
         """all-gather of table f (which = "tables"), or of its Adagrad accumulator ("state") — tests / checkpoints; a collective.
-        shard: this rank's rows of some other per-row array of table f (an optimizer's own state) to gather instead"""
+        shard: this rank's rows of some other per-row array of table f (an optimizer's own state) to gather instead — [rows, 16], or
+        1-D [rows] (row-wise Adagrad's accumulator, utils/optim.AdamAdagradTables(table_rowwise=True)): the result has its trailing shape"""
         src = self.tables if which == "tables" else self.state
         if shard is not None:
             src = {f: shard}
         n, rp = self.num_embeddings[f], self.rp[f]
-        mine = torch.zeros(rp, E, dtype=src[f].dtype, device=self.device)
+        mine = torch.zeros((rp,) + tuple(src[f].shape[1:]), dtype=src[f].dtype, device=self.device)
         k = self.hi[f] - self.lo[f]
         if k > 0:
             mine[:k] = src[f][:k]

@@ -634,7 +634,7 @@ class SuperNet(nn.Module):
         is BCE + get_l2_loss(self, weight_decay, no_reg_param_name) — every regularised parameter and every table row is decayed
         (engine_last_l2 = that term on the pre-step weights).  optim: an OptimSpec (nasrec_amd/optim_spec.py) of torch.optim.Adam / SGD
         replaces Adagrad (eps unused) — every table row moves every step, or with sparse_rows (utils/optim.RowSparseAdam) or
-        table_kind "adagrad" (utils/optim.AdamAdagradTables: Adagrad on the tables at lr * table_lr_scale) only the
+        table_kind "adagrad" / "rowwise_adagrad" (utils/optim.AdamAdagradTables: Adagrad on the tables at lr * table_lr_scale) only the
         batch's rows, which weight decay must then leave out; engine_bind_optimizer / engine_sync_optimizer_steps share its
         state with the torch optimizer.  Both need whole tables; under data parallelism they run in the exchange step's optimizer over
         the global batch (nasrec_amd/parallel.py).  ema_decay != 0: the step also averages every parameter (utils/optim.WeightEMA's
@@ -771,7 +771,8 @@ class SuperNet(nn.Module):
         keeps it so), so a table's row stamps start at that table's step count; the optimizer gets the engine's flush as its hook
         (utils/optim.LazyRMSprop), and last_layer keeps the Adagrad accumulators: that step has no RMSprop.  AdamAdagradTables: the
         dense parameters as with Adam; a table shares `sum` with the engine's Adagrad accumulators (table_state) and its step counter
-        with the state's `step`, and the engine holds no moment array of a table."""
+        with the state's `step`, and the engine holds no moment array of a table; with table_rowwise the `sum` is the engine's
+        table_row_state, one float per row, and an existing `sum` of another shape is refused (ValueError)."""
         eng = self._engine
         assert eng is not None, "run one forward first (lazy shapes)"
         from ..optim_spec import OptimSpec
@@ -801,6 +802,11 @@ class SuperNet(nn.Module):
                     if src is None:
                         tgt.zero_()
                     elif src.data_ptr() != tgt.data_ptr():
+                        if key == "sum" and tuple(src.shape) != tuple(tgt.shape):
+                            # (an element-wise checkpoint under the row-wise rule or the reverse: nothing may be reshaped or broadcast)
+                            raise ValueError("engine_bind_optimizer: the optimizer's `sum` of a table has shape %s, the %s rule keeps %s"
+                                             % (tuple(src.shape), "row-wise" if spec.table_kind == "rowwise_adagrad" else "element-wise",
+                                                tuple(tgt.shape)))
                         tgt.copy_(src.to(tgt.device).view_as(tgt))
                 if st:
                     if spec.kind in ("adam", "rmsprop"):
@@ -898,12 +904,13 @@ class SuperNet(nn.Module):
             arrays = eng.ensure_last_layer_state(spec.kind)
             return [(params[n], {k: arrays[k][i] for k in spec.state_keys}, i) for i, n in enumerate(self._FINAL)], eng.ll_steps
         eng.ensure_moments_state(spec.kind, tables=not spec.table_kind)
-        if spec.table_kind:  # (AdamAdagradTables: a table's state is Adagrad's sum, the engine's table_state; its counter is the state's step)
-            eng._ensure_table_state()
+        if spec.table_kind:  # (AdamAdagradTables: a table's state is Adagrad's sum, the engine's table_state or, row-wise, table_row_state;
+            eng._ensure_split_table_state(spec)  # its counter is the state's step)
+        table_sums = eng.table_row_state if spec.table_kind == "rowwise_adagrad" else eng.table_state
 
         def views(n):
             if spec.table_kind and n.startswith("_embedding."):
-                return {"sum": eng.table_state[int(n.split(".")[1])]}
+                return {"sum": table_sums[int(n.split(".")[1])]}
             return {k: eng.moments_view(k, n) for k in spec.state_keys}
         return [(p, views(n), eng.param_index[n]) for n, p in params.items() if n in eng.param_index], eng.opt_steps
 

@@ -35,7 +35,8 @@ def train_and_eval_one_model(model, args):
 
     l2_loss_fn = L2Loss(args.wd, args.no_reg_param_name, gpu=args.gpu)
 
-    optimizer = build_optimizer(args.optimizer, model, args.learning_rate, args.table_lr_scale, args.table_eps)
+    optimizer = build_optimizer(args.optimizer, model, args.learning_rate, args.table_lr_scale, args.table_eps,
+                                table_rowwise=args.table_rowwise)
     steps_per_epoch = args.train_limit // args.train_batch_size
     num_train_steps = steps_per_epoch * args.num_epochs
     lr_scheduler = build_lr_scheduler(args.lr_schedule, optimizer, num_train_steps, num_train_steps // 10, args.learning_rate)
@@ -128,6 +129,9 @@ def build_parser():
                         "(Adam's 1e-3 with 160 gives the tables 0.16)")
     p.add_argument("--table-eps", dest="table_eps", type=float, default=1e-2,
                    help="--optimizer adam-adagrad-tables: eps of the tables' Adagrad (> 0)")
+    p.add_argument("--table-rowwise", dest="table_rowwise", action="store_true",
+                   help="--optimizer adam-adagrad-tables: row-wise Adagrad on the tables — one accumulator per embedding row, fed the "
+                        "mean of the row's squared gradient (1/16 of the element-wise state); refused with any other --optimizer")
     p.add_argument("--pretrained_dlrm_emb_path", type=str, default=None, help="Pretrained embedding path from DLRM model.")
     p.add_argument("--gpu", type=int, default=0, help="GPU ID to use.")
     # not a reference flag: placement of the embedding tables under torchrun (nasrec_amd/sharded_tables.py)

@@ -54,7 +54,8 @@ def world_info():
 
 def _replica_tensors(model):
     """every tensor that defines a replica: parameters, buffers, and the engine's optimizer state once it exists — Adagrad's
-    accumulators (under a moments spec too: AdamAdagradTables keeps the tables' `sum` there and no table moments), Adam's / SGD's /
+    accumulators (under a moments spec too: AdamAdagradTables keeps the tables' `sum` there, or row-wise in table_row_state, and no
+    table moments), Adam's / SGD's /
     RMSprop's moments (flat arena and table arrays), their step counters and RMSprop's row stamps"""
     sharded = getattr(model, "_table_sharding", None) == "row"  # row-sharded tables: every rank owns DIFFERENT rows — not replica state
     out = [p.data for n, p in model.named_parameters() if not (sharded and n.startswith("_embedding."))] + [b.data for b in model.buffers()]
@@ -63,6 +64,8 @@ def _replica_tensors(model):
         if getattr(eng, "flat_s", None) is not None:
             out.append(eng.flat_s)
         for t in (getattr(eng, "table_state", None) or []):
+            out.append(t)
+        for t in (getattr(eng, "table_row_state", None) or []):
             out.append(t)
         for key in sorted(getattr(eng, "moments", None) or {}):
             flat, tabs = eng.moments[key]
@@ -92,10 +95,20 @@ def replica_checksum(model) -> torch.Tensor:
     return acc
 
 
+def table_rule_code(spec) -> int:
+    """the tables' rule of an OptimSpec (None = an optimizer the fused step does not reproduce) as the number the ranks compare:
+    0 = the tables take the optimizer's own dense rule, 1 = row-sparse Adam, 2 = Adagrad on the tables, 3 = row-wise Adagrad on them"""
+    if spec is None:
+        return 0
+    if spec.table_kind:
+        return {"adagrad": 2, "rowwise_adagrad": 3}[spec.table_kind]
+    return int(bool(spec.sparse_rows))
+
+
 def assert_replicas_identical(model, optimizer=None):
     """raise unless every rank holds the same weights (checked before the first step of a data-parallel run); optimizer: also unless
-    every rank runs the same table semantic (OptimSpec.sparse_rows / table_kind: row-sparse Adam or Adagrad on the tables on some ranks
-    and Adam on others would drift)"""
+    every rank runs the same table semantic (table_rule_code: row-sparse Adam or Adagrad on the tables on some ranks and Adam on
+    others, or element-wise accumulators here and row-wise ones there, would drift)"""
     rank, world = world_info()
     if world <= 1:
         return
@@ -113,7 +126,7 @@ def assert_replicas_identical(model, optimizer=None):
     if optimizer is not None:
         from ..optim_spec import OptimSpec
         spec = OptimSpec.from_optimizer(optimizer)
-        sparse = (2 if spec.table_kind else int(bool(spec.sparse_rows))) if spec is not None else 0  # (the tables' rule)
+        sparse = table_rule_code(spec)
         lo = torch.tensor([float(sparse)], dtype=mine.dtype, device=mine.device)
         hi = lo.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)

@@ -55,7 +55,7 @@ def _embedding_state_slots(model, optimizer):
 
 def optimizer_state_for_checkpoint(model, optimizer):
     """optimizer.state_dict(), except that with row-sharded tables (SuperNet(table_sharding="row"), world > 1) the Adagrad accumulator of
-    every table is returned WHOLE ([num_embeddings, 16], all-gather of the ranks' shards: a collective, every rank calls it) — like
+    every table is returned WHOLE ([num_embeddings, 16], or [num_embeddings] under row-wise Adagrad; all-gather of the ranks' shards: a collective, every rank calls it) — like
     `model.state_dict()` does for the tables themselves — so that a checkpoint holds every rank's accumulators in the reference's
     shapes, whatever the placement that wrote it."""
     sd = optimizer.state_dict()
@@ -88,7 +88,7 @@ def load_optimizer_state(model, optimizer, state_dict):
             if int(t.shape[0]) == int(model._num_embeddings[f]) and (hi - lo != int(t.shape[0]) or lo != 0):
                 part = t[lo:hi]
                 if hi - lo < rows:
-                    part = torch.cat([part, torch.zeros(rows - (hi - lo), t.shape[1], dtype=t.dtype, device=t.device)])
+                    part = torch.cat([part, torch.zeros((rows - (hi - lo),) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)])
                 st = dict(state[i])
                 st["sum"] = part.clone()
                 state[i] = st

@@ -123,11 +123,17 @@ class AdamAdagradTables(torch.optim.Optimizer):
     table_lr_scale and table_eps — so a scheduler that publishes one lr moves both halves together.  State: step, exp_avg, exp_avg_sq
     on a dense parameter (Adam's), step, sum on a table (Adagrad's).
 
+    table_rowwise: row-wise Adagrad on the tables (the "exact row-wise Adagrad" of DLRM-style trainers) — `sum` has shape [rows], one
+    accumulator per embedding row, fed the mean of the row's squared gradient, and divides the whole row:
+        sum += (g * g).mean(dim=1);  W -= table_lr * g / (sqrt(sum) + table_eps)[:, None]
+    As exactly row-sparse as the element-wise form, with 1/16 of its state at embedding width 16.  A table must be 2-D, and a `sum`
+    of the other form's shape (a checkpoint of the other rule) is refused: nothing broadcasts silently.
+
     `step()` is the torch route, on any device; the fused engine step reproduces it (OptimSpec.table_kind, csrc/optim_moments.hip)
     and shares its state through SuperNet.engine_bind_optimizer."""
 
     def __init__(self, params, table_params: Iterable[torch.Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 table_lr_scale: float = 1.0, table_eps: float = 1e-2):
+                 table_lr_scale: float = 1.0, table_eps: float = 1e-2, table_rowwise: bool = False):
         if lr < 0.0 or eps < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError("AdamAdagradTables: lr %r, betas %r, eps %r" % (lr, betas, eps))
         if not table_eps > 0.0:
@@ -135,7 +141,8 @@ class AdamAdagradTables(torch.optim.Optimizer):
         if not table_lr_scale > 0.0:
             raise ValueError("AdamAdagradTables: table_lr_scale %r is not positive" % (table_lr_scale,))
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0, amsgrad=False, maximize=False, capturable=False,
-                        differentiable=False, fused=None, table_lr_scale=table_lr_scale, table_eps=table_eps)
+                        differentiable=False, fused=None, table_lr_scale=table_lr_scale, table_eps=table_eps,
+                        table_rowwise=bool(table_rowwise))
         super().__init__(params, defaults)
         if len(self.param_groups) != 1:
             raise ValueError("AdamAdagradTables keeps one param group")
@@ -144,6 +151,38 @@ class AdamAdagradTables(torch.optim.Optimizer):
         if not all(id(t) in own for t in tables):
             raise ValueError("AdamAdagradTables: every table must be one of params")
         self._table_ids = {id(t) for t in tables}
+        if table_rowwise:
+            for t in tables:
+                if t.dim() != 2:
+                    raise ValueError("AdamAdagradTables: table_rowwise needs 2-D tables [rows, width], got shape %s" % (tuple(t.shape),))
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for g in self.param_groups:
+            g.setdefault("table_rowwise", False)  # (a pickle from before the flag)
+
+    def load_state_dict(self, state_dict):
+        """torch's, after a check that changes nothing: the checkpoint's rule (its group's table_rowwise; absent = element-wise) and
+        the shape of every table's `sum` must be this optimizer's — an element-wise state under table_rowwise, or the reverse, is
+        refused (ValueError), never reshaped or broadcast"""
+        rowwise = bool(self.param_groups[0].get("table_rowwise", False))
+        groups = state_dict.get("param_groups") or [{}]
+        if len(groups) == 1 and bool(groups[0].get("table_rowwise", False)) != rowwise:
+            raise ValueError("AdamAdagradTables.load_state_dict: the checkpoint was written with table_rowwise=%r, this optimizer was built "
+                             "with table_rowwise=%r" % (bool(groups[0].get("table_rowwise", False)), rowwise))
+        ids = groups[0].get("params", []) if len(groups) == 1 else []
+        for k, p in zip(ids, self.param_groups[0]["params"]):
+            st = state_dict.get("state", {}).get(k)
+            if id(p) in self._table_ids and st and "sum" in st and tuple(st["sum"].shape) != self._sum_shape(p, rowwise):
+                raise ValueError("AdamAdagradTables.load_state_dict: `sum` of a table of shape %s has shape %s, table_rowwise=%r keeps %s"
+                                 % (tuple(p.shape), tuple(st["sum"].shape), rowwise, self._sum_shape(p, rowwise)))
+        super().load_state_dict(state_dict)
+
+    @staticmethod
+    def _sum_shape(p, rowwise):
+        if rowwise and p.dim() != 2:
+            raise ValueError("AdamAdagradTables: table_rowwise needs 2-D tables [rows, width], got shape %s" % (tuple(p.shape),))
+        return (p.shape[0],) if rowwise else tuple(p.shape)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -155,6 +194,7 @@ class AdamAdagradTables(torch.optim.Optimizer):
         beta1, beta2 = group["betas"]
         lr, eps = group["lr"], group["eps"]
         table_lr, table_eps = lr * group["table_lr_scale"], group["table_eps"]
+        rowwise = bool(group.get("table_rowwise", False))
         dense = ([], [], [], [], [])
         for p in group["params"]:
             if p.grad is None:
@@ -166,8 +206,19 @@ class AdamAdagradTables(torch.optim.Optimizer):
                 # torch.optim.Adagrad's dense single-tensor statements (torch/optim/adagrad.py), lr_decay 0 and weight_decay 0
                 if len(st) == 0:
                     st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    st["sum"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["sum"] = torch.zeros(p.shape[0], dtype=p.dtype, device=p.device) if rowwise and p.dim() == 2 else \
+                        torch.zeros_like(p, memory_format=torch.preserve_format)
+                if tuple(st["sum"].shape) != self._sum_shape(p, rowwise):
+                    raise ValueError("AdamAdagradTables: `sum` of a table of shape %s has shape %s, table_rowwise=%r keeps %s (a checkpoint "
+                                     "of the other rule?)" % (tuple(p.shape), tuple(st["sum"].shape), rowwise, self._sum_shape(p, rowwise)))
                 st["step"] += 1
+                if rowwise:
+                    g = p.grad
+                    msq = (g * g).mean(dim=1)
+                    st["sum"].add_(msq)
+                    std = st["sum"].sqrt().add_(table_eps)
+                    p.addcdiv_(g, std.unsqueeze(1), value=-table_lr)
+                    continue
                 st["sum"].addcmul_(p.grad, p.grad, value=1)
                 std = st["sum"].sqrt().add_(table_eps)
                 p.addcdiv_(p.grad, std, value=-table_lr)

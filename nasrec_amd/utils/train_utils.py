@@ -271,7 +271,8 @@ def _announce_split_route(optimizer, l2_loss_fn, fused, switched_off=False):
         return
     optimizer._route_announced = True
     g = optimizer.param_groups[0]
-    head = "Adam + Adagrad on the tables (table lr = lr x {}, table eps {})".format(g["table_lr_scale"], g["table_eps"])
+    head = "Adam + {}Adagrad on the tables (table lr = lr x {}, table eps {})".format(
+        "row-wise " if g.get("table_rowwise", False) else "", g["table_lr_scale"], g["table_eps"])
     if fused:
         print(head + ": fused step, exactly row-sparse table update.")
         return

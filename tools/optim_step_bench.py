@@ -4,7 +4,8 @@ the Criteo best-1shot sub-network, full tables (33.76 M rows), batch 256, clip 5
 Nesterov), row-sparse Adam (Adam's lr and eps; with --wd the L2 term leaves the tables out, as the optimizer requires), RMSprop (torch's
 defaults; fused: lazily decayed rows, with --wd the tables left out too; its line also carries `flush_ms`, the one launch that brings
 every row's square_avg current after the timed steps), adam-adagrad-tables (Adam's lr and eps on the network, Adagrad at lr x
-`--table-lr-scale` on the tables: one phase-0 launch, W and `sum` of the batch's rows; with --wd the tables left out).  `--ema DECAY` keeps utils/optim.WeightEMA beside the step: inside the fused
+`--table-lr-scale` on the tables: one phase-0 launch, W and `sum` of the batch's rows; with --wd the tables left out; `--table-rowwise`:
+row-wise Adagrad on the tables, one accumulator per row).  `--ema DECAY` keeps utils/optim.WeightEMA beside the step: inside the fused
 step (Adagrad, row-sparse Adam, RMSprop), by WeightEMA.update() on the torch route; the line then carries `ema`, `flush_ms` (the launch
 that brings every row's average current) and `swap_ms` (flush + exchange with the parameters: what entering `averaged()` costs).
 `--decoupled-wd LAMBDA` applies utils/optim.DecoupledWeightDecay in front of the update: inside the fused step (Adagrad, row-sparse Adam,
@@ -38,6 +39,8 @@ def main():
     ap.add_argument("--optimizer", choices=["adagrad", "adam", "sgd", "row-sparse-adam", "rmsprop", "adam-adagrad-tables"], default="adam")
     ap.add_argument("--table-lr-scale", dest="table_lr_scale", type=float, default=1.0,
                     help="adam-adagrad-tables: the tables' learning rate as a multiple of the network's")
+    ap.add_argument("--table-rowwise", dest="table_rowwise", action="store_true",
+                    help="adam-adagrad-tables: row-wise Adagrad on the tables (one accumulator per row)")
     ap.add_argument("--wd", type=float, default=0.0)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
@@ -55,7 +58,8 @@ def main():
     if a.bytes:
         tb = rows * 64
         print(json.dumps({"table_rows": rows, "table_bytes": tb, "adam_phase1_bytes": 6 * tb, "sgd_phase1_bytes": 4 * tb,
-                          "adagrad_wd_phase1_bytes": 4 * tb, "wd_phase0_table_bytes": tb}))
+                          "adagrad_wd_phase1_bytes": 4 * tb, "wd_phase0_table_bytes": tb,
+                          "table_sum_bytes_elementwise": tb, "table_sum_bytes_rowwise": rows * 4}))
         return
     if a.all:
         for route in ("fused", "torch"):
@@ -96,7 +100,7 @@ def main():
     with torch.no_grad():
         m(batches[0][0], batches[0][1])
     lr = LR[a.optimizer]
-    opt = MT.build_optimizer(a.optimizer, m, lr, a.table_lr_scale)
+    opt = MT.build_optimizer(a.optimizer, m, lr, a.table_lr_scale, table_rowwise=a.table_rowwise)
     spec = OptimSpec.from_optimizer(opt) if a.optimizer != "adagrad" else None
     lazy = a.optimizer in ("row-sparse-adam", "rmsprop", "adam-adagrad-tables") and a.route == "fused"  # (the fused step needs the tables left out of the L2 term)
     no_reg = "_embedding" if ((a.optimizer == "row-sparse-adam" or lazy) and a.wd) else None
@@ -180,6 +184,7 @@ def main():
         extra["flush_again_ms"] = round((time.perf_counter() - wall) * 1e3, 4)  # (nothing owed: the stamps are read, nothing else)
     if a.optimizer == "adam-adagrad-tables":
         extra["table_lr_scale"] = a.table_lr_scale
+        extra["table_rowwise"] = bool(a.table_rowwise)
     print(json.dumps({**extra, "route": a.route, "optimizer": a.optimizer, "wd": a.wd, "B": a.B, "steps": a.steps, "ms_per_step": round(ms, 4),
                       "samples_per_s": round(a.B / ms * 1e3), "wall_ms_per_step": round(wall_ms, 4),
                       "table_rows": rows}))
