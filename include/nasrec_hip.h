@@ -176,13 +176,19 @@ enum { NASREC_PRECISION_HIGHEST = 0, NASREC_PRECISION_HIGH = 1, NASREC_PRECISION
 /* ------------------------------------------------------------------------------------------------
  * Embedding stem.  out[b,f,:] = table_f[idx[b,f],:]  — replaces Fs × nn.Embedding + torch.stack
  * (supernet.py:404-430).  Bit-exact copy.
+ * table_dtype (the slot of a padding word, which every earlier caller left zero: the structure keeps its size and nasrec_abi_version()
+ * stays): NASREC_TABLE_DTYPE_F32 = rows of 16 floats; NASREC_TABLE_DTYPE_BF16 = every table is [rows_f, 16] bfloat16 with 32-byte
+ * rows (table[f] keeps its declared type and is reinterpreted), and an element is widened exactly, bits << 16, into the unchanged fp32
+ * `out`.  Any other value is refused (-1, nothing launched).  An id outside its table gives a zero row and sets `oob` in both forms.
  * ---------------------------------------------------------------------------------------------- */
+#define NASREC_TABLE_DTYPE_F32 0
+#define NASREC_TABLE_DTYPE_BF16 1
 typedef struct nasrec_embed_desc {
   int32_t kind; /* NASREC_OP_EMBED_GATHER */
   int32_t B, Fs;
-  int32_t _pad;
+  int32_t table_dtype;                     /* NASREC_TABLE_DTYPE_* (above) */
   const int64_t* idx;                      /* [B, Fs] */
-  const float* table[NASREC_MAX_TABLES];   /* table f: [rows_f, 16] */
+  const float* table[NASREC_MAX_TABLES];   /* table f: [rows_f, 16] (fp32, or bfloat16 behind the same pointer type) */
   int64_t rows[NASREC_MAX_TABLES];
   float* out;                              /* [B, Fs, 16] */
   int32_t* oob;                            /* optional: set to 1 if any index is out of range */
@@ -597,10 +603,27 @@ typedef struct nasrec_weight_decay_desc {
  *   sum[row] = sum[row] + (g[0]^2 + ... + g[15]^2) / 16;  p[e] = p[e] - tlr * (g[e] / (sqrt(sum[row]) + table_eps)),  e = 0 .. 15
  * A zero gradient changes neither, so it is exactly row-sparse in the same way: no bit is marked, every other row keeps its bits in
  * table and tv, steps are counted as above.  The same refusals as NASREC_TABLE_ALGO_ADAGRAD.
+ *
+ * table_algo = NASREC_TABLE_ALGO_ROWWISE_ADAGRAD_BF16 (4): the row-wise rule on tables stored as bfloat16 — table[f] points at
+ * [rows_f, 16] bfloat16 with 32-byte rows (the pointer keeps its declared type and is reinterpreted); tv[f] is rows[f] floats as above.
+ * A leader row is widened exactly (bits << 16), takes the two statements above in fp32, and each of its 16 new weights x is stored
+ * with stochastic rounding:
+ *   out16 = (bits(x) + r) >> 16,  r = 0 where x is not finite (stored truncated), else the top 16 bits of
+ *   mix(mix(mix(seed ^ t * 0x9E3779B9) ^ f * 0x85EBCA6B) ^ (row * 16 + e))       (32-bit arithmetic; row * 16 + e may wrap)
+ *   mix(h): h ^= h >> 16; h *= 0x7feb352d; h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16
+ * with t = (uint32_t)step[table_step0 + f] + 1 — the table's step count after this step, read ON THE DEVICE, so a replayed graph and a
+ * relaunched program round differently every step with a constant descriptor — f the table, e = 0 .. 15 the element, and seed =
+ * (uint32_t)(sr_seed ^ (sr_seed >> 32)).  A value that already is a bfloat16 has low bits zero and never moves, so a touched row with
+ * a zero gradient keeps its bits and the rule stays exactly row-sparse; the largest finite value may carry into inf.  `sr_seed` travels
+ * in the storage of tm[0], which the split rules never read (as RMSprop's `stamp` does): the structure does not grow.  utils/optim.
+ * stochastic_round_bf16 is the definition the kernel matches bit for bit.
+ * Refused in addition to the row-wise rule's refusals: phase 1 and phase 2 (no launch but phase 0 knows bfloat16 tables), and a tm[f],
+ * f >= 1, that is not NULL (a caller that filled tm expects a first moment; tm[0] cannot be told from a seed).
  * ---------------------------------------------------------------------------------------------- */
 #define NASREC_TABLE_ALGO_SAME 0    /* the tables take `algo` */
 #define NASREC_TABLE_ALGO_ADAGRAD 1 /* Adagrad on the tables (above) */
 #define NASREC_TABLE_ALGO_ROWWISE_ADAGRAD 3 /* row-wise Adagrad on the tables: tv[f] = one float per row (above) */
+#define NASREC_TABLE_ALGO_ROWWISE_ADAGRAD_BF16 4 /* the same on bfloat16 tables, stored with stochastic rounding (above) */
 typedef struct nasrec_opt_moments_desc {
   int32_t kind;  /* NASREC_OP_OPT_MOMENTS */
   int32_t phase; /* 0 / 1 (above); 2 = RMSprop's flush */
@@ -628,6 +651,7 @@ typedef struct nasrec_opt_moments_desc {
   union {
     float* tm[NASREC_MAX_TABLES];
     uint32_t* stamp[NASREC_MAX_TABLES]; /* NASREC_OPTIM_RMSPROP: per-row stamps (above); that algorithm has no first moment */
+    uint64_t sr_seed;                   /* NASREC_TABLE_ALGO_ROWWISE_ADAGRAD_BF16: the stochastic rounding's seed (above), over tm[0] */
   };
   float* tv[NASREC_MAX_TABLES];
   int64_t rows[NASREC_MAX_TABLES];
@@ -646,7 +670,7 @@ typedef struct nasrec_opt_moments_desc {
                           *   (the slot of a padding word): NASREC_TABLE_ALGO_ADAGRAD: the tables' learning rate as a multiple of *lr */
   int64_t rank_stride;
   int32_t sparse_rows;   /* 0 = every table row moves every step; != 0 = row-sparse Adam (above) */
-  int32_t table_algo;    /* NASREC_TABLE_ALGO_SAME / _ADAGRAD / _ROWWISE_ADAGRAD (above; the slot of a padding word) */
+  int32_t table_algo;    /* NASREC_TABLE_ALGO_SAME / _ADAGRAD / _ROWWISE_ADAGRAD / _ROWWISE_ADAGRAD_BF16 (above; the slot of a padding word) */
 } nasrec_opt_moments_desc_t;
 
 /* ------------------------------------------------------------------------------------------------
@@ -943,7 +967,8 @@ typedef struct nasrec_stage_desc {
   const float* y_src;     float* y_dst;       /* [B] (may be NULL) */
   float* lr_dst;                              /* device scalar (may be NULL) */
   nasrec_embed_desc_t gather;                 /* gather.out != NULL: the same launch also runs the embedding stem on
-                                                 cat_src (gather.idx and gather.kind are ignored; B, Fs from above) */
+                                                 cat_src (gather.idx and gather.kind are ignored; B, Fs from above; gather.table_dtype
+                                                 selects the form as in the stand-alone launch) */
   nasrec_dedup_ids_desc_t dedup_ids;          /* dedup_ids.order != NULL: Fs more workgroups run NASREC_OP_DEDUP_IDS on cat_src (B <= 256;
                                                  idx / B / Fs / kind are ignored): the id-only half of the optimizer's row dedup, off the
                                                  step's tail */

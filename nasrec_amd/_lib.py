@@ -41,6 +41,8 @@ OP_OPT_MOMENTS = 40
 OP_LAST_LAYER_STEP = 41
 OPTIM_ADAGRAD, OPTIM_ADAM, OPTIM_SGD, OPTIM_RMSPROP = 0, 1, 2, 3  # NASREC_OPTIM_* (algorithm of NASREC_OP_OPT_MOMENTS / _LAST_LAYER_STEP)
 TABLE_ALGO_SAME, TABLE_ALGO_ADAGRAD, TABLE_ALGO_ROWWISE_ADAGRAD = 0, 1, 3  # NASREC_TABLE_ALGO_* (nasrec_opt_moments_desc_t.table_algo: the split optimizer)
+TABLE_ALGO_ROWWISE_ADAGRAD_BF16 = 4  # ... the row-wise rule on bf16 tables, stored with stochastic rounding (seed: OptMomentsDesc.sr_seed)
+TABLE_DTYPE_F32, TABLE_DTYPE_BF16 = 0, 1  # NASREC_TABLE_DTYPE_* (nasrec_embed_desc_t.table_dtype)
 LAST_LAYER_MAX = 8192  # NASREC_LAST_LAYER_MAX: K + 1 of NASREC_OP_LAST_LAYER_STEP
 OP_ROC_AUC = 42
 OP_WEIGHT_EMA = 43
@@ -73,7 +75,8 @@ class SplitkEpiloguesDesc(C.Structure):
 
 
 class EmbedDesc(C.Structure):
-    _fields_ = [("kind", i32), ("B", i32), ("Fs", i32), ("_pad", i32), ("idx", vp), ("table", vp * MAX_TABLES),
+    # (table_dtype sits where _pad was: 0 = fp32 tables, what every earlier caller left there; 1 = bf16 tables)
+    _fields_ = [("kind", i32), ("B", i32), ("Fs", i32), ("table_dtype", i32), ("idx", vp), ("table", vp * MAX_TABLES),
                 ("rows", i64 * MAX_TABLES), ("out", vp), ("oob", vp)]
 
 
@@ -290,6 +293,16 @@ class OptMomentsDesc(C.Structure):
                 ("bitmap", vp), ("step", vp), ("inc", vp), ("n_inc", i64), ("zero_chunks", vp), ("n_zero", i64), ("counter", vp),
                 ("lr", vp), ("coef", vp), ("rank_B", i32), ("table_lr_scale", f32), ("rank_stride", i64), ("sparse_rows", i32),
                 ("table_algo", i32)]
+
+    # TABLE_ALGO_ROWWISE_ADAGRAD_BF16: the stochastic rounding's seed, `sr_seed` in the header's union — the 8 bytes of tm[0], which the
+    # split rules never read (as RMSprop's stamps travel in tm): the structure does not grow
+    @property
+    def sr_seed(self):
+        return C.c_uint64.from_buffer(self, OptMomentsDesc.tm.offset).value
+
+    @sr_seed.setter
+    def sr_seed(self, v):
+        C.c_uint64.from_buffer(self, OptMomentsDesc.tm.offset).value = int(v) & 0xFFFFFFFFFFFFFFFF
 
 
 class LastLayerStepDesc(C.Structure):

@@ -9,6 +9,9 @@
 #include "dedup_bodies.h"
 
 // thread t of the gather: (pair = t >> 2 = (b, f), q = t & 3 = which float4 of the 64-byte row)
+// BF16 (table_dtype = NASREC_TABLE_DTYPE_BF16): the row is 32 bytes of bfloat16; the same lane loads 8 bytes — its four elements —
+// and widens them exactly (bits << 16) into the same float4 of the unchanged fp32 output
+template <bool BF16>
 __device__ __forceinline__ void embed_gather_body(const nasrec_embed_desc_t& d, const int64_t* idx, int B, int Fs, long t) {
   const long pair = t >> 2;
   const int q = (int)(t & 3);
@@ -17,7 +20,13 @@ __device__ __forceinline__ void embed_gather_body(const nasrec_embed_desc_t& d, 
   long row = idx[pair];
   float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
   if (row >= 0 && row < d.rows[f]) {
-    v = *reinterpret_cast<const float4*>(d.table[f] + row * NASREC_EMB_DIM + q * 4);
+    if (BF16) {
+      const uint2 w = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(d.table[f]) + row * NASREC_EMB_DIM + q * 4);
+      v = make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16),
+                      __uint_as_float(w.y & 0xffff0000u));
+    } else {
+      v = *reinterpret_cast<const float4*>(d.table[f] + row * NASREC_EMB_DIM + q * 4);
+    }
   } else if (d.oob) {
     *d.oob = 1;  // torch raises IndexError; the host shim turns this flag into one
   }
@@ -25,13 +34,25 @@ __device__ __forceinline__ void embed_gather_body(const nasrec_embed_desc_t& d, 
 }
 
 __global__ __launch_bounds__(256) void embed_gather_kernel(const nasrec_embed_desc_t d) {
-  embed_gather_body(d, d.idx, d.B, d.Fs, (long)blockIdx.x * 256 + threadIdx.x);
+  embed_gather_body<false>(d, d.idx, d.B, d.Fs, (long)blockIdx.x * 256 + threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void embed_gather_bf16_kernel(const nasrec_embed_desc_t d) {
+  embed_gather_body<true>(d, d.idx, d.B, d.Fs, (long)blockIdx.x * 256 + threadIdx.x);
+}
+
+static int table_dtype_check(const nasrec_embed_desc_t& g, const char* who) {
+  if (g.table_dtype != NASREC_TABLE_DTYPE_F32 && g.table_dtype != NASREC_TABLE_DTYPE_BF16)
+    return nasrec_set_error(-1, "%s: table_dtype %d (0 = fp32, 1 = bf16)", who, g.table_dtype);
+  return 0;
 }
 
 // per-step input staging + learning-rate store (one launch instead of three copies and a fill), optionally with the
 // embedding gather of the step riding along — and, in `ids_blocks` more workgroups behind them, the id-only half of the optimizer's
 // row dedup (dedup_bodies.h): the ids are in this launch's hands, and nothing reads that half's result before the backward is done
-__global__ __launch_bounds__(256) void stage_inputs_kernel(const nasrec_stage_desc_t d, int base_blocks) {
+// (BF16: the gather that rides along reads bfloat16 tables — an entry of its own below, so the fp32 step runs the code it always ran)
+template <bool BF16>
+__device__ __forceinline__ void stage_inputs_body(const nasrec_stage_desc_t& d, int base_blocks) {
   __shared__ __attribute__((aligned(16))) int dd_sidx[256];
   __shared__ int dd_sh[4];
   if ((int)blockIdx.x >= base_blocks) {
@@ -44,8 +65,12 @@ __global__ __launch_bounds__(256) void stage_inputs_kernel(const nasrec_stage_de
   if (t < n_cat) d.cat_dst[t] = d.cat_src[t];
   if (d.y_src != nullptr && t < d.B) d.y_dst[t] = d.y_src[t];
   if (t == 0 && d.lr_dst != nullptr) d.lr_dst[0] = d.lr;
-  if (d.gather.out != nullptr) embed_gather_body(d.gather, d.cat_src, d.B, d.Fs, t);
+  if (d.gather.out != nullptr) embed_gather_body<BF16>(d.gather, d.cat_src, d.B, d.Fs, t);
 }
+
+__global__ __launch_bounds__(256) void stage_inputs_kernel(const nasrec_stage_desc_t d, int base_blocks) { stage_inputs_body<false>(d, base_blocks); }
+
+__global__ __launch_bounds__(256) void stage_inputs_bf16_kernel(const nasrec_stage_desc_t d, int base_blocks) { stage_inputs_body<true>(d, base_blocks); }
 
 static int dedup_ids_check(const nasrec_dedup_ids_desc_t* d, int B, int Fs, const char* who) {
   if (B < 1 || B > NASREC_DEDUP_IDS_MAX_B || Fs < 1 || Fs > NASREC_MAX_TABLES) return nasrec_set_error(-2, "%s: B=%d Fs=%d out of range", who, B, Fs);
@@ -57,8 +82,12 @@ static int dedup_ids_check(const nasrec_dedup_ids_desc_t* d, int B, int Fs, cons
 
 int launch_stage(hipStream_t st, const nasrec_stage_desc_t* d) {
   long n = (long)d->B * (d->Fd > d->Fs ? d->Fd : d->Fs);
+  bool bf16 = false;
   if (d->gather.out != nullptr) {
     if (d->Fs < 1 || d->Fs > NASREC_MAX_TABLES) return nasrec_set_error(-2, "stage: Fs=%d out of range", d->Fs);
+    const int rc = table_dtype_check(d->gather, "stage.gather");
+    if (rc) return rc;
+    bf16 = d->gather.table_dtype == NASREC_TABLE_DTYPE_BF16;
     if ((long)d->B * d->Fs * 4 > n) n = (long)d->B * d->Fs * 4;
   }
   if (n < 1) n = 1;
@@ -70,15 +99,19 @@ int launch_stage(hipStream_t st, const nasrec_stage_desc_t* d) {
     if (rc) return rc;
     ids = d->Fs;
   }
-  hipLaunchKernelGGL(stage_inputs_kernel, dim3((unsigned)(base + ids)), dim3(256), 0, st, *d, base);
+  if (bf16) hipLaunchKernelGGL(stage_inputs_bf16_kernel, dim3((unsigned)(base + ids)), dim3(256), 0, st, *d, base);
+  else hipLaunchKernelGGL(stage_inputs_kernel, dim3((unsigned)(base + ids)), dim3(256), 0, st, *d, base);
   return nasrec_check_launch("stage_inputs");
 }
 
 int launch_embed_gather(hipStream_t st, const nasrec_embed_desc_t* d) {
   if (d->Fs < 1 || d->Fs > NASREC_MAX_TABLES) return nasrec_set_error(-2, "embed: Fs=%d out of range", d->Fs);
+  const int rc = table_dtype_check(*d, "embed");
+  if (rc) return rc;
   long threads = (long)d->B * d->Fs * 4;
   if (threads == 0) return 0;
-  hipLaunchKernelGGL(embed_gather_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, *d);
+  if (d->table_dtype == NASREC_TABLE_DTYPE_BF16) hipLaunchKernelGGL(embed_gather_bf16_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, *d);
+  else hipLaunchKernelGGL(embed_gather_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, *d);
   return nasrec_check_launch("embed_gather");
 }
 

@@ -4,7 +4,8 @@
 // (a zero gradient still moves a row whose moments are non-zero: W and its one or two moment arrays, read and written once) and,
 // in the workgroup that finishes last, counts the step of every parameter it updated.
 // Phase 0 is one kernel, opt_moments_phase0_kernel<Rows>; what happens to one touched row, and whether the launch marks the bitmap or
-// counts the steps itself, is the row policy `Rows` (DenseRows, SparseAdamRows, LazyRmspropRows, AdagradTableRows, RowwiseAdagradTableRows below).
+// counts the steps itself, is the row policy `Rows` (DenseRows, SparseAdamRows, LazyRmspropRows, AdagradTableRows, RowwiseAdagradTableRows,
+// RowwiseAdagradBf16TableRows below).
 // Row-sparse Adam (sparse_rows, include/nasrec_hip.h): the same clip and dense chunks, torch.optim.SparseAdam on the touched rows, no
 // bitmap, and no phase 1 unless weight decay has gradients to restore.
 // RMSprop (NASREC_OPTIM_RMSPROP: momentum 0, not centered): a row whose gradient is zero does not move and its square_avg only decays,
@@ -225,6 +226,68 @@ struct RowwiseAdagradTableRows {
   }
 };
 
+// Row-wise Adagrad on bfloat16 tables (table_algo = NASREC_TABLE_ALGO_ROWWISE_ADAGRAD_BF16): table[f] is [rows, 16] bfloat16 with
+// 32-byte rows behind the float pointer; a lane loads its quarter's 8 bytes, widens it exactly (bits << 16), takes
+// RowwiseAdagradTableRows' statements in fp32 — the same quad sum under the same invariant: no branch on q in front of it — and stores
+// each new weight with stochastic rounding, out16 = (bits + r) >> 16, four results in one 8-byte store.  r = the top 16 bits of a
+// counter hash of (seed, t, f, row, e) (include/nasrec_hip.h; utils/optim.stochastic_round_bf16 is the definition): t is the table's
+// step count after this step, read from the device counter, so the descriptor stays constant from step to step; the (seed, t, f)
+// prefix of the chain is a per-table scalar in LDS.  A non-finite weight is stored truncated.  A weight that did not move has low
+// bits zero and keeps its bits, so a zero gradient leaves the row alone as above.
+__device__ __forceinline__ uint32_t sr_mix(uint32_t h) {
+  h ^= h >> 16;
+  h *= 0x7feb352du;
+  h ^= h >> 15;
+  h *= 0x846ca68bu;
+  h ^= h >> 16;
+  return h;
+}
+
+__device__ __forceinline__ uint32_t sr_round_bf16(float x, uint32_t h) {
+  const uint32_t bits = __float_as_uint(x);
+  const uint32_t r = (bits & 0x7f800000u) == 0x7f800000u ? 0u : sr_mix(h) >> 16;
+  return (bits + r) >> 16;  // (a finite x is at most 0xff7fffff: the sum cannot wrap)
+}
+
+struct RowwiseAdagradBf16TableRows {
+  static constexpr int DENSE = NASREC_OPTIM_ADAM;
+  static constexpr bool COUNTS = true;
+  uint32_t prefix[NASREC_MAX_TABLES];
+  __device__ __forceinline__ void scalars(const nasrec_opt_moments_desc_t& d, float) {
+    const int f = (int)threadIdx.x - 64;
+    if (f >= 0 && f < d.Fs) {
+      const uint32_t seed = (uint32_t)(d.sr_seed ^ (d.sr_seed >> 32));
+      const uint32_t t = (uint32_t)(long)d.step[d.table_step0 + f] + 1u;
+      prefix[f] = sr_mix(sr_mix(seed ^ t * 0x9E3779B9u) ^ (uint32_t)f * 0x85EBCA6Bu);
+    }
+  }
+  __device__ __forceinline__ void row(const nasrec_opt_moments_desc_t& d, int f, long row, int q, const f32x4& g4, float lr) const {
+    const float tlr = lr * d.table_lr_scale;
+    uint2* wp = reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(d.table[f]) + row * 16 + q * 4);
+    const uint2 w = *wp;
+    f32x4 p4 = {__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u)};
+    float s = d.tv[f][row];  // (all four lanes load it; lane q == 0 stores it below, after the loads in program order)
+    float sq = g4[0] * g4[0];
+    sq = fmaf(g4[1], g4[1], sq);
+    sq = fmaf(g4[2], g4[2], sq);
+    sq = fmaf(g4[3], g4[3], sq);
+    // (the quad sum of RowwiseAdagradTableRows: its lanes arrive together — nothing in front of this line branches on q)
+    sq += dpp_mov<0xb1>(sq);  // quad_perm:[1,0,3,2]
+    sq += dpp_mov<0x4e>(sq);  // quad_perm:[2,3,0,1]
+    s += sq * 0.0625f;
+    const uint32_t h = prefix[f], pos = (uint32_t)row * 16u + (uint32_t)q * 4u;  // (row * 16 + e may wrap in 32 bits: part of the definition)
+    uint32_t o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float pe = p4[e];
+      adagrad_weight(g4[e], s, pe, tlr, d.table_eps);
+      o[e] = sr_round_bf16(pe, h ^ (pos + (uint32_t)e));
+    }
+    *wp = make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
+    if (q == 0) d.tv[f][row] = s;
+  }
+};
+
 template <class Rows>
 __global__ __launch_bounds__(256) void opt_moments_phase0_kernel(const nasrec_opt_moments_desc_t d) {
   __shared__ float sh_coef;
@@ -340,13 +403,14 @@ void launch_phase1(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
 }  // namespace
 
 // Every refusal comes before anything is launched.  The row form — dense (every row moves: bitmap + phase 1), row-sparse Adam, lazy
-// RMSprop, Adagrad or row-wise Adagrad on the tables — decides what a launch needs; all but the first move the batch's rows only, so their phase 0 counts the
+// RMSprop, Adagrad or row-wise Adagrad (on fp32 or bf16 tables) on the tables — decides what a launch needs; all but the first move the batch's rows only, so their phase 0 counts the
 // steps unless zero_chunks call for a phase 1, which then owns no tile.  Phase 2 is RMSprop's flush.
 int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
   if (d->Fs < 0 || d->Fs > NASREC_MAX_TABLES) return nasrec_set_error(-1, "opt_moments: Fs = %d", d->Fs);
   if (!d->lr || !d->step) return nasrec_set_error(-1, "opt_moments: lr / step missing");
   const bool adam = d->algo == NASREC_OPTIM_ADAM, rmsprop = d->algo == NASREC_OPTIM_RMSPROP;
-  const bool rowwise = d->table_algo == NASREC_TABLE_ALGO_ROWWISE_ADAGRAD;  // (tv: one float per row)
+  const bool bf16 = d->table_algo == NASREC_TABLE_ALGO_ROWWISE_ADAGRAD_BF16;  // (table: [rows, 16] bfloat16; the seed in tm[0]'s storage)
+  const bool rowwise = d->table_algo == NASREC_TABLE_ALGO_ROWWISE_ADAGRAD || bf16;  // (tv: one float per row)
   const bool split = d->table_algo == NASREC_TABLE_ALGO_ADAGRAD || rowwise, lazy = rmsprop || d->sparse_rows || split;
   if (d->table_algo != NASREC_TABLE_ALGO_SAME && !split) return nasrec_set_error(-1, "opt_moments: table_algo %d", d->table_algo);
   if (split && !adam) return nasrec_set_error(-1, "opt_moments: table_algo (Adagrad on the tables) goes with Adam on the rest (algo %d)", d->algo);
@@ -355,6 +419,10 @@ int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
     return nasrec_set_error(-1, "opt_moments: table_eps %g must be positive (a zero gradient must leave its row alone)", (double)d->table_eps);
   if (split && d->reg_mask != 0u)
     return nasrec_set_error(-1, "opt_moments: table_algo with reg_mask %u: a regularised table moves in every row", d->reg_mask);
+  if (bf16 && d->phase != 0)
+    return nasrec_set_error(-1, "opt_moments: table_algo %d (bf16 tables) has phase 0 only: phase %d knows fp32 tables", d->table_algo, d->phase);
+  for (int f = 1; bf16 && f < NASREC_MAX_TABLES; ++f)  // (a caller that filled tm expects a first moment: there is none, and tm[0] is the seed)
+    if (d->tm[f]) return nasrec_set_error(-1, "opt_moments: table_algo %d (bf16 tables) keeps the seed in tm[0]'s storage and takes no tm (tm[%d] is set)", d->table_algo, f);
   const char* lazy_name = rmsprop ? "RMSprop" : split ? "table_algo" : "sparse_rows";
   if (rmsprop && d->momentum != 0.f) return nasrec_set_error(-1, "opt_moments: RMSprop with momentum %g moves untouched rows", (double)d->momentum);
   if (d->sparse_rows && !adam) return nasrec_set_error(-1, "opt_moments: sparse_rows is row-sparse Adam (algo %d)", d->algo);
@@ -374,6 +442,7 @@ int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
     if (lazy && d->n_zero <= 0 && (!d->counter || (d->n_inc > 0 && !d->inc)))
       return nasrec_set_error(-1, "opt_moments: %s without zero_chunks counts the steps: counter / inc missing", lazy_name);
     if (rmsprop) launch_phase0<LazyRmspropRows>(st, d, nblk);
+    else if (bf16) launch_phase0<RowwiseAdagradBf16TableRows>(st, d, nblk);
     else if (rowwise) launch_phase0<RowwiseAdagradTableRows>(st, d, nblk);
     else if (split) launch_phase0<AdagradTableRows>(st, d, nblk);
     else if (d->sparse_rows) launch_phase0<SparseAdamRows>(st, d, nblk);

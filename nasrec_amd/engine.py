@@ -318,8 +318,11 @@ class SupernetEngine:
             if self.host_embedding:
                 self.tables = []
             elif tables is not None:  # adopt the caller's nn.Embedding storage (no copy; PyTorch keeps ownership)
+                # (fp32, or all of them bf16 — SuperNet(table_dtype=torch.bfloat16): [rows, 16] with 32-byte rows, read by the gather and
+                # written by the row-wise Adagrad of the fused step alone; every other consumer refuses them, _refuse_bf16_tables)
                 for t, n in zip(tables, self.num_embeddings):
-                    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n, E)
+                    assert t.is_cuda and t.dtype in (torch.float32, torch.bfloat16) and t.is_contiguous() and tuple(t.shape) == (n, E)
+                    assert t.dtype == tables[0].dtype, "the tables are fp32 or bf16, not a mixture"
                 self.tables = list(tables)
             else:
                 self.tables = [torch.zeros(n, E, dtype=torch.float32, device=self.device) for n in self.num_embeddings]
@@ -328,6 +331,7 @@ class SupernetEngine:
             self.lr_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
             self.clip_out = torch.ones(2, dtype=torch.float32, device=self.device)  # [coef, total_norm]
             self.oob = torch.zeros(2, dtype=torch.int32, device=self.device)  # [index out of range, dedup hash partition overflow]
+        self.tables_bf16 = bool(self.tables) and self.tables[0].dtype == torch.bfloat16
         self.params: Dict[str, torch.Tensor] = {}
         self.grads: Dict[str, torch.Tensor] = {}
         self.state: Dict[str, torch.Tensor] = {}
@@ -372,7 +376,10 @@ class SupernetEngine:
                 is_ln = ("_ln" in name) or ("layernorm" in name)
                 if name.startswith("_embedding."):
                     std = (2.0 / (p.shape[0] + p.shape[1])) ** 0.5
-                    p.normal_(0.0, std, generator=g)
+                    if p.dtype == torch.bfloat16:  # (drawn in fp32 as ever, then rounded to nearest even: one table of overhead)
+                        p.copy_(torch.empty(p.shape, dtype=torch.float32, device=p.device).normal_(0.0, std, generator=g))
+                    else:
+                        p.normal_(0.0, std, generator=g)
                 elif is_ln:
                     if name.endswith(".weight"):
                         p.fill_(0.17 if ("_attn_ln" in name or "_attn_fc_ln" in name) else 1.0)
@@ -398,7 +405,15 @@ class SupernetEngine:
         self.stream.synchronize()
         return {k: v.detach().cpu().clone() for k, v in self.params.items()}
 
+    def _refuse_bf16_tables(self, what: str):
+        """bf16 tables are read by the gather and written by the fused row-wise Adagrad (OptimSpec.table_kind "rowwise_adagrad_bf16")
+        alone: every other kernel that takes a table indexes fp32 rows of 64 bytes, and is refused before anything is launched"""
+        if getattr(self, "tables_bf16", False):
+            raise L.EngineError("bf16 tables: %s reads and writes fp32 table rows; bf16 tables train with AdamAdagradTables("
+                                "table_rowwise=True) on the fused step (engine_train_step) and nothing else" % what)
+
     def _ensure_table_state(self):
+        self._refuse_bf16_tables("Adagrad's [rows, 16] table state (the Adagrad apply launch, adagrad_rows, weight decay's phase 1)")
         if self.table_state is None:
             with torch.cuda.stream(self.stream):
                 self.table_state = [torch.zeros_like(t) for t in self.tables]
@@ -412,7 +427,7 @@ class SupernetEngine:
 
     def _ensure_split_table_state(self, spec):
         """the tables' state of a split-optimizer spec: `table_row_state` for the row-wise rule, `table_state` for the element-wise one"""
-        if spec.table_kind == "rowwise_adagrad":
+        if spec.table_rowwise:  # (fp32 accumulators whatever the tables' storage type)
             self._ensure_table_row_state()
         else:
             self._ensure_table_state()
@@ -437,6 +452,22 @@ class SupernetEngine:
             raise L.EngineError("Adam / SGD are the fused training step's optimizer: they need train=True")
         if spec.dwd and not (train and local_optimizer):
             raise L.EngineError("decoupled weight decay is part of the one-process fused training step's optimizer")
+        if spec.bf16_tables != (self.tables_bf16 and train):
+            if not self.tables_bf16:
+                raise L.EngineError("table_kind %r is the rule of bf16 tables: this engine's tables are fp32" % (spec.table_kind,))
+            self._refuse_bf16_tables("a training plan with %s" % ("Adagrad" if not spec.moments else
+                                                                 "dense or row-sparse %s%s" % (spec.kind, " + " + spec.table_kind if spec.table_kind else "")))
+        if self.tables_bf16 and train:
+            if spec.wd:
+                self._refuse_bf16_tables("weight decay (its two phases, and the moments launch's phase 1 behind them)")
+            if spec.ema:
+                self._refuse_bf16_tables("the fused weight EMA")
+            if spec.dwd:
+                self._refuse_bf16_tables("the fused decoupled weight decay")
+            if not local_optimizer:
+                self._refuse_bf16_tables("the data-parallel step")
+            if self.persist and self.level_schedule and self.cfg.fixed and B <= 256:
+                self._refuse_bf16_tables("the persistent step (NASREC_PERSIST_DEFAULT=1)")
         fast = (id(choice), B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, spec)
         hit = self._last_plan
         if self.cfg.fixed and hit is not None and hit[0] == fast and hit[1] is choice:  # fixed sub-network, same choice object: skip the JSON key
@@ -510,6 +541,7 @@ class SupernetEngine:
             g.kind = L.OP_EMBED_GATHER
             g.B, g.Fs = B, self.Fs
             g.idx = cp.cat_x.data_ptr()
+            g.table_dtype = L.TABLE_DTYPE_BF16 if self.tables_bf16 else L.TABLE_DTYPE_F32  # (the stage descriptor below copies it)
             if not self.host_embedding:
                 for f in range(self.Fs):
                     g.table[f] = self.tables[f].data_ptr()
@@ -864,6 +896,8 @@ class SupernetEngine:
         "rmsprop": square_avg, and `lazy_stamps` — per table one int32 per row, the table's step count at which that row's square_avg
         is current (csrc/optim_moments.hip); engine-private, never part of optimizer.state.
         -> {state key: (flat arena, [table arrays])}"""
+        if tables:
+            self._refuse_bf16_tables("%s on every table row (its table moments)" % kind)
         keys = {"adam": ("exp_avg", "exp_avg_sq"), "rmsprop": ("square_avg",)}.get(kind, ("momentum_buffer",))
         st = self.__dict__.setdefault("moments", {})
         with torch.cuda.stream(self.stream):
@@ -973,7 +1007,7 @@ class SupernetEngine:
     @staticmethod
     def _optim_scalars(d, spec):
         """algo and hyperparameters of an Adam / SGD spec on an OptMomentsDesc or a LastLayerStepDesc"""
-        if spec.table_kind not in ("", "adagrad", "rowwise_adagrad") or (spec.table_kind and spec.kind != "adam"):
+        if (spec.table_kind not in ("", "adagrad", "rowwise_adagrad") and not spec.bf16_tables) or (spec.table_kind and spec.kind != "adam"):
             raise L.EngineError("table_kind %r with %s: the split optimizer is Adam with (row-wise) Adagrad on the tables" % (spec.table_kind, spec.kind))
         d.algo = {"adam": L.OPTIM_ADAM, "rmsprop": L.OPTIM_RMSPROP}.get(spec.kind, L.OPTIM_SGD)
         d.eps, d.momentum, d.nesterov = spec.eps, spec.momentum, int(bool(spec.nesterov))
@@ -987,18 +1021,21 @@ class SupernetEngine:
         are millions of floats).  RMSprop: the same shape of launches (its rows rest too, owing only a decay); m is unused and the
         slots of `tm` carry the stamps.  Adagrad on the tables (spec.table_kind): the same shape again; tv carries `table_state`, tm
         nothing, and the tables' learning rate is lr * table_lr_scale in the kernel; row-wise Adagrad: tv carries `table_row_state`,
-        one float per row."""
+        one float per row; on bf16 tables (table_kind "rowwise_adagrad_bf16") the same with the other table_algo and the rounding's seed
+        in tm[0]'s storage — constant from step to step: the kernel reads the step count on the device."""
         spec = t.spec
         st = self.moments
         lazy = spec.rows_only  # (the tables move in the batch's rows only)
-        split, rowwise = bool(spec.table_kind), spec.table_kind == "rowwise_adagrad"
+        split, rowwise = bool(spec.table_kind), spec.table_rowwise
+        if spec.bf16_tables != self.tables_bf16:
+            raise L.EngineError("table_kind %r on %s tables" % (spec.table_kind, "bf16" if self.tables_bf16 else "fp32"))
         m = L.OptMomentsDesc()
         m.kind, m.phase = L.OP_OPT_MOMENTS, 0
         self._optim_scalars(m, spec)
         m.dense_blocks = min(2048, t.mom_chunks[1])
         m.sparse_rows = int(bool(spec.sparse_rows))
         if split:
-            m.table_algo = L.TABLE_ALGO_ROWWISE_ADAGRAD if rowwise else L.TABLE_ALGO_ADAGRAD
+            m.table_algo = L.TABLE_ALGO_ROWWISE_ADAGRAD_BF16 if spec.bf16_tables else L.TABLE_ALGO_ROWWISE_ADAGRAD if rowwise else L.TABLE_ALGO_ADAGRAD
             m.table_eps, m.table_lr_scale = spec.table_eps, spec.table_lr_scale
         m.nblocks = self.WD_BLOCKS if (t.mom_tables or lazy) else 1  # (no table moves: phase 1 only counts the step and restores g)
         m.B, m.Fs = (Bg, self.Fs) if gsum is not None else (0, self.Fs)
@@ -1026,6 +1063,8 @@ class SupernetEngine:
             m.tm[f] = first[1][f].data_ptr()
             if second is not None:
                 m.tv[f] = second[1][f].data_ptr()
+        if spec.bf16_tables:
+            m.sr_seed = spec.table_seed  # (over tm[0], which the loop above left null)
         m.reg_mask = sum(1 << f for f in t.wd_tables) if spec.wd else 0
         m.bitmap = self._row_bitmap().data_ptr()
         m.step = self.opt_steps.data_ptr()
@@ -1043,6 +1082,7 @@ class SupernetEngine:
     def _weight_decay_descs(self, t, Bg, cat_x, gsum, eps, clip_partial, rank_layout=None):
         """the two NASREC_OP_WEIGHT_DECAY launches of a plan: (phase 0, in front of the clip; phase 1, behind the touched rows' Adagrad).
         rank_layout: (samples per rank, floats between the ranks' chunks) of `gsum` (_optimizer_descs)"""
+        self._refuse_bf16_tables("weight decay (its two phases)")
         w = L.WeightDecayDesc()
         w.kind, w.phase, w.nblocks = L.OP_WEIGHT_DECAY, 0, self.WD_BLOCKS
         w.wd, w.eps = t.spec.wd, eps
@@ -1220,6 +1260,7 @@ class SupernetEngine:
         level at which that row's weights are current; and the last-arrival counter.  All zero: every row current."""
         if self.host_embedding:
             raise L.EngineError("the fused decoupled weight decay needs the embedding tables on the device")
+        self._refuse_bf16_tables("the fused decoupled weight decay")
         if getattr(self, "decay_level", None) is not None:
             return
         with torch.cuda.stream(self.stream):
@@ -1306,6 +1347,7 @@ class SupernetEngine:
             raise L.EngineError("weight EMA: decay %r is not inside (0, 1)" % (decay,))
         if self.host_embedding:
             raise L.EngineError("the fused weight EMA needs the embedding tables on the device")
+        self._refuse_bf16_tables("the fused weight EMA (its fp32 shadow tables)")
         have = getattr(self, "ema_decay", None)
         if have is not None:
             if have != decay:
@@ -1745,6 +1787,7 @@ class SupernetEngine:
         choice = choice if choice is not None else self.warm_choice
         if self.host_embedding:
             raise L.EngineError("the last-layer step needs the embedding tables on the device")
+        self._refuse_bf16_tables("the last-layer step (its plan is the Adagrad training plan)")
         if optim is not None and optim.kind == "rmsprop":
             raise L.EngineError("the last-layer step has no RMSprop: the fine-tune keeps the torch route with it")
         if optim is not None and optim.table_kind:

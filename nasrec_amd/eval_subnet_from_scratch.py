@@ -22,7 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from nasrec_amd.main_train import _num_embedding_dict, _num_sparse_inputs_dict, build_lr_scheduler, build_optimizer  # noqa: E402
+from nasrec_amd.main_train import (TABLE_DTYPES, _num_embedding_dict, _num_sparse_inputs_dict, add_table_dtype_flags,  # noqa: E402
+                                   build_lr_scheduler, build_optimizer, check_table_dtype)
 from nasrec_amd.supernet.supernet import SuperNet, ops_config_lib  # noqa: E402
 from nasrec_amd.utils.data_pipes import make_loaders  # noqa: E402
 from nasrec_amd.utils.io_utils import create_dir, dump_pickle_data, load_pickle_data  # noqa: E402
@@ -44,7 +45,7 @@ def train_and_eval_one_model(model, args):
     loss_fn = torch.nn.BCEWithLogitsLoss()
     model.apply(init_weights)
     optimizer = build_optimizer(args.optimizer, model, args.learning_rate, args.table_lr_scale, args.table_eps,
-                                table_rowwise=args.table_rowwise)
+                                table_rowwise=args.table_rowwise, table_seed=args.table_seed)
     steps_per_epoch = args.train_limit // args.train_batch_size
     # (the warm-up shrinks with the number of epochs here — :134 — unlike main_train.py)
     lr_scheduler = build_lr_scheduler(args.lr_schedule, optimizer, steps_per_epoch * args.num_epochs, steps_per_epoch // 10 // args.num_epochs,
@@ -62,6 +63,7 @@ def train_and_eval_one_model(model, args):
 
 
 def main(args):
+    check_table_dtype(args)
     print("Matmul precision: {}".format(args.matmul_precision))
     np.random.seed(args.random_seed)  # the candidates come from the global stream (supernet.py `fixed-path`)
     if args.choice_from_pickle_file is not None:
@@ -79,7 +81,7 @@ def main(args):
         model = SuperNet(sparse_input_size=_num_sparse_inputs_dict[args.dataset], num_blocks=args.num_blocks, ops_config=ops_config_lib[args.config],
                          use_layernorm=(args.use_layernorm == 1), activation=args.activation, num_embeddings=tables,
                          path_sampling_strategy="fixed-path", fixed=True, fixed_choice=choice,
-                         matmul_precision=args.matmul_precision)
+                         matmul_precision=args.matmul_precision, table_dtype=TABLE_DTYPES[args.table_dtype])
         model = model.to(args.gpu)
         logs = train_and_eval_one_model(model, args)
         print("Trained model with the following choice...")
@@ -132,6 +134,7 @@ def build_parser():
     p.add_argument("--table-rowwise", dest="table_rowwise", action="store_true",
                    help="--optimizer adam-adagrad-tables: row-wise Adagrad on the tables — one accumulator per embedding row, fed the "
                         "mean of the row's squared gradient (1/16 of the element-wise state); refused with any other --optimizer")
+    add_table_dtype_flags(p)
     p.add_argument("--loss_function", type=str, default="bce", choices=["bce"])
     p.add_argument("--gpu", type=int, default=0, help="GPU ID to use.")
     p.add_argument("--matmul-precision", dest="matmul_precision", type=str, default="highest", choices=["highest", "high", "medium"],

@@ -43,12 +43,56 @@ def summary_writer(logging_dir):
         return None
 
 
-def build_optimizer(name, model, lr, table_lr_scale=1.0, table_eps=1e-2, table_rowwise=False):
+TABLE_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+
+
+def check_table_dtype(args, world: int = 1, use_amp: bool = False, last_layer: bool = False):
+    """--table-dtype bf16 at start-up: the recipe must be the one the fused step has for bf16 tables (--optimizer adam-adagrad-tables
+    --table-rowwise, one process, whole tables, nothing else that reads or writes a table row) — anything else is a ValueError that
+    names the flag, never a silent torch route (which could not train them: utils/optim.AdamAdagradTables.step raises).
+    world / use_amp / last_layer: what the caller knows beyond the flags (the process group's size, torch.autocast, the last-layer
+    fine-tune mode)"""
+    if getattr(args, "table_dtype", "fp32") != "bf16":
+        return
+    head = "--table-dtype bf16 "
+    if args.optimizer != "adam-adagrad-tables" or not getattr(args, "table_rowwise", False):
+        raise ValueError(head + "needs --optimizer adam-adagrad-tables --table-rowwise (got --optimizer %s%s): row-wise Adagrad in fp32 on "
+                         "the widened row, stored with stochastic rounding, is the one rule bf16 tables train with"
+                         % (args.optimizer, " --table-rowwise" if getattr(args, "table_rowwise", False) else ""))
+    if getattr(args, "ema", 0.0):
+        raise ValueError(head + "with --ema: the weight average keeps fp32 shadow tables; not built for bf16 tables")
+    if getattr(args, "decoupled_wd", 0.0):
+        raise ValueError(head + "with --decoupled-wd: the lazily paid decay rewrites fp32 table rows; not built for bf16 tables")
+    if args.wd:
+        from nasrec_amd.optim_spec import regularises_tables
+        if regularises_tables(args.wd, args.no_reg_param_name):
+            raise ValueError(head + "with --wd %r reaching the embedding tables: every row would move every step (--wd 0, the published "
+                             "recipes' value)" % (args.wd,))
+        raise ValueError(head + "with --wd %r: weight decay's launches are not built for bf16 tables (--wd 0)" % (args.wd,))
+    if use_amp:
+        raise ValueError(head + "with AMP (use_amp): autocast keeps the torch route, which cannot train bf16 tables")
+    if getattr(args, "table_sharding", "none") == "row":
+        raise ValueError(head + "with --table-sharding row: bf16 tables are whole tables on one device")
+    if world > 1:
+        raise ValueError(head + "with a world size of %d: the data-parallel step is not built for bf16 tables (one process)" % world)
+    if last_layer:
+        raise ValueError(head + "with the last-layer fine-tune mode: its fused step and its torch route both take fp32 tables")
+
+
+def add_table_dtype_flags(p):
+    p.add_argument("--table-dtype", dest="table_dtype", type=str, default="fp32", choices=sorted(TABLE_DTYPES),
+                   help="storage type of the embedding tables (SuperNet(table_dtype=...)): bf16 halves their memory and their checkpoint; "
+                        "needs --optimizer adam-adagrad-tables --table-rowwise, one process, --wd 0 and neither --ema nor --decoupled-wd")
+    p.add_argument("--table-seed", dest="table_seed", type=int, default=0,
+                   help="--table-dtype bf16: seed of the stochastic rounding the tables' new weights are stored with")
+
+
+def build_optimizer(name, model, lr, table_lr_scale=1.0, table_eps=1e-2, table_rowwise=False, table_seed=0):
     """main_train.py:150-160 (Adagrad eps 1e-2; Adam eps 1e-8; SGD nesterov momentum 0.9); row-sparse-adam: Adam's lr and eps, the
     tables moving in the batch's rows only (utils/optim.RowSparseAdam); rmsprop: torch's defaults (alpha 0.99, eps 1e-8) as
     utils/optim.LazyRMSprop, which is torch.optim.RMSprop and the type the fused step takes; adam-adagrad-tables: Adam's lr and eps
     on the dense parameters, Adagrad with lr * table_lr_scale and table_eps on the tables (utils/optim.AdamAdagradTables), row-wise
-    Adagrad with table_rowwise — which goes with that optimizer only"""
+    Adagrad with table_rowwise — which goes with that optimizer only; table_seed: the stochastic rounding's seed of bf16 tables"""
     if table_rowwise and name != "adam-adagrad-tables":
         raise ValueError("--table-rowwise is the tables' rule of --optimizer adam-adagrad-tables; it does nothing with --optimizer %s" % name)
     if name == "adagrad":
@@ -66,7 +110,7 @@ def build_optimizer(name, model, lr, table_lr_scale=1.0, table_eps=1e-2, table_r
     if name == "adam-adagrad-tables":
         from nasrec_amd.utils.optim import AdamAdagradTables
         return AdamAdagradTables(model.parameters(), list(model._embedding.parameters()), lr=lr, eps=1e-8, table_lr_scale=table_lr_scale,
-                                 table_eps=table_eps, table_rowwise=table_rowwise)
+                                 table_eps=table_eps, table_rowwise=table_rowwise, table_seed=table_seed)
     if name == "rmsprop":
         from nasrec_amd.utils.optim import LazyRMSprop
         return LazyRMSprop(model.parameters(), lr=lr)
@@ -97,7 +141,7 @@ def train_and_eval_one_model(model, args):
     l2_loss_fn = L2Loss(args.wd, args.no_reg_param_name, gpu=args.gpu)  # (a spec the fused engine step folds in: any --wd)
 
     optimizer = build_optimizer(args.optimizer, model, args.learning_rate, args.table_lr_scale, args.table_eps,
-                                table_rowwise=args.table_rowwise)
+                                table_rowwise=args.table_rowwise, table_seed=args.table_seed)
     steps_per_epoch = args.train_limit // args.train_batch_size
     num_train_steps = steps_per_epoch * args.num_epochs
     num_warmup_steps = steps_per_epoch // 10 // args.num_epochs
@@ -144,7 +188,7 @@ def get_model(args):
         return SuperNet(sparse_input_size=_num_sparse_inputs_dict[args.dataset], num_blocks=7, ops_config=ops_config_lib["xlarge"],
                         use_layernorm=True, activation=args.activation, num_embeddings=_num_embedding_dict[args.dataset],
                         path_sampling_strategy="full-path", table_sharding=args.table_sharding,
-                        matmul_precision=args.matmul_precision)
+                        matmul_precision=args.matmul_precision, table_dtype=TABLE_DTYPES[args.table_dtype])
     if args.net == "supernet-config":
         choice = load_json(args.supernet_config)
         print(choice)
@@ -152,13 +196,15 @@ def get_model(args):
         return SuperNet(sparse_input_size=_num_sparse_inputs_dict[args.dataset], num_blocks=choice["num_blocks"],
                         ops_config=ops_config_lib[choice["config"]], use_layernorm=False, activation=args.activation,
                         num_embeddings=_num_embedding_dict[args.dataset], path_sampling_strategy="fixed-path", fixed=True,
-                        fixed_choice=choice, table_sharding=args.table_sharding, matmul_precision=args.matmul_precision)
+                        fixed_choice=choice, table_sharding=args.table_sharding, matmul_precision=args.matmul_precision,
+                        table_dtype=TABLE_DTYPES[args.table_dtype])
     raise NotImplementedError("Model {} is not implemented!".format(args.net))
 
 
 def main(args):
     from nasrec_amd.utils.dist import init_from_env
     rank, world = init_from_env(args)  # torchrun: one process per GPU, args.gpu = the local rank
+    check_table_dtype(args, world=world)
     create_dir(args.logging_dir)
     print("Matmul precision: {}".format(args.matmul_precision))
     model = get_model(args).to(args.gpu)
@@ -205,6 +251,7 @@ def build_parser():
     p.add_argument("--table-rowwise", dest="table_rowwise", action="store_true",
                    help="--optimizer adam-adagrad-tables: row-wise Adagrad on the tables — one accumulator per embedding row, fed the "
                         "mean of the row's squared gradient (1/16 of the element-wise state); refused with any other --optimizer")
+    add_table_dtype_flags(p)
     # Criteo: train 36672495 / val 4584061 / test 4584061 / trainval 41256556; Avazu: 32343175 / 4042896 / 4042896 / 36386071;
     # KDD: 119711284 / 14963910 / 14963910 / 134675194
     p.add_argument("--train_limit", type=int, default=41256556, help="Maximum number of training examples.")

@@ -24,7 +24,10 @@ class OptimSpec(NamedTuple):
     table_kind: str = ""    # "" = the tables take `kind`; "adagrad" (kind "adam": utils/optim.AdamAdagradTables) = torch.optim.Adagrad on
                             # the tables, exactly row-sparse, with table_eps and the learning rate lr * table_lr_scale;
                             # "rowwise_adagrad" (AdamAdagradTables(table_rowwise=True)) = the same with ONE accumulator per row, fed
-                            # the mean of the row's squared gradient
+                            # the mean of the row's squared gradient; "rowwise_adagrad_bf16" / "rowwise_adagrad_bf16:<seed>"
+                            # (bf16_table_kind) = that rule on tables STORED as bf16 (SuperNet(table_dtype=torch.bfloat16)): computed
+                            # in fp32 on the widened row, stored with stochastic rounding (utils/optim.stochastic_round_bf16) under
+                            # the seed the value carries — `table_seed` reads it; no field of its own: tests pin the tuple's fields
     table_eps: float = 1e-2
     table_lr_scale: float = 1.0
     dwd: float = 0.0        # decoupled weight decay p <- p (1 - lr dwd) before the update (utils/optim.DecoupledWeightDecay,
@@ -41,7 +44,29 @@ class OptimSpec(NamedTuple):
     def rows_only(self) -> bool:
         """the tables move in the batch's rows only (a row outside it keeps its bits, or owes only a closed-form factor): Adagrad,
         row-sparse Adam, RMSprop and Adam with Adagrad (element- or row-wise) on the tables"""
-        return self.kind in ("adagrad", "rmsprop") or bool(self.sparse_rows) or self.table_kind in ("adagrad", "rowwise_adagrad")
+        return self.kind in ("adagrad", "rmsprop") or bool(self.sparse_rows) or \
+            self.table_kind in ("adagrad", "rowwise_adagrad") or self.bf16_tables
+
+    @property
+    def table_rowwise(self) -> bool:
+        """the tables' accumulator is one float per row (the engine's table_row_state), whatever the tables' storage type"""
+        return self.table_kind == "rowwise_adagrad" or self.bf16_tables
+
+    @property
+    def bf16_tables(self) -> bool:
+        """the rule of tables stored as bf16: the only one the fused step has for them"""
+        return self.table_kind.partition(":")[0] == "rowwise_adagrad_bf16"
+
+    @property
+    def table_seed(self) -> int:
+        """the seed of the stochastic rounding of bf16 tables (0 for every other rule)"""
+        head, _, seed = self.table_kind.partition(":")
+        return int(seed) if (head == "rowwise_adagrad_bf16" and seed) else 0
+
+    @staticmethod
+    def bf16_table_kind(seed: int = 0) -> str:
+        """the table_kind of row-wise Adagrad on bf16 tables with this seed"""
+        return "rowwise_adagrad_bf16:%d" % int(seed) if int(seed) else "rowwise_adagrad_bf16"
 
     @property
     def state_keys(self):
@@ -75,7 +100,8 @@ class OptimSpec(NamedTuple):
         SGD: one group, momentum != 0 (plain SGD keeps the torch route), dampening 0, weight_decay 0, not maximize / differentiable / fused.
         RowSparseAdam: Adam's conditions (its one group carries Adam's keys) -> sparse_rows.
         AdamAdagradTables: Adam's conditions -> table_kind "adagrad", or "rowwise_adagrad" where the group's table_rowwise is set, with
-        the group's table_eps / table_lr_scale (plain numbers).
+        the group's table_eps / table_lr_scale (plain numbers); tables of dtype bfloat16 (accepted by that optimizer only with
+        table_rowwise) -> bf16_table_kind(the group's table_seed).
         LazyRMSprop (that type exactly: a hand-built torch.optim.RMSprop keeps the torch route): one group, momentum 0, not centered,
         weight_decay 0, not maximize / capturable / differentiable."""
         from .utils.optim import AdamAdagradTables, LazyRMSprop, RowSparseAdam
@@ -93,8 +119,12 @@ class OptimSpec(NamedTuple):
             if type(optimizer) is AdamAdagradTables:
                 if torch.is_tensor(g["table_eps"]) or torch.is_tensor(g["table_lr_scale"]) or torch.is_tensor(g["eps"]):
                     return None
-                return OptimSpec("adam", beta1=float(b1), beta2=float(b2), eps=float(g["eps"]),
-                                 table_kind="rowwise_adagrad" if g.get("table_rowwise", False) else "adagrad",
+                kind = "rowwise_adagrad" if g.get("table_rowwise", False) else "adagrad"
+                if optimizer.bf16_tables:
+                    if kind != "rowwise_adagrad":
+                        return None
+                    kind = OptimSpec.bf16_table_kind(g.get("table_seed", 0))
+                return OptimSpec("adam", beta1=float(b1), beta2=float(b2), eps=float(g["eps"]), table_kind=kind,
                                  table_eps=float(g["table_eps"]), table_lr_scale=float(g["table_lr_scale"]))
             return OptimSpec("adam", beta1=float(b1), beta2=float(b2), eps=float(g["eps"]), sparse_rows=type(optimizer) is RowSparseAdam)
         if type(optimizer) is LazyRMSprop:

@@ -83,7 +83,9 @@ class _SupernetFunction(torch.autograd.Function):
         eng = model._engine
         B = int(int_x.shape[0])
         with _tracing_paused():
-            cp = eng.compile(choice, B, train=True)
+            # (bf16 tables have no differentiable forward — SuperNet.forward refuses it: only torch.jit.trace arrives here with them,
+            # and takes the forward-only plan)
+            cp = eng.compile(choice, B, train=not eng.tables_bf16)
             eng.run_forward(cp, int_x, cat_x, rows=rows)
         out = cp.logits.view(B, 1).clone()  # (outside the pause: a result the tracer has not seen cannot become the node's output)
         ctx.has_rows = rows is not None
@@ -95,6 +97,9 @@ class _SupernetFunction(torch.autograd.Function):
     def backward(ctx, dlogits):
         model, cp = ctx.model, ctx.cp
         eng = model._engine
+        if eng.tables_bf16:
+            from .._lib import EngineError
+            raise EngineError("bf16 tables have no backward through autograd: train them on the fused step (engine_train_step)")
         if getattr(cp, "evicted", False):
             raise RuntimeError("the launch plan of this forward was recycled for another sampled path before its backward ran (the "
                                "engine keeps 4 supernet plans): run backward before sampling further paths")
@@ -169,8 +174,14 @@ class SuperNet(nn.Module):
                  last_n_blocks_out: int = 1, path_sampling_strategy: str = "default", fixed: bool = False, fixed_choice: Any = None,
                  place_embedding_on_cpu: bool = False, anypath_choice: str = "uniform", supernet_training_steps: int = 0,
                  candidate_choices: Optional[List] = None, use_final_sigmoid: bool = False, table_sharding: Optional[str] = None,
-                 matmul_precision: Optional[str] = None):
-        """matmul_precision (not a reference argument): "highest" | "high" | "medium"; None = the environment variable
+                 matmul_precision: Optional[str] = None, table_dtype: torch.dtype = torch.float32):
+        """table_dtype (not a reference argument): torch.float32, or torch.bfloat16 = the embedding tables are STORED as bf16 ([rows, 16]
+        with 32-byte rows: half the memory and half the checkpoint).  They are initialised in fp32 exactly as ever and rounded to nearest
+        even, one table at a time; the forward widens a row exactly and everything downstream stays fp32.  They train on the fused step
+        with AdamAdagradTables(table_rowwise=True) alone (row-wise Adagrad in fp32 on the widened row, stored with stochastic rounding:
+        utils/optim.stochastic_round_bf16); evaluation is the ordinary no-grad forward.  Refused with place_embedding_on_cpu,
+        table_sharding="row" and use_final_sigmoid.
+        matmul_precision (not a reference argument): "highest" | "high" | "medium"; None = the environment variable
         NASREC_MATMUL_PRECISION, else "highest".  What torch.set_float32_matmul_precision is to torch, for the engine: parameters,
         activations, optimizer state and checkpoints stay fp32 and products accumulate in fp32; "medium" permits the large-batch
         products of the Linear family — forward, input gradient, weight gradient; the throughput-regime GEMMs and, at batch >= 1024,
@@ -203,6 +214,17 @@ class SuperNet(nn.Module):
         from .._lib import matmul_precision_name
         self._matmul_precision = matmul_precision_name(matmul_precision)  # (ValueError on anything else)
         self._sharded = self._sharded_ops = None
+        if table_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("table_dtype %r: the tables are stored as torch.float32 or torch.bfloat16" % (table_dtype,))
+        self._table_dtype = table_dtype
+        if table_dtype == torch.bfloat16:
+            for flag, on in (("place_embedding_on_cpu", place_embedding_on_cpu), ("table_sharding='row'", self._table_sharding == "row"),
+                             ("use_final_sigmoid", use_final_sigmoid)):
+                if on:
+                    raise ValueError("table_dtype=torch.bfloat16 with %s: bf16 tables are whole tables on one device, read by the "
+                                     "engine's gather and trained by its fused step" % flag)
+            if embedding_dim != 16:
+                raise ValueError("table_dtype=torch.bfloat16 needs embedding_dim 16 (32-byte rows), got %d" % embedding_dim)
         self._embedding = self._embedding_layers(sparse_input_size, num_embeddings, embedding_dim)
         self._final = nn.LazyLinear(1)
         self._final_sigmoid = nn.Sigmoid() if use_final_sigmoid else None
@@ -261,7 +283,13 @@ class SuperNet(nn.Module):
                 lo, hi, rows = self._shard_rows(num_embeddings[i])
                 out.append(ShardEmbedding(rows, embedding_dim, whole_rows=num_embeddings[i], row_lo=lo, row_hi=hi, field=i))
             return nn.ModuleList(out)
-        return nn.ModuleList([nn.Embedding(num_embeddings[i], embedding_dim) for i in range(sparse_input_size)])
+        out = []
+        for i in range(sparse_input_size):
+            emb = nn.Embedding(num_embeddings[i], embedding_dim)  # (nn.Embedding's own fp32 draw, whatever the storage type)
+            if self._table_dtype == torch.bfloat16:
+                emb.weight.data = emb.weight.data.to(torch.bfloat16)  # (nearest even; one table at a time: the peak overhead is one table)
+            out.append(emb)
+        return nn.ModuleList(out)
 
     def apply(self, fn):
         """nn.Module.apply; with row-sharded tables, the reference's `init_weights` (train_utils.py:70-89: xavier_normal_ on every
@@ -274,6 +302,16 @@ class SuperNet(nn.Module):
                 else:
                     _fn(m)
             return super().apply(routed)
+        if self._table_dtype == torch.bfloat16 and getattr(fn, "__name__", "") == "init_weights":
+            # bf16 tables: the same xavier_normal_ draw in fp32 (the random stream is consumed as by the fp32 model), rounded to nearest
+            # even into the table, one table at a time
+            def rounded(m, _fn=fn):
+                if type(m) is nn.Embedding and m.weight.dtype == torch.bfloat16:
+                    with torch.no_grad():
+                        m.weight.copy_(torch.nn.init.xavier_normal_(torch.empty(m.weight.shape, dtype=torch.float32, device=m.weight.device)))
+                else:
+                    _fn(m)
+            return super().apply(rounded)
         return super().apply(fn)
 
     @staticmethod
@@ -495,8 +533,11 @@ class SuperNet(nn.Module):
         self._param_names = [(n, p) for n, p in self.named_parameters() if not (host and n.startswith("_embedding."))]
         st = self.__dict__.pop("_stashed_opt_state", None)
         if st is not None:  # accumulators of the engine this one replaces
-            eng._ensure_table_state()
+            if not eng.tables_bf16:  # (bf16 tables have no [rows, 16] state)
+                eng._ensure_table_state()
             for n, t in st.items():
+                if n.startswith("_embedding.") and eng.table_state is None:
+                    continue
                 tgt = eng.table_state[int(n.split(".")[1])] if n.startswith("_embedding.") else eng.state.get(n)
                 if tgt is not None and tuple(tgt.shape) == tuple(t.shape):
                     tgt.copy_(t.to(tgt.device))
@@ -612,6 +653,13 @@ class SuperNet(nn.Module):
             ids = cat_feats.cpu()
             rows = torch.stack([emb(ids[:, f]) for f, emb in enumerate(self._embedding)], dim=1).to(int_feats.device)
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for _, p in self._param_names)
+        if needs_grad and self._table_dtype == torch.bfloat16 and not torch.jit.is_tracing():
+            from .._lib import EngineError
+            raise EngineError("bf16 tables: train through the fused engine step (engine_train_step with AdamAdagradTables("
+                              "table_rowwise=True) — the route train_and_test_one_epoch takes for --table-dtype bf16); a differentiable "
+                              "forward would hand torch.autograd a dense bf16 gradient the size of every table, which is neither the "
+                              "rule (fp32 row-wise Adagrad, stored with stochastic rounding) nor affordable.  Evaluate under "
+                              "torch.no_grad().")
         # torch.jit.trace (TensorBoard's writer.add_graph, main_train.py:137 / train_supernet.py:192; fvcore's FLOP counter,
         # train_utils.py:444-452): the network traces as ONE opaque node (prim::PythonOp) that consumes the inputs and every
         # parameter — the no-grad route would hand the tracer a result that depends on nothing it has seen
@@ -634,7 +682,7 @@ class SuperNet(nn.Module):
         is BCE + get_l2_loss(self, weight_decay, no_reg_param_name) — every regularised parameter and every table row is decayed
         (engine_last_l2 = that term on the pre-step weights).  optim: an OptimSpec (nasrec_amd/optim_spec.py) of torch.optim.Adam / SGD
         replaces Adagrad (eps unused) — every table row moves every step, or with sparse_rows (utils/optim.RowSparseAdam) or
-        table_kind "adagrad" / "rowwise_adagrad" (utils/optim.AdamAdagradTables: Adagrad on the tables at lr * table_lr_scale) only the
+        table_kind "adagrad" / "rowwise_adagrad" / "rowwise_adagrad_bf16" (utils/optim.AdamAdagradTables: Adagrad on the tables at lr * table_lr_scale) only the
         batch's rows, which weight decay must then leave out; engine_bind_optimizer / engine_sync_optimizer_steps share its
         state with the torch optimizer.  Both need whole tables; under data parallelism they run in the exchange step's optimizer over
         the global batch (nasrec_amd/parallel.py).  ema_decay != 0: the step also averages every parameter (utils/optim.WeightEMA's
@@ -805,7 +853,7 @@ class SuperNet(nn.Module):
                         if key == "sum" and tuple(src.shape) != tuple(tgt.shape):
                             # (an element-wise checkpoint under the row-wise rule or the reverse: nothing may be reshaped or broadcast)
                             raise ValueError("engine_bind_optimizer: the optimizer's `sum` of a table has shape %s, the %s rule keeps %s"
-                                             % (tuple(src.shape), "row-wise" if spec.table_kind == "rowwise_adagrad" else "element-wise",
+                                             % (tuple(src.shape), "row-wise" if spec.table_rowwise else "element-wise",
                                                 tuple(tgt.shape)))
                         tgt.copy_(src.to(tgt.device).view_as(tgt))
                 if st:
@@ -906,7 +954,7 @@ class SuperNet(nn.Module):
         eng.ensure_moments_state(spec.kind, tables=not spec.table_kind)
         if spec.table_kind:  # (AdamAdagradTables: a table's state is Adagrad's sum, the engine's table_state or, row-wise, table_row_state;
             eng._ensure_split_table_state(spec)  # its counter is the state's step)
-        table_sums = eng.table_row_state if spec.table_kind == "rowwise_adagrad" else eng.table_state
+        table_sums = eng.table_row_state if spec.table_rowwise else eng.table_state
 
         def views(n):
             if spec.table_kind and n.startswith("_embedding."):
@@ -919,7 +967,9 @@ class SuperNet(nn.Module):
         """Adam / SGD: the state of every parameter the engine has stepped (counts > 0) aliases the engine's arrays, as torch creates it on
         a parameter's first step"""
         for p, views, k in slots:
-            if counts[k] <= 0:
+            # (a bf16 table has its state from the optimizer's constructor — no step() of its own ever creates it: it aliases the
+            # engine's accumulators at once, so the constructor's zeros are not kept beside them)
+            if counts[k] <= 0 and not (spec.bf16_tables and "sum" in views):
                 continue
             st = optimizer.state[p]
             st.update(views)

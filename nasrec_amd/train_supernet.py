@@ -14,7 +14,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from nasrec_amd.main_train import _num_embedding_dict, _num_sparse_inputs_dict, _decoupled_wd, build_lr_scheduler, build_optimizer, summary_writer  # noqa: E402
+from nasrec_amd.main_train import (TABLE_DTYPES, _decoupled_wd, _num_embedding_dict, _num_sparse_inputs_dict, add_table_dtype_flags,  # noqa: E402
+                                   build_lr_scheduler, build_optimizer, check_table_dtype, summary_writer)
 from nasrec_amd.supernet.supernet import SuperNet, ops_config_lib  # noqa: E402
 from nasrec_amd.utils.data_pipes import make_loaders  # noqa: E402
 from nasrec_amd.utils.io_utils import create_dir, dump_pickle_data, load_model_checkpoint, load_optimizer_state, save_model_checkpoint  # noqa: E402
@@ -36,7 +37,7 @@ def train_and_eval_one_model(model, args):
     l2_loss_fn = L2Loss(args.wd, args.no_reg_param_name, gpu=args.gpu)
 
     optimizer = build_optimizer(args.optimizer, model, args.learning_rate, args.table_lr_scale, args.table_eps,
-                                table_rowwise=args.table_rowwise)
+                                table_rowwise=args.table_rowwise, table_seed=args.table_seed)
     steps_per_epoch = args.train_limit // args.train_batch_size
     num_train_steps = steps_per_epoch * args.num_epochs
     lr_scheduler = build_lr_scheduler(args.lr_schedule, optimizer, num_train_steps, num_train_steps // 10, args.learning_rate)
@@ -81,12 +82,14 @@ def train_and_eval_one_model(model, args):
 def main(args):
     from nasrec_amd.utils.dist import init_from_env
     rank, world = init_from_env(args)  # torchrun: one process per GPU, args.gpu = the local rank; same path seed on every rank
+    check_table_dtype(args, world=world)
     print("Matmul precision: {}".format(args.matmul_precision))
     model = SuperNet(sparse_input_size=_num_sparse_inputs_dict[args.dataset], num_blocks=args.num_blocks,
                      ops_config=ops_config_lib[args.config], use_layernorm=(args.use_layernorm == 1), activation="relu",
                      num_embeddings=_num_embedding_dict[args.dataset], path_sampling_strategy=args.strategy,
                      anypath_choice=args.anypath_choice, supernet_training_steps=args.supernet_training_steps, candidate_choices=None,
-                     table_sharding=args.table_sharding, matmul_precision=args.matmul_precision)
+                     table_sharding=args.table_sharding, matmul_precision=args.matmul_precision,
+                     table_dtype=TABLE_DTYPES[args.table_dtype])
     return train_and_eval_one_model(model.to(args.gpu), args)
 
 
@@ -132,6 +135,7 @@ def build_parser():
     p.add_argument("--table-rowwise", dest="table_rowwise", action="store_true",
                    help="--optimizer adam-adagrad-tables: row-wise Adagrad on the tables — one accumulator per embedding row, fed the "
                         "mean of the row's squared gradient (1/16 of the element-wise state); refused with any other --optimizer")
+    add_table_dtype_flags(p)
     p.add_argument("--pretrained_dlrm_emb_path", type=str, default=None, help="Pretrained embedding path from DLRM model.")
     p.add_argument("--gpu", type=int, default=0, help="GPU ID to use.")
     # not a reference flag: placement of the embedding tables under torchrun (nasrec_amd/sharded_tables.py)

@@ -113,6 +113,53 @@ class RowSparseAdam(torch.optim.Optimizer):
         return loss
 
 
+_SR_T, _SR_F = 0x9E3779B9, 0x85EBCA6B  # the odd constants that spread the step count and the table index over 32 bits
+_M32 = 0xFFFFFFFF
+
+
+def _sr_mix(h: torch.Tensor) -> torch.Tensor:
+    """one 32-bit avalanche round (xorshift-multiply, 0x7feb352d / 0x846ca68b) on int64 tensors holding values below 2^32; a product
+    wraps modulo 2^64, which leaves its low 32 bits right, and is masked before the next shift"""
+    h = h ^ (h >> 16)
+    h = (h * 0x7feb352d) & _M32
+    h = h ^ (h >> 15)
+    h = (h * 0x846ca68b) & _M32
+    return h ^ (h >> 16)
+
+
+def stochastic_round_bits(seed: int, step: int, table: int, row_ids: torch.Tensor, width: int = 16) -> torch.Tensor:
+    """r [n, width] (int64, 0 .. 65535): the 16 uniform bits of stochastic_round_bf16 for element e of row row_ids[i] of table `table`
+    at step `step` — the top half of mix(mix(mix(seed32 ^ step * 0x9E3779B9) ^ table * 0x85EBCA6B) ^ (row * 16 + e)), all in 32-bit
+    arithmetic (row * 16 + e wraps), seed32 = the seed's two halves xor-ed.  A counter hash: nothing is carried from call to call."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    seed32 = (seed ^ (seed >> 32)) & _M32
+    head = torch.tensor(seed32 ^ ((int(step) * _SR_T) & _M32), dtype=torch.int64)
+    head = _sr_mix(_sr_mix(head) ^ ((int(table) * _SR_F) & _M32))
+    rows = torch.as_tensor(row_ids).to(torch.int64).cpu().reshape(-1, 1)
+    pos = (rows * 16 + torch.arange(width, dtype=torch.int64)) & _M32
+    return _sr_mix(head ^ pos) >> 16
+
+
+def stochastic_round_bf16(x_fp32: torch.Tensor, seed: int, step: int, table: int, row_ids: torch.Tensor) -> torch.Tensor:
+    """THE definition of how a bf16 embedding table stores an fp32 weight (csrc/optim_moments.hip RowwiseAdagradBf16TableRows matches
+    it bit for bit): x_fp32 [n, 16] = the new weights of rows row_ids [n] of table `table`, step = that table's step count AFTER the
+    step that produced them -> bfloat16 [n, 16],
+        out16 = (bits(x) + r) >> 16,   r = stochastic_round_bits(seed, step, table, row_ids)
+    so x moves up to the next bf16 with probability (low 16 bits of x) / 65536 and down otherwise: unbiased.  A value that already is
+    a bf16 (low bits 0) never moves; a non-finite x is stored truncated (r = 0); the largest finite values may carry into inf, which
+    is the overflow rounding up means.  Pure integer torch ops, on the CPU."""
+    x = x_fp32.detach().to(torch.float32).cpu().contiguous()
+    if x.dim() != 2 or x.shape[1] != 16:
+        raise ValueError("stochastic_round_bf16: rows of 16 floats expected, got shape %s" % (tuple(x.shape),))
+    bits = x.view(torch.int32).to(torch.int64) & _M32
+    r = stochastic_round_bits(seed, step, table, row_ids, 16)
+    if tuple(r.shape) != tuple(bits.shape):
+        raise ValueError("stochastic_round_bf16: %d row ids for %d rows" % (r.shape[0], bits.shape[0]))
+    finite = (bits & 0x7F800000) != 0x7F800000
+    out = ((bits + torch.where(finite, r, torch.zeros_like(r))) >> 16) & 0xFFFF
+    return ((out ^ 0x8000) - 0x8000).to(torch.int16).view(torch.bfloat16)  # (the 16 bits as a signed word, then reinterpreted)
+
+
 class AdamAdagradTables(torch.optim.Optimizer):
     """`--optimizer adam-adagrad-tables`: torch.optim.Adam on the dense parameters, torch.optim.Adagrad on the embedding tables with
     their own learning rate `lr * table_lr_scale` and `table_eps` — how recommendation models are usually trained.  Adagrad with a
@@ -129,11 +176,16 @@ class AdamAdagradTables(torch.optim.Optimizer):
     As exactly row-sparse as the element-wise form, with 1/16 of its state at embedding width 16.  A table must be 2-D, and a `sum`
     of the other form's shape (a checkpoint of the other rule) is refused: nothing broadcasts silently.
 
+    Tables of dtype bfloat16 (SuperNet(table_dtype=torch.bfloat16)) are accepted with table_rowwise only; their `sum` is fp32 [rows],
+    created here, and `table_seed` — the seed of the stochastic rounding their new weights are stored with (stochastic_round_bf16) —
+    sits in the param group, so a checkpoint carries it.  They train on the fused step alone: `step()` raises, because autograd would
+    hand it a dense bf16 gradient the size of the table, which is neither that rule nor affordable.
+
     `step()` is the torch route, on any device; the fused engine step reproduces it (OptimSpec.table_kind, csrc/optim_moments.hip)
     and shares its state through SuperNet.engine_bind_optimizer."""
 
     def __init__(self, params, table_params: Iterable[torch.Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 table_lr_scale: float = 1.0, table_eps: float = 1e-2, table_rowwise: bool = False):
+                 table_lr_scale: float = 1.0, table_eps: float = 1e-2, table_rowwise: bool = False, table_seed: int = 0):
         if lr < 0.0 or eps < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError("AdamAdagradTables: lr %r, betas %r, eps %r" % (lr, betas, eps))
         if not table_eps > 0.0:
@@ -142,7 +194,7 @@ class AdamAdagradTables(torch.optim.Optimizer):
             raise ValueError("AdamAdagradTables: table_lr_scale %r is not positive" % (table_lr_scale,))
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0, amsgrad=False, maximize=False, capturable=False,
                         differentiable=False, fused=None, table_lr_scale=table_lr_scale, table_eps=table_eps,
-                        table_rowwise=bool(table_rowwise))
+                        table_rowwise=bool(table_rowwise), table_seed=int(table_seed))
         super().__init__(params, defaults)
         if len(self.param_groups) != 1:
             raise ValueError("AdamAdagradTables keeps one param group")
@@ -155,11 +207,33 @@ class AdamAdagradTables(torch.optim.Optimizer):
             for t in tables:
                 if t.dim() != 2:
                     raise ValueError("AdamAdagradTables: table_rowwise needs 2-D tables [rows, width], got shape %s" % (tuple(t.shape),))
+        self._bf16_tables = [t for t in tables if t.dtype == torch.bfloat16]
+        if self._bf16_tables and not table_rowwise:
+            raise ValueError("AdamAdagradTables: bf16 tables take the row-wise rule only (table_rowwise=True): element-wise Adagrad on "
+                             "bf16 tables is not built")
+        if self._bf16_tables and len(self._bf16_tables) != len(tables):
+            raise ValueError("AdamAdagradTables: the tables are bf16 or fp32, not a mixture")
+        for t in self._bf16_tables:  # (no step() will: the fused step's binding finds the state and shares it)
+            self.state[t] = {"step": torch.tensor(0.0, dtype=torch.float32), "sum": self._new_sum(t, True)}
+
+    @property
+    def bf16_tables(self) -> bool:
+        """the tables are stored as bfloat16: the fused step is the only route (OptimSpec.table_kind "rowwise_adagrad_bf16")"""
+        return bool(self._bf16_tables)
+
+    @staticmethod
+    def _new_sum(p, rowwise):
+        """a table's zero accumulator: [rows] under the row-wise rule, else the table's shape; fp32 where the table is bf16"""
+        dt = torch.float32 if p.dtype == torch.bfloat16 else p.dtype
+        if rowwise and p.dim() == 2:
+            return torch.zeros(p.shape[0], dtype=dt, device=p.device)
+        return torch.zeros_like(p, dtype=dt, memory_format=torch.preserve_format)
 
     def __setstate__(self, state):
         super().__setstate__(state)
         for g in self.param_groups:
             g.setdefault("table_rowwise", False)  # (a pickle from before the flag)
+            g.setdefault("table_seed", 0)
 
     def load_state_dict(self, state_dict):
         """torch's, after a check that changes nothing: the checkpoint's rule (its group's table_rowwise; absent = element-wise) and
@@ -177,6 +251,11 @@ class AdamAdagradTables(torch.optim.Optimizer):
                 raise ValueError("AdamAdagradTables.load_state_dict: `sum` of a table of shape %s has shape %s, table_rowwise=%r keeps %s"
                                  % (tuple(p.shape), tuple(st["sum"].shape), rowwise, self._sum_shape(p, rowwise)))
         super().load_state_dict(state_dict)
+        # (torch casts a floating-point parameter's state to the parameter's dtype: a bf16 table's `sum` is fp32 and stays so)
+        for k, p in zip(ids, self.param_groups[0]["params"]):
+            st = state_dict.get("state", {}).get(k)
+            if p.dtype == torch.bfloat16 and id(p) in self._table_ids and st and "sum" in st:
+                self.state[p]["sum"] = st["sum"].detach().to(device=p.device, dtype=torch.float32).clone()
 
     @staticmethod
     def _sum_shape(p, rowwise):
@@ -190,6 +269,10 @@ class AdamAdagradTables(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self._bf16_tables:
+            raise RuntimeError("AdamAdagradTables.step: bf16 tables train on the fused step only (SuperNet.engine_train_step): autograd "
+                               "would hand this step a dense bf16 gradient the size of a table, which is neither the rule "
+                               "(fp32 row-wise Adagrad, stored with stochastic rounding) nor affordable")
         group = self.param_groups[0]
         beta1, beta2 = group["betas"]
         lr, eps = group["lr"], group["eps"]
@@ -206,8 +289,7 @@ class AdamAdagradTables(torch.optim.Optimizer):
                 # torch.optim.Adagrad's dense single-tensor statements (torch/optim/adagrad.py), lr_decay 0 and weight_decay 0
                 if len(st) == 0:
                     st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    st["sum"] = torch.zeros(p.shape[0], dtype=p.dtype, device=p.device) if rowwise and p.dim() == 2 else \
-                        torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["sum"] = self._new_sum(p, rowwise)
                 if tuple(st["sum"].shape) != self._sum_shape(p, rowwise):
                     raise ValueError("AdamAdagradTables: `sum` of a table of shape %s has shape %s, table_rowwise=%r keeps %s (a checkpoint "
                                      "of the other rule?)" % (tuple(p.shape), tuple(st["sum"].shape), rowwise, self._sum_shape(p, rowwise)))

@@ -273,6 +273,14 @@ def _announce_split_route(optimizer, l2_loss_fn, fused, switched_off=False):
     g = optimizer.param_groups[0]
     head = "Adam + {}Adagrad on the tables (table lr = lr x {}, table eps {})".format(
         "row-wise " if g.get("table_rowwise", False) else "", g["table_lr_scale"], g["table_eps"])
+    if optimizer.bf16_tables:
+        if not fused:  # (AdamAdagradTables.step would raise at the first batch: say why before anything runs)
+            raise ValueError("bf16 tables (--table-dtype bf16) train on the fused step only, and it does not apply here: they need "
+                             "every parameter trainable under one AdamAdagradTables(table_rowwise=True), one process, no AMP, no "
+                             "weight decay, no --ema / --decoupled-wd and no last-layer mode")
+        print(head + ": fused step, exactly row-sparse table update; bf16 tables stored with stochastic rounding (seed {}).".format(
+            g.get("table_seed", 0)))
+        return
     if fused:
         print(head + ": fused step, exactly row-sparse table update.")
         return
@@ -335,6 +343,9 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
     if decay is not None and not decay.weight_decay:
         decay = None  # (lambda = 0 is "no helper")
     fused = _fused_step_applies(model, optimizer, l2_loss_fn, use_amp, ema, decay) if use_engine_step is None else bool(use_engine_step)
+    if getattr(optimizer, "bf16_tables", False) and (use_amp or last_layer_step or ema is not None or decay is not None):
+        raise ValueError("bf16 tables (--table-dtype bf16) run with neither AMP (use_amp), the last-layer fine-tune step, a weight EMA "
+                         "(--ema) nor a decoupled weight decay (--decoupled-wd): none of them is built for bf16 tables")
     _announce_split_route(optimizer, l2_loss_fn, fused, switched_off=use_engine_step is False)
     if ema is not None:
         if fused and use_engine_step is not None and not _fused_step_applies(model, optimizer, l2_loss_fn, use_amp, ema):

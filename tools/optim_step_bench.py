@@ -5,7 +5,8 @@ Nesterov), row-sparse Adam (Adam's lr and eps; with --wd the L2 term leaves the 
 defaults; fused: lazily decayed rows, with --wd the tables left out too; its line also carries `flush_ms`, the one launch that brings
 every row's square_avg current after the timed steps), adam-adagrad-tables (Adam's lr and eps on the network, Adagrad at lr x
 `--table-lr-scale` on the tables: one phase-0 launch, W and `sum` of the batch's rows; with --wd the tables left out; `--table-rowwise`:
-row-wise Adagrad on the tables, one accumulator per row).  `--ema DECAY` keeps utils/optim.WeightEMA beside the step: inside the fused
+row-wise Adagrad on the tables, one accumulator per row; `--table-dtype bf16` with it: the tables stored as bf16, written with stochastic
+rounding — fused route only).  Every line carries `mem_alloc_mb`, torch.cuda.memory_allocated after construction and the timed steps.  `--ema DECAY` keeps utils/optim.WeightEMA beside the step: inside the fused
 step (Adagrad, row-sparse Adam, RMSprop), by WeightEMA.update() on the torch route; the line then carries `ema`, `flush_ms` (the launch
 that brings every row's average current) and `swap_ms` (flush + exchange with the parameters: what entering `averaged()` costs).
 `--decoupled-wd LAMBDA` applies utils/optim.DecoupledWeightDecay in front of the update: inside the fused step (Adagrad, row-sparse Adam,
@@ -41,6 +42,9 @@ def main():
                     help="adam-adagrad-tables: the tables' learning rate as a multiple of the network's")
     ap.add_argument("--table-rowwise", dest="table_rowwise", action="store_true",
                     help="adam-adagrad-tables: row-wise Adagrad on the tables (one accumulator per row)")
+    ap.add_argument("--table-dtype", dest="table_dtype", choices=["fp32", "bf16"], default="fp32",
+                    help="adam-adagrad-tables --table-rowwise, fused route: the tables' storage type")
+    ap.add_argument("--table-seed", dest="table_seed", type=int, default=0, help="--table-dtype bf16: the stochastic rounding's seed")
     ap.add_argument("--wd", type=float, default=0.0)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
@@ -59,7 +63,7 @@ def main():
         tb = rows * 64
         print(json.dumps({"table_rows": rows, "table_bytes": tb, "adam_phase1_bytes": 6 * tb, "sgd_phase1_bytes": 4 * tb,
                           "adagrad_wd_phase1_bytes": 4 * tb, "wd_phase0_table_bytes": tb,
-                          "table_sum_bytes_elementwise": tb, "table_sum_bytes_rowwise": rows * 4}))
+                          "table_sum_bytes_elementwise": tb, "table_sum_bytes_rowwise": rows * 4, "table_bytes_bf16": rows * 32}))
         return
     if a.all:
         for route in ("fused", "torch"):
@@ -92,15 +96,19 @@ def main():
     from nasrec_amd.supernet.supernet import SuperNet, ops_config_lib
     from nasrec_amd.utils.train_utils import get_l2_loss
     dev = torch.device("cuda", 0)
+    if a.table_dtype == "bf16" and not (a.route == "fused" and a.optimizer == "adam-adagrad-tables" and a.table_rowwise and not a.wd
+                                        and not a.ema and not a.decoupled_wd):
+        raise SystemExit("--table-dtype bf16 goes with --route fused --optimizer adam-adagrad-tables --table-rowwise, --wd 0, no --ema / --decoupled-wd")
     choice_all = json.load(open(os.path.join(ROOT, "nasrec_amd", "configs", "criteo", "ea_criteo_kaggle_xlarge_best_1shot.json")))
     torch.manual_seed(0)
     m = SuperNet(num_blocks=choice_all["num_blocks"], ops_config=ops_config_lib[choice_all["config"]], use_layernorm=False, num_embeddings=tables,
-                 sparse_input_size=26, path_sampling_strategy="fixed-path", fixed=True, fixed_choice=choice_all).to(dev)
+                 sparse_input_size=26, path_sampling_strategy="fixed-path", fixed=True, fixed_choice=choice_all,
+                 table_dtype=MT.TABLE_DTYPES[a.table_dtype]).to(dev)
     batches = synthetic_batches(8, a.B, 13, tables, dev, seed=1)
     with torch.no_grad():
         m(batches[0][0], batches[0][1])
     lr = LR[a.optimizer]
-    opt = MT.build_optimizer(a.optimizer, m, lr, a.table_lr_scale, table_rowwise=a.table_rowwise)
+    opt = MT.build_optimizer(a.optimizer, m, lr, a.table_lr_scale, table_rowwise=a.table_rowwise, table_seed=a.table_seed)
     spec = OptimSpec.from_optimizer(opt) if a.optimizer != "adagrad" else None
     lazy = a.optimizer in ("row-sparse-adam", "rmsprop", "adam-adagrad-tables") and a.route == "fused"  # (the fused step needs the tables left out of the L2 term)
     no_reg = "_embedding" if ((a.optimizer == "row-sparse-adam" or lazy) and a.wd) else None
@@ -185,6 +193,8 @@ def main():
     if a.optimizer == "adam-adagrad-tables":
         extra["table_lr_scale"] = a.table_lr_scale
         extra["table_rowwise"] = bool(a.table_rowwise)
+        extra["table_dtype"] = a.table_dtype
+    extra["mem_alloc_mb"] = round(torch.cuda.memory_allocated(dev) / 2 ** 20, 1)
     print(json.dumps({**extra, "route": a.route, "optimizer": a.optimizer, "wd": a.wd, "B": a.B, "steps": a.steps, "ms_per_step": round(ms, 4),
                       "samples_per_s": round(a.B / ms * 1e3), "wall_ms_per_step": round(wall_ms, 4),
                       "table_rows": rows}))
