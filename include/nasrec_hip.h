@@ -619,11 +619,24 @@ typedef struct nasrec_weight_decay_desc {
  * stochastic_round_bf16 is the definition the kernel matches bit for bit.
  * Refused in addition to the row-wise rule's refusals: phase 1 and phase 2 (no launch but phase 0 knows bfloat16 tables), and a tm[f],
  * f >= 1, that is not NULL (a caller that filled tm expects a first moment; tm[0] cannot be told from a seed).
+ *
+ * table_algo = NASREC_TABLE_ALGO_ROWWISE_ADAM (5; algo = NASREC_OPTIM_ADAM only, sparse_rows = 0): row-sparse Adam with ONE second
+ * moment per row ("partial row-wise Adam").  The dense chunks are updated as above.  tm[f] is [rows_f, 16] as with sparse_rows; tv[f]
+ * points at rows[f] floats, ONE per row, the moving average of the mean of the row's squared gradient.  A leader row with its id in
+ * range, t = step[table_step0 + f] + 1, g = its summed gradient * coef (16 floats, zero or not):
+ *   m[e] = m[e] + (1 - b1) (g[e] - m[e]),  e = 0 .. 15;   v[row] = v[row] + (1 - b2) ((g[0]^2 + ... + g[15]^2) / 16 - v[row]);
+ *   p[e] = p[e] - (lr sqrt(1 - b2^t) / (1 - b1^t)) * m[e] / (sqrt(v[row]) + eps)
+ * — the statements and the step size of sparse_rows, the sum of squares associated as with NASREC_TABLE_ALGO_ROWWISE_ADAGRAD.  A
+ * touched row with a zero gradient still decays m and v and moves; no bit is marked and every other row keeps its bits in table, tm
+ * and tv.  table_eps and table_lr_scale are unused.  Steps are counted as with sparse_rows.
+ * Refused (-1, nothing launched): algo != NASREC_OPTIM_ADAM, sparse_rows != 0, reg_mask != 0, a missing table[f], tm[f] or tv[f] when
+ * there are rows, counter / inc missing when n_zero == 0, a table owning a tile in phase 1 (phase 2 is RMSprop's alone).
  * ---------------------------------------------------------------------------------------------- */
 #define NASREC_TABLE_ALGO_SAME 0    /* the tables take `algo` */
 #define NASREC_TABLE_ALGO_ADAGRAD 1 /* Adagrad on the tables (above) */
 #define NASREC_TABLE_ALGO_ROWWISE_ADAGRAD 3 /* row-wise Adagrad on the tables: tv[f] = one float per row (above) */
 #define NASREC_TABLE_ALGO_ROWWISE_ADAGRAD_BF16 4 /* the same on bfloat16 tables, stored with stochastic rounding (above) */
+#define NASREC_TABLE_ALGO_ROWWISE_ADAM 5 /* row-sparse Adam on the tables with one second moment per row: tv[f] = one float per row (above) */
 typedef struct nasrec_opt_moments_desc {
   int32_t kind;  /* NASREC_OP_OPT_MOMENTS */
   int32_t phase; /* 0 / 1 (above); 2 = RMSprop's flush */
@@ -670,7 +683,7 @@ typedef struct nasrec_opt_moments_desc {
                           *   (the slot of a padding word): NASREC_TABLE_ALGO_ADAGRAD: the tables' learning rate as a multiple of *lr */
   int64_t rank_stride;
   int32_t sparse_rows;   /* 0 = every table row moves every step; != 0 = row-sparse Adam (above) */
-  int32_t table_algo;    /* NASREC_TABLE_ALGO_SAME / _ADAGRAD / _ROWWISE_ADAGRAD / _ROWWISE_ADAGRAD_BF16 (above; the slot of a padding word) */
+  int32_t table_algo;    /* NASREC_TABLE_ALGO_SAME / _ADAGRAD / _ROWWISE_ADAGRAD / _ROWWISE_ADAGRAD_BF16 / _ROWWISE_ADAM (above; the slot of a padding word) */
 } nasrec_opt_moments_desc_t;
 
 /* ------------------------------------------------------------------------------------------------

@@ -42,6 +42,7 @@ OP_LAST_LAYER_STEP = 41
 OPTIM_ADAGRAD, OPTIM_ADAM, OPTIM_SGD, OPTIM_RMSPROP = 0, 1, 2, 3  # NASREC_OPTIM_* (algorithm of NASREC_OP_OPT_MOMENTS / _LAST_LAYER_STEP)
 TABLE_ALGO_SAME, TABLE_ALGO_ADAGRAD, TABLE_ALGO_ROWWISE_ADAGRAD = 0, 1, 3  # NASREC_TABLE_ALGO_* (nasrec_opt_moments_desc_t.table_algo: the split optimizer)
 TABLE_ALGO_ROWWISE_ADAGRAD_BF16 = 4  # ... the row-wise rule on bf16 tables, stored with stochastic rounding (seed: OptMomentsDesc.sr_seed)
+TABLE_ALGO_ROWWISE_ADAM = 5  # row-sparse Adam with one second moment per table row (utils/optim.RowwiseSparseAdam): tm [rows, 16], tv [rows]
 TABLE_DTYPE_F32, TABLE_DTYPE_BF16 = 0, 1  # NASREC_TABLE_DTYPE_* (nasrec_embed_desc_t.table_dtype)
 LAST_LAYER_MAX = 8192  # NASREC_LAST_LAYER_MAX: K + 1 of NASREC_OP_LAST_LAYER_STEP
 OP_ROC_AUC = 42

@@ -5,7 +5,7 @@
 // in the workgroup that finishes last, counts the step of every parameter it updated.
 // Phase 0 is one kernel, opt_moments_phase0_kernel<Rows>; what happens to one touched row, and whether the launch marks the bitmap or
 // counts the steps itself, is the row policy `Rows` (DenseRows, SparseAdamRows, LazyRmspropRows, AdagradTableRows, RowwiseAdagradTableRows,
-// RowwiseAdagradBf16TableRows below).
+// RowwiseAdagradBf16TableRows, RowwiseSparseAdamRows below).
 // Row-sparse Adam (sparse_rows, include/nasrec_hip.h): the same clip and dense chunks, torch.optim.SparseAdam on the touched rows, no
 // bitmap, and no phase 1 unless weight decay has gradients to restore.
 // RMSprop (NASREC_OPTIM_RMSPROP: momentum 0, not centered): a row whose gradient is zero does not move and its square_avg only decays,
@@ -288,6 +288,52 @@ struct RowwiseAdagradBf16TableRows {
   }
 };
 
+// Row-wise row-sparse Adam (table_algo = NASREC_TABLE_ALGO_ROWWISE_ADAM; Adam on the dense chunks): SparseAdamRows with ONE second
+// moment per row.  tm[f] is [rows, 16] as there; tv[f] holds one float per row, the moving average of the mean of the row's squared
+// gradient, and divides the whole row.  The statements and the step size are SparseAdamRows' (sparse_adam_elem, sparse_adam_step_size);
+// the sum of squares and its quad sum are RowwiseAdagradTableRows', under the same invariant: nothing in front of the quad sum
+// branches on q.  A touched row moves with its summed gradient, zero or not; no bit is marked, and no other row moves.
+struct RowwiseSparseAdamRows {
+  static constexpr int DENSE = NASREC_OPTIM_ADAM;
+  static constexpr bool COUNTS = true;
+  float ss[NASREC_MAX_TABLES];
+  __device__ __forceinline__ void scalars(const nasrec_opt_moments_desc_t& d, float lr) {
+    const int f = (int)threadIdx.x - 64;
+    if (f >= 0 && f < d.Fs) ss[f] = sparse_adam_step_size(d, d.step[d.table_step0 + f], lr);
+  }
+  __device__ __forceinline__ void row(const nasrec_opt_moments_desc_t& d, int f, long row, int q, const f32x4& g4, float) const {
+    const long o = row * 16 + q * 4;
+    f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o), m4 = *reinterpret_cast<const f32x4*>(d.tm[f] + o);
+    float v = d.tv[f][row];  // (all four lanes load it; lane q == 0 stores it below, after the loads in program order)
+    float sq = g4[0] * g4[0];
+    sq = fmaf(g4[1], g4[1], sq);
+    sq = fmaf(g4[2], g4[2], sq);
+    sq = fmaf(g4[3], g4[3], sq);
+    // (the quad sum of RowwiseAdagradTableRows: its lanes arrive together — nothing in front of this line branches on q)
+    sq += dpp_mov<0xb1>(sq);  // quad_perm:[1,0,3,2]
+    sq += dpp_mov<0x4e>(sq);  // quad_perm:[2,3,0,1]
+    const float w1 = (float)(1.0 - d.beta1), w2 = (float)(1.0 - d.beta2), step_size = ss[f];
+    float vu = sq * 0.0625f;  // (the mean of 16: an exact scaling)
+    vu = vu - v;
+    vu = vu * w2;
+    v = v + vu;
+    float den = sqrtf(v);
+    den = den + d.eps;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float mu = g4[e] - m4[e];
+      mu = mu * w1;
+      m4[e] = m4[e] + mu;
+      float u = m4[e] / den;
+      u = (-step_size) * u;
+      p4[e] = p4[e] + u;
+    }
+    *reinterpret_cast<f32x4*>(d.table[f] + o) = p4;
+    *reinterpret_cast<f32x4*>(d.tm[f] + o) = m4;
+    if (q == 0) d.tv[f][row] = v;
+  }
+};
+
 template <class Rows>
 __global__ __launch_bounds__(256) void opt_moments_phase0_kernel(const nasrec_opt_moments_desc_t d) {
   __shared__ float sh_coef;
@@ -403,27 +449,31 @@ void launch_phase1(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
 }  // namespace
 
 // Every refusal comes before anything is launched.  The row form — dense (every row moves: bitmap + phase 1), row-sparse Adam, lazy
-// RMSprop, Adagrad or row-wise Adagrad (on fp32 or bf16 tables) on the tables — decides what a launch needs; all but the first move the batch's rows only, so their phase 0 counts the
-// steps unless zero_chunks call for a phase 1, which then owns no tile.  Phase 2 is RMSprop's flush.
+// RMSprop, Adagrad or row-wise Adagrad (on fp32 or bf16 tables) on the tables, row-wise row-sparse Adam — decides what a launch needs;
+// all but the first move the batch's rows only, so their phase 0 counts the steps unless zero_chunks call for a phase 1, which then
+// owns no tile.  Phase 2 is RMSprop's flush.
 int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
   if (d->Fs < 0 || d->Fs > NASREC_MAX_TABLES) return nasrec_set_error(-1, "opt_moments: Fs = %d", d->Fs);
   if (!d->lr || !d->step) return nasrec_set_error(-1, "opt_moments: lr / step missing");
   const bool adam = d->algo == NASREC_OPTIM_ADAM, rmsprop = d->algo == NASREC_OPTIM_RMSPROP;
   const bool bf16 = d->table_algo == NASREC_TABLE_ALGO_ROWWISE_ADAGRAD_BF16;  // (table: [rows, 16] bfloat16; the seed in tm[0]'s storage)
   const bool rowwise = d->table_algo == NASREC_TABLE_ALGO_ROWWISE_ADAGRAD || bf16;  // (tv: one float per row)
-  const bool split = d->table_algo == NASREC_TABLE_ALGO_ADAGRAD || rowwise, lazy = rmsprop || d->sparse_rows || split;
-  if (d->table_algo != NASREC_TABLE_ALGO_SAME && !split) return nasrec_set_error(-1, "opt_moments: table_algo %d", d->table_algo);
-  if (split && !adam) return nasrec_set_error(-1, "opt_moments: table_algo (Adagrad on the tables) goes with Adam on the rest (algo %d)", d->algo);
-  if (split && d->sparse_rows) return nasrec_set_error(-1, "opt_moments: table_algo with sparse_rows: the tables take one rule");
+  const bool rwadam = d->table_algo == NASREC_TABLE_ALGO_ROWWISE_ADAM;  // (tm: [rows, 16]; tv: one float per row)
+  const bool split = d->table_algo == NASREC_TABLE_ALGO_ADAGRAD || rowwise;  // (Adagrad on the tables)
+  const bool own = split || rwadam, lazy = rmsprop || d->sparse_rows || own;  // (own: the tables take a rule of their own)
+  if (d->table_algo != NASREC_TABLE_ALGO_SAME && !own) return nasrec_set_error(-1, "opt_moments: table_algo %d", d->table_algo);
+  if (own && !adam)
+    return nasrec_set_error(-1, "opt_moments: table_algo %d (a rule of their own on the tables) goes with Adam on the rest (algo %d)", d->table_algo, d->algo);
+  if (own && d->sparse_rows) return nasrec_set_error(-1, "opt_moments: table_algo with sparse_rows: the tables take one rule");
   if (split && !(d->table_eps > 0.f))
     return nasrec_set_error(-1, "opt_moments: table_eps %g must be positive (a zero gradient must leave its row alone)", (double)d->table_eps);
-  if (split && d->reg_mask != 0u)
+  if (own && d->reg_mask != 0u)
     return nasrec_set_error(-1, "opt_moments: table_algo with reg_mask %u: a regularised table moves in every row", d->reg_mask);
   if (bf16 && d->phase != 0)
     return nasrec_set_error(-1, "opt_moments: table_algo %d (bf16 tables) has phase 0 only: phase %d knows fp32 tables", d->table_algo, d->phase);
   for (int f = 1; bf16 && f < NASREC_MAX_TABLES; ++f)  // (a caller that filled tm expects a first moment: there is none, and tm[0] is the seed)
     if (d->tm[f]) return nasrec_set_error(-1, "opt_moments: table_algo %d (bf16 tables) keeps the seed in tm[0]'s storage and takes no tm (tm[%d] is set)", d->table_algo, f);
-  const char* lazy_name = rmsprop ? "RMSprop" : split ? "table_algo" : "sparse_rows";
+  const char* lazy_name = rmsprop ? "RMSprop" : own ? "table_algo" : "sparse_rows";
   if (rmsprop && d->momentum != 0.f) return nasrec_set_error(-1, "opt_moments: RMSprop with momentum %g moves untouched rows", (double)d->momentum);
   if (d->sparse_rows && !adam) return nasrec_set_error(-1, "opt_moments: sparse_rows is row-sparse Adam (algo %d)", d->algo);
   if (!adam && !rmsprop && d->algo != NASREC_OPTIM_SGD) return nasrec_set_error(-1, "opt_moments: algo %d", d->algo);
@@ -435,8 +485,10 @@ int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
     const int nrows = (int)((threads + 255) / 256), nblk = d->dense_blocks + nrows;
     if (d->dense_blocks < 0 || nblk < 1) return nasrec_set_error(-2, "opt_moments: empty launch");
     if (nrows > 0 && (!d->idx || !d->leader || !d->gsum || (!d->bitmap && !lazy))) return nasrec_set_error(-1, "opt_moments: row inputs missing");
-    for (int f = 0; split && nrows > 0 && f < d->Fs; ++f)
+    for (int f = 0; own && nrows > 0 && f < d->Fs; ++f) {
       if (!d->table[f] || !d->tv[f]) return nasrec_set_error(-1, "opt_moments: table_algo without the weights / accumulator (tv) of table %d", f);
+      if (rwadam && !d->tm[f]) return nasrec_set_error(-1, "opt_moments: table_algo %d (row-wise Adam) without the first moment (tm) of table %d", d->table_algo, f);
+    }
     if (d->rank_B < 0 || (d->rank_B > 0 && (d->rank_stride < (int64_t)d->rank_B * d->Fs * 16 || d->B % d->rank_B != 0)))
       return nasrec_set_error(-2, "opt_moments: rank layout %d / %ld", d->rank_B, (long)d->rank_stride);
     if (lazy && d->n_zero <= 0 && (!d->counter || (d->n_inc > 0 && !d->inc)))
@@ -445,6 +497,7 @@ int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
     else if (bf16) launch_phase0<RowwiseAdagradBf16TableRows>(st, d, nblk);
     else if (rowwise) launch_phase0<RowwiseAdagradTableRows>(st, d, nblk);
     else if (split) launch_phase0<AdagradTableRows>(st, d, nblk);
+    else if (rwadam) launch_phase0<RowwiseSparseAdamRows>(st, d, nblk);
     else if (d->sparse_rows) launch_phase0<SparseAdamRows>(st, d, nblk);
     else if (adam) launch_phase0<DenseRows<NASREC_OPTIM_ADAM>>(st, d, nblk);
     else launch_phase0<DenseRows<NASREC_OPTIM_SGD>>(st, d, nblk);

@@ -576,7 +576,7 @@ class SupernetEngine:
             cp.fwd_levels = cp.bwd_levels = None
             cp.dead_forward = []
             if train:  # (the backward program decides which forward results are read: built further down, before the packing)
-                if not spec.moments or spec.table_kind:  # (Adagrad's table state: Adam / SGD keep theirs in `moments` instead)
+                if not spec.moments or spec.adagrad_tables:  # (Adagrad's table state: Adam / SGD keep theirs in `moments` instead)
                     self._ensure_split_table_state(spec)
                 self._build_training_tail(cp, ctx, w, bptr, fsegs, B, K, grad_scale)
             fwd_list = list(ctx.fwd)
@@ -888,24 +888,34 @@ class SupernetEngine:
             setattr(self, name, t)
         return t
 
-    def ensure_moments_state(self, kind: str, tables: bool = True):
+    def ensure_moments_state(self, kind: str, tables: bool = True, rowwise_v: bool = False):
         """Adam's exp_avg / exp_avg_sq or SGD's momentum_buffer for the dense arena (flat, the layout of flat_p) and for every table,
         allocated on first use, zero; and the per-parameter step counters (dense parameters in dense_names order, then the tables).
         tables = False (the split optimizer, OptimSpec.table_kind): the dense arena's arrays only — the tables' state is Adagrad's
         `table_state` (row-wise: `table_row_state`), and no moment array the size of a table is allocated ([] until a plan that needs them asks).
         "rmsprop": square_avg, and `lazy_stamps` — per table one int32 per row, the table's step count at which that row's square_avg
         is current (csrc/optim_moments.hip); engine-private, never part of optimizer.state.
+        rowwise_v (row-wise Adam, OptimSpec.table_kind "rowwise_adam"): a table's exp_avg_sq is ONE float per row, [rows] — the
+        [rows, 16] array is never allocated; an engine keeps one form, and asking for the other is refused.
         -> {state key: (flat arena, [table arrays])}"""
         if tables:
             self._refuse_bf16_tables("%s on every table row (its table moments)" % kind)
         keys = {"adam": ("exp_avg", "exp_avg_sq"), "rmsprop": ("square_avg",)}.get(kind, ("momentum_buffer",))
         st = self.__dict__.setdefault("moments", {})
+        held = st.get("exp_avg_sq", (None, []))[1]
+        if tables and kind == "adam" and held and (held[0].dim() == 1) != bool(rowwise_v):
+            raise L.EngineError("this engine holds the tables' exp_avg_sq %s: Adam's second moment per %s on the tables needs an engine "
+                                "of its own (RowSparseAdam / torch.optim.Adam and RowwiseSparseAdam do not share table moments)"
+                                % (("per row ([rows])", "element") if held[0].dim() == 1 else ("per element ([rows, 16])", "row")))
         with torch.cuda.stream(self.stream):
             for k in keys:
                 if k not in st:
                     st[k] = (torch.zeros(self.flat_numel, dtype=torch.float32, device=self.device), [])
                 if tables and not st[k][1]:
-                    st[k][1].extend(torch.zeros_like(t) for t in self.tables)
+                    if rowwise_v and k == "exp_avg_sq":
+                        st[k][1].extend(torch.zeros(t.shape[0], dtype=torch.float32, device=self.device) for t in self.tables)
+                    else:
+                        st[k][1].extend(torch.zeros_like(t) for t in self.tables)
             if kind == "rmsprop" and getattr(self, "lazy_stamps", None) is None:
                 self.lazy_stamps = [torch.zeros(n, dtype=torch.int32, device=self.device) for n in self.num_embeddings]
             if getattr(self, "opt_steps", None) is None:
@@ -918,7 +928,7 @@ class SupernetEngine:
         return {k: st[k] for k in keys}
 
     def moments_view(self, key: str, name: str):
-        """engine storage of moment `key` of parameter `name` (shape of the parameter)"""
+        """engine storage of moment `key` of parameter `name` (shape of the parameter; a table's exp_avg_sq under row-wise Adam: [rows])"""
         flat, tabs = self.moments[key]
         if name.startswith("_embedding."):
             if not tabs:
@@ -981,10 +991,13 @@ class SupernetEngine:
         if spec.sparse_rows and spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
             raise L.EngineError("row-sparse Adam with a regularised table: the L2 term puts a gradient on every row; leave the tables out "
                                 "(no_reg_param_name='_embedding') or use weight_decay=0")
-        if spec.table_kind and spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
+        if spec.rowwise_adam and spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
+            raise L.EngineError("row-wise Adam with a regularised table: the L2 term puts a gradient on every row; leave the tables out "
+                                "(no_reg_param_name='_embedding') or use weight_decay=0")
+        if spec.adagrad_tables and spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
             raise L.EngineError("Adagrad on the tables with a regularised table: the L2 term puts a gradient on every row; leave the "
                                 "tables out (no_reg_param_name='_embedding') or use weight_decay=0")
-        self.ensure_moments_state(spec.kind, tables=not spec.table_kind)
+        self.ensure_moments_state(spec.kind, tables=not spec.adagrad_tables, rowwise_v=spec.rowwise_adam)
         names = [n for n in list(ctx.grad_params) + ["_final.weight", "_final.bias"] if not n.startswith("_embedding.")]
         if spec.wd:
             names += P.regularised(self.shapes, spec.no_reg)[0]
@@ -1007,8 +1020,9 @@ class SupernetEngine:
     @staticmethod
     def _optim_scalars(d, spec):
         """algo and hyperparameters of an Adam / SGD spec on an OptMomentsDesc or a LastLayerStepDesc"""
-        if (spec.table_kind not in ("", "adagrad", "rowwise_adagrad") and not spec.bf16_tables) or (spec.table_kind and spec.kind != "adam"):
-            raise L.EngineError("table_kind %r with %s: the split optimizer is Adam with (row-wise) Adagrad on the tables" % (spec.table_kind, spec.kind))
+        if (spec.table_kind not in ("", "adagrad", "rowwise_adagrad", "rowwise_adam") and not spec.bf16_tables) or (spec.table_kind and spec.kind != "adam"):
+            raise L.EngineError("table_kind %r with %s: the tables' own rules (Adagrad, row-wise Adagrad, row-wise Adam) go with Adam on "
+                                "the dense parameters" % (spec.table_kind, spec.kind))
         d.algo = {"adam": L.OPTIM_ADAM, "rmsprop": L.OPTIM_RMSPROP}.get(spec.kind, L.OPTIM_SGD)
         d.eps, d.momentum, d.nesterov = spec.eps, spec.momentum, int(bool(spec.nesterov))
         d.beta1, d.beta2 = spec.beta1, (spec.alpha if spec.kind == "rmsprop" else spec.beta2)  # (RMSprop's alpha travels in beta2)
@@ -1022,11 +1036,12 @@ class SupernetEngine:
         slots of `tm` carry the stamps.  Adagrad on the tables (spec.table_kind): the same shape again; tv carries `table_state`, tm
         nothing, and the tables' learning rate is lr * table_lr_scale in the kernel; row-wise Adagrad: tv carries `table_row_state`,
         one float per row; on bf16 tables (table_kind "rowwise_adagrad_bf16") the same with the other table_algo and the rounding's seed
-        in tm[0]'s storage — constant from step to step: the kernel reads the step count on the device."""
+        in tm[0]'s storage — constant from step to step: the kernel reads the step count on the device.  Row-wise Adam (table_kind
+        "rowwise_adam"): row-sparse Adam's launches under its own table_algo; tm carries exp_avg [rows, 16], tv exp_avg_sq [rows]."""
         spec = t.spec
         st = self.moments
         lazy = spec.rows_only  # (the tables move in the batch's rows only)
-        split, rowwise = bool(spec.table_kind), spec.table_rowwise
+        split, rowwise = spec.adagrad_tables, spec.table_rowwise
         if spec.bf16_tables != self.tables_bf16:
             raise L.EngineError("table_kind %r on %s tables" % (spec.table_kind, "bf16" if self.tables_bf16 else "fp32"))
         m = L.OptMomentsDesc()
@@ -1037,6 +1052,8 @@ class SupernetEngine:
         if split:
             m.table_algo = L.TABLE_ALGO_ROWWISE_ADAGRAD_BF16 if spec.bf16_tables else L.TABLE_ALGO_ROWWISE_ADAGRAD if rowwise else L.TABLE_ALGO_ADAGRAD
             m.table_eps, m.table_lr_scale = spec.table_eps, spec.table_lr_scale
+        elif spec.rowwise_adam:
+            m.table_algo = L.TABLE_ALGO_ROWWISE_ADAM
         m.nblocks = self.WD_BLOCKS if (t.mom_tables or lazy) else 1  # (no table moves: phase 1 only counts the step and restores g)
         m.B, m.Fs = (Bg, self.Fs) if gsum is not None else (0, self.Fs)
         m.table_step0 = len(self.dense_names)
@@ -1062,6 +1079,8 @@ class SupernetEngine:
                 continue
             m.tm[f] = first[1][f].data_ptr()
             if second is not None:
+                if second[1][f].dim() != (1 if spec.rowwise_adam else 2):  # (the kernel indexes tv by row or by element: never the other array)
+                    raise L.EngineError("exp_avg_sq of table %d has shape %s under table_kind %r" % (f, tuple(second[1][f].shape), spec.table_kind))
                 m.tv[f] = second[1][f].data_ptr()
         if spec.bf16_tables:
             m.sr_seed = spec.table_seed  # (over tm[0], which the loop above left null)
@@ -1790,7 +1809,7 @@ class SupernetEngine:
         self._refuse_bf16_tables("the last-layer step (its plan is the Adagrad training plan)")
         if optim is not None and optim.kind == "rmsprop":
             raise L.EngineError("the last-layer step has no RMSprop: the fine-tune keeps the torch route with it")
-        if optim is not None and optim.table_kind:
+        if optim is not None and optim.adagrad_tables:
             raise L.EngineError("the last-layer step has no split optimizer: the fine-tune keeps the torch route with it")
         B = int(int_x.shape[0])
         cp = self.compile(choice, B, train=True)

@@ -125,7 +125,7 @@ def build_parser():
     p.add_argument("--choice_from_pickle_file", type=str, default=None,
                    help="Pre-sampled cached choices from a pickle file; the number of records overrides 'num_subnets'.")
     p.add_argument("--no-reg-param-name", type=str, default=None, help="Name of the parameters that do not need to be regularized.")
-    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rmsprop", "adam-adagrad-tables"])
+    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rowwise-adam", "rmsprop", "adam-adagrad-tables"])
     p.add_argument("--table-lr-scale", dest="table_lr_scale", type=float, default=1.0,
                    help="--optimizer adam-adagrad-tables: the embedding tables' learning rate as a multiple of --learning_rate "
                         "(Adam's 1e-3 with 160 gives the tables 0.16)")

@@ -32,6 +32,9 @@ def make_optimizer_and_schedule(model, args):
     elif args.optimizer == "row-sparse-adam":
         from .utils.optim import RowSparseAdam
         optimizer = RowSparseAdam(model.parameters(), list(model._embedding.parameters()), lr=args.learning_rate, eps=1e-8)
+    elif args.optimizer == "rowwise-adam":
+        from .utils.optim import RowwiseSparseAdam
+        optimizer = RowwiseSparseAdam(model.parameters(), list(model._embedding.parameters()), lr=args.learning_rate, eps=1e-8)
     else:
         raise KeyError(args.optimizer)
     num_train_steps = args.max_train_steps * args.num_epochs
@@ -165,7 +168,7 @@ def build_parser():
     p.add_argument("--init_population", type=int, default=8)
     p.add_argument("--ea_top_k", type=int, default=5)
     p.add_argument("--sample_size", type=int, default=6)
-    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "row-sparse-adam"])
+    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rowwise-adam"])
     p.add_argument("--criterion", type=str, default="test_loss")
     p.add_argument("--beta", type=float, default=0.0)
     p.add_argument("--target_latency", type=float, default=-1)

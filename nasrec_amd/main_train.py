@@ -89,7 +89,8 @@ def add_table_dtype_flags(p):
 
 def build_optimizer(name, model, lr, table_lr_scale=1.0, table_eps=1e-2, table_rowwise=False, table_seed=0):
     """main_train.py:150-160 (Adagrad eps 1e-2; Adam eps 1e-8; SGD nesterov momentum 0.9); row-sparse-adam: Adam's lr and eps, the
-    tables moving in the batch's rows only (utils/optim.RowSparseAdam); rmsprop: torch's defaults (alpha 0.99, eps 1e-8) as
+    tables moving in the batch's rows only (utils/optim.RowSparseAdam); rowwise-adam: the same with one second-moment float per
+    table row (utils/optim.RowwiseSparseAdam); rmsprop: torch's defaults (alpha 0.99, eps 1e-8) as
     utils/optim.LazyRMSprop, which is torch.optim.RMSprop and the type the fused step takes; adam-adagrad-tables: Adam's lr and eps
     on the dense parameters, Adagrad with lr * table_lr_scale and table_eps on the tables (utils/optim.AdamAdagradTables), row-wise
     Adagrad with table_rowwise — which goes with that optimizer only; table_seed: the stochastic rounding's seed of bf16 tables"""
@@ -107,6 +108,12 @@ def build_optimizer(name, model, lr, table_lr_scale=1.0, table_eps=1e-2, table_r
             raise ValueError("--optimizer row-sparse-adam needs whole tables: a row-sharded table holds one rank's rows under local ids; "
                              "use --optimizer adam with --table-sharding row")
         return RowSparseAdam(model.parameters(), list(model._embedding.parameters()), lr=lr, eps=1e-8)
+    if name == "rowwise-adam":
+        from nasrec_amd.utils.optim import RowwiseSparseAdam
+        if getattr(model, "_table_sharding", None) == "row":
+            raise ValueError("--optimizer rowwise-adam needs whole tables: a row-sharded table holds one rank's rows under local ids; "
+                             "use --optimizer adam with --table-sharding row")
+        return RowwiseSparseAdam(model.parameters(), list(model._embedding.parameters()), lr=lr, eps=1e-8)
     if name == "adam-adagrad-tables":
         from nasrec_amd.utils.optim import AdamAdagradTables
         return AdamAdagradTables(model.parameters(), list(model._embedding.parameters()), lr=lr, eps=1e-8, table_lr_scale=table_lr_scale,
@@ -242,7 +249,7 @@ def build_parser():
                    help="Data split for validation (evaluation). Can be one of ['val', 'test']")
     p.add_argument("--train_batch_size", type=int, default=200, help="Training batch size.")
     p.add_argument("--test_batch_size", type=int, default=16368, help="Testing batch size.")
-    p.add_argument("--optimizer", type=str, default="adagrad", help="Optimizer", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rmsprop", "adam-adagrad-tables", "ds-optimizer"])
+    p.add_argument("--optimizer", type=str, default="adagrad", help="Optimizer", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rowwise-adam", "rmsprop", "adam-adagrad-tables", "ds-optimizer"])
     p.add_argument("--table-lr-scale", dest="table_lr_scale", type=float, default=1.0,
                    help="--optimizer adam-adagrad-tables: the embedding tables' learning rate as a multiple of --learning_rate "
                         "(Adam's 1e-3 with 160 gives the tables 0.16)")
@@ -267,12 +274,12 @@ def build_parser():
                    help="EMA strength in [0, 1); 0.9 / 0.99 / ... is recommended, 0 = off.  Keeps an exponential moving average of every "
                         "weight, s += (1 - ema) (w - s) after every optimizer step (utils/optim.WeightEMA); the tests run on the averaged "
                         "weights and the checkpoint carries them as ema_state_dict.  Inside the fused step with --optimizer adagrad / "
-                        "row-sparse-adam / rmsprop / adam-adagrad-tables and no weight decay on the tables, on the torch route otherwise")
+                        "row-sparse-adam / rowwise-adam / rmsprop / adam-adagrad-tables and no weight decay on the tables, on the torch route otherwise")
     p.add_argument("--decoupled-wd", dest="decoupled_wd", type=_decoupled_wd, default=0.0,
                    help="decoupled weight decay (the W of AdamW), 0 = off: before every optimizer step w *= 1 - lr * LAMBDA on the "
                         "parameters --wd would regularise (>= 2 dimensions, --no-reg-param-name left out) that have a gradient "
                         "(utils/optim.DecoupledWeightDecay).  Independent of --wd.  Inside the fused step with --optimizer adagrad / "
-                        "row-sparse-adam / rmsprop / adam-adagrad-tables (embedding rows outside the batch pay lazily), on the torch route otherwise")
+                        "row-sparse-adam / rowwise-adam / rmsprop / adam-adagrad-tables (embedding rows outside the batch pay lazily), on the torch route otherwise")
     p.add_argument("--gpu", type=int, default=None, help="GPU ID to use.")
     # not a reference flag: placement of the embedding tables under torchrun (nasrec_amd/sharded_tables.py)
     p.add_argument("--table-sharding", dest="table_sharding", type=str, default="none", choices=["none", "row"],

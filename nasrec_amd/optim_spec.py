@@ -2,7 +2,7 @@
 hyperparameters, and the weight decay of get_l2_loss, whose gradient the step folds in.
 
 `OptimSpec.for_step` decides which torch optimizers the fused step reproduces: torch.optim.Adagrad, and torch.optim.Adam / torch.optim.SGD
-with momentum / RowSparseAdam / LazyRMSprop / AdamAdagradTables (nasrec_amd/utils/optim.py) under the conditions of `from_optimizer`, in one process or in every rank of a data-parallel run with whole tables
+with momentum / RowSparseAdam / RowwiseSparseAdam / LazyRMSprop / AdamAdagradTables (nasrec_amd/utils/optim.py) under the conditions of `from_optimizer`, in one process or in every rank of a data-parallel run with whole tables
 (nasrec_amd/parallel.py).  The public entry points (SuperNet.engine_*, SupernetEngine.train_step / last_layer_step, DataParallelStep)
 normalise their arguments into one spec (`of`); everything below them passes that."""
 from typing import NamedTuple, Optional
@@ -27,7 +27,9 @@ class OptimSpec(NamedTuple):
                             # the mean of the row's squared gradient; "rowwise_adagrad_bf16" / "rowwise_adagrad_bf16:<seed>"
                             # (bf16_table_kind) = that rule on tables STORED as bf16 (SuperNet(table_dtype=torch.bfloat16)): computed
                             # in fp32 on the widened row, stored with stochastic rounding (utils/optim.stochastic_round_bf16) under
-                            # the seed the value carries — `table_seed` reads it; no field of its own: tests pin the tuple's fields
+                            # the seed the value carries — `table_seed` reads it; no field of its own: tests pin the tuple's fields;
+                            # "rowwise_adam" (kind "adam": utils/optim.RowwiseSparseAdam) = row-sparse Adam on the tables with ONE
+                            # second moment per row, fed the mean of the row's squared gradient; table_eps and table_lr_scale unused
     table_eps: float = 1e-2
     table_lr_scale: float = 1.0
     dwd: float = 0.0        # decoupled weight decay p <- p (1 - lr dwd) before the update (utils/optim.DecoupledWeightDecay,
@@ -43,14 +45,25 @@ class OptimSpec(NamedTuple):
     @property
     def rows_only(self) -> bool:
         """the tables move in the batch's rows only (a row outside it keeps its bits, or owes only a closed-form factor): Adagrad,
-        row-sparse Adam, RMSprop and Adam with Adagrad (element- or row-wise) on the tables"""
+        row-sparse Adam (with a second moment per element or per row), RMSprop and Adam with Adagrad (element- or row-wise) on the tables"""
         return self.kind in ("adagrad", "rmsprop") or bool(self.sparse_rows) or \
-            self.table_kind in ("adagrad", "rowwise_adagrad") or self.bf16_tables
+            self.table_kind in ("adagrad", "rowwise_adagrad", "rowwise_adam") or self.bf16_tables
 
     @property
     def table_rowwise(self) -> bool:
-        """the tables' accumulator is one float per row (the engine's table_row_state), whatever the tables' storage type"""
-        return self.table_kind == "rowwise_adagrad" or self.bf16_tables
+        """the tables' accumulator / second moment is one float per row (row-wise Adagrad: the engine's table_row_state, whatever the
+        tables' storage type; row-wise Adam: the table arrays of the engine's exp_avg_sq)"""
+        return self.table_kind in ("rowwise_adagrad", "rowwise_adam") or self.bf16_tables
+
+    @property
+    def rowwise_adam(self) -> bool:
+        """row-sparse Adam on the tables with one second moment per row (utils/optim.RowwiseSparseAdam)"""
+        return self.table_kind == "rowwise_adam"
+
+    @property
+    def adagrad_tables(self) -> bool:
+        """the split optimizer: the tables' state is Adagrad's `sum` (table_state / table_row_state), not a moment array"""
+        return bool(self.table_kind) and not self.rowwise_adam
 
     @property
     def bf16_tables(self) -> bool:
@@ -99,18 +112,19 @@ class OptimSpec(NamedTuple):
         Adam: one group, amsgrad, weight_decay, maximize, capturable, differentiable and fused all off.
         SGD: one group, momentum != 0 (plain SGD keeps the torch route), dampening 0, weight_decay 0, not maximize / differentiable / fused.
         RowSparseAdam: Adam's conditions (its one group carries Adam's keys) -> sparse_rows.
+        RowwiseSparseAdam: the same conditions -> table_kind "rowwise_adam" (sparse_rows stays False: the tables take one rule).
         AdamAdagradTables: Adam's conditions -> table_kind "adagrad", or "rowwise_adagrad" where the group's table_rowwise is set, with
         the group's table_eps / table_lr_scale (plain numbers); tables of dtype bfloat16 (accepted by that optimizer only with
         table_rowwise) -> bf16_table_kind(the group's table_seed).
         LazyRMSprop (that type exactly: a hand-built torch.optim.RMSprop keeps the torch route): one group, momentum 0, not centered,
         weight_decay 0, not maximize / capturable / differentiable."""
-        from .utils.optim import AdamAdagradTables, LazyRMSprop, RowSparseAdam
+        from .utils.optim import AdamAdagradTables, LazyRMSprop, RowSparseAdam, RowwiseSparseAdam
         if len(optimizer.param_groups) != 1:
             return None
         g = optimizer.param_groups[0]
         if g.get("weight_decay", 0) != 0 or g.get("maximize", False) or g.get("differentiable", False) or g.get("fused"):
             return None
-        if type(optimizer) in (torch.optim.Adam, RowSparseAdam, AdamAdagradTables):
+        if type(optimizer) in (torch.optim.Adam, RowSparseAdam, RowwiseSparseAdam, AdamAdagradTables):
             if g.get("amsgrad", False) or g.get("capturable", False):
                 return None
             b1, b2 = g["betas"]
@@ -126,6 +140,10 @@ class OptimSpec(NamedTuple):
                     kind = OptimSpec.bf16_table_kind(g.get("table_seed", 0))
                 return OptimSpec("adam", beta1=float(b1), beta2=float(b2), eps=float(g["eps"]), table_kind=kind,
                                  table_eps=float(g["table_eps"]), table_lr_scale=float(g["table_lr_scale"]))
+            if type(optimizer) is RowwiseSparseAdam:
+                if torch.is_tensor(g["eps"]):
+                    return None
+                return OptimSpec("adam", beta1=float(b1), beta2=float(b2), eps=float(g["eps"]), table_kind="rowwise_adam")
             return OptimSpec("adam", beta1=float(b1), beta2=float(b2), eps=float(g["eps"]), sparse_rows=type(optimizer) is RowSparseAdam)
         if type(optimizer) is LazyRMSprop:
             if g.get("momentum", 0) != 0 or g.get("centered", False) or g.get("capturable", False):
@@ -144,7 +162,7 @@ class OptimSpec(NamedTuple):
         """the spec of the fused step that stands in for `optimizer.step()` on the loss + get_l2_loss(model, weight_decay,
         no_reg_param_name), or None when the fused step does not reproduce the optimizer.  torch.optim.Adagrad: one group,
         weight_decay, lr_decay and initial_accumulator_value 0, not maximize; Adam / SGD / RowSparseAdam: from_optimizer.  Row-sparse
-        Adam, RMSprop and AdamAdagradTables with a regularised table are None too (`regularises_tables`): the L2 term puts a gradient
+        Adam (either form), RMSprop and AdamAdagradTables with a regularised table are None too (`regularises_tables`): the L2 term puts a gradient
         on every row, and RMSprop's rows rest only while their gradient is zero."""
         if type(optimizer) is not torch.optim.Adagrad:
             optim = OptimSpec.from_optimizer(optimizer)

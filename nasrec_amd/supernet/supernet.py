@@ -682,7 +682,8 @@ class SuperNet(nn.Module):
         is BCE + get_l2_loss(self, weight_decay, no_reg_param_name) — every regularised parameter and every table row is decayed
         (engine_last_l2 = that term on the pre-step weights).  optim: an OptimSpec (nasrec_amd/optim_spec.py) of torch.optim.Adam / SGD
         replaces Adagrad (eps unused) — every table row moves every step, or with sparse_rows (utils/optim.RowSparseAdam) or
-        table_kind "adagrad" / "rowwise_adagrad" / "rowwise_adagrad_bf16" (utils/optim.AdamAdagradTables: Adagrad on the tables at lr * table_lr_scale) only the
+        table_kind "adagrad" / "rowwise_adagrad" / "rowwise_adagrad_bf16" (utils/optim.AdamAdagradTables: Adagrad on the tables at lr * table_lr_scale)
+        or "rowwise_adam" (utils/optim.RowwiseSparseAdam: one second moment per table row) only the
         batch's rows, which weight decay must then leave out; engine_bind_optimizer / engine_sync_optimizer_steps share its
         state with the torch optimizer.  Both need whole tables; under data parallelism they run in the exchange step's optimizer over
         the global batch (nasrec_amd/parallel.py).  ema_decay != 0: the step also averages every parameter (utils/optim.WeightEMA's
@@ -820,19 +821,21 @@ class SuperNet(nn.Module):
         (utils/optim.LazyRMSprop), and last_layer keeps the Adagrad accumulators: that step has no RMSprop.  AdamAdagradTables: the
         dense parameters as with Adam; a table shares `sum` with the engine's Adagrad accumulators (table_state) and its step counter
         with the state's `step`, and the engine holds no moment array of a table; with table_rowwise the `sum` is the engine's
-        table_row_state, one float per row, and an existing `sum` of another shape is refused (ValueError)."""
+        table_row_state, one float per row, and an existing `sum` of another shape is refused (ValueError).  RowwiseSparseAdam: as
+        RowSparseAdam, but a table's exp_avg_sq is the engine's [rows] array; an exp_avg_sq of the other form (a RowSparseAdam's
+        state under a row-wise plan, or the reverse) is refused (ValueError)."""
         eng = self._engine
         assert eng is not None, "run one forward first (lazy shapes)"
         from ..optim_spec import OptimSpec
         spec = OptimSpec.for_step(optimizer)
-        if spec is None or not spec.moments or (last_layer and (spec.kind == "rmsprop" or spec.table_kind)):
+        if spec is None or not spec.moments or (last_layer and (spec.kind == "rmsprop" or spec.adagrad_tables)):
             spec = OptimSpec.of()  # (the Adagrad accumulators: also what an optimizer the fused step does not reproduce gets)
         if spec.moments and not last_layer and self._table_sharding == "row":
             from .._lib import EngineError
             raise EngineError("Adam / SGD in the fused step need whole tables on the device")
+        slots, counters = self._state_slots(spec, last_layer)  # (raises for the other Adam form: nothing is bound then)
         self.__dict__["_bound"] = (spec, bool(last_layer))
         self._bound_optimizer_steps = getattr(self, "_last_layer_steps" if last_layer else "_engine_steps", 0)
-        slots, counters = self._state_slots(spec, last_layer)
         if counters is None:
             for p, views, _ in slots:
                 st, tgt = optimizer.state[p], views["sum"]
@@ -850,6 +853,11 @@ class SuperNet(nn.Module):
                     if src is None:
                         tgt.zero_()
                     elif src.data_ptr() != tgt.data_ptr():
+                        if key == "exp_avg_sq" and src.dim() != tgt.dim():
+                            # (row-sparse Adam's [rows, 16] under the row-wise rule or the reverse: view_as would fail or, worse, fit)
+                            raise ValueError("engine_bind_optimizer: the optimizer's exp_avg_sq of a table has shape %s, %s keeps %s"
+                                             % (tuple(src.shape), "row-wise Adam (RowwiseSparseAdam)" if spec.rowwise_adam else
+                                                "row-sparse Adam (RowSparseAdam)", tuple(tgt.shape)))
                         if key == "sum" and tuple(src.shape) != tuple(tgt.shape):
                             # (an element-wise checkpoint under the row-wise rule or the reverse: nothing may be reshaped or broadcast)
                             raise ValueError("engine_bind_optimizer: the optimizer's `sum` of a table has shape %s, the %s rule keeps %s"
@@ -951,13 +959,13 @@ class SuperNet(nn.Module):
         if last_layer:
             arrays = eng.ensure_last_layer_state(spec.kind)
             return [(params[n], {k: arrays[k][i] for k in spec.state_keys}, i) for i, n in enumerate(self._FINAL)], eng.ll_steps
-        eng.ensure_moments_state(spec.kind, tables=not spec.table_kind)
-        if spec.table_kind:  # (AdamAdagradTables: a table's state is Adagrad's sum, the engine's table_state or, row-wise, table_row_state;
+        eng.ensure_moments_state(spec.kind, tables=not spec.adagrad_tables, rowwise_v=spec.rowwise_adam)
+        if spec.adagrad_tables:  # (AdamAdagradTables: a table's state is Adagrad's sum, the engine's table_state or, row-wise, table_row_state;
             eng._ensure_split_table_state(spec)  # its counter is the state's step)
-        table_sums = eng.table_row_state if spec.table_rowwise else eng.table_state
+        table_sums = (eng.table_row_state if spec.table_rowwise else eng.table_state) if spec.adagrad_tables else None
 
         def views(n):
-            if spec.table_kind and n.startswith("_embedding."):
+            if spec.adagrad_tables and n.startswith("_embedding."):
                 return {"sum": table_sums[int(n.split(".")[1])]}
             return {k: eng.moments_view(k, n) for k in spec.state_keys}
         return [(p, views(n), eng.param_index[n]) for n, p in params.items() if n in eng.param_index], eng.opt_steps

@@ -126,7 +126,7 @@ def build_parser():
                    help="decoupled weight decay (the W of AdamW), 0 = off: before every optimizer step w *= 1 - lr * LAMBDA on the parameters "
                         "--wd would regularise that have a gradient (utils/optim.DecoupledWeightDecay; main_train.py --decoupled-wd)")
     p.add_argument("--loss_function", type=str, default="bce", choices=["bce"])
-    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rmsprop", "adam-adagrad-tables", "ds-optimizer"])
+    p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rowwise-adam", "rmsprop", "adam-adagrad-tables", "ds-optimizer"])
     p.add_argument("--table-lr-scale", dest="table_lr_scale", type=float, default=1.0,
                    help="--optimizer adam-adagrad-tables: the embedding tables' learning rate as a multiple of --learning_rate "
                         "(Adam's 1e-3 with 160 gives the tables 0.16)")

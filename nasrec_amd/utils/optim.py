@@ -6,7 +6,9 @@ reference builds them), so the optimizer cannot see which rows the batch touched
 whose summed gradient is exactly zero still decays its moments and moves, as a row of a coalesced sparse gradient does.
 
 `step()` is the torch route; the fused engine step reproduces it (OptimSpec.sparse_rows, csrc/optim_moments.hip) and shares its state
-through SuperNet.engine_bind_optimizer, as with torch.optim.Adam."""
+through SuperNet.engine_bind_optimizer, as with torch.optim.Adam.
+
+RowwiseSparseAdam is the same optimizer with one second-moment float per table row (`--optimizer rowwise-adam`)."""
 import contextlib
 import math
 from typing import Iterable
@@ -56,13 +58,37 @@ class RowSparseAdam(torch.optim.Optimizer):
                              "not row-sharded ones" % [int(t.shape[0]) for t in self._tables])
         self._ids = ids
 
+    RULE = "element-wise"  # the second moment's form on a table: one per element here, one per row in RowwiseSparseAdam
+
+    def _second_moment_shape(self, p):
+        """shape of exp_avg_sq of parameter p under this optimizer's rule"""
+        return tuple(p.shape)
+
     def _init_state(self, p):
         st = self.state[p]
         if len(st) == 0:
             st["step"] = torch.tensor(0.0, dtype=torch.float32)
             st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if self._second_moment_shape(p) == tuple(p.shape):
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            else:
+                st["exp_avg_sq"] = torch.zeros(self._second_moment_shape(p), dtype=p.dtype, device=p.device)
         return st
+
+    def load_state_dict(self, state_dict):
+        """torch's, after a check that changes nothing: every table's exp_avg_sq in the checkpoint must have this rule's shape — a
+        RowwiseSparseAdam checkpoint ([rows]) under RowSparseAdam ([rows, width]), or the reverse, is refused (ValueError), never
+        reshaped or broadcast"""
+        groups = state_dict.get("param_groups") or [{}]
+        ids = groups[0].get("params", []) if len(groups) == 1 else []
+        for k, p in zip(ids, self.param_groups[0]["params"]):
+            st = state_dict.get("state", {}).get(k)
+            if id(p) in self._table_index and st and "exp_avg_sq" in st and tuple(st["exp_avg_sq"].shape) != self._second_moment_shape(p):
+                raise ValueError("%s.load_state_dict: exp_avg_sq of a table of shape %s has shape %s; this optimizer keeps the %s second "
+                                 "moment %s (a checkpoint of %s?)"
+                                 % (type(self).__name__, tuple(p.shape), tuple(st["exp_avg_sq"].shape), self.RULE,
+                                    self._second_moment_shape(p), "RowSparseAdam" if self.RULE == "row-wise" else "RowwiseSparseAdam"))
+        super().load_state_dict(state_dict)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -94,23 +120,71 @@ class RowSparseAdam(torch.optim.Optimizer):
             _adam(dense[0], dense[1], dense[2], dense[3], [], dense[4], amsgrad=False, beta1=beta1, beta2=beta2, lr=lr, weight_decay=0,
                   eps=eps, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None, has_complex=False)
         for p, st in tables:
-            # torch.optim.SparseAdam on the rows of the batch (torch/optim/_functional.py sparse_adam, statement by statement)
             st["step"] += 1
-            t = float(st["step"])
             rows = torch.unique(self._ids[:, self._table_index[id(p)]]).to(p.device)
-            g = p.grad.index_select(0, rows)
-            m_old, v_old = st["exp_avg"].index_select(0, rows), st["exp_avg_sq"].index_select(0, rows)
-            m_upd = g.sub(m_old).mul_(1 - beta1)
-            v_upd = g.pow(2).sub_(v_old).mul_(1 - beta2)
-            numer = m_upd.add(m_old)
-            v_new = v_upd.add(v_old)
-            st["exp_avg"].index_copy_(0, rows, numer)
-            st["exp_avg_sq"].index_copy_(0, rows, v_new)
-            denom = v_new.sqrt().add_(eps)
-            step_size = lr * math.sqrt(1 - beta2 ** t) / (1 - beta1 ** t)
-            p.index_add_(0, rows, numer.div(denom).mul_(-step_size))
+            self._update_rows(p, st, rows, float(st["step"]), lr, beta1, beta2, eps)
         self._ids = None  # consumed: the next gradients need their own ids
         return loss
+
+    def _update_rows(self, p, st, rows, t, lr, beta1, beta2, eps):
+        """torch.optim.SparseAdam on the rows of the batch (torch/optim/_functional.py sparse_adam, statement by statement)"""
+        g = p.grad.index_select(0, rows)
+        m_old, v_old = st["exp_avg"].index_select(0, rows), st["exp_avg_sq"].index_select(0, rows)
+        m_upd = g.sub(m_old).mul_(1 - beta1)
+        v_upd = g.pow(2).sub_(v_old).mul_(1 - beta2)
+        numer = m_upd.add(m_old)
+        v_new = v_upd.add(v_old)
+        st["exp_avg"].index_copy_(0, rows, numer)
+        st["exp_avg_sq"].index_copy_(0, rows, v_new)
+        denom = v_new.sqrt().add_(eps)
+        step_size = lr * math.sqrt(1 - beta2 ** t) / (1 - beta1 ** t)
+        p.index_add_(0, rows, numer.div(denom).mul_(-step_size))
+
+
+class RowwiseSparseAdam(RowSparseAdam):
+    """`--optimizer rowwise-adam`: RowSparseAdam with ONE second moment per embedding row ("partial row-wise Adam") — torch.optim.Adam
+    on the dense parameters; on a table the first moment stays per element and `exp_avg_sq` has shape [rows], fed the mean of the
+    row's squared gradient, and divides the whole row.  A row r whose id is in the batch, g = its summed, clipped gradient, zero or not:
+
+        m[r] += (g - m[r]) * (1 - beta1)
+        v[r] += ((g * g).mean() - v[r]) * (1 - beta2)
+        p[r] -= lr * sqrt(1 - beta2^t) / (1 - beta1^t) * m[r] / (sqrt(v[r]) + eps)         t = the table's step count after this step
+
+    — the order of statements and the step size of RowSparseAdam.  A row outside the batch keeps its bits in p, m and v.  At embedding
+    width 16 the tables' optimizer state is 17/32 of RowSparseAdam's.  Same constructor, `touch()` protocol and param-group keys; a
+    table must be 2-D, and a checkpoint of the other form is refused by either class (load_state_dict): nothing broadcasts silently.
+
+    `step()` is the torch route, on any device; the fused engine step reproduces it (OptimSpec.table_kind "rowwise_adam",
+    csrc/optim_moments.hip RowwiseSparseAdamRows) and shares its state through SuperNet.engine_bind_optimizer."""
+
+    RULE = "row-wise"
+
+    def __init__(self, params, table_params: Iterable[torch.Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8):
+        table_params = list(table_params)
+        for t in table_params:
+            if t.dim() != 2:
+                raise ValueError("RowwiseSparseAdam: the row-wise second moment needs 2-D tables [rows, width], got shape %s" % (tuple(t.shape),))
+        super().__init__(params, table_params, lr=lr, betas=betas, eps=eps)
+
+    def _second_moment_shape(self, p):
+        return (p.shape[0],) if id(p) in self._table_index else tuple(p.shape)
+
+    def _update_rows(self, p, st, rows, t, lr, beta1, beta2, eps):
+        """RowSparseAdam's statements with the row's mean squared gradient in place of g^2 and one denominator per row"""
+        if tuple(st["exp_avg_sq"].shape) != (p.shape[0],):
+            raise ValueError("RowwiseSparseAdam: exp_avg_sq of a table of shape %s has shape %s, the row-wise rule keeps %s (a checkpoint "
+                             "of RowSparseAdam?)" % (tuple(p.shape), tuple(st["exp_avg_sq"].shape), (p.shape[0],)))
+        g = p.grad.index_select(0, rows)
+        m_old, v_old = st["exp_avg"].index_select(0, rows), st["exp_avg_sq"].index_select(0, rows)
+        m_upd = g.sub(m_old).mul_(1 - beta1)
+        v_upd = (g * g).mean(dim=1).sub_(v_old).mul_(1 - beta2)
+        numer = m_upd.add(m_old)
+        v_new = v_upd.add(v_old)
+        st["exp_avg"].index_copy_(0, rows, numer)
+        st["exp_avg_sq"].index_copy_(0, rows, v_new)
+        denom = v_new.sqrt().add_(eps)
+        step_size = lr * math.sqrt(1 - beta2 ** t) / (1 - beta1 ** t)
+        p.index_add_(0, rows, numer.div(denom.unsqueeze(1)).mul_(-step_size))
 
 
 _SR_T, _SR_F = 0x9E3779B9, 0x85EBCA6B  # the odd constants that spread the step count and the table index over 32 bits

@@ -126,7 +126,8 @@ def _refuse_regularised_tables(optimizer, l2_loss_fn):
     """row-sparse Adam moves a table in the batch's rows only; an L2 term over a table puts a gradient on every row, on either route"""
     from ..optim_spec import OptimSpec, regularises_tables
     spec = OptimSpec.from_optimizer(optimizer) if isinstance(optimizer, torch.optim.Optimizer) else None
-    if spec is not None and spec.sparse_rows and isinstance(l2_loss_fn, L2Loss) and regularises_tables(l2_loss_fn.wd, l2_loss_fn.no_reg_param_name):
+    if spec is not None and (spec.sparse_rows or spec.rowwise_adam) and isinstance(l2_loss_fn, L2Loss) and \
+            regularises_tables(l2_loss_fn.wd, l2_loss_fn.no_reg_param_name):
         raise ValueError("row-sparse Adam cannot train a regularised embedding table (weight decay %g reaches every row): pass "
                          "--no-reg-param-name _embedding to leave the tables out of the L2 term, or --wd 0" % l2_loss_fn.wd)
 
@@ -141,7 +142,7 @@ def _last_layer_step_applies(model, optimizer, l2_loss_fn, use_amp):
     if world_info()[1] > 1 or getattr(model, "_table_sharding", None) == "row" or getattr(model, "_place_embedding_on_cpu", False):
         return False
     spec = _optim_spec(optimizer, l2_loss_fn)
-    if spec is None or spec.kind == "rmsprop" or spec.table_kind or not model._last_layer_only():  # (RMSprop, AdamAdagradTables: the fine-tune keeps the torch route)
+    if spec is None or spec.kind == "rmsprop" or spec.adagrad_tables or not model._last_layer_only():  # (RMSprop, AdamAdagradTables: the fine-tune keeps the torch route)
         return False
     g = optimizer.param_groups[0]
     if not {id(p) for p in model._final.parameters()} <= {id(p) for p in g["params"]}:
@@ -291,6 +292,22 @@ def _announce_split_route(optimizer, l2_loss_fn, fused, switched_off=False):
     print(head + ": torch route, AdamAdagradTables.step() ({}).".format(why))
 
 
+def _announce_rowwise_adam_route(model, optimizer, l2_loss_fn, use_amp, fused, switched_off=False):
+    """one line per run with RowwiseSparseAdam (utils/optim.py): which route takes the step, and why"""
+    from .optim import RowwiseSparseAdam
+    if type(optimizer) is not RowwiseSparseAdam or getattr(optimizer, "_route_announced", False):
+        return
+    optimizer._route_announced = True
+    head = "Row-wise Adam (row-sparse Adam, one second-moment float per embedding row)"
+    if fused:
+        print(head + ": fused step, the batch's table rows only.")
+        return
+    why = "the fused step was switched off" if switched_off else "the fused step does not apply"
+    if use_amp:
+        why = "AMP keeps the torch route"
+    print(head + ": torch route, RowwiseSparseAdam.step() on the rows of touch() ({}).".format(why))
+
+
 def _agreed_batches(train_loader, train_batch_size: int, world: int, gpu):
     """The batches of one epoch.  Single process: the loader as it is (incl. its short last batch, which the reference evaluates
     without training on it).  Data parallel: every rank reads its own shards, which differ in length — the ranks agree one step
@@ -347,6 +364,7 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
         raise ValueError("bf16 tables (--table-dtype bf16) run with neither AMP (use_amp), the last-layer fine-tune step, a weight EMA "
                          "(--ema) nor a decoupled weight decay (--decoupled-wd): none of them is built for bf16 tables")
     _announce_split_route(optimizer, l2_loss_fn, fused, switched_off=use_engine_step is False)
+    _announce_rowwise_adam_route(model, optimizer, l2_loss_fn, use_amp, fused, switched_off=use_engine_step is False)
     if ema is not None:
         if fused and use_engine_step is not None and not _fused_step_applies(model, optimizer, l2_loss_fn, use_amp, ema):
             raise ValueError("use_engine_step=True with a weight EMA the fused step cannot keep exactly: leave use_engine_step=None")

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the optimizer choice (`--optimizer adagrad | adam | sgd | row-sparse-adam | rmsprop | adam-adagrad-tables`, main_train.py:150-160) on the bench cfg-2 network:
+"""Cost of the optimizer choice (`--optimizer adagrad | adam | sgd | row-sparse-adam | rowwise-adam | rmsprop | adam-adagrad-tables`, main_train.py:150-160) on the bench cfg-2 network:
 the Criteo best-1shot sub-network, full tables (33.76 M rows), batch 256, clip 5.0; Adagrad(eps 1e-2), Adam(eps 1e-8), SGD(momentum 0.9,
 Nesterov), row-sparse Adam (Adam's lr and eps; with --wd the L2 term leaves the tables out, as the optimizer requires), RMSprop (torch's
 defaults; fused: lazily decayed rows, with --wd the tables left out too; its line also carries `flush_ms`, the one launch that brings
@@ -31,13 +31,13 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-LR = {"adagrad": 1e-3, "adam": 1e-3, "sgd": 1e-3, "row-sparse-adam": 1e-3, "rmsprop": 1e-4, "adam-adagrad-tables": 1e-3}
+LR = {"adagrad": 1e-3, "adam": 1e-3, "sgd": 1e-3, "row-sparse-adam": 1e-3, "rowwise-adam": 1e-3, "rmsprop": 1e-4, "adam-adagrad-tables": 1e-3}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--route", choices=["fused", "torch"], default="fused")
-    ap.add_argument("--optimizer", choices=["adagrad", "adam", "sgd", "row-sparse-adam", "rmsprop", "adam-adagrad-tables"], default="adam")
+    ap.add_argument("--optimizer", choices=["adagrad", "adam", "sgd", "row-sparse-adam", "rowwise-adam", "rmsprop", "adam-adagrad-tables"], default="adam")
     ap.add_argument("--table-lr-scale", dest="table_lr_scale", type=float, default=1.0,
                     help="adam-adagrad-tables: the tables' learning rate as a multiple of the network's")
     ap.add_argument("--table-rowwise", dest="table_rowwise", action="store_true",
@@ -67,7 +67,7 @@ def main():
         return
     if a.all:
         for route in ("fused", "torch"):
-            for opt in ("adagrad", "adam", "sgd", "row-sparse-adam", "rmsprop", "adam-adagrad-tables"):
+            for opt in ("adagrad", "adam", "sgd", "row-sparse-adam", "rowwise-adam", "rmsprop", "adam-adagrad-tables"):
                 for wd in (0.0, 1e-8):
                     steps = a.steps if route == "fused" else min(a.steps, 20)
                     cmd = [sys.executable, os.path.abspath(__file__), "--route", route, "--optimizer", opt, "--wd", str(wd), "--steps", str(steps),
@@ -77,7 +77,7 @@ def main():
                         sys.stderr.write(r.stdout + r.stderr)
                         raise SystemExit("%s exited with %d" % (" ".join(cmd[2:]), r.returncode))
                     print(r.stdout.strip().splitlines()[-1], flush=True)
-        for opt in ("adagrad", "row-sparse-adam", "rmsprop"):
+        for opt in ("adagrad", "row-sparse-adam", "rowwise-adam", "rmsprop"):
             for lam in (0.0, 1e-5):
                 cmd = [sys.executable, os.path.abspath(__file__), "--route", "fused", "--optimizer", opt, "--decoupled-wd", str(lam),
                        "--steps", str(a.steps), "--warmup", str(a.warmup), "--B", str(a.B)]
@@ -110,7 +110,7 @@ def main():
     lr = LR[a.optimizer]
     opt = MT.build_optimizer(a.optimizer, m, lr, a.table_lr_scale, table_rowwise=a.table_rowwise, table_seed=a.table_seed)
     spec = OptimSpec.from_optimizer(opt) if a.optimizer != "adagrad" else None
-    lazy = a.optimizer in ("row-sparse-adam", "rmsprop", "adam-adagrad-tables") and a.route == "fused"  # (the fused step needs the tables left out of the L2 term)
+    lazy = a.optimizer in ("row-sparse-adam", "rowwise-adam", "rmsprop", "adam-adagrad-tables") and a.route == "fused"  # (the fused step needs the tables left out of the L2 term)
     no_reg = "_embedding" if ((a.optimizer == "row-sparse-adam" or lazy) and a.wd) else None
     loss_fn = torch.nn.BCEWithLogitsLoss()
     if a.route == "fused":
