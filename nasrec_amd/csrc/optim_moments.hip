@@ -4,13 +4,11 @@
 // (a zero gradient still moves a row whose moments are non-zero: W and its one or two moment arrays, read and written once) and,
 // in the workgroup that finishes last, counts the step of every parameter it updated.
 // Phase 0 is one kernel, opt_moments_phase0_kernel<Rows>; what happens to one touched row, and whether the launch marks the bitmap or
-// counts the steps itself, is the row policy `Rows` (DenseRows, SparseAdamRows, LazyRmspropRows, AdagradTableRows, RowwiseAdagradTableRows,
-// RowwiseAdagradBf16TableRows, RowwiseSparseAdamRows below).
-// Row-sparse Adam (sparse_rows, include/nasrec_hip.h): the same clip and dense chunks, torch.optim.SparseAdam on the touched rows, no
-// bitmap, and no phase 1 unless weight decay has gradients to restore.
-// RMSprop (NASREC_OPTIM_RMSPROP: momentum 0, not centered): a row whose gradient is zero does not move and its square_avg only decays,
-// so the touched rows pay the decay they owe (per-row stamps) and take torch.optim.RMSprop's update; opt_moments_flush_kernel (phase 2)
-// brings every row's square_avg current for whoever reads the state.
+// counts the steps itself, is the row policy `Rows` (DenseRows, SparseAdamRows, LazyRmspropRows, AdagradTableRows, RowwiseAdagradRows over
+// fp32 or bf16 rows, RowwiseSparseAdamRows below); which descriptor takes which policy, and what it must bring, is ROW_FORMS.
+// The other forms (include/nasrec_hip.h) move the batch's rows only: the same clip and dense chunks, no bitmap, and no phase 1 unless
+// weight decay has gradients to restore.  RMSprop (momentum 0, not centered) among them lets a row whose gradient is zero rest while
+// its square_avg only decays: opt_moments_flush_kernel (phase 2) brings every row's square_avg current for whoever reads the state.
 #include "optimizer_bodies.h"
 
 namespace {
@@ -91,12 +89,15 @@ __device__ __forceinline__ void dense_chunks(const nasrec_opt_moments_desc_t& d,
   }
 }
 
-// ---------------------------------------------------------------------------------------------------
 // Row policies of phase 0: a small struct in LDS.  DENSE = the ALGO dense_chunks runs with; COUNTS = a launch without zero_chunks
 // counts the steps itself (there is no phase 1 behind it); scalars(d, lr) = the per-table scalars, by threads [64, 64 + Fs) of a row
 // workgroup (the kernel synchronises); row(d, f, row, q, g4, lr) = quarter q of touched row `row` of table f, g4 = the clipped quarter
-// of its summed gradient.
-// ---------------------------------------------------------------------------------------------------
+// of its summed gradient.  RowsOnly = what the policies that move the batch's rows alone start from.
+struct RowsOnly {
+  static constexpr int DENSE = NASREC_OPTIM_ADAM;
+  static constexpr bool COUNTS = true;
+  __device__ __forceinline__ void scalars(const nasrec_opt_moments_desc_t&, float) {}
+};
 
 // Adam / momentum SGD on every row: the touched rows here, marked in the bitmap, the others in phase 1 (which counts the steps)
 template <int ALGO>
@@ -117,16 +118,16 @@ struct DenseRows {
   }
 };
 
-// Row-sparse Adam (sparse_rows): a touched row takes torch.optim.SparseAdam's update with its summed gradient, zero or not; no bit is
-// marked, and no other row moves.
-struct SparseAdamRows {
-  static constexpr int DENSE = NASREC_OPTIM_ADAM;
-  static constexpr bool COUNTS = true;
+struct SparseAdamStepSizes : RowsOnly {  // (the per-table scalars of both row-sparse Adam policies)
   float ss[NASREC_MAX_TABLES];
   __device__ __forceinline__ void scalars(const nasrec_opt_moments_desc_t& d, float lr) {
     const int f = (int)threadIdx.x - 64;
     if (f >= 0 && f < d.Fs) ss[f] = sparse_adam_step_size(d, d.step[d.table_step0 + f], lr);
   }
+};
+// Row-sparse Adam (sparse_rows): a touched row takes torch.optim.SparseAdam's update with its summed gradient, zero or not; no bit is
+// marked, and no other row moves.
+struct SparseAdamRows : SparseAdamStepSizes {
   __device__ __forceinline__ void row(const nasrec_opt_moments_desc_t& d, int f, long row, int q, const f32x4& g4, float) const {
     const long o = row * 16 + q * 4;
     f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o), m4 = *reinterpret_cast<const f32x4*>(d.tm[f] + o);
@@ -149,10 +150,8 @@ struct SparseAdamRows {
 // RMSprop (p / g / v): a touched row first pays the decay its square_avg owes since its stamp (lazy_decay, optimizer_bodies.h), then
 // takes torch.optim.RMSprop's update with its summed gradient, and is stamped with this step; no bit is marked.  The four lanes of a
 // row read its stamp before lane 0 writes it: they sit in one wavefront, and the store follows the loads in program order.
-struct LazyRmspropRows {
+struct LazyRmspropRows : RowsOnly {
   static constexpr int DENSE = NASREC_OPTIM_RMSPROP;
-  static constexpr bool COUNTS = true;
-  __device__ __forceinline__ void scalars(const nasrec_opt_moments_desc_t&, float) {}
   __device__ __forceinline__ void row(const nasrec_opt_moments_desc_t& d, int f, long row, int q, const f32x4& g4, float lr) const {
     const long o = row * 16 + q * 4;
     const long step = (long)d.step[d.table_step0 + f] + 1;
@@ -171,10 +170,7 @@ struct LazyRmspropRows {
 // update with its summed gradient, at the tables' own learning rate lr * table_lr_scale and eps; tv holds the accumulator `sum`, tm is
 // never read or written, no bit is marked.  A zero gradient leaves sum and W as they are (table_eps > 0: the quotient is an exact zero),
 // so every row outside the batch AND a touched row whose gradient sums to zero keep their bits: exact, nothing is owed.
-struct AdagradTableRows {
-  static constexpr int DENSE = NASREC_OPTIM_ADAM;
-  static constexpr bool COUNTS = true;
-  __device__ __forceinline__ void scalars(const nasrec_opt_moments_desc_t&, float) {}
+struct AdagradTableRows : RowsOnly {
   __device__ __forceinline__ void row(const nasrec_opt_moments_desc_t& d, int f, long row, int q, const f32x4& g4, float lr) const {
     const long o = row * 16 + q * 4;
     const float tlr = lr * d.table_lr_scale;
@@ -191,30 +187,33 @@ struct AdagradTableRows {
   }
 };
 
+// The sum of the squares of a row's 16 gradient elements, in each of its four lanes (g4 = the lane's quarter); the callers scale it to
+// the mean (* 0.0625f: exact) in a statement of their own.  The sum over the four lanes goes into each of them (a + b is commutative:
+// the four totals have the same bits).  The quad is the aligned lanes 4k .. 4k + 3 of one wavefront, and its lanes arrive here
+// together or not at all: every branch in front of a call (pair < B * Fs, leader[pair], the row-range test) is a function of
+// `pair` = t >> 2 alone.  quad_perm reads inside the quad only, so the other quads of the wavefront may be inactive.  A branch on q in
+// front of a call would break it.
+__device__ __forceinline__ float row_sum_of_squares(const f32x4& g4) {
+  float sq = g4[0] * g4[0];
+  sq = fmaf(g4[1], g4[1], sq);
+  sq = fmaf(g4[2], g4[2], sq);
+  sq = fmaf(g4[3], g4[3], sq);
+  sq += dpp_mov<0xb1>(sq);  // quad_perm:[1,0,3,2]
+  sq += dpp_mov<0x4e>(sq);  // quad_perm:[2,3,0,1]
+  return sq;
+}
+
 // Row-wise Adagrad on the tables (table_algo = NASREC_TABLE_ALGO_ROWWISE_ADAGRAD; Adam on the dense chunks): tv[f] holds ONE float per
 // row, the accumulator of the mean of the row's squared gradient; sum += mean(g^2), then Adagrad's weight statement with that one sum
-// for all 16 elements, at lr * table_lr_scale and table_eps.  tm is never read or written, no bit is marked, and a zero gradient leaves
-// sum and W as they are, as with AdagradTableRows.
-struct RowwiseAdagradTableRows {
-  static constexpr int DENSE = NASREC_OPTIM_ADAM;
-  static constexpr bool COUNTS = true;
-  __device__ __forceinline__ void scalars(const nasrec_opt_moments_desc_t&, float) {}
+// for all 16 elements, at lr * table_lr_scale and table_eps.  A zero gradient leaves sum and W as they are, as with AdagradTableRows.
+struct RowwiseAdagradTableRows : RowsOnly {
   __device__ __forceinline__ void row(const nasrec_opt_moments_desc_t& d, int f, long row, int q, const f32x4& g4, float lr) const {
     const long o = row * 16 + q * 4;
     const float tlr = lr * d.table_lr_scale;
     f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o);
     float s = d.tv[f][row];  // (all four lanes load it; lane q == 0 stores it below, after the loads in program order)
-    float sq = g4[0] * g4[0];
-    sq = fmaf(g4[1], g4[1], sq);
-    sq = fmaf(g4[2], g4[2], sq);
-    sq = fmaf(g4[3], g4[3], sq);
-    // Sum over the row's four lanes, into each of them (a + b is commutative: the four totals have the same bits).  The quad is the
-    // aligned lanes 4k .. 4k + 3 of one wavefront, and its lanes arrive here together or not at all: every branch in front of this
-    // (pair < B * Fs, leader[pair], the row-range test) is a function of `pair` = t >> 2 alone.  quad_perm reads inside the quad only,
-    // so the other quads of the wavefront may be inactive.  A branch on q in front of this line would break it.
-    sq += dpp_mov<0xb1>(sq);  // quad_perm:[1,0,3,2]
-    sq += dpp_mov<0x4e>(sq);  // quad_perm:[2,3,0,1]
-    s += sq * 0.0625f;        // (the mean of 16: an exact scaling)
+    const float sq = row_sum_of_squares(g4);
+    s += sq * 0.0625f;  // (the mean of 16: an exact scaling)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float pe = p4[e];
@@ -226,14 +225,13 @@ struct RowwiseAdagradTableRows {
   }
 };
 
-// Row-wise Adagrad on bfloat16 tables (table_algo = NASREC_TABLE_ALGO_ROWWISE_ADAGRAD_BF16): table[f] is [rows, 16] bfloat16 with
-// 32-byte rows behind the float pointer; a lane loads its quarter's 8 bytes, widens it exactly (bits << 16), takes
-// RowwiseAdagradTableRows' statements in fp32 — the same quad sum under the same invariant: no branch on q in front of it — and stores
-// each new weight with stochastic rounding, out16 = (bits + r) >> 16, four results in one 8-byte store.  r = the top 16 bits of a
-// counter hash of (seed, t, f, row, e) (include/nasrec_hip.h; utils/optim.stochastic_round_bf16 is the definition): t is the table's
-// step count after this step, read from the device counter, so the descriptor stays constant from step to step; the (seed, t, f)
-// prefix of the chain is a per-table scalar in LDS.  A non-finite weight is stored truncated.  A weight that did not move has low
-// bits zero and keeps its bits, so a zero gradient leaves the row alone as above.
+// The same rule on bfloat16 tables (table_algo = NASREC_TABLE_ALGO_ROWWISE_ADAGRAD_BF16): table[f] is [rows, 16] bfloat16 with 32-byte
+// rows behind the float pointer; a lane loads its quarter's 8 bytes, widens it exactly (bits << 16), takes RowwiseAdagradTableRows'
+// statements in fp32 and stores each new weight with stochastic rounding, out16 = (bits + r) >> 16, four results in one 8-byte store.
+// r = the top 16 bits of a counter hash of (seed, t, f, row, e) (include/nasrec_hip.h; utils/optim.stochastic_round_bf16 is the
+// definition): t is the table's step count after this step, read from the device counter, so the descriptor stays constant from step
+// to step; the (seed, t, f) prefix of the chain is a per-table scalar in LDS.  A non-finite weight is stored truncated.  A weight that
+// did not move has low bits zero and keeps its bits, so a zero gradient leaves the row alone as above.
 __device__ __forceinline__ uint32_t sr_mix(uint32_t h) {
   h ^= h >> 16;
   h *= 0x7feb352du;
@@ -242,16 +240,13 @@ __device__ __forceinline__ uint32_t sr_mix(uint32_t h) {
   h ^= h >> 16;
   return h;
 }
-
 __device__ __forceinline__ uint32_t sr_round_bf16(float x, uint32_t h) {
   const uint32_t bits = __float_as_uint(x);
   const uint32_t r = (bits & 0x7f800000u) == 0x7f800000u ? 0u : sr_mix(h) >> 16;
   return (bits + r) >> 16;  // (a finite x is at most 0xff7fffff: the sum cannot wrap)
 }
 
-struct RowwiseAdagradBf16TableRows {
-  static constexpr int DENSE = NASREC_OPTIM_ADAM;
-  static constexpr bool COUNTS = true;
+struct RowwiseAdagradBf16TableRows : RowsOnly {
   uint32_t prefix[NASREC_MAX_TABLES];
   __device__ __forceinline__ void scalars(const nasrec_opt_moments_desc_t& d, float) {
     const int f = (int)threadIdx.x - 64;
@@ -267,13 +262,7 @@ struct RowwiseAdagradBf16TableRows {
     const uint2 w = *wp;
     f32x4 p4 = {__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u)};
     float s = d.tv[f][row];  // (all four lanes load it; lane q == 0 stores it below, after the loads in program order)
-    float sq = g4[0] * g4[0];
-    sq = fmaf(g4[1], g4[1], sq);
-    sq = fmaf(g4[2], g4[2], sq);
-    sq = fmaf(g4[3], g4[3], sq);
-    // (the quad sum of RowwiseAdagradTableRows: its lanes arrive together — nothing in front of this line branches on q)
-    sq += dpp_mov<0xb1>(sq);  // quad_perm:[1,0,3,2]
-    sq += dpp_mov<0x4e>(sq);  // quad_perm:[2,3,0,1]
+    const float sq = row_sum_of_squares(g4);
     s += sq * 0.0625f;
     const uint32_t h = prefix[f], pos = (uint32_t)row * 16u + (uint32_t)q * 4u;  // (row * 16 + e may wrap in 32 bits: part of the definition)
     uint32_t o[4];
@@ -290,43 +279,23 @@ struct RowwiseAdagradBf16TableRows {
 
 // Row-wise row-sparse Adam (table_algo = NASREC_TABLE_ALGO_ROWWISE_ADAM; Adam on the dense chunks): SparseAdamRows with ONE second
 // moment per row.  tm[f] is [rows, 16] as there; tv[f] holds one float per row, the moving average of the mean of the row's squared
-// gradient, and divides the whole row.  The statements and the step size are SparseAdamRows' (sparse_adam_elem, sparse_adam_step_size);
-// the sum of squares and its quad sum are RowwiseAdagradTableRows', under the same invariant: nothing in front of the quad sum
-// branches on q.  A touched row moves with its summed gradient, zero or not; no bit is marked, and no other row moves.
-struct RowwiseSparseAdamRows {
-  static constexpr int DENSE = NASREC_OPTIM_ADAM;
-  static constexpr bool COUNTS = true;
-  float ss[NASREC_MAX_TABLES];
-  __device__ __forceinline__ void scalars(const nasrec_opt_moments_desc_t& d, float lr) {
-    const int f = (int)threadIdx.x - 64;
-    if (f >= 0 && f < d.Fs) ss[f] = sparse_adam_step_size(d, d.step[d.table_step0 + f], lr);
-  }
+// gradient (row_sum_of_squares, under its invariant), and divides the whole row.  The statements and the step size are
+// SparseAdamRows'.  A touched row moves with its summed gradient, zero or not; no bit is marked, and no other row moves.
+struct RowwiseSparseAdamRows : SparseAdamStepSizes {
   __device__ __forceinline__ void row(const nasrec_opt_moments_desc_t& d, int f, long row, int q, const f32x4& g4, float) const {
     const long o = row * 16 + q * 4;
     f32x4 p4 = *reinterpret_cast<const f32x4*>(d.table[f] + o), m4 = *reinterpret_cast<const f32x4*>(d.tm[f] + o);
     float v = d.tv[f][row];  // (all four lanes load it; lane q == 0 stores it below, after the loads in program order)
-    float sq = g4[0] * g4[0];
-    sq = fmaf(g4[1], g4[1], sq);
-    sq = fmaf(g4[2], g4[2], sq);
-    sq = fmaf(g4[3], g4[3], sq);
-    // (the quad sum of RowwiseAdagradTableRows: its lanes arrive together — nothing in front of this line branches on q)
-    sq += dpp_mov<0xb1>(sq);  // quad_perm:[1,0,3,2]
-    sq += dpp_mov<0x4e>(sq);  // quad_perm:[2,3,0,1]
+    const float sq = row_sum_of_squares(g4);
     const float w1 = (float)(1.0 - d.beta1), w2 = (float)(1.0 - d.beta2), step_size = ss[f];
-    float vu = sq * 0.0625f;  // (the mean of 16: an exact scaling)
-    vu = vu - v;
-    vu = vu * w2;
-    v = v + vu;
-    float den = sqrtf(v);
-    den = den + d.eps;
+    const float den = sparse_adam_second_moment(w2, d.eps, sq * 0.0625f, v);  // (the mean of 16: an exact scaling)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float mu = g4[e] - m4[e];
-      mu = mu * w1;
-      m4[e] = m4[e] + mu;
-      float u = m4[e] / den;
-      u = (-step_size) * u;
-      p4[e] = p4[e] + u;
+      float pe = p4[e], me = m4[e];
+      sparse_adam_first_moment(w1, g4[e], me);
+      sparse_adam_weight(me, den, pe, step_size);
+      p4[e] = pe;
+      m4[e] = me;
     }
     *reinterpret_cast<f32x4*>(d.table[f] + o) = p4;
     *reinterpret_cast<f32x4*>(d.tm[f] + o) = m4;
@@ -446,26 +415,64 @@ void launch_phase1(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
   hipLaunchKernelGGL(opt_moments_phase1_kernel<ALGO>, dim3((unsigned)d->nblocks), dim3(256), 0, st, *d);
 }
 
-}  // namespace
+// The row forms: what a launch does to the tables, one line each; launch_opt_moments reads nothing else about a form.  algo,
+// sparse_rows, table_algo = the descriptors that take it; name = how the refusals call a rows-only form.  ROWS_ONLY = it moves the
+// batch's rows only, so its phase 0 counts the steps unless zero_chunks call for a phase 1, which then owns no tile (the dense forms
+// move every row: bitmap + phase 1); OWN_TM = a rule of the tables' own whose rows read tm[f] as a first moment; TV_PER_ROW = tv[f] is
+// one float per row, not [rows, 16] (for the reader: a length cannot be checked here); STAMPS = per-row stamps in tm's storage; BF16 =
+// table[f] is bfloat16, tm[0]'s storage the seed; EPS_POSITIVE = table_eps > 0 (a zero gradient must leave its row alone).
+enum : unsigned { ROWS_ONLY = 1, OWN_TM = 2, TV_PER_ROW = 4, STAMPS = 8, BF16 = 16, EPS_POSITIVE = 32 };
+struct RowForm {
+  int algo, sparse_rows, table_algo;
+  const char* name;
+  unsigned flags;
+  int last_phase;  // (2 = the flush)
+  void (*phase0)(hipStream_t, const nasrec_opt_moments_desc_t*, int);
+  void (*phase1)(hipStream_t, const nasrec_opt_moments_desc_t*);  // (null: no phase 1, which last_phase says too)
+};
+constexpr int ADAM = NASREC_OPTIM_ADAM, SGD = NASREC_OPTIM_SGD, RMSPROP = NASREC_OPTIM_RMSPROP, SAME = NASREC_TABLE_ALGO_SAME;
+constexpr RowForm ROW_FORMS[] = {
+    {ADAM, 0, SAME, "", 0, 1, launch_phase0<DenseRows<ADAM>>, launch_phase1<ADAM>},
+    {SGD, 0, SAME, "", 0, 1, launch_phase0<DenseRows<SGD>>, launch_phase1<SGD>},
+    {ADAM, 1, SAME, "sparse_rows", ROWS_ONLY, 1, launch_phase0<SparseAdamRows>, launch_phase1<ADAM>},
+    {RMSPROP, 0, SAME, "RMSprop", ROWS_ONLY | STAMPS, 2, launch_phase0<LazyRmspropRows>, launch_phase1<RMSPROP>},
+    {ADAM, 0, NASREC_TABLE_ALGO_ADAGRAD, "table_algo", ROWS_ONLY | EPS_POSITIVE, 1, launch_phase0<AdagradTableRows>, launch_phase1<ADAM>},
+    {ADAM, 0, NASREC_TABLE_ALGO_ROWWISE_ADAGRAD, "table_algo", ROWS_ONLY | TV_PER_ROW | EPS_POSITIVE, 1, launch_phase0<RowwiseAdagradTableRows>, launch_phase1<ADAM>},
+    {ADAM, 0, NASREC_TABLE_ALGO_ROWWISE_ADAGRAD_BF16, "table_algo", ROWS_ONLY | TV_PER_ROW | BF16 | EPS_POSITIVE, 0, launch_phase0<RowwiseAdagradBf16TableRows>, nullptr},
+    {ADAM, 0, NASREC_TABLE_ALGO_ROWWISE_ADAM, "table_algo", ROWS_ONLY | TV_PER_ROW | OWN_TM, 1, launch_phase0<RowwiseSparseAdamRows>, launch_phase1<ADAM>},
+};
 
-// Every refusal comes before anything is launched.  The row form — dense (every row moves: bitmap + phase 1), row-sparse Adam, lazy
-// RMSprop, Adagrad or row-wise Adagrad (on fp32 or bf16 tables) on the tables, row-wise row-sparse Adam — decides what a launch needs;
-// all but the first move the batch's rows only, so their phase 0 counts the steps unless zero_chunks call for a phase 1, which then
-// owns no tile.  Phase 2 is RMSprop's flush.
-int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
-  if (d->Fs < 0 || d->Fs > NASREC_MAX_TABLES) return nasrec_set_error(-1, "opt_moments: Fs = %d", d->Fs);
-  if (!d->lr || !d->step) return nasrec_set_error(-1, "opt_moments: lr / step missing");
-  const bool adam = d->algo == NASREC_OPTIM_ADAM, rmsprop = d->algo == NASREC_OPTIM_RMSPROP;
-  const bool bf16 = d->table_algo == NASREC_TABLE_ALGO_ROWWISE_ADAGRAD_BF16;  // (table: [rows, 16] bfloat16; the seed in tm[0]'s storage)
-  const bool rowwise = d->table_algo == NASREC_TABLE_ALGO_ROWWISE_ADAGRAD || bf16;  // (tv: one float per row)
-  const bool rwadam = d->table_algo == NASREC_TABLE_ALGO_ROWWISE_ADAM;  // (tm: [rows, 16]; tv: one float per row)
-  const bool split = d->table_algo == NASREC_TABLE_ALGO_ADAGRAD || rowwise;  // (Adagrad on the tables)
-  const bool own = split || rwadam, lazy = rmsprop || d->sparse_rows || own;  // (own: the tables take a rule of their own)
-  if (d->table_algo != NASREC_TABLE_ALGO_SAME && !own) return nasrec_set_error(-1, "opt_moments: table_algo %d", d->table_algo);
+// (algo, sparse_rows, table_algo) -> the row form, or a refusal (its return code; 0 = *form is set).  A table_algo other than SAME is a
+// rule of the tables' own: it goes with Adam on the rest and without sparse_rows, and its refusals come first.
+int resolve_row_form(const nasrec_opt_moments_desc_t* d, const RowForm** form) {
+  bool known = false;
+  *form = nullptr;
+  for (const RowForm& r : ROW_FORMS) {
+    known |= r.table_algo == d->table_algo;
+    if (r.algo == d->algo && r.sparse_rows == (d->sparse_rows != 0) && r.table_algo == d->table_algo) *form = &r;
+  }
+  const bool adam = d->algo == ADAM, own = d->table_algo != SAME;
+  if (!known) return nasrec_set_error(-1, "opt_moments: table_algo %d", d->table_algo);
   if (own && !adam)
     return nasrec_set_error(-1, "opt_moments: table_algo %d (a rule of their own on the tables) goes with Adam on the rest (algo %d)", d->table_algo, d->algo);
   if (own && d->sparse_rows) return nasrec_set_error(-1, "opt_moments: table_algo with sparse_rows: the tables take one rule");
-  if (split && !(d->table_eps > 0.f))
+  if (d->algo == RMSPROP && d->momentum != 0.f) return nasrec_set_error(-1, "opt_moments: RMSprop with momentum %g moves untouched rows", (double)d->momentum);
+  if (d->sparse_rows && !adam) return nasrec_set_error(-1, "opt_moments: sparse_rows is row-sparse Adam (algo %d)", d->algo);
+  return *form ? 0 : nasrec_set_error(-1, "opt_moments: algo %d", d->algo);
+}
+
+}  // namespace
+
+// Every refusal comes before anything is launched, in one order: the form's (resolve_row_form), then what the form's flags ask of the
+// descriptor, then the phase's.
+int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
+  if (d->Fs < 0 || d->Fs > NASREC_MAX_TABLES) return nasrec_set_error(-1, "opt_moments: Fs = %d", d->Fs);
+  if (!d->lr || !d->step) return nasrec_set_error(-1, "opt_moments: lr / step missing");
+  const RowForm* form;
+  if (const int rc = resolve_row_form(d, &form)) return rc;
+  const RowForm& r = *form;
+  const bool rows_only = r.flags & ROWS_ONLY, bf16 = r.flags & BF16, own = d->table_algo != SAME;  // (own: the tables take a rule of their own)
+  if ((r.flags & EPS_POSITIVE) && !(d->table_eps > 0.f))
     return nasrec_set_error(-1, "opt_moments: table_eps %g must be positive (a zero gradient must leave its row alone)", (double)d->table_eps);
   if (own && d->reg_mask != 0u)
     return nasrec_set_error(-1, "opt_moments: table_algo with reg_mask %u: a regularised table moves in every row", d->reg_mask);
@@ -473,42 +480,29 @@ int launch_opt_moments(hipStream_t st, const nasrec_opt_moments_desc_t* d) {
     return nasrec_set_error(-1, "opt_moments: table_algo %d (bf16 tables) has phase 0 only: phase %d knows fp32 tables", d->table_algo, d->phase);
   for (int f = 1; bf16 && f < NASREC_MAX_TABLES; ++f)  // (a caller that filled tm expects a first moment: there is none, and tm[0] is the seed)
     if (d->tm[f]) return nasrec_set_error(-1, "opt_moments: table_algo %d (bf16 tables) keeps the seed in tm[0]'s storage and takes no tm (tm[%d] is set)", d->table_algo, f);
-  const char* lazy_name = rmsprop ? "RMSprop" : own ? "table_algo" : "sparse_rows";
-  if (rmsprop && d->momentum != 0.f) return nasrec_set_error(-1, "opt_moments: RMSprop with momentum %g moves untouched rows", (double)d->momentum);
-  if (d->sparse_rows && !adam) return nasrec_set_error(-1, "opt_moments: sparse_rows is row-sparse Adam (algo %d)", d->algo);
-  if (!adam && !rmsprop && d->algo != NASREC_OPTIM_SGD) return nasrec_set_error(-1, "opt_moments: algo %d", d->algo);
-  if (d->phase < 0 || d->phase > (rmsprop ? 2 : 1)) return nasrec_set_error(-1, "opt_moments: phase %d", d->phase);
-  for (int f = 0; rmsprop && f < d->Fs; ++f)
+  if (d->phase < 0 || d->phase > r.last_phase || (d->phase == 1 && !r.phase1)) return nasrec_set_error(-1, "opt_moments: phase %d", d->phase);
+  for (int f = 0; (r.flags & STAMPS) && f < d->Fs; ++f)
     if (!d->stamp[f] || !d->tv[f]) return nasrec_set_error(-1, "opt_moments: RMSprop without the stamps / square_avg of table %d", f);
   if (d->phase == 0) {
     const long threads = (long)d->B * d->Fs * 4;
     const int nrows = (int)((threads + 255) / 256), nblk = d->dense_blocks + nrows;
     if (d->dense_blocks < 0 || nblk < 1) return nasrec_set_error(-2, "opt_moments: empty launch");
-    if (nrows > 0 && (!d->idx || !d->leader || !d->gsum || (!d->bitmap && !lazy))) return nasrec_set_error(-1, "opt_moments: row inputs missing");
+    if (nrows > 0 && (!d->idx || !d->leader || !d->gsum || (!d->bitmap && !rows_only))) return nasrec_set_error(-1, "opt_moments: row inputs missing");
     for (int f = 0; own && nrows > 0 && f < d->Fs; ++f) {
       if (!d->table[f] || !d->tv[f]) return nasrec_set_error(-1, "opt_moments: table_algo without the weights / accumulator (tv) of table %d", f);
-      if (rwadam && !d->tm[f]) return nasrec_set_error(-1, "opt_moments: table_algo %d (row-wise Adam) without the first moment (tm) of table %d", d->table_algo, f);
+      if ((r.flags & OWN_TM) && !d->tm[f]) return nasrec_set_error(-1, "opt_moments: table_algo %d (row-wise Adam) without the first moment (tm) of table %d", d->table_algo, f);
     }
     if (d->rank_B < 0 || (d->rank_B > 0 && (d->rank_stride < (int64_t)d->rank_B * d->Fs * 16 || d->B % d->rank_B != 0)))
       return nasrec_set_error(-2, "opt_moments: rank layout %d / %ld", d->rank_B, (long)d->rank_stride);
-    if (lazy && d->n_zero <= 0 && (!d->counter || (d->n_inc > 0 && !d->inc)))
-      return nasrec_set_error(-1, "opt_moments: %s without zero_chunks counts the steps: counter / inc missing", lazy_name);
-    if (rmsprop) launch_phase0<LazyRmspropRows>(st, d, nblk);
-    else if (bf16) launch_phase0<RowwiseAdagradBf16TableRows>(st, d, nblk);
-    else if (rowwise) launch_phase0<RowwiseAdagradTableRows>(st, d, nblk);
-    else if (split) launch_phase0<AdagradTableRows>(st, d, nblk);
-    else if (rwadam) launch_phase0<RowwiseSparseAdamRows>(st, d, nblk);
-    else if (d->sparse_rows) launch_phase0<SparseAdamRows>(st, d, nblk);
-    else if (adam) launch_phase0<DenseRows<NASREC_OPTIM_ADAM>>(st, d, nblk);
-    else launch_phase0<DenseRows<NASREC_OPTIM_SGD>>(st, d, nblk);
+    if (rows_only && d->n_zero <= 0 && (!d->counter || (d->n_inc > 0 && !d->inc)))
+      return nasrec_set_error(-1, "opt_moments: %s without zero_chunks counts the steps: counter / inc missing", r.name);
+    r.phase0(st, d, nblk);
   } else if (d->phase == 1) {
     if (d->nblocks <= 0) return nasrec_set_error(-1, "opt_moments: nblocks must be positive");
     if (!d->bitmap || !d->counter || !d->coef) return nasrec_set_error(-1, "opt_moments: phase 1 inputs missing");
-    if (lazy && (d->n_zero <= 0 || d->tile_off[d->Fs] != 0))
-      return nasrec_set_error(-1, "opt_moments: %s has a phase 1 only to restore zero_chunks, and no table owns a tile", lazy_name);
-    if (rmsprop) launch_phase1<NASREC_OPTIM_RMSPROP>(st, d);
-    else if (adam) launch_phase1<NASREC_OPTIM_ADAM>(st, d);
-    else launch_phase1<NASREC_OPTIM_SGD>(st, d);
+    if (rows_only && (d->n_zero <= 0 || d->tile_off[d->Fs] != 0))
+      return nasrec_set_error(-1, "opt_moments: %s has a phase 1 only to restore zero_chunks, and no table owns a tile", r.name);
+    r.phase1(st, d);
   } else {
     if (d->nblocks <= 0 || !d->bitmap) return nasrec_set_error(-1, "opt_moments: flush needs nblocks > 0 and the (all-zero) bitmap");
     if (d->tile_off[d->Fs] <= 0) return 0;

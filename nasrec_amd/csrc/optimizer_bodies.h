@@ -187,23 +187,31 @@ __device__ __forceinline__ float sparse_adam_step_size(const D& d, float step, f
   return (float)((double)lr * sqrt(1.0 - pow(d.beta2, t)) / (1.0 - pow(d.beta1, t)));
 }
 
-// one element; g = the clipped summed gradient.  One statement per torch call (sub, mul_, add_; pow, sub_, mul_, add_; sqrt_, add_; div_,
-// mul, add_), as in moments_elem
-template <class D>
-__device__ __forceinline__ void sparse_adam_elem(const D& d, float g, float& p, float& m, float& v, float step_size) {
-  const float w1 = (float)(1.0 - d.beta1), w2 = (float)(1.0 - d.beta2);
+// g = the clipped summed gradient.  One statement per torch call, as in moments_elem, in the three groups a row-wise second moment
+// takes apart: the first moment (sub, mul_, add_); the second moment from its g^2 term — g * g, or the row's mean of it — and the
+// denominator it gives (pow, sub_, mul_, add_; sqrt_, add_); the weight statement (div_, mul, add_)
+__device__ __forceinline__ void sparse_adam_first_moment(float w1, float g, float& m) {  // (w1 = 1 - beta1)
   float mu = g - m;
   mu = mu * w1;
   m = m + mu;
-  float vu = g * g;
-  vu = vu - v;
+}
+__device__ __forceinline__ float sparse_adam_second_moment(float w2, float eps, float g2, float& v) {  // (w2 = 1 - beta2) -> the denominator
+  float vu = g2 - v;
   vu = vu * w2;
   v = v + vu;
-  float den = sqrtf(v);
-  den = den + d.eps;
+  return sqrtf(v) + eps;
+}
+__device__ __forceinline__ void sparse_adam_weight(float m, float den, float& p, float step_size) {
   float u = m / den;
   u = (-step_size) * u;
   p = p + u;
+}
+template <class D>
+__device__ __forceinline__ void sparse_adam_elem(const D& d, float g, float& p, float& m, float& v, float step_size) {
+  const float w1 = (float)(1.0 - d.beta1), w2 = (float)(1.0 - d.beta2);
+  sparse_adam_first_moment(w1, g, m);
+  const float den = sparse_adam_second_moment(w2, d.eps, g * g, v);
+  sparse_adam_weight(m, den, p, step_size);
 }
 
 // RMSprop's lazily decayed table rows: a row whose gradient was zero for n steps owes its square_avg the factor alpha^n; power and

@@ -427,10 +427,7 @@ class SupernetEngine:
 
     def _ensure_split_table_state(self, spec):
         """the tables' state of a split-optimizer spec: `table_row_state` for the row-wise rule, `table_state` for the element-wise one"""
-        if spec.table_rowwise:  # (fp32 accumulators whatever the tables' storage type)
-            self._ensure_table_row_state()
-        else:
-            self._ensure_table_state()
+        getattr(self, "_ensure_" + spec.table_rule.state)()  # (_ensure_table_state / _ensure_table_row_state: fp32 whatever the tables' storage type)
 
     # -------------------------------------------------------------------------------------------------------
     @_on_device
@@ -576,7 +573,7 @@ class SupernetEngine:
             cp.fwd_levels = cp.bwd_levels = None
             cp.dead_forward = []
             if train:  # (the backward program decides which forward results are read: built further down, before the packing)
-                if not spec.moments or spec.adagrad_tables:  # (Adagrad's table state: Adam / SGD keep theirs in `moments` instead)
+                if spec.table_rule.state != "moments":  # (Adagrad's table state: Adam / SGD keep theirs in `moments` instead)
                     self._ensure_split_table_state(spec)
                 self._build_training_tail(cp, ctx, w, bptr, fsegs, B, K, grad_scale)
             fwd_list = list(ctx.fwd)
@@ -985,19 +982,11 @@ class SupernetEngine:
             raise L.EngineError("Adam / SGD in the fused step need the embedding tables on the device")
         t = cp.tail
         spec = t.spec
-        if spec.kind == "rmsprop" and spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
-            raise L.EngineError("lazy RMSprop with a regularised table: the L2 term puts a gradient on every row; leave the tables out "
-                                "(no_reg_param_name='_embedding') or use weight_decay=0")
-        if spec.sparse_rows and spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
-            raise L.EngineError("row-sparse Adam with a regularised table: the L2 term puts a gradient on every row; leave the tables out "
-                                "(no_reg_param_name='_embedding') or use weight_decay=0")
-        if spec.rowwise_adam and spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
-            raise L.EngineError("row-wise Adam with a regularised table: the L2 term puts a gradient on every row; leave the tables out "
-                                "(no_reg_param_name='_embedding') or use weight_decay=0")
-        if spec.adagrad_tables and spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
-            raise L.EngineError("Adagrad on the tables with a regularised table: the L2 term puts a gradient on every row; leave the "
-                                "tables out (no_reg_param_name='_embedding') or use weight_decay=0")
-        self.ensure_moments_state(spec.kind, tables=not spec.adagrad_tables, rowwise_v=spec.rowwise_adam)
+        rule = spec.table_rule
+        if rule.rows_only and spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
+            raise L.EngineError("%s with a regularised table: the L2 term puts a gradient on every row; leave the tables out "
+                                "(no_reg_param_name='_embedding') or use weight_decay=0" % rule.phrase)
+        self.ensure_moments_state(spec.kind, tables=rule.state == "moments", rowwise_v=spec.rowwise_adam)
         names = [n for n in list(ctx.grad_params) + ["_final.weight", "_final.bias"] if not n.startswith("_embedding.")]
         if spec.wd:
             names += P.regularised(self.shapes, spec.no_reg)[0]
@@ -1020,7 +1009,7 @@ class SupernetEngine:
     @staticmethod
     def _optim_scalars(d, spec):
         """algo and hyperparameters of an Adam / SGD spec on an OptMomentsDesc or a LastLayerStepDesc"""
-        if (spec.table_kind not in ("", "adagrad", "rowwise_adagrad", "rowwise_adam") and not spec.bf16_tables) or (spec.table_kind and spec.kind != "adam"):
+        if spec.table_kind and spec.kind not in spec.table_rule.kinds:  # (an unknown table_kind goes with no kind)
             raise L.EngineError("table_kind %r with %s: the tables' own rules (Adagrad, row-wise Adagrad, row-wise Adam) go with Adam on "
                                 "the dense parameters" % (spec.table_kind, spec.kind))
         d.algo = {"adam": L.OPTIM_ADAM, "rmsprop": L.OPTIM_RMSPROP}.get(spec.kind, L.OPTIM_SGD)
@@ -1030,30 +1019,26 @@ class SupernetEngine:
     def _moments_descs(self, t, Bg, cat_x, gsum, clip_desc, rank_layout=None):
         """the two NASREC_OP_OPT_MOMENTS launches of a plan with Adam / SGD: (phase 0 in place of the Adagrad apply launch, phase 1).
         rank_layout: (samples per rank, floats between the ranks' chunks) of `gsum` (_optimizer_descs).
-        Row-sparse Adam: no table owns a tile, and phase 1 is None unless weight decay left unreached ranges of g to restore — phase 0
-        then counts the steps itself; with them phase 1 runs in its no-table-moves form on all its workgroups (the ranges of a supernet
-        are millions of floats).  RMSprop: the same shape of launches (its rows rest too, owing only a decay); m is unused and the
-        slots of `tm` carry the stamps.  Adagrad on the tables (spec.table_kind): the same shape again; tv carries `table_state`, tm
-        nothing, and the tables' learning rate is lr * table_lr_scale in the kernel; row-wise Adagrad: tv carries `table_row_state`,
-        one float per row; on bf16 tables (table_kind "rowwise_adagrad_bf16") the same with the other table_algo and the rounding's seed
-        in tm[0]'s storage — constant from step to step: the kernel reads the step count on the device.  Row-wise Adam (table_kind
-        "rowwise_adam"): row-sparse Adam's launches under its own table_algo; tm carries exp_avg [rows, 16], tv exp_avg_sq [rows]."""
+        What differs between the tables' rules is read from spec.table_rule (optim_spec.TableRule).  A rows-only rule: no table owns a
+        tile, and phase 1 is None unless weight decay left unreached ranges of g to restore — phase 0 then counts the steps itself;
+        with them phase 1 runs in its no-table-moves form on all its workgroups (the ranges of a supernet are millions of floats).
+        RMSprop: m is unused and the slots of `tm` carry the stamps.  Adagrad on the tables: tv carries the rule's state array, tm
+        nothing (bf16 tables: the rounding's seed in tm[0]'s storage — constant from step to step: the kernel reads the step count on
+        the device).  Row-wise Adam: tm carries exp_avg [rows, 16], tv exp_avg_sq [rows]."""
         spec = t.spec
         st = self.moments
-        lazy = spec.rows_only  # (the tables move in the batch's rows only)
-        split, rowwise = spec.adagrad_tables, spec.table_rowwise
-        if spec.bf16_tables != self.tables_bf16:
+        rule = spec.table_rule
+        lazy = rule.rows_only  # (the tables move in the batch's rows only)
+        split = rule.state != "moments"  # (Adagrad's accumulators, table_state or table_row_state, stand in for the tables' moments)
+        if rule.bf16 != self.tables_bf16:
             raise L.EngineError("table_kind %r on %s tables" % (spec.table_kind, "bf16" if self.tables_bf16 else "fp32"))
         m = L.OptMomentsDesc()
         m.kind, m.phase = L.OP_OPT_MOMENTS, 0
         self._optim_scalars(m, spec)
         m.dense_blocks = min(2048, t.mom_chunks[1])
-        m.sparse_rows = int(bool(spec.sparse_rows))
+        m.sparse_rows, m.table_algo = int(bool(spec.sparse_rows)), rule.table_algo
         if split:
-            m.table_algo = L.TABLE_ALGO_ROWWISE_ADAGRAD_BF16 if spec.bf16_tables else L.TABLE_ALGO_ROWWISE_ADAGRAD if rowwise else L.TABLE_ALGO_ADAGRAD
             m.table_eps, m.table_lr_scale = spec.table_eps, spec.table_lr_scale
-        elif spec.rowwise_adam:
-            m.table_algo = L.TABLE_ALGO_ROWWISE_ADAM
         m.nblocks = self.WD_BLOCKS if (t.mom_tables or lazy) else 1  # (no table moves: phase 1 only counts the step and restores g)
         m.B, m.Fs = (Bg, self.Fs) if gsum is not None else (0, self.Fs)
         m.table_step0 = len(self.dense_names)
@@ -1075,14 +1060,14 @@ class SupernetEngine:
         self._tile_layout(m, lambda f: f in t.mom_tables and not lazy)  # (a table that does not move owns no tile)
         for f in range(self.Fs):
             if split:  # (Adagrad's accumulators; the kernel never looks at tm)
-                m.tv[f] = (self.table_row_state if rowwise else self.table_state)[f].data_ptr()
+                m.tv[f] = getattr(self, rule.state)[f].data_ptr()
                 continue
             m.tm[f] = first[1][f].data_ptr()
             if second is not None:
-                if second[1][f].dim() != (1 if spec.rowwise_adam else 2):  # (the kernel indexes tv by row or by element: never the other array)
+                if second[1][f].dim() != (1 if rule.rowwise else 2):  # (the kernel indexes tv by row or by element: never the other array)
                     raise L.EngineError("exp_avg_sq of table %d has shape %s under table_kind %r" % (f, tuple(second[1][f].shape), spec.table_kind))
                 m.tv[f] = second[1][f].data_ptr()
-        if spec.bf16_tables:
+        if rule.bf16:
             m.sr_seed = spec.table_seed  # (over tm[0], which the loop above left null)
         m.reg_mask = sum(1 << f for f in t.wd_tables) if spec.wd else 0
         m.bitmap = self._row_bitmap().data_ptr()

@@ -10,6 +10,33 @@ from typing import NamedTuple, Optional
 import torch
 
 
+class TableRule(NamedTuple):
+    """One rule for an embedding-table row of the fused step, stated once: OptimSpec.table_rule finds it, and the engine, the
+    data-parallel agreement check, the optimizer binding and the harness read it (its kernel-side twin: ROW_FORMS, csrc/optim_moments.hip)."""
+    phrase: str                    # the rule in messages
+    table_algo: Optional[int]      # NASREC_TABLE_ALGO_* of the NASREC_OP_OPT_MOMENTS descriptor; None = no such launch (Adagrad's apply launch)
+    kinds: tuple = ("adam",)       # the OptimSpec.kind values (the dense parameters' rule) it goes with
+    rows_only: bool = True         # the tables move in the batch's rows only
+    state: str = "moments"         # the engine attribute that keeps the tables' state: moments, table_state ([rows, 16]) or table_row_state ([rows])
+    rowwise: bool = False          # the second moment / the sum is ONE float per row, fed the mean of the row's squared gradient
+    first_moment: bool = False     # the tables keep a first moment (exp_avg / momentum_buffer)
+    bf16: bool = False             # the tables are STORED as bf16 (stochastic rounding under the seed that table_kind carries)
+    dp_code: int = 0               # what data-parallel ranks compare (utils/dist.table_rule_code): ranks that differ would drift
+
+
+TABLE_RULES = {  # (the four keys with a table_algo of their own are the values of OptimSpec.table_kind; bf16: in front of its ":<seed>")
+    "dense": TableRule("dense Adam / momentum SGD", 0, kinds=("adam", "sgd"), rows_only=False, first_moment=True),
+    "plain_adagrad": TableRule("Adagrad", None, kinds=("adagrad",), state="table_state"),
+    "row_sparse_adam": TableRule("row-sparse Adam", 0, first_moment=True, dp_code=1),  # (descriptor: sparse_rows = 1)
+    "lazy_rmsprop": TableRule("lazy RMSprop", 0, kinds=("rmsprop",)),
+    "adagrad": TableRule("Adagrad on the tables", 1, state="table_state", dp_code=2),
+    "rowwise_adagrad": TableRule("Adagrad on the tables", 3, state="table_row_state", rowwise=True, dp_code=3),
+    "rowwise_adagrad_bf16": TableRule("Adagrad on the tables", 4, state="table_row_state", rowwise=True, bf16=True, dp_code=4),
+    "rowwise_adam": TableRule("row-wise Adam", 5, rowwise=True, first_moment=True, dp_code=5),
+}
+_UNKNOWN_RULE = TableRule("an unknown table_kind", -1, kinds=(), rows_only=False, state="table_state", dp_code=-1)
+
+
 class OptimSpec(NamedTuple):
     kind: str               # "adagrad" | "adam" | "sgd" | "rmsprop" (with table_kind: the dense parameters' rule)
     beta1: float = 0.9      # Adam
@@ -21,15 +48,12 @@ class OptimSpec(NamedTuple):
     no_reg: Optional[str] = None
     sparse_rows: bool = False  # Adam: row-sparse on the tables (utils/optim.RowSparseAdam: torch.optim.SparseAdam on the batch's rows)
     alpha: float = 0.99     # RMSprop's smoothing constant (utils/optim.LazyRMSprop: momentum 0, not centered)
-    table_kind: str = ""    # "" = the tables take `kind`; "adagrad" (kind "adam": utils/optim.AdamAdagradTables) = torch.optim.Adagrad on
-                            # the tables, exactly row-sparse, with table_eps and the learning rate lr * table_lr_scale;
-                            # "rowwise_adagrad" (AdamAdagradTables(table_rowwise=True)) = the same with ONE accumulator per row, fed
-                            # the mean of the row's squared gradient; "rowwise_adagrad_bf16" / "rowwise_adagrad_bf16:<seed>"
-                            # (bf16_table_kind) = that rule on tables STORED as bf16 (SuperNet(table_dtype=torch.bfloat16)): computed
-                            # in fp32 on the widened row, stored with stochastic rounding (utils/optim.stochastic_round_bf16) under
-                            # the seed the value carries — `table_seed` reads it; no field of its own: tests pin the tuple's fields;
-                            # "rowwise_adam" (kind "adam": utils/optim.RowwiseSparseAdam) = row-sparse Adam on the tables with ONE
-                            # second moment per row, fed the mean of the row's squared gradient; table_eps and table_lr_scale unused
+    table_kind: str = ""    # "" = the tables take `kind`; else (kind "adam") a key of TABLE_RULES: "adagrad" / "rowwise_adagrad"
+                            # (utils/optim.AdamAdagradTables: torch.optim.Adagrad on the tables, exactly row-sparse, with table_eps and
+                            # the learning rate lr * table_lr_scale; row-wise: ONE accumulator per row), "rowwise_adagrad_bf16[:<seed>]"
+                            # (bf16_table_kind: that rule on tables STORED as bf16, rounded stochastically under the seed the value
+                            # carries — no field of its own: tests pin the tuple's fields), "rowwise_adam" (utils/optim.RowwiseSparseAdam:
+                            # row-sparse Adam with ONE second moment per row; table_eps and table_lr_scale unused)
     table_eps: float = 1e-2
     table_lr_scale: float = 1.0
     dwd: float = 0.0        # decoupled weight decay p <- p (1 - lr dwd) before the update (utils/optim.DecoupledWeightDecay,
@@ -38,37 +62,27 @@ class OptimSpec(NamedTuple):
     ema: float = 0.0        # decay of a weight average kept beside the step (utils/optim.WeightEMA, csrc/weight_ema.hip); 0 = none
 
     @property
+    def table_rule(self) -> TableRule:
+        """what the fused step does to a table row under this spec.  A table_kind that is no rule of the tables' own (only the bf16
+        rule takes a ":<seed>") gives _UNKNOWN_RULE, which goes with no dense rule: SupernetEngine._optim_scalars refuses it"""
+        if self.table_kind:
+            head = self.table_kind.partition(":")[0]
+            rule = TABLE_RULES.get(head if head == "rowwise_adagrad_bf16" else self.table_kind)
+            return rule if rule is not None and rule.table_algo else _UNKNOWN_RULE
+        if self.kind in ("adagrad", "rmsprop"):
+            return TABLE_RULES["plain_adagrad" if self.kind == "adagrad" else "lazy_rmsprop"]
+        return TABLE_RULES["row_sparse_adam" if self.sparse_rows else "dense"]
+
+    @property
     def moments(self) -> bool:
         """Adam / SGD / RMSprop: state in the engine's moment arrays and step counters (Adagrad: its accumulators)"""
-        return self.kind != "adagrad"
+        return self.kind != "adagrad"  # (the dense parameters' rule: no fact about the tables)
 
-    @property
-    def rows_only(self) -> bool:
-        """the tables move in the batch's rows only (a row outside it keeps its bits, or owes only a closed-form factor): Adagrad,
-        row-sparse Adam (with a second moment per element or per row), RMSprop and Adam with Adagrad (element- or row-wise) on the tables"""
-        return self.kind in ("adagrad", "rmsprop") or bool(self.sparse_rows) or \
-            self.table_kind in ("adagrad", "rowwise_adagrad", "rowwise_adam") or self.bf16_tables
-
-    @property
-    def table_rowwise(self) -> bool:
-        """the tables' accumulator / second moment is one float per row (row-wise Adagrad: the engine's table_row_state, whatever the
-        tables' storage type; row-wise Adam: the table arrays of the engine's exp_avg_sq)"""
-        return self.table_kind in ("rowwise_adagrad", "rowwise_adam") or self.bf16_tables
-
-    @property
-    def rowwise_adam(self) -> bool:
-        """row-sparse Adam on the tables with one second moment per row (utils/optim.RowwiseSparseAdam)"""
-        return self.table_kind == "rowwise_adam"
-
-    @property
-    def adagrad_tables(self) -> bool:
-        """the split optimizer: the tables' state is Adagrad's `sum` (table_state / table_row_state), not a moment array"""
-        return bool(self.table_kind) and not self.rowwise_adam
-
-    @property
-    def bf16_tables(self) -> bool:
-        """the rule of tables stored as bf16: the only one the fused step has for them"""
-        return self.table_kind.partition(":")[0] == "rowwise_adagrad_bf16"
+    rows_only = property(lambda self: self.table_rule.rows_only, doc="the tables move in the batch's rows only (a row outside it keeps its bits, or owes only a closed-form factor)")
+    table_rowwise = property(lambda self: self.table_rule.rowwise, doc="the tables' accumulator / second moment is one float per row")
+    rowwise_adam = property(lambda self: self.table_rule is TABLE_RULES["rowwise_adam"], doc="row-sparse Adam on the tables with one second moment per row (utils/optim.RowwiseSparseAdam)")
+    adagrad_tables = property(lambda self: bool(self.table_kind) and self.table_rule.state != "moments", doc="the split optimizer: the tables' state is Adagrad's `sum`, not a moment array")
+    bf16_tables = property(lambda self: self.table_rule.bf16, doc="the rule of tables stored as bf16: the only one the fused step has for them")
 
     @property
     def table_seed(self) -> int:

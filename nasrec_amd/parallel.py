@@ -583,7 +583,7 @@ class EngineDP:
 
         with torch.cuda.stream(eng.stream):
             base = self._tail = over(plan_tail, chunk_table or (None, 0))
-            if not spec.moments or spec.adagrad_tables:  # (Adagrad's table state: Adam / SGD keep theirs in engine.moments)
+            if spec.table_rule.state != "moments":  # (Adagrad's table state: Adam / SGD keep theirs in engine.moments)
                 eng._ensure_split_table_state(spec)
             prog = Program(eng._optimizer_descs(base, Bg, cat_all, sg_all, clip, eps, rank_layout=rank_layout))
             prog.opt_tail = base

@@ -959,14 +959,15 @@ class SuperNet(nn.Module):
         if last_layer:
             arrays = eng.ensure_last_layer_state(spec.kind)
             return [(params[n], {k: arrays[k][i] for k in spec.state_keys}, i) for i, n in enumerate(self._FINAL)], eng.ll_steps
-        eng.ensure_moments_state(spec.kind, tables=not spec.adagrad_tables, rowwise_v=spec.rowwise_adam)
-        if spec.adagrad_tables:  # (AdamAdagradTables: a table's state is Adagrad's sum, the engine's table_state or, row-wise, table_row_state;
-            eng._ensure_split_table_state(spec)  # its counter is the state's step)
-        table_sums = (eng.table_row_state if spec.table_rowwise else eng.table_state) if spec.adagrad_tables else None
+        rule = spec.table_rule
+        split = rule.state != "moments"  # (AdamAdagradTables: a table's state is Adagrad's sum — rule.state; its counter the state's step)
+        eng.ensure_moments_state(spec.kind, tables=not split, rowwise_v=spec.rowwise_adam)
+        if split:
+            eng._ensure_split_table_state(spec)
 
         def views(n):
-            if spec.adagrad_tables and n.startswith("_embedding."):
-                return {"sum": table_sums[int(n.split(".")[1])]}
+            if split and n.startswith("_embedding."):
+                return {"sum": getattr(eng, rule.state)[int(n.split(".")[1])]}
             return {k: eng.moments_view(k, n) for k in spec.state_keys}
         return [(p, views(n), eng.param_index[n]) for n, p in params.items() if n in eng.param_index], eng.opt_steps
 

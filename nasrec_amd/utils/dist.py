@@ -96,15 +96,9 @@ def replica_checksum(model) -> torch.Tensor:
 
 
 def table_rule_code(spec) -> int:
-    """the tables' rule of an OptimSpec (None = an optimizer the fused step does not reproduce) as the number the ranks compare:
-    0 = the tables take the optimizer's own dense rule, 1 = row-sparse Adam, 2 = Adagrad on the tables, 3 = row-wise Adagrad on them,
-    4 = row-wise Adagrad on bf16 tables (one process only: no data-parallel step runs it), 5 = row-wise Adam (row-sparse Adam with one
-    second moment per row: ranks that mix it with row-sparse Adam hold different state)"""
-    if spec is None:
-        return 0
-    if spec.table_kind:
-        return 4 if spec.bf16_tables else {"adagrad": 2, "rowwise_adagrad": 3, "rowwise_adam": 5}[spec.table_kind]
-    return int(bool(spec.sparse_rows))
+    """the tables' rule of an OptimSpec (None = an optimizer the fused step does not reproduce) as the number the ranks compare: 0 = the
+    tables take the dense rule; a rule that keeps other state or moves other rows has its own (TableRule.dp_code, optim_spec.py)"""
+    return 0 if spec is None else spec.table_rule.dp_code
 
 
 def assert_replicas_identical(model, optimizer=None):
