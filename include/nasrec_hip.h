@@ -90,7 +90,8 @@ enum {
   NASREC_OP_LAST_LAYER_STEP = 41,
   NASREC_OP_ROC_AUC = 42,
   NASREC_OP_WEIGHT_EMA = 43,
-  NASREC_OP_DECOUPLED_DECAY = 44
+  NASREC_OP_DECOUPLED_DECAY = 44,
+  NASREC_OP_COWCLIP = 45
 };
 
 /* algorithm of NASREC_OP_OPT_MOMENTS (ADAGRAD: NASREC_OP_LAST_LAYER_STEP only) */
@@ -842,6 +843,42 @@ typedef struct nasrec_decoupled_decay_desc {
   const float* lr;       /* device scalar, phase 1 */
   uint32_t* counter;     /* phases 1 and 2: the last arrival (zero before, left zero) */
 } nasrec_decoupled_decay_desc_t;
+
+/* ------------------------------------------------------------------------------------------------
+ * CowClip (Zheng et al., AAAI 2023; utils/optim.CowClip; DESIGN.md §4 "CowClip"): per-row adaptive gradient clipping of the embedding
+ * tables, a modifier in front of the optimizer.  For every table f and every row k that the batch touches with an in-range id, behind
+ * the global-norm clip and in front of every optimizer statement, in fp32:
+ *   sg = g[0]^2 + ... + g[15]^2     g = the row's summed gradient (the leader's row of gsum); the association of row_sum_of_squares
+ *   sw = w[0]^2 + ... + w[15]^2     w = the row's weights as the optimizer is about to read them; the same association
+ *   G  = coef * sqrtf(sg)           coef = the step's global clip coefficient (clip_head on `clip`: the optimizer's own bits)
+ *   T  = (float)cnt * fmaxf(r * sqrtf(sw), zeta)       cnt = the samples of the batch whose id in field f is k
+ *   if (G > T)  g[e] = g[e] * (T / G), e = 0 .. 15     else the row keeps its bits (a zero or NaN gradient is never clipped)
+ * The optimizer then multiplies by coef as it always did; the global norm stays the norm of the unclipped gradients.
+ * Appended WITHOUT a new nasrec_abi_version(), as NASREC_OP_DECOUPLED_DECAY was (a binding's layout check covers it).
+ *   phase 0 (count; depends on the ids only): one thread per (sample, field) pair adds 1 to cnt[f][row] (integer atomics: no value
+ *     depends on the order); ids outside [0, rows[f]) are skipped.  cnt[f]: rows[f] words, all zero before.
+ *   phase 1 (clip; behind the row dedup, in front of the optimizer's first launch that reads gsum): 4 lanes x float4 per pair, leaders
+ *     with an in-range id only.  A clipped row is scaled in place in gsum (one contiguous [B, Fs, 16] array), an unclipped row is not
+ *     stored; cnt[f][row] goes back to 0, so the scratch is all zero again after every step.  stat (optional): stat[0] += rows
+ *     touched, stat[1] += rows clipped.  Workgroup 0 writes clip.out as every clip_head does (the same values).
+ * Refused (-1, nothing launched): Fs outside [0, NASREC_MAX_TABLES], B < 0, idx / leader / gsum / cnt[f] / table[f] missing where
+ * the phase reads them, the clip's partials or out missing (phase 1), r < 0, zeta not > 0, a phase outside [0, 1].  B = 0: an empty
+ * launch that succeeds.  Same inputs -> same bits.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct nasrec_cowclip_desc {
+  int32_t kind;  /* NASREC_OP_COWCLIP */
+  int32_t phase; /* 0 count, 1 clip */
+  int32_t B, Fs; /* [B, Fs] id / leader arrays */
+  float r, zeta;
+  const int64_t* idx;    /* [B,Fs] */
+  const int32_t* leader; /* [B,Fs], phase 1 */
+  float* gsum;           /* [B,Fs,16], phase 1: a leader's row holds its sum */
+  const float* table[NASREC_MAX_TABLES]; /* phase 1 */
+  uint32_t* cnt[NASREC_MAX_TABLES];      /* [rows[f]] */
+  int64_t rows[NASREC_MAX_TABLES];
+  nasrec_clip_coef_desc_t clip; /* phase 1: a copy of the step's */
+  uint32_t* stat;               /* optional, phase 1: [2] rows touched, rows clipped */
+} nasrec_cowclip_desc_t;
 
 /* ------------------------------------------------------------------------------------------------
  * The row-sparse embedding backward in two halves (round 5).  NASREC_OP_EMB_DEDUP above does everything behind the backward pass;

@@ -48,6 +48,7 @@ LAST_LAYER_MAX = 8192  # NASREC_LAST_LAYER_MAX: K + 1 of NASREC_OP_LAST_LAYER_ST
 OP_ROC_AUC = 42
 OP_WEIGHT_EMA = 43
 OP_DECOUPLED_DECAY = 44
+OP_COWCLIP = 45  # per-row adaptive gradient clipping in front of the optimizer (utils/optim.CowClip), launched through nasrec_launch
 ROC_AUC_MAX_N = 1 << 30  # NASREC_ROC_AUC_MAX_N
 ROC_AUC_TOO_FEW, ROC_AUC_BAD_LABEL, ROC_AUC_NOT_FINITE, ROC_AUC_ONE_CLASS = 1, 2, 4, 8  # NASREC_ROC_AUC_* status bits
 
@@ -332,6 +333,11 @@ class DecoupledDecayDesc(C.Structure):
                 ("bitmap", vp), ("p", vp), ("chunks", vp), ("level", vp), ("lr", vp), ("counter", vp)]
 
 
+class CowClipDesc(C.Structure):
+    _fields_ = [("kind", i32), ("phase", i32), ("B", i32), ("Fs", i32), ("r", f32), ("zeta", f32), ("idx", vp), ("leader", vp), ("gsum", vp),
+                ("table", vp * MAX_TABLES), ("cnt", vp * MAX_TABLES), ("rows", i64 * MAX_TABLES), ("clip", ClipCoefDesc), ("stat", vp)]
+
+
 DESC_BY_KIND = {
     OP_GEMM: GemmDesc, OP_EMBED_GATHER: EmbedDesc, OP_DOT_TRI_FWD: DotTriDesc, OP_DOT_TRI_BWD: DotTriDesc, OP_FM_FWD: FmDesc,
     OP_FM_BWD: FmDesc, OP_MHA_FWD: MhaDesc, OP_MHA_BWD: MhaDesc, OP_REDUCE_ROWS: ReduceRowsDesc, OP_COPY_SEGS: CopySegsDesc,
@@ -343,6 +349,7 @@ DESC_BY_KIND = {
     OP_OPT_REDUCE2: OptReduce2Desc, OP_FINAL_FUSED: FinalDesc, OP_PERSIST: PersistDesc, OP_WORKLIST_DEV: WorklistDevDesc,
     OP_WEIGHT_DECAY: WeightDecayDesc, OP_OPT_MOMENTS: OptMomentsDesc, OP_LAST_LAYER_STEP: LastLayerStepDesc,
     OP_ROC_AUC: RocAucDesc, OP_WEIGHT_EMA: WeightEmaDesc, OP_DECOUPLED_DECAY: DecoupledDecayDesc,
+    OP_COWCLIP: CowClipDesc,
 }
 
 # every symbol include/nasrec_hip.h declares
@@ -405,8 +412,8 @@ def load():
     lib.nasrec_gemm_route.argtypes = [vp, C.POINTER(C.c_uint)]
     if lib.nasrec_abi_version() != 17:
         raise EngineError("ABI version mismatch: library %d, binding 17" % lib.nasrec_abi_version())
-    sizes = (i32 * 45)()
-    n = lib.nasrec_desc_sizes(sizes, 45)
+    sizes = (i32 * 46)()
+    n = lib.nasrec_desc_sizes(sizes, 46)
     for kind, cls in DESC_BY_KIND.items():
         if kind >= n or sizes[kind] != C.sizeof(cls):
             raise EngineError("struct layout mismatch for op kind %d: library %d bytes, binding %d bytes"

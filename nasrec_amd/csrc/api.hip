@@ -72,6 +72,7 @@ static int dispatch(hipStream_t st, const void* desc) {
     case NASREC_OP_ROC_AUC: return launch_roc_auc(st, (const nasrec_roc_auc_desc_t*)desc);
     case NASREC_OP_WEIGHT_EMA: return launch_weight_ema(st, (const nasrec_weight_ema_desc_t*)desc);
     case NASREC_OP_DECOUPLED_DECAY: return launch_decoupled_decay(st, (const nasrec_decoupled_decay_desc_t*)desc);
+    case NASREC_OP_COWCLIP: return launch_cowclip(st, (const nasrec_cowclip_desc_t*)desc);
     default: return nasrec_set_error(-1, "unknown op kind %d", kind);
   }
 }
@@ -266,6 +267,7 @@ int nasrec_desc_sizes(int32_t* out, int n) {
       (int32_t)sizeof(nasrec_roc_auc_desc_t),       // 42
       (int32_t)sizeof(nasrec_weight_ema_desc_t),    // 43
       (int32_t)sizeof(nasrec_decoupled_decay_desc_t), // 44
+      (int32_t)sizeof(nasrec_cowclip_desc_t),       // 45
   };
   const int total = (int)(sizeof(sizes) / sizeof(sizes[0]));
   int w = 0;

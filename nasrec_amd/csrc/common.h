@@ -144,3 +144,4 @@ int launch_last_layer_step(hipStream_t s, const nasrec_last_layer_step_desc_t* d
 int launch_roc_auc(hipStream_t s, const nasrec_roc_auc_desc_t* d);
 int launch_weight_ema(hipStream_t s, const nasrec_weight_ema_desc_t* d);
 int launch_decoupled_decay(hipStream_t s, const nasrec_decoupled_decay_desc_t* d);
+int launch_cowclip(hipStream_t s, const nasrec_cowclip_desc_t* d);

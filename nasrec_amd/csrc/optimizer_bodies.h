@@ -214,6 +214,22 @@ __device__ __forceinline__ void sparse_adam_elem(const D& d, float g, float& p, 
   sparse_adam_weight(m, den, p, step_size);
 }
 
+// The sum of the squares of a row's 16 gradient elements, in each of its four lanes (g4 = the lane's quarter); the callers scale it to
+// the mean (* 0.0625f: exact) in a statement of their own.  The sum over the four lanes goes into each of them (a + b is commutative:
+// the four totals have the same bits).  The quad is the aligned lanes 4k .. 4k + 3 of one wavefront, and its lanes arrive here
+// together or not at all: every branch in front of a call (pair < B * Fs, leader[pair], the row-range test) is a function of
+// `pair` = t >> 2 alone.  quad_perm reads inside the quad only, so the other quads of the wavefront may be inactive.  A branch on q in
+// front of a call would break it.
+__device__ __forceinline__ float row_sum_of_squares(const f32x4& g4) {
+  float sq = g4[0] * g4[0];
+  sq = fmaf(g4[1], g4[1], sq);
+  sq = fmaf(g4[2], g4[2], sq);
+  sq = fmaf(g4[3], g4[3], sq);
+  sq += dpp_mov<0xb1>(sq);  // quad_perm:[1,0,3,2]
+  sq += dpp_mov<0x4e>(sq);  // quad_perm:[2,3,0,1]
+  return sq;
+}
+
 // RMSprop's lazily decayed table rows: a row whose gradient was zero for n steps owes its square_avg the factor alpha^n; power and
 // product in fp64, rounded once (n = 0: v as it is, so a row touched every step has the bits of the dense statements)
 __device__ __forceinline__ float lazy_decay(float v, double alpha, long n) {

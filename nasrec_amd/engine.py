@@ -102,6 +102,7 @@ class OptimizerTail:
         self.chunk_tab, self.nchunks = chunks
         self.bufs = bufs if bufs is not None else TailBuffers()
         self.dedup_ids = None
+        self.cowclip = None  # (r, zeta) of a plan with CowClip in front of its optimizer (compile), else None
 
     def over(self, chunks, bufs):
         """this plan's optimizer and chunk tables over another dense chunk table and a data-parallel run's work buffers"""
@@ -433,16 +434,21 @@ class SupernetEngine:
     @_on_device
     def compile(self, choice, B: int, train: bool, clip: Optional[float] = 5.0, eps: float = 1e-2, graph: bool = False,
                 grad_scale: Optional[float] = None, defer_dw: bool = True, row_grad_out: Optional[torch.Tensor] = None,
-                local_optimizer: bool = True, spec: Optional[OptimSpec] = None) -> CompiledPlan:
+                local_optimizer: bool = True, spec: Optional[OptimSpec] = None, cowclip=None) -> CompiledPlan:
         """row_grad_out: storage [B * Fs * 16] the backward writes the per-sample embedding-row gradients into (a data-parallel step
         hands in the head of its all-gather send buffer: no copy between the backward and the exchange); local_optimizer = False: the
         plan gets no clip + Adagrad program of its own (a data-parallel step runs its optimizer over the GLOBAL batch).
         spec: the optimizer (nasrec_amd/optim_spec.py, OptimSpec.of); None = Adagrad with `eps`.  Weight decay adds get_l2_loss's
         gradient (_weight_decay_descs), Adam / SGD replace Adagrad (_moments_descs).  With local_optimizer = False the spec only shapes
         the plan's chunk tables (_weight_decay_tables, _moments_tables), which the data-parallel optimizer program reads
-        (parallel.EngineDP.dp_optimizer)"""
+        (parallel.EngineDP.dp_optimizer)
+        cowclip: (r, zeta) = CowClip on the summed table rows in front of the optimizer (_cowclip_descs), part of the plan's key: a
+        step with other values, or with none, is another plan"""
         rgo = row_grad_out.data_ptr() if row_grad_out is not None else None
         spec = spec if spec is not None else OptimSpec.of(eps)
+        if cowclip is not None:
+            cowclip = (float(cowclip[0]), float(cowclip[1]))
+            self._refuse_cowclip(spec, train, local_optimizer, B)
         if spec.wd and not train:
             raise L.EngineError("weight decay is part of the fused training step's optimizer: it needs train=True")
         if spec.moments and not train:
@@ -465,12 +471,12 @@ class SupernetEngine:
                 self._refuse_bf16_tables("the data-parallel step")
             if self.persist and self.level_schedule and self.cfg.fixed and B <= 256:
                 self._refuse_bf16_tables("the persistent step (NASREC_PERSIST_DEFAULT=1)")
-        fast = (id(choice), B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, spec)
+        fast = (id(choice), B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, spec, cowclip)
         hit = self._last_plan
         if self.cfg.fixed and hit is not None and hit[0] == fast and hit[1] is choice:  # fixed sub-network, same choice object: skip the JSON key
             return hit[2]
-        key = json.dumps([choice, B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, spec], sort_keys=True,
-                         default=_jsonable)
+        key = json.dumps([choice, B, train, clip, eps, graph, grad_scale, defer_dw, rgo, local_optimizer, spec] +
+                         ([list(cowclip)] if cowclip is not None else []), sort_keys=True, default=_jsonable)
         if key in self._plans:
             self._last_plan = (fast, choice, self._plans[key])
             return self._plans[key]
@@ -507,6 +513,7 @@ class SupernetEngine:
             cp = CompiledPlan()
             cp.arena, cp.evicted = arena, False
             cp.tail = OptimizerTail(spec, arena)
+            cp.tail.cowclip = cowclip
             ctx = P.Ctx(B, self.device, self.params, self.grads, shape_only=False, train=train)
             ctx.sk_workspace = self._sk_workspace
             ctx.matmul_precision = L.PRECISION_BY_NAME[self.matmul_precision]
@@ -1250,7 +1257,64 @@ class SupernetEngine:
             # decoupled weight decay (csrc/decoupled_decay.hip): torch's order — the L2 term's gradient of the weights as they were,
             # then p (1 - lr lambda), then the update
             dec1 = self._decay_step_descs(t, Bg, rows, cat_x, b.leader)
-        return reduce + ema0 + ([wd0] if wd0 is not None else []) + dec1 + apply + ([phase1] if phase1 is not None else []) + ema1
+        cw0, cw1 = [], []
+        if rows and t.cowclip is not None:
+            # CowClip (csrc/cowclip.hip): the ids are counted beside the reduce stage; the leaders' summed rows are scaled directly in
+            # front of the apply stage, behind the decoupled decay, whose launch has paid a touched row's debt: current weights
+            if rank_layout:
+                raise L.EngineError("cowclip: the summed rows of a data-parallel step lie in a rank layout, and the counts would have to be global")
+            cw0, cw1 = self._cowclip_descs(t, Bg, cat_x, b.leader, gsum, app.clip)
+        return cw0 + reduce + ema0 + ([wd0] if wd0 is not None else []) + dec1 + cw1 + apply + ([phase1] if phase1 is not None else []) + ema1
+
+    def _refuse_cowclip(self, spec, train=True, local_optimizer=True, B=0):
+        """what a plan with CowClip (`cowclip`, the harness's --cowclip) is not built for: refused by name, never routed elsewhere"""
+        if not train:
+            raise L.EngineError("cowclip is part of the fused training step's optimizer: it needs train=True")
+        if self.host_embedding:
+            raise L.EngineError("cowclip in the fused step needs the embedding tables on the device (place_embedding_on_cpu keeps them "
+                                "on the host): CowClip.apply() on the torch route is the dense form")
+        if self.tables_bf16:
+            self._refuse_bf16_tables("cowclip (it reads fp32 table rows)")
+        if not local_optimizer:
+            raise L.EngineError("cowclip covers the one-process step: under data parallelism the counts would have to be global")
+        if spec.wd and P.regularised(self.shapes, spec.no_reg)[1]:
+            raise L.EngineError("cowclip with an L2 term on the embedding tables: the term's 2 wd W would be clipped with the gradient "
+                                "(no_reg_param_name='_embedding' leaves the tables out)")
+        if self.persist and self.level_schedule and self.cfg.fixed and B <= 256:
+            raise L.EngineError("cowclip is not built into the persistent step (NASREC_PERSIST_DEFAULT=1): the default launches take it")
+
+    def ensure_cowclip_state(self):
+        """CowClip's scratch: cowclip_cnt[f], one uint32 word per row of table f (4 bytes x the rows of all tables: 135 MB at Criteo
+        size), zero-filled once — the clip launch leaves it all zero after every step; cowclip_stat, two words: rows touched, rows
+        clipped since construction."""
+        if getattr(self, "cowclip_cnt", None) is not None:
+            return
+        with torch.cuda.stream(self.stream):
+            self.cowclip_cnt = [torch.zeros(n, dtype=torch.int32, device=self.device) for n in self.num_embeddings]
+            self.cowclip_stat = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self.stream.synchronize()
+
+    def cowclip_stats(self):
+        """(rows touched, rows clipped) by the fused steps with CowClip since construction (waits for the device)"""
+        if getattr(self, "cowclip_stat", None) is None:
+            return 0, 0
+        a = self.cowclip_stat.tolist()
+        return int(a[0]) & 0xFFFFFFFF, int(a[1]) & 0xFFFFFFFF
+
+    def _cowclip_descs(self, t, Bg, cat_x, leader, gsum, clip_desc):
+        """([count], [clip]): the two NASREC_OP_COWCLIP launches of a plan with t.cowclip over the contiguous [Bg, Fs, 16] `gsum`"""
+        self.ensure_cowclip_state()
+        c = L.CowClipDesc()
+        c.kind, c.phase, c.B, c.Fs = L.OP_COWCLIP, 0, Bg, self.Fs
+        c.r, c.zeta = t.cowclip
+        c.idx, c.leader, c.gsum = cat_x.data_ptr(), leader.data_ptr(), gsum
+        for f in range(self.Fs):
+            c.table[f], c.cnt[f], c.rows[f] = self.tables[f].data_ptr(), self.cowclip_cnt[f].data_ptr(), self.num_embeddings[f]
+        c.clip = clip_desc
+        c.stat = self.cowclip_stat.data_ptr()
+        c1 = L.CowClipDesc.from_buffer_copy(c)
+        c1.phase = 1
+        return [c], [c1]
 
     DECAY_DENSE_BLOCKS = 1024  # workgroups on the dense ranges (EMA_DENSE_BLOCKS: the same stream)
     DECAY_REBASE = 1.0         # -level at which a step flushes first: a stamp's quantisation (|L| 2^-24) stays below one rounding of a weight
@@ -1643,7 +1707,7 @@ class SupernetEngine:
     @_on_device
     def train_step(self, int_x, cat_x, y, lr: float, choice=None, clip: Optional[float] = 5.0, eps: float = 1e-2, graph: Optional[bool] = False,
                    staged: bool = False, weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None, ema: float = 0.0,
-                   decoupled_wd: float = 0.0):
+                   decoupled_wd: float = 0.0, cowclip=None):
         """zero_grad -> forward -> BCE -> backward -> clip_grad_norm_ -> Adagrad (train_utils.py:262-286).
         Returns the (device) loss tensor of this step.  `staged`: inputs are already in the plan's static buffers.  graph: True = replay
         the captured step, False = launch its program, None = whichever is faster for this plan (prefers_graph).
@@ -1659,7 +1723,10 @@ class SupernetEngine:
         DecoupledWeightDecay; csrc/decoupled_decay.hip) over the parameters get_l2_loss's rule selects (no_reg_param_name) and the
         step reaches: two more launches, the table rows outside the batch rest and owe — a raw read of a table needs
         flush_decay_rows() first.  Refused where the tables move outside the batch's rows, and, when it reaches the tables, beside a
-        weight average or an L2 term on them."""
+        weight average or an L2 term on them.
+        cowclip: (r, zeta) = CowClip (utils/optim.CowClip; csrc/cowclip.hip) on the batch's summed table rows, behind the global clip
+        and in front of every optimizer statement: two more launches, whatever rule the tables take.  Refused on bf16 tables, beside
+        an L2 term on the tables and in the persistent form; cowclip_stats() counts the rows it touched and clipped."""
         self._refuse_swapped("train_step")
         if decoupled_wd:
             if optim is not None and not optim.rows_only:
@@ -1683,7 +1750,8 @@ class SupernetEngine:
         else:  # pre-staged inputs: the batch size is the one of the plan they were staged into
             assert staged and self._last_plan is not None, "train_step without inputs needs a previously compiled plan holding them"
             B = int(self._last_plan[2].cat_x.shape[0])
-        cp = self.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, spec=OptimSpec.of(eps, weight_decay, no_reg_param_name, optim, ema, decoupled_wd))
+        cp = self.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, spec=OptimSpec.of(eps, weight_decay, no_reg_param_name, optim, ema, decoupled_wd),
+                          cowclip=cowclip)
         sp = self._sp()
         dec0 = None
         if cp.tail.spec.dwd:

@@ -22,8 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from nasrec_amd.main_train import (TABLE_DTYPES, _num_embedding_dict, _num_sparse_inputs_dict, add_table_dtype_flags,  # noqa: E402
-                                   build_lr_scheduler, build_optimizer, check_table_dtype)
+from nasrec_amd.main_train import (TABLE_DTYPES, _num_embedding_dict, _num_sparse_inputs_dict, add_cowclip_flag, add_table_dtype_flags,  # noqa: E402
+                                   build_cowclip, build_lr_scheduler, build_optimizer, check_cowclip, check_table_dtype)
 from nasrec_amd.supernet.supernet import SuperNet, ops_config_lib  # noqa: E402
 from nasrec_amd.utils.data_pipes import make_loaders  # noqa: E402
 from nasrec_amd.utils.io_utils import create_dir, dump_pickle_data, load_pickle_data  # noqa: E402
@@ -50,13 +50,14 @@ def train_and_eval_one_model(model, args):
     # (the warm-up shrinks with the number of epochs here — :134 — unlike main_train.py)
     lr_scheduler = build_lr_scheduler(args.lr_schedule, optimizer, steps_per_epoch * args.num_epochs, steps_per_epoch // 10 // args.num_epochs,
                                       args.learning_rate)
+    cowclip = build_cowclip(args, model)
     epoch_logs = []
     for epoch in range(args.num_epochs):
         logs = train_and_test_one_epoch(
             model, epoch, optimizer, lr_scheduler, train_loader, test_loader, loss_fn,
             L2Loss(args.wd, args.no_reg_param_name, gpu=args.gpu), args.train_batch_size, args.gpu,
             test_interval=args.test_interval, max_train_steps=steps_per_epoch if args.max_train_steps == -1 else args.max_train_steps,
-            max_eval_steps=args.max_eval_steps, test_only_at_last_step=True, grad_clip_value=5.0)
+            max_eval_steps=args.max_eval_steps, test_only_at_last_step=True, grad_clip_value=5.0, cowclip=cowclip)
         logs["flops(M)"], logs["Params(M)"] = flops / 1e6, params / 1e6
         epoch_logs.append(logs)
     return epoch_logs
@@ -64,6 +65,7 @@ def train_and_eval_one_model(model, args):
 
 def main(args):
     check_table_dtype(args)
+    check_cowclip(args)
     print("Matmul precision: {}".format(args.matmul_precision))
     np.random.seed(args.random_seed)  # the candidates come from the global stream (supernet.py `fixed-path`)
     if args.choice_from_pickle_file is not None:
@@ -135,6 +137,7 @@ def build_parser():
                    help="--optimizer adam-adagrad-tables: row-wise Adagrad on the tables — one accumulator per embedding row, fed the "
                         "mean of the row's squared gradient (1/16 of the element-wise state); refused with any other --optimizer")
     add_table_dtype_flags(p)
+    add_cowclip_flag(p)
     p.add_argument("--loss_function", type=str, default="bce", choices=["bce"])
     p.add_argument("--gpu", type=int, default=0, help="GPU ID to use.")
     p.add_argument("--matmul-precision", dest="matmul_precision", type=str, default="highest", choices=["highest", "high", "medium"],

@@ -79,6 +79,51 @@ def check_table_dtype(args, world: int = 1, use_amp: bool = False, last_layer: b
         raise ValueError(head + "with the last-layer fine-tune mode: its fused step and its torch route both take fp32 tables")
 
 
+def _cowclip(text):
+    from nasrec_amd.utils.optim import parse_cowclip
+    try:
+        return parse_cowclip(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def add_cowclip_flag(p):
+    p.add_argument("--cowclip", type=_cowclip, default=None, metavar="R[,ZETA]",
+                   help="CowClip (Zheng et al., AAAI 2023), absent = off: behind the global clip every embedding row the batch touches has "
+                        "its summed gradient held to cnt * max(R * |w|, ZETA), cnt = how often its id occurs in the batch (ZETA defaults "
+                        "to 1e-5; utils/optim.CowClip) - what a large --train_batch_size needs.  Inside the fused step under every "
+                        "--optimizer, by CowClip.apply() on the torch route; one process, whole fp32 tables, no --wd on the tables")
+
+
+def check_cowclip(args, world: int = 1, last_layer: bool = False):
+    """--cowclip at start-up, from the flags alone: what CowClip is not built for is a ValueError that names the flag
+    (train_utils.refuse_cowclip asks the model and the optimizer the same questions before the first step)"""
+    if getattr(args, "cowclip", None) is None:
+        return
+    head = "--cowclip "
+    if getattr(args, "table_dtype", "fp32") == "bf16":
+        raise ValueError(head + "with --table-dtype bf16: CowClip reads fp32 table rows; not built for bf16 tables")
+    if args.wd:
+        from nasrec_amd.optim_spec import regularises_tables
+        if regularises_tables(args.wd, args.no_reg_param_name):
+            raise ValueError(head + "with --wd %r reaching the embedding tables: the L2 term's 2 wd W would be clipped with the gradient "
+                             "(--no-reg-param-name _embedding leaves the tables out, or --wd 0)" % (args.wd,))
+    if getattr(args, "table_sharding", "none") == "row":
+        raise ValueError(head + "with --table-sharding row: a row-sharded table holds one rank's rows; CowClip needs whole tables")
+    if world > 1:
+        raise ValueError(head + "with a world size of %d: the ids' counts would have to be global; one process" % world)
+    if last_layer:
+        raise ValueError(head + "with the last-layer fine-tune mode: the tables are frozen there, nothing to clip")
+
+
+def build_cowclip(args, model):
+    """the CowClip helper of a run with --cowclip (over the model's tables), or None"""
+    if getattr(args, "cowclip", None) is None:
+        return None
+    from nasrec_amd.utils.optim import CowClip
+    return CowClip(list(model._embedding.parameters()), *args.cowclip)
+
+
 def add_table_dtype_flags(p):
     p.add_argument("--table-dtype", dest="table_dtype", type=str, default="fp32", choices=sorted(TABLE_DTYPES),
                    help="storage type of the embedding tables (SuperNet(table_dtype=...)): bf16 halves their memory and their checkpoint; "
@@ -165,6 +210,7 @@ def train_and_eval_one_model(model, args):
     if args.decoupled_wd > 0:
         from nasrec_amd.utils.optim import DecoupledWeightDecay
         decay = DecoupledWeightDecay(model, args.decoupled_wd, args.no_reg_param_name)
+    cowclip = build_cowclip(args, model)
     print(model)
     create_dir(args.logging_dir)
     with open(os.path.join(args.logging_dir, "configs_args.json"), "w") as f:
@@ -176,7 +222,7 @@ def train_and_eval_one_model(model, args):
             model, epoch, optimizer, lr_scheduler, train_loader, test_loader, loss_fn, l2_loss_fn, args.train_batch_size, args.gpu,
             display_interval=args.display_interval, test_interval=args.test_interval if epoch != 1 else 100,
             max_train_steps=steps_per_epoch if epoch != 1 else 1000, test_only_at_last_step=(args.test_only_at_last_step) == 1,
-            tb_writer=writer, use_amp=False, grad_clip_value=5.0, ema=ema, decay=decay)
+            tb_writer=writer, use_amp=False, grad_clip_value=5.0, ema=ema, decay=decay, cowclip=cowclip)
         epoch_logs.append(logs)
     print("Dumping logs to {}!".format(args.logging_dir))
     from nasrec_amd.utils.dist import world_info
@@ -212,6 +258,7 @@ def main(args):
     from nasrec_amd.utils.dist import init_from_env
     rank, world = init_from_env(args)  # torchrun: one process per GPU, args.gpu = the local rank
     check_table_dtype(args, world=world)
+    check_cowclip(args, world=world)
     create_dir(args.logging_dir)
     print("Matmul precision: {}".format(args.matmul_precision))
     model = get_model(args).to(args.gpu)
@@ -280,6 +327,7 @@ def build_parser():
                         "parameters --wd would regularise (>= 2 dimensions, --no-reg-param-name left out) that have a gradient "
                         "(utils/optim.DecoupledWeightDecay).  Independent of --wd.  Inside the fused step with --optimizer adagrad / "
                         "row-sparse-adam / rowwise-adam / rmsprop / adam-adagrad-tables (embedding rows outside the batch pay lazily), on the torch route otherwise")
+    add_cowclip_flag(p)
     p.add_argument("--gpu", type=int, default=None, help="GPU ID to use.")
     # not a reference flag: placement of the embedding tables under torchrun (nasrec_amd/sharded_tables.py)
     p.add_argument("--table-sharding", dest="table_sharding", type=str, default="none", choices=["none", "row"],

@@ -287,6 +287,17 @@ def desc_io(d, part="whole") -> Tuple[List[Acc], List[Acc]]:
         W += [_flat(d.leader, d.B * d.Fs), _flat(d.order, d.Fs * d.cap), _flat(d.lists, d.Fs * d.cap), _flat(d.counts, d.Fs * 2)]
         if d.heads:
             W.append(_flat(d.heads, d.Fs * d.cap))
+    elif k == L.OP_COWCLIP:  # phase 0: ids in, counts out; phase 1: ids, leaders, table rows, the clip partials and counts in; gsum, counts, stat out
+        both = [(d.cnt[f], d.rows[f]) for f in range(d.Fs)]  # (an atomic add reads what it writes: two count launches stay in program order)
+        ins = [(d.idx, d.B * d.Fs * 2)]
+        outs = []
+        if d.phase == 1:
+            ins += [(d.leader, d.B * d.Fs), (d.clip.partial_a, d.clip.n_a), (d.clip.partial_b, d.clip.n_b)]
+            ins += [(d.table[f], d.rows[f] * E) for f in range(d.Fs)]
+            both += [(d.gsum, d.B * d.Fs * E), (d.stat, 2)]
+            outs.append((d.clip.out, 2))
+        R += [_flat(p, n) for p, n in ins + both if p]
+        W += [_flat(p, n) for p, n in outs + both if p]
     elif k == L.OP_MEMSET and not d.chunks:
         W.append(_flat(d.ptr, (d.bytes + 3) // 4))
     else:

@@ -676,7 +676,7 @@ class SuperNet(nn.Module):
 
     def engine_train_step(self, int_feats, cat_feats, y, lr: float, clip: Optional[float] = 5.0, eps: float = 1e-2, graph=None,
                           weight_decay: float = 0.0, no_reg_param_name: Optional[str] = None, optim=None, ema_decay: float = 0.0,
-                          decoupled_wd: float = 0.0):
+                          decoupled_wd: float = 0.0, cowclip=None):
         """Fused step on the engine (forward, BCE, backward, clip_grad_norm_, Adagrad with row-sparse table update):
         the counterpart of train_utils.py:262-286 for optimizer == Adagrad (torch's own weight_decay == 0).  weight_decay != 0: the loss
         is BCE + get_l2_loss(self, weight_decay, no_reg_param_name) — every regularised parameter and every table row is decayed
@@ -694,11 +694,23 @@ class SuperNet(nn.Module):
         rests and pays the factors it missed when it is next in a batch or read.  Same conditions as ema_decay, and, when the decay
         reaches the tables, neither ema_decay nor an L2 term on the tables.  Between fused steps `_embedding.<f>.weight` holds rows that
         still owe: a RAW read of it needs engine_flush_decay() first.  forward (outside this step), state_dict,
-        engine_sync_optimizer_steps and a bound DecoupledWeightDecay's apply (engine_bind_decay) flush by themselves."""
+        engine_sync_optimizer_steps and a bound DecoupledWeightDecay's apply (engine_bind_decay) flush by themselves.
+        cowclip = (r, zeta): utils/optim.CowClip's apply(cat_feats) in front of the update, in the engine (csrc/cowclip.hip): the batch's
+        summed table rows are held to cnt max(r ||w||, zeta) behind the global clip, under every optimizer.  One process, whole fp32
+        tables on the device, no L2 term on the tables; engine_cowclip_stats() counts the rows touched and clipped."""
         if self._place_embedding_on_cpu:
             from .._lib import EngineError
             raise EngineError("engine_train_step needs the tables on the device; with place_embedding_on_cpu use forward / backward "
                               "and a torch optimizer")
+        if cowclip is not None:
+            import torch.distributed as dist
+            from .._lib import EngineError
+            if self._table_sharding == "row":
+                raise EngineError("cowclip in the fused step needs whole tables: row-sharded tables hold one rank's rows (CowClip.apply() "
+                                  "on the torch route needs whole tables too)")
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                raise EngineError("cowclip in the fused step covers one process: under data parallelism the counts would have to be global")
+            cowclip = (float(cowclip[0]), float(cowclip[1]))
         if ema_decay or decoupled_wd:
             import torch.distributed as dist
             if self._table_sharding == "row" or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
@@ -720,6 +732,7 @@ class SuperNet(nn.Module):
         from ..optim_spec import OptimSpec
         spec = OptimSpec.of(eps, weight_decay, no_reg_param_name, optim, ema_decay, decoupled_wd)
         d["_last_step_key"] = (choice, clip, eps, graph, spec)
+        d["_last_step_cowclip"] = cowclip
         d["_last_step_last_layer"] = False
         opt_kw = {}
         if spec.wd or spec.moments:
@@ -728,9 +741,11 @@ class SuperNet(nn.Module):
                 raise EngineError("weight decay, Adam and SGD in the fused step need whole tables: row-sharded tables train them "
                                   "through the torch route")
             opt_kw = dict(weight_decay=spec.wd, no_reg_param_name=spec.no_reg, optim=optim)
+        if cowclip is not None:  # (refused above for row-sharded tables and several ranks: from here on the one-process step)
+            opt_kw = dict(opt_kw, cowclip=cowclip)
         if spec.dwd:
             return self._engine.train_step(int_feats, cat_feats, y, lr, choice, clip, eps, graph=graph, ema=spec.ema, weight_decay=spec.wd,
-                                           no_reg_param_name=spec.no_reg, optim=optim, decoupled_wd=spec.dwd)
+                                           no_reg_param_name=spec.no_reg, optim=optim, decoupled_wd=spec.dwd, cowclip=cowclip)
         if spec.ema:
             return self._engine.train_step(int_feats, cat_feats, y, lr, choice, clip, eps, graph=graph, ema=spec.ema, **opt_kw)
         if self._table_sharding == "row":
@@ -797,7 +812,7 @@ class SuperNet(nn.Module):
         dp = self.__dict__.get("_dp_step")
         if dp is not None and dp[1].exchange:
             return dp[1].last_plan().logits.view(B, 1)
-        cp = self._engine.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, spec=spec)
+        cp = self._engine.compile(choice, B, train=True, clip=clip, eps=eps, graph=graph, spec=spec, cowclip=self.__dict__.get("_last_step_cowclip"))
         return cp.logits.view(B, 1)
 
     def engine_last_l2(self):
@@ -920,6 +935,11 @@ class SuperNet(nn.Module):
         eng = self.__dict__.get("_engine")
         if eng is not None and eng._decay_dirty:
             eng.flush_decay_rows()
+
+    def engine_cowclip_stats(self):
+        """(rows touched, rows clipped) by the fused steps with `cowclip=` since the engine was built (waits for the device)"""
+        eng = self.__dict__.get("_engine")
+        return eng.cowclip_stats() if eng is not None else (0, 0)
 
     def engine_bind_decay(self, decay):
         """Give a DecoupledWeightDecay (utils/optim.py) the engine's flush as its hook: a torch-route `apply()` in the middle of a fused

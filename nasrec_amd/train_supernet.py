@@ -14,8 +14,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from nasrec_amd.main_train import (TABLE_DTYPES, _decoupled_wd, _num_embedding_dict, _num_sparse_inputs_dict, add_table_dtype_flags,  # noqa: E402
-                                   build_lr_scheduler, build_optimizer, check_table_dtype, summary_writer)
+from nasrec_amd.main_train import (TABLE_DTYPES, _decoupled_wd, _num_embedding_dict, _num_sparse_inputs_dict, add_cowclip_flag,  # noqa: E402
+                                   add_table_dtype_flags, build_cowclip, build_lr_scheduler, build_optimizer, check_cowclip, check_table_dtype,
+                                   summary_writer)
 from nasrec_amd.supernet.supernet import SuperNet, ops_config_lib  # noqa: E402
 from nasrec_amd.utils.data_pipes import make_loaders  # noqa: E402
 from nasrec_amd.utils.io_utils import create_dir, dump_pickle_data, load_model_checkpoint, load_optimizer_state, save_model_checkpoint  # noqa: E402
@@ -55,6 +56,7 @@ def train_and_eval_one_model(model, args):
     if args.decoupled_wd > 0:
         from nasrec_amd.utils.optim import DecoupledWeightDecay
         decay = DecoupledWeightDecay(model, args.decoupled_wd, args.no_reg_param_name)
+    cowclip = build_cowclip(args, model)
     print(model)
     strategy_name = args.strategy if args.strategy == "single-path" else args.strategy + "-" + args.anypath_choice
     logging_dir = os.path.join(args.logging_dir, "supernet_{}blocks_layernorm{:d}_{}_lr{:.2f}_supernetwarmup_{}".format(
@@ -67,7 +69,7 @@ def train_and_eval_one_model(model, args):
         logs = train_and_test_one_epoch(
             model, epoch, optimizer, lr_scheduler, train_loader, test_loader, loss_fn, l2_loss_fn, args.train_batch_size, args.gpu,
             display_interval=args.display_interval, test_interval=args.test_interval, max_train_steps=steps_per_epoch,
-            test_only_at_last_step=True, grad_clip_value=5.0, tb_writer=writer, decay=decay)
+            test_only_at_last_step=True, grad_clip_value=5.0, tb_writer=writer, decay=decay, cowclip=cowclip)
         epoch_logs.append(logs)
     print("Dumping logs to {}!".format(logging_dir))
     from nasrec_amd.utils.dist import world_info
@@ -83,6 +85,7 @@ def main(args):
     from nasrec_amd.utils.dist import init_from_env
     rank, world = init_from_env(args)  # torchrun: one process per GPU, args.gpu = the local rank; same path seed on every rank
     check_table_dtype(args, world=world)
+    check_cowclip(args, world=world)
     print("Matmul precision: {}".format(args.matmul_precision))
     model = SuperNet(sparse_input_size=_num_sparse_inputs_dict[args.dataset], num_blocks=args.num_blocks,
                      ops_config=ops_config_lib[args.config], use_layernorm=(args.use_layernorm == 1), activation="relu",
@@ -125,6 +128,7 @@ def build_parser():
     p.add_argument("--decoupled-wd", dest="decoupled_wd", type=_decoupled_wd, default=0.0,
                    help="decoupled weight decay (the W of AdamW), 0 = off: before every optimizer step w *= 1 - lr * LAMBDA on the parameters "
                         "--wd would regularise that have a gradient (utils/optim.DecoupledWeightDecay; main_train.py --decoupled-wd)")
+    add_cowclip_flag(p)
     p.add_argument("--loss_function", type=str, default="bce", choices=["bce"])
     p.add_argument("--optimizer", type=str, default="adagrad", choices=["adagrad", "sgd", "adam", "row-sparse-adam", "rowwise-adam", "rmsprop", "adam-adagrad-tables", "ds-optimizer"])
     p.add_argument("--table-lr-scale", dest="table_lr_scale", type=float, default=1.0,

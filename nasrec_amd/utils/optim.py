@@ -539,3 +539,81 @@ class DecoupledWeightDecay:
         for _, p in self.selected():
             if p.grad is not None:
                 p.mul_(1 - lr * self.weight_decay)
+
+
+def parse_cowclip(text):
+    """`--cowclip R[,ZETA]` -> (r, zeta), or None for an absent flag (None / ""); ZETA defaults to 1e-5.  r >= 0 and zeta > 0, both
+    finite: anything else is a ValueError that names the flag."""
+    if text is None or text == "":
+        return None
+    if isinstance(text, (tuple, list)):
+        parts = [str(v) for v in text]
+    else:
+        parts = str(text).split(",")
+    try:
+        if not 1 <= len(parts) <= 2:
+            raise ValueError
+        r = float(parts[0])
+        zeta = float(parts[1]) if len(parts) == 2 else 1e-5
+    except ValueError:
+        raise ValueError("--cowclip takes R or R,ZETA (two numbers), got %r" % (text,)) from None
+    if not (math.isfinite(r) and r >= 0.0):
+        raise ValueError("--cowclip: R = %r must be a finite number >= 0" % (r,))
+    if not (math.isfinite(zeta) and zeta > 0.0):
+        raise ValueError("--cowclip: ZETA = %r must be a finite number > 0" % (zeta,))
+    return r, zeta
+
+
+class CowClip:
+    """`--cowclip R[,ZETA]`: CowClip (Zheng et al., "CowClip: Reducing CTR Prediction Model Training Time from 12 hours to 10 minutes on
+    1 GPU", AAAI 2023), per-row adaptive gradient clipping of the embedding tables — what lets the batch grow: a frequent id receives
+    the sum of many per-sample gradients, a rare id one, and a single global clip cannot serve both.
+
+    `apply(cat_x)`, called after `clip_grad_norm_` and `DecoupledWeightDecay.apply`, before `optimizer.step()` (beside
+    `optimizer.touch(cat_x)`), rescales rows of the tables' dense `.grad` (which already carries the global clip coefficient).  For
+    table f and every in-range id k of column f of the batch, with cnt = how often k occurs there, in fp32:
+
+        G = sqrt(sum(grad[k]^2));  T = cnt * max(r * sqrt(sum(w[k]^2)), zeta);  if G > T: grad[k] *= T / G
+
+    A zero or NaN gradient row is never clipped (the comparison is false), ids outside the table are skipped, no other row is read or
+    written.  No state beyond two counters (rows touched, rows clipped): nothing goes into a checkpoint.
+
+    This is the definition the fused engine step is held to (SuperNet.engine_train_step(..., cowclip=(r, zeta)); csrc/cowclip.hip),
+    which scales the summed gradient rows in front of the optimizer's launch, whatever rule the tables take."""
+
+    def __init__(self, tables: Iterable[torch.Tensor], r: float = 1.0, zeta: float = 1e-5):
+        self.r, self.zeta = parse_cowclip((r, zeta))
+        self.tables = list(tables)
+        self.touched = self.clipped = 0
+
+    def rows(self, cat_x: torch.Tensor, f: int):
+        """(unique in-range ids of column f, their counts)"""
+        ids = cat_x[:, f].detach().long()
+        ids = ids[(ids >= 0) & (ids < self.tables[f].shape[0])]
+        return torch.unique(ids, return_counts=True)
+
+    @torch.no_grad()
+    def apply(self, cat_x: torch.Tensor):
+        """-> (rows touched, rows clipped) of this batch; a table whose grad is None (a backward that stops short of the stem) is skipped"""
+        if cat_x.dim() != 2 or cat_x.shape[1] != len(self.tables):
+            raise ValueError("CowClip.apply: ids of shape [B, %d] expected, got %s" % (len(self.tables), tuple(cat_x.shape)))
+        touched = clipped = 0
+        for f, w in enumerate(self.tables):
+            if w.grad is None:
+                continue
+            ids, cnt = self.rows(cat_x.to(w.device), f)
+            if not ids.numel():
+                continue
+            g = w.grad[ids].float()
+            G = g.square().sum(1).sqrt()
+            T = cnt.float() * torch.fmax(self.r * w[ids].float().square().sum(1).sqrt(), torch.tensor(self.zeta, dtype=torch.float32, device=w.device))
+            clip = G > T
+            scale = torch.where(clip, T / G, torch.ones_like(G))
+            sel = ids[clip]
+            if sel.numel():
+                w.grad[sel] = (g[clip] * scale[clip, None]).to(w.grad.dtype)
+            touched += int(ids.numel())
+            clipped += int(clip.sum())
+        self.touched += touched
+        self.clipped += clipped
+        return touched, clipped

@@ -15,6 +15,7 @@ Not available in this environment: fvcore and tensorboard.  FLOPs are counted an
 operators), the TensorBoard writer is optional (None disables it)."""
 import contextlib
 import copy
+import os
 import time
 from typing import Any, Optional, Union
 
@@ -308,6 +309,44 @@ def _announce_rowwise_adam_route(model, optimizer, l2_loss_fn, use_amp, fused, s
     print(head + ": torch route, RowwiseSparseAdam.step() on the rows of touch() ({}).".format(why))
 
 
+def refuse_cowclip(model, optimizer, l2_loss_fn, use_amp=False, last_layer_step=False, table_dtype=None):
+    """`--cowclip` at start-up: what CowClip is not built for is a ValueError that names the flag, never a silent route elsewhere —
+    bf16 tables, an L2 term that reaches the embedding tables (its 2 wd W would be clipped with the gradient), tables on the host,
+    row-sharded tables, a data-parallel run (the counts would have to be global), the last-layer fine-tune step and the opt-in
+    persistent form of the batch-256 step"""
+    from ..optim_spec import regularises_tables
+    from .dist import world_info
+    head = "--cowclip "
+    if getattr(optimizer, "bf16_tables", False) or table_dtype in ("bf16", torch.bfloat16):
+        raise ValueError(head + "with bf16 tables (--table-dtype bf16): CowClip reads fp32 table rows; not built for bf16 tables")
+    if isinstance(l2_loss_fn, L2Loss) and regularises_tables(l2_loss_fn.wd, l2_loss_fn.no_reg_param_name):
+        raise ValueError(head + "with --wd %r reaching the embedding tables: the L2 term's 2 wd W would be clipped with the gradient "
+                         "(--no-reg-param-name _embedding leaves the tables out, or --wd 0)" % (l2_loss_fn.wd,))
+    if getattr(model, "_place_embedding_on_cpu", False):
+        raise ValueError(head + "with the embedding tables on the host (place_embedding_on_cpu): CowClip needs them on the device")
+    if getattr(model, "_table_sharding", None) == "row":
+        raise ValueError(head + "with --table-sharding row: a row-sharded table holds one rank's rows; CowClip needs whole tables")
+    if world_info()[1] > 1:
+        raise ValueError(head + "with a world size of %d: the ids' counts would have to be global; one process" % world_info()[1])
+    if last_layer_step:
+        raise ValueError(head + "with the last-layer fine-tune step: the tables are frozen there, nothing to clip")
+    if os.environ.get("NASREC_PERSIST_DEFAULT", "0") == "1":
+        raise ValueError(head + "with the persistent step (NASREC_PERSIST_DEFAULT=1): CowClip is not built into it; unset the variable")
+
+
+def _announce_cowclip_route(cowclip, fused, use_amp=False, switched_off=False):
+    """one line per run: which route applies CowClip, and why"""
+    if getattr(cowclip, "_route_announced", False):
+        return
+    cowclip._route_announced = True
+    head = "CowClip (r {}, zeta {})".format(cowclip.r, cowclip.zeta)
+    if fused:
+        print(head + ": fused step, the batch's summed table rows scaled in front of the optimizer.")
+        return
+    why = "the fused step was switched off" if switched_off else ("AMP keeps the torch route" if use_amp else "the fused step does not apply")
+    print(head + ": torch route, CowClip.apply() before every step ({}).".format(why))
+
+
 def _agreed_batches(train_loader, train_batch_size: int, world: int, gpu):
     """The batches of one epoch.  Single process: the loader as it is (incl. its short last batch, which the reference evaluates
     without training on it).  Data parallel: every rank reads its own shards, which differ in length — the ranks agree one step
@@ -343,7 +382,7 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                              train_batch_size: int, gpu: Union[int, None], display_interval: int = 100, test_interval: int = 2000,
                              max_train_steps: int = -1, max_eval_steps: int = -1, test_only_at_last_step: bool = False,
                              grad_clip_value: float = None, tb_writer=None, use_amp: bool = False, use_engine_step: Optional[bool] = None,
-                             last_layer_step: bool = False, ema=None, decay=None):
+                             last_layer_step: bool = False, ema=None, decay=None, cowclip=None):
     """One epoch of training with tests in between; returns the reference's log dict (train_utils.py:181-390).
     `use_engine_step`: None = fused engine step whenever it applies, False = always the torch route.
     `last_layer_step`: a model in last-layer mode (set_mode_to_finelune_last_only) with a qualifying optimizer trains every full batch
@@ -352,8 +391,14 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
     (_fused_step_spec), by `ema.update()` otherwise — and the tests run on the averaged weights (`ema.averaged()`); None = no average.
     `decay`: a DecoupledWeightDecay (utils/optim.py): every step that is taken multiplies the selected parameters that have a gradient
     by 1 - lr lambda in front of the optimizer's update — inside the fused step where the lazily paid decay is exact
-    (_fused_step_spec), by `decay.apply(lr)` otherwise; None = no decay."""
+    (_fused_step_spec), by `decay.apply(lr)` otherwise; None = no decay.
+    `cowclip`: a CowClip (utils/optim.py) over the model's tables: every step that is taken holds the batch's table rows' gradients to
+    cnt max(r ||w||, zeta) behind the global clip — inside the fused step wherever that step applies, by `cowclip.apply(cat_x)` in
+    front of `optimizer.step()` otherwise; what it is not built for is refused here by the flag's name (refuse_cowclip).  Display
+    steps print the share of touched rows clipped since the last one.  None = off: nothing changes."""
     _refuse_regularised_tables(optimizer, l2_loss_fn)
+    if cowclip is not None:
+        refuse_cowclip(model, optimizer, l2_loss_fn, use_amp, last_layer_step)
     _peek(test_loader)  # the reference peeks one test batch here (train_utils.py:224-225)
     model.train()
     logs = {k: [] for k in ("train_loss", "train_AUROC", "train_Accuracy", "test_loss", "test_AUROC", "test_Accuracy", "epoch", "iters")}
@@ -374,6 +419,13 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
             raise ValueError("use_engine_step=True with a decoupled weight decay the fused step cannot keep exactly: leave "
                              "use_engine_step=None")
         _announce_decay_route(model, optimizer, l2_loss_fn, use_amp, ema, decay, fused)
+    if cowclip is not None:
+        _announce_cowclip_route(cowclip, fused, use_amp, switched_off=use_engine_step is False)
+
+    def cow_rows():  # (rows touched, rows clipped) so far on both routes: the engine's and the helper's counters are cumulative
+        fused_rows = model.engine_cowclip_stats() if (fused and hasattr(model, "engine_cowclip_stats")) else (0, 0)
+        return fused_rows[0] + cowclip.touched, fused_rows[1] + cowclip.clipped
+    cow_seen = cow_rows() if cowclip is not None else (0, 0)  # ... at the last display step (an earlier epoch's rows are not this one's)
     # (a decoupled decay keeps the last-layer fine-tune on the torch route: the fused last-layer step has none)
     last_only = bool(last_layer_step) and not fused and use_engine_step is not False and decay is None and \
         _last_layer_step_applies(model, optimizer, l2_loss_fn, use_amp)
@@ -402,6 +454,8 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
     step_kw = dict(opt_kw, ema_decay=float(ema.decay)) if (ema is not None and fused) else opt_kw
     if decay is not None and fused:
         step_kw = dict(step_kw, decoupled_wd=float(decay.weight_decay), no_reg_param_name=decay.no_reg_param_name)
+    if cowclip is not None and fused:
+        step_kw = dict(step_kw, cowclip=(cowclip.r, cowclip.zeta))
     wd = spec.wd if spec is not None else 0.0
     for batch_num, (int_x, cat_x, y) in enumerate(_agreed_batches(train_loader, train_batch_size, world, gpu)):
         t_data1 = time.time()
@@ -465,6 +519,8 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                         optimizer.touch(cat_x)
                     if decay is not None:
                         decay.apply(float(optimizer.param_groups[0]["lr"]))
+                    if cowclip is not None:
+                        cowclip.apply(cat_x)
                     scale0 = scaler.get_scale() if ema is not None else None
                     scaler.step(optimizer)
                     scaler.update()
@@ -480,6 +536,8 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                         optimizer.touch(cat_x)
                     if decay is not None:
                         decay.apply(float(optimizer.param_groups[0]["lr"]))
+                    if cowclip is not None:
+                        cowclip.apply(cat_x)
                     optimizer.step()
                     if ema is not None:
                         ema.update()
@@ -511,6 +569,12 @@ def train_and_test_one_epoch(model, epoch: int, optimizer: Any, lr_scheduler, tr
                 train_auroc = 1.0
             train_acc = accuracy(y_true.view(-1), prob).item()
             print("Train Acc: {}, Train AUROC: {}".format(train_acc, train_auroc))
+            if cowclip is not None:
+                now = cow_rows()
+                rows_seen, rows_clipped = now[0] - cow_seen[0], now[1] - cow_seen[1]
+                cow_seen = now
+                print("CowClip: {:.1f} % of {} touched rows clipped since the last display.".format(
+                    100.0 * rows_clipped / max(rows_seen, 1), rows_seen))
             if tb_writer is not None:
                 x = batch_num * train_batch_size
                 tb_writer.add_scalar("Loss/train/epoch{}".format(epoch), loss_v, x)

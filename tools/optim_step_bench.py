@@ -12,6 +12,9 @@ that brings every row's average current) and `swap_ms` (flush + exchange with th
 `--decoupled-wd LAMBDA` applies utils/optim.DecoupledWeightDecay in front of the update: inside the fused step (Adagrad, row-sparse Adam,
 RMSprop: the rows outside the batch pay lazily), by `apply(lr)` on the torch route; the line then carries `decoupled_wd` and
 `decay_flush_ms` (the launch that brings every table row current and re-bases the stamps).
+`--cowclip R[,ZETA]` puts utils/optim.CowClip in front of the update: inside the fused step (two more launches: count, clip), by
+`apply(cat_x)` on the torch route; the line then carries `cowclip` and, fused, `cowclip_rows` = [touched, clipped] over all steps.
+`--batch` is `--B`.
 Prints one JSON line per measured (route, optimizer, wd):
 
     python tools/optim_step_bench.py --route fused --optimizer adam --wd 0     # the fused engine step
@@ -48,7 +51,8 @@ def main():
     ap.add_argument("--wd", type=float, default=0.0)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--B", type=int, default=256)
+    ap.add_argument("--B", "--batch", dest="B", type=int, default=256)
+    ap.add_argument("--cowclip", type=str, default=None, help="R[,ZETA]: CowClip on the batch's table rows in front of the update (absent: none)")
     ap.add_argument("--ema", type=float, default=0.0, help="decay of a weight average kept beside the step (0: none)")
     ap.add_argument("--decoupled-wd", dest="decoupled_wd", type=float, default=0.0, help="lambda of a decoupled weight decay in front of the update (0: none)")
     ap.add_argument("--bytes", action="store_true")
@@ -129,6 +133,13 @@ def main():
         if a.route == "fused":
             m.engine_bind_decay(decay)
             ema_kw = dict(ema_kw, decoupled_wd=a.decoupled_wd)
+    cow = None
+    if a.cowclip:
+        from nasrec_amd.utils.optim import CowClip, parse_cowclip
+        if a.route == "fused":
+            ema_kw = dict(ema_kw, cowclip=parse_cowclip(a.cowclip))
+        else:
+            cow = CowClip(list(m._embedding.parameters()), *parse_cowclip(a.cowclip))
 
     def step(i):
         int_x, cat_x, y = batches[i % len(batches)]
@@ -146,6 +157,8 @@ def main():
             opt.touch(cat_x)
         if decay is not None:
             decay.apply(lr)
+        if cow is not None:
+            cow.apply(cat_x)
         opt.step()
         if ema is not None:
             ema.update()
@@ -190,6 +203,9 @@ def main():
         m._engine.flush_lazy_rows()
         torch.cuda.synchronize()
         extra["flush_again_ms"] = round((time.perf_counter() - wall) * 1e3, 4)  # (nothing owed: the stamps are read, nothing else)
+    if a.cowclip:
+        extra["cowclip"] = a.cowclip
+        extra["cowclip_rows"] = list(m.engine_cowclip_stats()) if a.route == "fused" else [cow.touched, cow.clipped]
     if a.optimizer == "adam-adagrad-tables":
         extra["table_lr_scale"] = a.table_lr_scale
         extra["table_rowwise"] = bool(a.table_rowwise)
